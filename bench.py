@@ -19,10 +19,11 @@ Frames / timesteps shard embarrassingly: rank r renders timestamp (r + 0.5) / N 
 replicated parameters (scaling = "weak": B views per GPU per step).  Inputs are synthetic
 (fdgs.synth, seed 0) and resident in HBM before the timed region.
 
-Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3]
+Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3] [--full] [--dump-outputs DIR]
         N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
                     --master-port P bench.py --gpus N --steps K --warmup W
-Rank 0 prints ONE JSON line (see README / DESIGN.md for the field definitions).
+Rank 0 prints ONE JSON line (see README / DESIGN.md for the field definitions): by default the headline of exactly K timed steps;
+--full adds every secondary leg, the stage table, the roofline and the baselines.
 """
 import argparse
 import gc
@@ -42,14 +43,22 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 # hardware queues, and RCCL brings streams of its own; streams that share a hardware queue give steps that take several times as
 # long now and then (measured on one GPU with a third stream in the step: DESIGN.md section 5a).  One rank stays on the default (8
 # queues cost the two-stream step 1 %).  Must be set before the HIP runtime starts; inherited by the ranks a self-launch starts.
+# An environment that already asks for fewer queues (e.g. the runtime's default of 4 spelt out) is raised to 8; more are left as they are.
 if int(os.environ.get("WORLD_SIZE", "1")) > 1 or any(a == "--gpus" and i + 1 < len(sys.argv) and sys.argv[i + 1] not in ("1", "0")
                                                       for i, a in enumerate(sys.argv)) or any(a.startswith("--gpus=") and a[7:] not in ("1", "0") for a in sys.argv):
-    os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
+    try:
+        _queues = int(os.environ.get("GPU_MAX_HW_QUEUES", "0"))
+    except ValueError:
+        _queues = 0
+    if _queues < 8:
+        os.environ["GPU_MAX_HW_QUEUES"] = "8"
 
 import torch  # noqa: E402
 
 PROFILE_EVERY = int(os.environ.get("FDGS_BENCH_PROFILE_EVERY", "5"))   # the dominant stage's live event pairs: every n-th launch
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak, /opt/skills/guides/MI355X_MICROARCH.md (6.29 TB/s measured copy)
+DUMP_MAX_ELEMS = 1 << 19   # --dump-outputs: larger arrays are sampled (4 views x 6 arrays + parameters: under 64 MB in all)
+REHEARSAL_MAX_STEPS = 500  # untimed steps per block of the rehearsal in front of the timed region (main)
 
 # Algorithmic HBM bytes per launch of each stage (BASELINE.md section 3 / SURVEY.md section 8d):
 # P Gaussians, Pv visible, M SH coefficients, R instances, N pixels, T tiles.
@@ -89,9 +98,19 @@ def parse_args():
     ap.add_argument("--min-warmup-ms", type=float, default=150.0,
                     help="the warm-up goes on (whole steps) until this much wall time has passed, whatever --warmup says: the shader clock "
                          "needs ~100 ms of load to settle")
-    ap.add_argument("--min-timed-ms", type=float, default=1000.0,
+    ap.add_argument("--min-timed-ms", type=float, default=0.0,
                     help="the timed region is --steps steps repeated (whole multiples) until it lasts at least this long; `steps_timed` in the "
-                         "JSON line says how many steps that was (0: exactly --steps)")
+                         "JSON line says how many steps that was (0, the default: exactly --steps)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline: the single-stream stage table, the dominant kernel's live roofline and the shader "
+                         "clock, per-rank timings and the replicas' parameter digest, the forward-only and rasterizer-only rates, every "
+                         "secondary leg below (other tile lists, storage order, cameras, C5, C3-clustered, host cost, drop-in), the CPU "
+                         "baseline with the reference's kernels on this GPU, and the step-end stages.  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (every view's image, radii, depth, alpha, flow, "
+                         "screen-space gradient, num_rendered and loss) and the parameters it left as DIR/<name>.npy, float32 / float64; "
+                         "an array of more than %d elements is written as a fixed, seeded sample of that many" % DUMP_MAX_ELEMS)
     ap.add_argument("--reflists-steps", type=int, default=20,
                     help="steps of the extra leg with the reference's bit-identical tile lists (tile_cull = 0): value_reference_lists (0 = skip)")
     ap.add_argument("--clustered-steps", type=int, default=10,
@@ -216,6 +235,36 @@ def max_over_ranks(x, world, dev):
     t = torch.tensor([x], dtype=torch.float64, device=dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     return float(t.item())
+
+
+def dump_outputs(dirname, results, losses, model):
+    """--dump-outputs: what the last timed step handed its caller -- per view v the results dict of StepPipeline.step (or of render() on the
+    other host paths) as view<v>_<key>.npy, its loss as view<v>_loss.npy -- and the parameters it left (params_flat.npy).  Floating
+    tensors keep float64 where they are float64 and are float32 otherwise (radii and counts are exact in float32 / float64).  An array of
+    more than the per-array budget is written as a sample at fixed positions (a seeded draw per array length, the same in every run):
+    the files stay under 64 MB in all."""
+    import numpy as np
+    arrays = {}
+    for v, r in enumerate(results):
+        for k, x in sorted(r.items()):
+            if isinstance(x, torch.Tensor):
+                arrays["view%d_%s" % (v, k)] = x.detach()
+            elif isinstance(x, (int, float)) and not isinstance(x, bool):
+                arrays["view%d_%s" % (v, k)] = torch.tensor([x], dtype=torch.float64)
+    for v, l_ in enumerate(losses or []):
+        if l_ is not None:
+            arrays["view%d_loss" % v] = (l_.detach() if isinstance(l_, torch.Tensor) else torch.tensor([float(l_)])).double()
+    arrays["params_flat"] = model.flat.detach()
+    cap = min(DUMP_MAX_ELEMS, (56 << 20) // (8 * max(len(arrays), 1)))
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.reshape(-1)
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng([20260, t.numel()]).choice(t.numel(), cap, replace=False))
+            t = t[torch.from_numpy(idx).to(t.device)]
+        a = t.cpu().numpy()
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def reference_kernels_on_this_gpu(scene, dev, passes=20):
@@ -709,13 +758,17 @@ def main():
                                 batch_views=args.batch_views, sh_group=args.sh_group, lazy=not args.no_lazy, sparse_lists=not args.no_sparse_lists,
                                 overlap_steps=not args.no_overlap_steps)
 
+    step_losses = []   # the losses of the latest step() (--dump-outputs)
+
     def step():
         if use_pipeline:
-            results, _losses = steppipe.step(cams, gts, pipe, bg)
+            results, losses_ = steppipe.step(cams, gts, pipe, bg)
+            step_losses[:] = losses_
             return results
         if args.reference_host:
             model.zero_grad()
         pkg = None
+        step_losses.clear()
         for b in range(B):
             if args.reference_host:
                 pkg = render(cams[b], model, pipe, bg)
@@ -728,6 +781,7 @@ def main():
                 loss = train_host.photometric_loss(pkg["render"], gts[b])
             else:
                 loss = fused_l1_ssim(pkg["render"], gts[b], 0.2)
+            step_losses.append(loss)
             (loss / (B * world)).backward()  # train.py:162; 1 / world: the all-reduce SUM is then the mean
         train_host.allreduce_gradients(model, world, average=False)
         opt.step()
@@ -736,7 +790,11 @@ def main():
     # The targets are noise, so hundreds of Adam steps at the reference's learning rates drive the model away from the workload the
     # metric is quoted on (opacities and scales shrink: a third of the instances are left after 400 steps).  Every timed leg therefore
     # starts from the SAME state: parameters, Adam moments and step count are put back (three device copies, INSIDE the timed region
-    # where one is timed: extra work, nothing skipped) after the warm-up and before every repetition of the --steps steps.
+    # where one is timed: extra work, nothing skipped) after the warm-up and before every repetition of the --steps steps -- and once
+    # more before the LAST timed step.  The backward sums per-Gaussian gradients with float atomics whose order differs from run to run,
+    # and Adam (eps = 1e-15) on noise targets grows that last-bit noise: after 10 steps two runs' images differ by up to 0.2.  The last
+    # step, whose results --dump-outputs writes, therefore starts from the seeded state: its inputs are the same in every run, and so
+    # are its outputs, up to the rounding of those atomics.
     snap = (model.flat.detach().clone(), opt.exp_avg.clone(), opt.exp_avg_sq.clone(), opt.step_count)
 
     def restore():
@@ -770,34 +828,35 @@ def main():
             step()
         warm_steps += 4
     torch.cuda.synchronize(dev)
-    # Untimed stage pass on ONE stream (kernel time, not queueing time behind the other stream's launches): every
-    # rasterizer stage bracketed with HIP events -> the per-stage table and the dominant stage.
-    if use_pipeline:
-        stage_pipe = StepPipeline(model, opt, world_size=world, lambda_dssim=0.2, overlap=False,
-                                  gather_max_views=0 if args.dense_sh_exchange else 32, batch_views=args.batch_views, sh_group=args.sh_group,
-                                  tile_cull=not args.no_tile_cull, lazy=not args.no_lazy, sparse_lists=not args.no_sparse_lists)
-        stage_step = lambda: stage_pipe.step(cams, gts, pipe, bg)[0]  # noqa: E731
-    else:
-        stage_step = step
-    stage_step()
-    torch.cuda.synchronize(dev)
-    _capi.profile_reset()
-    _capi.profile_enable(True)
-    n_stage_steps = max(1, min(3, args.steps))
-    r_seen = []
-    for _ in range(n_stage_steps):
-        r_seen += [r["num_rendered"] for r in stage_step() if "num_rendered" in r]
-    torch.cuda.synchronize(dev)
-    _capi.profile_enable(False)
-    prof_all = _capi.profile_read()
-    R_stage = (sum(r_seen) / len(r_seen)) if r_seen else (sum(_R_LOG) / max(len(_R_LOG), 1))
-    dom = max((k for k in prof_all if k != "readback"), key=lambda k: prof_all[k][0])
-    # Timed region (the two-stream pipeline): only the dominant kernel keeps its event pair -- the roofline figure is
-    # measured live here -- and one event per step boundary on the main stream gives the per-step distribution.
-    _capi.profile_reset()
-    # (every PROFILE_EVERY-th launch of it: an event pair costs the stream ~13 us of idle time around the launch -- 2 % of the step if
-    # every blend backward carried one; 5 is coprime to the 4 views of a step, so the samples rotate through the views)
-    _capi.profile_enable(True, stages=[dom], every=PROFILE_EVERY)
+    if args.full:
+        # Untimed stage pass on ONE stream (kernel time, not queueing time behind the other stream's launches): every
+        # rasterizer stage bracketed with HIP events -> the per-stage table and the dominant stage.
+        if use_pipeline:
+            stage_pipe = StepPipeline(model, opt, world_size=world, lambda_dssim=0.2, overlap=False,
+                                      gather_max_views=0 if args.dense_sh_exchange else 32, batch_views=args.batch_views, sh_group=args.sh_group,
+                                      tile_cull=not args.no_tile_cull, lazy=not args.no_lazy, sparse_lists=not args.no_sparse_lists)
+            stage_step = lambda: stage_pipe.step(cams, gts, pipe, bg)[0]  # noqa: E731
+        else:
+            stage_step = step
+        stage_step()
+        torch.cuda.synchronize(dev)
+        _capi.profile_reset()
+        _capi.profile_enable(True)
+        n_stage_steps = max(1, min(3, args.steps))
+        r_seen = []
+        for _ in range(n_stage_steps):
+            r_seen += [r["num_rendered"] for r in stage_step() if "num_rendered" in r]
+        torch.cuda.synchronize(dev)
+        _capi.profile_enable(False)
+        prof_all = _capi.profile_read()
+        R_stage = (sum(r_seen) / len(r_seen)) if r_seen else (sum(_R_LOG) / max(len(_R_LOG), 1))
+        dom = max((k for k in prof_all if k != "readback"), key=lambda k: prof_all[k][0])
+        # Timed region (the two-stream pipeline): only the dominant kernel keeps its event pair -- the roofline figure is
+        # measured live here -- and one event per step boundary on the main stream gives the per-step distribution.
+        _capi.profile_reset()
+        # (every PROFILE_EVERY-th launch of it: an event pair costs the stream ~13 us of idle time around the launch -- 2 % of the step if
+        # every blend backward carried one; 5 is coprime to the 4 views of a step, so the samples rotate through the views)
+        _capi.profile_enable(True, stages=[dom], every=PROFILE_EVERY)
     _R_LOG.clear()
     # the timed region: --steps steps, repeated (whole multiples) until it lasts >= --min-timed-ms
     torch.cuda.synchronize(dev)
@@ -823,28 +882,31 @@ def main():
     # (the step uses up to four streams -- the caller's, F, B, A -- and the runtime has four hardware queues by default: the sampler that sits
     # in a queue of its own for the whole region is the A/B aid now, FDGS_BENCH_CLOCK=span|both; the default takes two short samples on the
     # caller's stream, in front of the first and behind the last timed step)
-    clock_mode = os.environ.get("FDGS_BENCH_CLOCK", "pair")
+    clock_mode = os.environ.get("FDGS_BENCH_CLOCK", "pair") if args.full else "off"
     clock_pair = None
     try:
         clock = _capi.ClockSample(dev) if clock_mode in ("span", "both") else None
         clock_pair = _capi.ClockPair(dev) if clock_mode in ("pair", "both") else None
     except Exception:
         clock = clock_pair = None
-    # Rehearsal of the timed region's own pattern (round 6): two blocks of [restore, --steps steps], untimed.  The warm-up above walks ONE
+    # Rehearsal of the timed region's own pattern (round 6): two blocks of [restore, --steps steps, the last behind a restore again], untimed.  The warm-up above walks ONE
     # long trajectory away from the restored state -- the scene shrinks, the run-ahead buffers with it, the caching allocator splits
     # its large blocks to serve the smaller requests -- and the first restore inside the timed region then asks for the large sizes
     # again: one or two device allocations of ~10 ms each next to a busy device (`ms_per_step_max` 12 ms, `value` 3 % under
-    # `value_median` in one run of three).  The same cure as for the legs (warm_up).
+    # `value_median` in one run of three).  The same cure as for the legs (warm_up).  A block stops after REHEARSAL_MAX_STEPS steps: the
+    # large requests come right behind a restore, and a long run's untimed time stays bounded.
     for _rb in range(2):
-        restore()
-        for _ in range(args.steps):
+        n_rb = min(args.steps, REHEARSAL_MAX_STEPS)
+        for k in range(n_rb):
+            if k == 0 or k == n_rb - 1:
+                restore()
             step()
     torch.cuda.synchronize(dev)
     # no collector pauses inside the timed region (the host runs ~1.8 ms ahead of the GPU per step; a generation-2 collection of the
     # step's many small Python objects takes longer than that)
     gc.collect()
     gc.disable()
-    if use_pipeline and world > 1:
+    if use_pipeline and world > 1 and args.full:
         steppipe.exchange_pairs = []   # stream B's waits for the collectives, bracketed by timing events
     barrier(world)
     t0 = time.perf_counter()
@@ -854,8 +916,8 @@ def main():
         clock_pair.mark()
     _DBG, _host_ms = int(os.environ.get("FDGS_BENCH_DEBUG", "0")), []
     for i in range(steps_timed):
-        if i % args.steps == 0:
-            restore()   # inside the timed region: ~0.25 ms of copies per --steps steps (not part of any step's own event pair)
+        if i % args.steps == 0 or i == steps_timed - 1:
+            restore()   # inside the timed region: ~0.25 ms of copies per --steps steps + 1 (not part of any step's own event pair)
         starts[i].record()
         if _DBG:
             _th = time.perf_counter()
@@ -876,6 +938,8 @@ def main():
         _med = sorted(_ev)[len(_ev) // 2]
         print("step dbg: steps over twice the median (index, event ms, host ms)", [(i, round(_ev[i], 2), round(_host_ms[i], 2)) for i in range(steps_timed) if _ev[i] > 2 * _med],
               "host-only outliers", [(i, round(_host_ms[i], 2)) for i in range(steps_timed) if _host_ms[i] > 3 * _med and _ev[i] <= 2 * _med], file=sys.stderr)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, pkg, step_losses, model)
     # (the collector stays off for the rest of the run -- every leg below is a few dozen steps, i.e. tens of milliseconds, and one
     # generation-2 pause of the interpreter in it is 20-40 % of its reading: legs that read 1000-1400 where the next run read 1700;
     # warm_up() collects by hand in front of every leg)
@@ -915,11 +979,11 @@ def main():
             shader_ghz = pair_ghz
         finally:
             restore()
-    prof_dom = _capi.profile_read()[dom]
+    prof_dom = _capi.profile_read()[dom] if args.full else None
     # N > 1: every rank's own wall time per step and the exchange time nothing overlapped (the sum of stream B's waits for a
     # collective per step, train_host.timed_wait), so that a scaling run explains itself
     per_rank = None
-    if world > 1:
+    if world > 1 and args.full:
         import torch.distributed as dist
         exposed = None
         if use_pipeline and steppipe.exchange_pairs:
@@ -938,6 +1002,54 @@ def main():
     R_timed = (sum(r_last) / len(r_last)) if r_last else (sum(_R_LOG) / max(len(_R_LOG), 1))
     lazy_redone = steppipe.lazy_redone if use_pipeline else None
     pct = lambda q: step_ms[min(len(step_ms) - 1, int(q * len(step_ms)))]  # noqa: E731
+
+    P, M, W, H = model.P, model.M, scene["W"], scene["H"]
+    # visible Gaussians: mean over the views of the last step (every view has its own timestamp, hence its own cull)
+    Pv = sum(int((r["radii"] > 0).sum().item()) for r in pkg) / len(pkg)
+    mode = ("weak scaling, %d views per GPU and step (the reference's DyNeRF batch per GPU)" % B if B > 1 else
+            "BASELINE configs[3] as specified: one view per GPU and step, N timesteps frame-parallel")
+    out = {
+        "metric": "train-step images/sec + forward Mpix/s, 300k 4D Gaussians @1352x1014",
+        "value": round(world * B * steps_timed / dt, 3),
+        "unit": "images/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        # the timed region is --steps steps repeated `steps_timed / steps` times (>= --min-timed-ms of wall time), one barrier +
+        # synchronize pair around all of it; the warm-up ran `warmup_steps_run` steps (>= --warmup, >= --min-warmup-ms)
+        "steps_timed": steps_timed, "warmup_steps_run": warm_steps, "timed_region_ms": round(dt * 1e3, 2),
+        "value_median": round(world * B * 1e3 / pct(0.5), 3),
+        "ms_per_step": round(dt / steps_timed * 1e3, 4),
+        "ms_per_step_median": round(pct(0.5), 4), "ms_per_step_p10": round(pct(0.1), 4), "ms_per_step_p90": round(pct(0.9), 4),
+        "ms_per_step_max": round(step_ms[-1], 4), "steps_over_twice_the_median": int(sum(1 for t_ in step_ms if t_ > 2.0 * pct(0.5))),
+        "ms_per_image": round(dt / (steps_timed * B) * 1e3, 4),
+        "lazy_forward": bool(use_pipeline and not args.no_lazy and world == 1), "lazy_steps_redone": lazy_redone,
+        # fdgs_forward_out.sparse_lists: lazy forwards keep every tile's list at a fixed offset of the binning buffer (the same lists; no count /
+        # scan launch: their rows are then missing from `stages`)
+        "sparse_lists": bool(use_pipeline and not args.no_lazy and not args.no_sparse_lists and world == 1),
+        "overlap_steps": bool(use_pipeline and steppipe.overlap_steps),
+        "steps_started_under_the_previous_sh_update": int(steppipe.steps_carried) if use_pipeline else 0,
+        "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": ("[model stored in Morton order, as fdgs.harness.train keeps it] " if args.storage_order == "morton" else "[model stored in the generator's random order] ") + "%s: %d 4D Gaussians, %dx%d, SH degree %d + time degree %d (M=%d), rot_4d=%s, "
+                               "%d views/GPU/step, L1+SSIM loss (%s), Adam" % (cfg.name, P, W, H, cfg.sh_degree, cfg.sh_degree_t,
+                                                                        M, cfg.rot_4d, B, "PyTorch" if args.torch_loss else "fused HIP") + (", reference host path" if args.reference_host else (", fused activations, explicit fwd/loss/bwd on %s" % ("one stream" if args.no_overlap else "two HIP streams") if use_pipeline else ", fused activations, autograd")),
+                   "num_rendered": int(round(R_timed)), "cameras": ("4 different rotated off-axis cameras per step (fdgs.synth.POSES rig0..rig3)" if args.cameras == "rig" else "one unrotated on-axis camera for every view"), "tile_cull": not args.no_tile_cull, "visible": int(round(Pv)), "views_per_step_per_gpu": B, "global_batch": B * world,
+                   "parallelism": "frame-parallel dp%d" % world, "mode": mode},
+        "full": bool(args.full),
+    }
+    out["rccl_ranks"] = world
+    if world > 1:
+        # what the ranks exchanged per step (fdgs/pipeline.py): the views' 32-byte SH stages by all-gather + the 17 geometry floats by
+        # all-reduce (up to 32 views per step over all ranks), or the dense 161 P-float gradient bucket by all-reduce
+        out["sh_exchange"] = ("stage all-gather + geometry all-reduce" if (use_pipeline and not args.dense_sh_exchange and world * B <= 32)
+                              else "dense gradient all-reduce")
+    out["backend"] = backend if backend else "none (single process)"
+    out["storage_order"] = args.storage_order
+    if not args.full:
+        # a plain run: the headline and nothing else (the legs below, the tables and the baselines: --full)
+        if rank == 0:
+            print(json.dumps(front_loaded(out)))
+        return
 
     # digest of the parameters after all steps (tests compare N ranks x B views with one rank x N B views: the same update)
     param_digest = [float(model.flat.double().sum()), float(model.flat.double().abs().sum())]
@@ -1187,10 +1299,7 @@ def main():
 
     if rank != 0:
         return
-    P, M, W, H = model.P, model.M, scene["W"], scene["H"]
     N, T = W * H, ((W + 15) // 16) * ((H + 15) // 16)
-    # visible Gaussians: mean over the views of the last step (every view has its own timestamp, hence its own cull)
-    Pv = sum(int((r["radii"] > 0).sum().item()) for r in pkg) / len(pkg)
     # live Gaussians: those that contributed to some pixel (a non-zero screen-space gradient row), mean over the last step's views
     if use_pipeline:
         P_live = sum(int((r["viewspace_grad"] != 0).any(dim=1).sum().item()) for r in pkg) / len(pkg)
@@ -1257,36 +1366,9 @@ def main():
             roofline["valu_issue_frac_with_this_runs_duration"] = live
         else:
             roofline["valu_issue_frac"] = live
-    mode = ("weak scaling, %d views per GPU and step (the reference's DyNeRF batch per GPU)" % B if B > 1 else
-            "BASELINE configs[3] as specified: one view per GPU and step, N timesteps frame-parallel")
-    out = {
-        "metric": "train-step images/sec + forward Mpix/s, 300k 4D Gaussians @1352x1014",
-        "value": round(world * B * steps_timed / dt, 3),
-        "unit": "images/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        # the timed region is --steps steps repeated `steps_timed / steps` times (>= --min-timed-ms of wall time), one barrier +
-        # synchronize pair around all of it; the warm-up ran `warmup_steps_run` steps (>= --warmup, >= --min-warmup-ms)
-        "steps_timed": steps_timed, "warmup_steps_run": warm_steps, "timed_region_ms": round(dt * 1e3, 2),
-        "value_median": round(world * B * 1e3 / pct(0.5), 3),
-        "ms_per_step": round(dt / steps_timed * 1e3, 4),
-        "ms_per_step_median": round(pct(0.5), 4), "ms_per_step_p10": round(pct(0.1), 4), "ms_per_step_p90": round(pct(0.9), 4),
-        "ms_per_step_max": round(step_ms[-1], 4), "steps_over_twice_the_median": int(sum(1 for t_ in step_ms if t_ > 2.0 * pct(0.5))),
-        "ms_per_image": round(dt / (steps_timed * B) * 1e3, 4),
-        "lazy_forward": bool(use_pipeline and not args.no_lazy and world == 1), "lazy_steps_redone": lazy_redone,
-        # fdgs_forward_out.sparse_lists: lazy forwards keep every tile's list at a fixed offset of the binning buffer (the same lists; no count /
-        # scan launch: their rows are then missing from `stages`)
-        "sparse_lists": bool(use_pipeline and not args.no_lazy and not args.no_sparse_lists and world == 1),
-        "overlap_steps": bool(use_pipeline and steppipe.overlap_steps),
-        "steps_started_under_the_previous_sh_update": int(steppipe.steps_carried) if use_pipeline else 0,
-        "gpu_max_hw_queues": os.environ.get("GPU_MAX_HW_QUEUES", "runtime default (4)"),
+    out.update({
         "host_ms_per_view": None if host_ms_per_view is None else round(host_ms_per_view, 4),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "replicas_identical": replicas_identical, "param_digest": param_digest,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": ("[model stored in Morton order, as fdgs.harness.train keeps it] " if args.storage_order == "morton" else "[model stored in the generator's random order] ") + "%s: %d 4D Gaussians, %dx%d, SH degree %d + time degree %d (M=%d), rot_4d=%s, "
-                               "%d views/GPU/step, L1+SSIM loss (%s), Adam" % (cfg.name, P, W, H, cfg.sh_degree, cfg.sh_degree_t,
-                                                                        M, cfg.rot_4d, B, "PyTorch" if args.torch_loss else "fused HIP") + (", reference host path" if args.reference_host else (", fused activations, explicit fwd/loss/bwd on %s" % ("one stream" if args.no_overlap else "two HIP streams") if use_pipeline else ", fused activations, autograd")),
-                   "num_rendered": int(round(R_timed)), "cameras": ("4 different rotated off-axis cameras per step (fdgs.synth.POSES rig0..rig3)" if args.cameras == "rig" else "one unrotated on-axis camera for every view"), "tile_cull": not args.no_tile_cull, "visible": int(round(Pv)), "views_per_step_per_gpu": B, "global_batch": B * world,
-                   "parallelism": "frame-parallel dp%d" % world, "mode": mode},
+        "replicas_identical": replicas_identical, "param_digest": param_digest,
         "forward_mpix_s": round(world * n_fwd * N / dt_fwd / 1e6, 1),
         "forward_split_colour": bool(use_pipeline and args.split_colour != "off"),
         "forward_ms": round(dt_fwd / n_fwd * 1e3, 4),
@@ -1299,16 +1381,9 @@ def main():
                        "stage ('%s') is re-measured live inside the timed two-stream region: roofline.avg_kernel_ms" % (
                            n_stage_steps, int(round(R_stage)), dom),
         "roofline": roofline,
-    }
-    out["rccl_ranks"] = world
-    if world > 1:
-        # what the ranks exchanged per step (fdgs/pipeline.py): the views' 32-byte SH stages by all-gather + the 17 geometry floats by
-        # all-reduce (up to 32 views per step over all ranks), or the dense 161 P-float gradient bucket by all-reduce
-        out["sh_exchange"] = ("stage all-gather + geometry all-reduce" if (use_pipeline and not args.dense_sh_exchange and world * B <= 32)
-                              else "dense gradient all-reduce")
+    })
     if per_rank:
         out["per_rank"] = per_rank
-    out["backend"] = backend if backend else "none (single process)"
     if other_cams:
         out["value_%s_camera" % other_cams["cameras"]] = other_cams["images_s"]
         out["other_cameras"] = other_cams
@@ -1321,7 +1396,6 @@ def main():
     if reflists:
         out["value_reference_lists"] = reflists["images_s"]
         out["reference_lists"] = reflists
-    out["storage_order"] = args.storage_order
     if spatial:
         if args.storage_order == "morton":
             out["random_order_images_s"] = spatial["images_s"]

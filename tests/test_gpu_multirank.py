@@ -28,7 +28,7 @@ def test_bench_two_ranks_share_one_gpu(views, dense, gpu_device):
     env = dict(os.environ, FDGS_BENCH_DEBUG_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--min-warmup-ms", "0", "--min-timed-ms", "0",
-           "--workload", "C2", "--views-per-step", str(views), "--cpu-samples", "0"] + (["--dense-sh-exchange"] if dense else [])
+           "--workload", "C2", "--views-per-step", str(views), "--cpu-samples", "0", "--full"] + (["--dense-sh-exchange"] if dense else [])
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -49,7 +49,7 @@ def test_bench_launches_its_own_ranks(gpu_device):
     # time-based warm-up and a minimum timed duration, as the driver's flags leave them on: how many steps that makes is decided by
     # the ranks TOGETHER (a step holds collectives: a rank that took one more would hang the others)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--min-warmup-ms", "40", "--min-timed-ms", "60", "--workload", "C2",
-           "--cpu-samples", "0", "--host-cost-steps", "0"]
+           "--cpu-samples", "0", "--host-cost-steps", "0", "--full"]
     out = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
@@ -75,7 +75,7 @@ def test_bench_refuses_more_ranks_than_gpus(gpu_device):
 def _run_bench(nproc, views, extra=()):
     env = dict(os.environ, FDGS_BENCH_DEBUG_SHARE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     common = [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "2", "--min-warmup-ms", "0", "--min-timed-ms", "0", "--workload", "C2",
-              "--views-per-step", str(views), "--cpu-samples", "0", "--host-cost-steps", "0", "--dropin-steps", "0", "--spatial-order-steps", "0"] + list(extra)
+              "--views-per-step", str(views), "--cpu-samples", "0", "--host-cost-steps", "0", "--dropin-steps", "0", "--spatial-order-steps", "0", "--full"] + list(extra)
     if nproc == 1:
         cmd = [sys.executable] + common
     else:
@@ -125,7 +125,7 @@ def _run_bench_rccl(nproc, views, extra=()):
         env.pop(k, None)
     common = [os.path.join(ROOT, "bench.py"), "--gpus", str(nproc), "--steps", "3", "--warmup", "2", "--min-warmup-ms", "0", "--min-timed-ms", "0",
               "--workload", "C2", "--views-per-step", str(views), "--cpu-samples", "0", "--host-cost-steps", "0", "--dropin-steps", "0",
-              "--spatial-order-steps", "0", "--reflists-steps", "0"] + list(extra)
+              "--spatial-order-steps", "0", "--reflists-steps", "0", "--full"] + list(extra)
     if nproc == 1:
         cmd = [sys.executable] + common
     else:
@@ -162,7 +162,7 @@ def test_rccl_bench_launches_itself_on_two_gpus(gpu_device):
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "FDGS_BENCH_DEBUG_SHARE_GPU"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--workload", "C2", "--cpu-samples", "0",
-                          "--host-cost-steps", "0", "--dropin-steps", "0", "--spatial-order-steps", "0", "--reflists-steps", "0", "--min-timed-ms", "100"],
+                          "--host-cost-steps", "0", "--dropin-steps", "0", "--spatial-order-steps", "0", "--reflists-steps", "0", "--min-timed-ms", "100", "--full"],
                          cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])

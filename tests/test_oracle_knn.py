@@ -1,12 +1,17 @@
-"""oracle/knn_oracle.py (float32 restatement of simple-knn's distCUDA2) against an independent exact search."""
+"""oracle/knn_oracle.py (float32 restatement of simple-knn's distCUDA2) against the reference's own device code (recorded in
+tests/golden/knn_ref.npz by tests/golden/make_golden_knn.py) and against an independent exact search."""
+import os
+
 import numpy as np
 import pytest
 from scipy.spatial import cKDTree
 
 import util  # noqa: F401
-from oracle import knn_oracle, pyoracle
+from oracle import knn_oracle
 
-needs_ref = pytest.mark.skipif(not pyoracle.have_ref(), reason="oracle/_ref not built (no /root/reference here)")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "knn_ref.npz")
+PIN_CASES = [(1, "gauss"), (2, "gauss"), (3, "gauss"), (4, "gauss"), (7, "gauss"), (255, "gauss"), (1024, "gauss"), (1025, "shifted"),
+             (3000, "plane"), (4097, "dups"), (20000, "gauss")]
 
 
 def _cloud(P, seed, kind):
@@ -25,14 +30,15 @@ def _cloud(P, seed, kind):
     raise ValueError(kind)
 
 
-@needs_ref
-@pytest.mark.parametrize("P,kind", [(1, "gauss"), (2, "gauss"), (3, "gauss"), (4, "gauss"), (7, "gauss"), (255, "gauss"),
-                                    (1024, "gauss"), (1025, "shifted"), (3000, "plane"), (4097, "dups"), (20000, "gauss")])
+@pytest.mark.parametrize("P,kind", PIN_CASES)
 def test_knn_oracle_pinned_to_reference_source(P, kind):
     """The numpy restatement against the reference's OWN device code (simple_knn.cu:28-191 compiled verbatim, host sequence
-    :193-220 restated with std::sort / a fold; oracle/refbuild/ref_knn.cpp): bit-exact, contraction off on both sides."""
+    :193-220 restated with std::sort / a fold; oracle/refbuild/ref_knn.cpp): bit-exact, contraction off on both sides.  The
+    reference's results on these clouds are recorded in tests/golden/knn_ref.npz."""
     pts = _cloud(P, 100 + P, kind)
-    want = pyoracle.ref_dist2_knn3(pts)
+    with np.load(GOLDEN) as g:
+        want = g["%d_%s" % (P, kind)]
+    assert want.shape == (P,) and want.dtype == np.float32
     got = knn_oracle.dist2_knn3(pts)
     np.testing.assert_array_equal(got.view(np.uint32), want.view(np.uint32))
 

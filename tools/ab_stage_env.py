@@ -22,7 +22,7 @@ for r in range(rounds):
             env[k] = v
         out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "30", "--warmup", "10", "--cpu-samples", "0", "--host-cost-steps", "0",
                               "--dropin-steps", "0", "--spatial-order-steps", "0", "--reflists-steps", "0", "--clustered-steps", "0", "--axis-steps", "0",
-                              "--c5-steps", "0"] + extra, env=env, capture_output=True, text=True)
+                              "--c5-steps", "0", "--full", "--min-timed-ms", "1000"] + extra, env=env, capture_output=True, text=True)
         lines = [l for l in out.stdout.strip().splitlines() if l.startswith("{")]
         if not lines:
             print("run failed:", out.stderr[-500:])
