@@ -206,7 +206,6 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
                 stats.update(results, t_grad, batch_size * world_size)
                 if on_densify is not None:
                     on_densify(model, optimizer, stats, iteration)
-                    steppipe.sink = model.grad_sink()
                 elif cameras_extent is not None:
                     if iteration > densify_from_iter and iteration % densification_interval == 0:        # train.py:238-240
                         from .densify import densify_and_prune
@@ -216,7 +215,6 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
                                                 size_threshold, densify_grad_t_threshold, percent_dense=percent_dense, generator=gen)
                         if spatial_order:
                             resort(stats)
-                        steppipe.sink = model.grad_sink()
                         if rank == 0 and log_every:
                             log("[it %5d] densify: %d -> %d Gaussians (%d cloned, %d split)" % (iteration, rep["P_old"], rep["P_new"],
                                                                                               rep["cloned"], rep["split_parents"]))

@@ -403,6 +403,13 @@ class FlatAdam:
         denom = self.exp_avg_sq[sl].sqrt().div_(math.sqrt(bc2)).add_(self.eps)
         m.flat[sl].sub_(self._lr_vec[sl] / bc1 * (self.exp_avg[sl] / denom))
 
+    def geometry_adam(self) -> dict:
+        """The Adam step of the geometry segments (``step_range(0, features)``) for the CURRENT step_count, as the
+        ``geometry_adam`` dict of the rasterizer backward (fdgs_backward_out.adam: taken inside the geometry backward)."""
+        lr = {s["name"]: s["lr"] for s in self.named_segments()}
+        return dict(flat=self.model.flat, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, betas=self.betas, eps=self.eps,
+                    step=self.step_count, lr=dict(means3D=lr["_xyz"], opacities=lr["_opacity"], ts=lr["_t"], scales=lr["_scaling"],
+                                                  scales_t=lr["_scaling_t"], rotations=lr["_rotation"], rotations_r=lr["_rotation_r"]))
 
     @torch.no_grad()
     def step_sh_staged(self, stages: torch.Tensor, rs, analytic_sh_grad: bool = False, write_grad: bool = False) -> bool:

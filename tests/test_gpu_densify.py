@@ -118,6 +118,48 @@ def test_densify_larger_scene_vs_oracle_and_training_continues(gpu_device):
     assert results[0]["radii"].shape[0] == model.P and torch.isfinite(model.flat).all() and not torch.equal(before, model.flat)
 
 
+def test_step_pipeline_follows_a_pruned_model(gpu_device):
+    """A StepPipeline built before a densification writes the next step's gradients into the re-laid-out model's bucket without
+    being told (its sink follows ``model.flat_grad``): after a prune-only densify_and_prune (P shrinks) its step equals that of a
+    fresh pipeline on a copy of the same state."""
+    from fdgs import harness, train_host
+    from fdgs.densify import densify_and_prune
+    from fdgs.pipeline import StepPipeline
+    cfg = synth.SceneConfig("d", 20000, 160, 128, 3, 2, 0.04, 10.0, True, 4, False)
+    scene = synth.make_scene(cfg, seed=9)
+    model = train_host.GaussianParams(scene, gpu_device)
+    opt = train_host.make_optimizer(model)
+    pipe, bg = train_host.PipelineFlags(), torch.zeros(3, device=gpu_device)
+    cams = [train_host.SyntheticCamera(scene, gpu_device, timestamp=t) for t in (2.0, 6.0)]
+    gen = torch.Generator(device="cpu").manual_seed(5)
+    gts = [torch.rand(3, scene["H"], scene["W"], generator=gen).to(gpu_device) for _ in cams]
+    sp = StepPipeline(model, opt)
+    sp.step(cams, gts, pipe, bg)
+    min_opacity = float(torch.sigmoid(model._opacity).flatten().quantile(0.25))
+    rep = densify_and_prune(model, opt, harness.DensificationStats(model.P, gpu_device, 1), 2e-4, min_opacity, 1.0, None, prune_only=True)
+    assert model.P * 2 > rep["P_old"] > rep["P_new"] == model.P, rep
+    # the same state in a model, an optimizer and a pipeline of their own
+    fresh = train_host.GaussianParams(scene, gpu_device)
+    fresh._bind(model.flat.detach().clone(), torch.zeros_like(model.flat_grad), model.P)
+    fresh_opt = train_host.make_optimizer(fresh)
+    fresh_opt.rebind(opt.exp_avg.clone(), opt.exp_avg_sq.clone())
+    fresh_opt.step_count = opt.step_count
+    runs = []
+    for m, o, p in ((model, opt, sp), (fresh, fresh_opt, StepPipeline(fresh, fresh_opt))):
+        _res, losses = p.step(cams, gts, pipe, bg)
+        torch.cuda.synchronize()
+        runs.append((m.flat.detach().clone(), o.exp_avg.clone(), o.exp_avg_sq.clone(), [float(l) for l in losses]))
+    assert sp.sink["dL_dmeans3D"].data_ptr() == model.flat_grad.data_ptr()
+    (pa, ma, va, la), (pb, mb, vb, lb) = runs
+    np.testing.assert_allclose(la, lb, rtol=1e-6, atol=1e-7)      # identical inputs
+    # (Adam on float-atomics noise: a parameter whose gradient is noise around zero may move by 2 lr either way)
+    perr = (pa - pb).abs()
+    assert (perr > 2e-3).float().mean().item() <= 2e-3 and perr.max().item() <= 0.25, ((perr > 2e-3).float().mean().item(), perr.max().item())
+    for name, a, b in (("exp_avg", ma, mb), ("exp_avg_sq", va, vb)):
+        sc = b.abs().max().item()
+        assert (a - b).abs().max().item() <= 5e-3 * sc, (name, (a - b).abs().max().item(), sc)
+
+
 def test_stats_update_gpu_matches_host_statement(gpu_device):
     """DensificationStats.update on the GPU (two kernels) equals the PyTorch statement of train.py:164-184 run on the CPU."""
     from fdgs import harness
