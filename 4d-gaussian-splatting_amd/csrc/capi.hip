@@ -28,6 +28,13 @@ static int fail(int code, const char* fmt, ...)
 	return code;
 }
 
+// for the other translation units (fdgs_common.h)
+int fdgs::set_error(int code, const char* msg)
+{
+	snprintf(g_err, sizeof g_err, "%s", msg);
+	return code;
+}
+
 #define HIP_TRY(expr, what)                                                                         \
 	do {                                                                                            \
 		hipError_t e__ = (expr);                                                                    \

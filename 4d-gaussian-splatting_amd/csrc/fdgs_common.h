@@ -141,7 +141,10 @@ namespace fdgs
 	hipError_t launch_colour_batch(int nviews, const fdgs_scene* const* views, const fdgs_forward_out* const* outs, char* const* geoms,
 	                               hipStream_t stream);
 
-	// Stable LSD radix sort of (key,value) u32 pairs on key bits [bit_lo, bit_hi) (radix_sort.hip; used by knn.hip).
+	// records msg as fdgs_last_error() of this thread (capi.hip) and returns code
+	int set_error(int code, const char* msg);
+
+	// Stable LSD radix sort of (key,value) u32 pairs on key bits [bit_lo, bit_hi) (radix_sort.hip; used by knn.hip and regularize.hip).
 	// keys[0]/vals[0] hold the input; *result receives the index (0/1) of the buffers holding the output.
 	hipError_t radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], int n, int bit_lo, int bit_hi,
 	                            uint32_t* hist, hipStream_t stream, int* result);

@@ -86,6 +86,50 @@ namespace fdgs
 			for (int i = 0; i < 4; i++) { L.c[j][i] = l[j][i]; Rr.c[j][i] = m[j][i]; }
 	}
 
+	// The 4D covariance Sigma = M^T M, M = S (M_r M_l) (reference forward.cu:279-352) and its backward (backward.cu:689-834):
+	// dSig (symmetric, the off-diagonal halves already split) -> d scale (x, y, z, t) and d rot / rot_r of the NORMALISED quaternions.
+	struct Cov4 { M4 Ml, Mr, R, M, Sigma; float scl[4]; };
+	__device__ __forceinline__ Cov4 cov4_build(const float3 sc, float sct, float mod, const float4 q, const float4 qr)
+	{
+		Cov4 c;
+		c.scl[0] = mod * sc.x; c.scl[1] = mod * sc.y; c.scl[2] = mod * sc.z; c.scl[3] = mod * sct;
+		const M4 S = diag4(c.scl[0], c.scl[1], c.scl[2], c.scl[3]);
+		build_Ml_Mr(q, qr, c.Ml, c.Mr);
+		c.R = mul(c.Mr, c.Ml);
+		c.M = mul(S, c.R);
+		c.Sigma = mul(transpose(c.M), c.M);
+		return c;
+	}
+	__device__ __forceinline__ void cov4_backward(const Cov4& c, const M4& dSig, float3& dscale, float& dscale_t, float4& drot, float4& drot_r)
+	{
+		M4 M2;
+#pragma unroll
+		for (int j = 0; j < 4; j++)
+#pragma unroll
+			for (int i = 0; i < 4; i++) M2.c[j][i] = 2.0f * c.M.c[j][i];
+		const M4 dM = mul(M2, dSig);
+		const M4 Rt = transpose(c.R);
+		M4 dMt = transpose(dM);
+		dscale.x = dot4(Rt.c[0], dMt.c[0]);
+		dscale.y = dot4(Rt.c[1], dMt.c[1]);
+		dscale.z = dot4(Rt.c[2], dMt.c[2]);
+		dscale_t = dot4(Rt.c[3], dMt.c[3]);
+#pragma unroll
+		for (int k = 0; k < 4; k++)
+#pragma unroll
+			for (int i = 0; i < 4; i++) dMt.c[k][i] *= c.scl[k];
+		const M4 A = mul(dMt, c.Mr);
+		drot.x = A.c[0][0] + A.c[1][1] + A.c[2][2] + A.c[3][3];
+		drot.y = -A.c[0][1] + A.c[1][0] - A.c[2][3] + A.c[3][2];
+		drot.z = A.c[0][2] - A.c[1][3] - A.c[2][0] + A.c[3][1];
+		drot.w = -A.c[0][3] - A.c[1][2] + A.c[2][1] + A.c[3][0];
+		const M4 B = mul(c.Ml, dMt);
+		drot_r.x = B.c[0][0] + B.c[1][1] + B.c[2][2] + B.c[3][3];
+		drot_r.y = -B.c[0][1] + B.c[1][0] + B.c[2][3] - B.c[3][2];
+		drot_r.z = B.c[0][2] + B.c[1][3] - B.c[2][0] - B.c[3][1];
+		drot_r.w = B.c[0][3] - B.c[1][2] + B.c[2][1] - B.c[3][0];
+	}
+
 	// quaternion (w,x,y,z) -> rotation, column-major (reference forward.cu:251-262)
 	__device__ __forceinline__ M3 quat_to_R(const float4 q)
 	{

@@ -158,7 +158,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
           thresh_opa_prune: float = 0.005, percent_dense: float = 0.01, cameras_extent: Optional[float] = None,
           densify_until_num_points: int = -1, on_densify: Optional[Callable] = None, log_every: int = 0,
           log: Callable[[str], None] = print, spatial_order: bool = True,
-          on_resort: Optional[Callable] = None) -> Dict[str, List[float]]:
+          on_resort: Optional[Callable] = None, lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0,
+          alpha_masks: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, List[float]]:
     """The reference's training loop (train.py:82-254) over ``cameras`` / ``gts`` (all views, identical on every rank;
     each rank renders its FrameShard slice).  Returns the logged history {"iteration", "loss", "psnr"}.
     Densification (train.py:229-244) runs when ``cameras_extent`` is given: every rank takes the same decisions from the
@@ -173,7 +174,9 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     after every densification, when the statistics have just been reset) -- a memory-layout choice with no effect on the
     arithmetic; every rank derives the same permutation from its (identical) parameters.  NOTE: the caller's ``model`` and the
     optimizer's moments are REORDERED IN PLACE (row j becomes the old row perm[j]); a caller that keeps per-Gaussian side data
-    indexed like the model passes ``spatial_order=False`` or applies ``on_resort(perm)`` to it (called with every permutation)."""
+    indexed like the model passes ``spatial_order=False`` or applies ``on_resort(perm)`` to it (called with every permutation).
+    ``lambda_rigid`` / ``lambda_motion`` / ``lambda_opa_mask``: the reference's other loss terms (train.py:119-159; StepPipeline);
+    ``alpha_masks``: every camera's ``gt_alpha_mask`` (indexed like ``cameras``), needed with ``lambda_opa_mask`` > 0."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -187,7 +190,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     if spatial_order:
         resort()
     shard = iter(FrameShard(len(cameras), batch_size, world_size, rank, seed))
-    steppipe = StepPipeline(model, optimizer, world_size=world_size, lambda_dssim=lambda_dssim)
+    steppipe = StepPipeline(model, optimizer, world_size=world_size, lambda_dssim=lambda_dssim, lambda_rigid=lambda_rigid,
+                            lambda_motion=lambda_motion, lambda_opa_mask=lambda_opa_mask)
     stats = DensificationStats(model.P, model.flat.device, world_size)
     if sh_degree_start is not None:
         model.active_sh_degree = min(int(sh_degree_start[0]), model.max_sh_degree)
@@ -199,7 +203,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
         if iteration % sh_increase_interval == 0:                                       # train.py:93-94
             model.oneupSHdegree()
         idx = next(shard)
-        results, losses = steppipe.step([cameras[i] for i in idx], [gts[i] for i in idx], pipe, bg)
+        masks = [alpha_masks[i] for i in idx] if lambda_opa_mask > 0 else None
+        results, losses = steppipe.step([cameras[i] for i in idx], [gts[i] for i in idx], pipe, bg, alpha_masks=masks)
         if iteration < densify_until_iter:                                              # train.py:229-244
             t_grad = model.params["_t"].grad if model.gaussian_dim == 4 else None      # already all-reduced (mean over the batch)
             if densify_until_num_points < 0 or model.P < densify_until_num_points:

@@ -133,3 +133,102 @@ def l1_ssim_value_and_grad(image: torch.Tensor, gt: torch.Tensor, lambda_dssim: 
     float32 GPU tensor (e.g. 1 / batch_size).  All kernels are enqueued on the current stream."""
     g, handle = l1_ssim_grad(image, gt, lambda_dssim, upstream)
     return l1_ssim_loss(handle), g
+
+
+# ---- the reference trainer's other loss terms (train.py:119-159) ----
+
+class _RigidMotion(torch.autograd.Function):
+    """(L_rigid, L_motion) from the raw parameters: k-NN of the means, velocities and both values in the forward
+    (fdgs_knn_query + fdgs_rigid_motion_forward), one fused backward weighted by both upstream scalars."""
+
+    @staticmethod
+    def forward(ctx, scaling, scaling_t, rotation, rotation_r, t, xyz, k):
+        from .knn import knn
+        dev = scaling.device
+        P = int(scaling.shape[0])
+        ins = [v.detach().contiguous().float() for v in (scaling, scaling_t, rotation, rotation_r, t)]
+        idx, d2 = knn(xyz.detach()[None], xyz.detach()[None], k)
+        velocity = torch.empty((P, 3), dtype=torch.float32, device=dev)
+        losses = torch.empty(2, dtype=torch.float32, device=dev)
+        scratch = torch.empty(_capi.lib.fdgs_rigid_motion_scratch_bytes(P, k), dtype=torch.uint8, device=dev)
+        with torch.cuda.device(dev):
+            rc = _capi.lib.fdgs_rigid_motion_forward(P, k, *[v.data_ptr() for v in ins], idx.data_ptr(), d2.data_ptr(), velocity.data_ptr(),
+                                                     losses.data_ptr(), scratch.data_ptr(), _capi.current_stream_handle(dev))
+        _capi._check(rc, "fdgs_rigid_motion_forward")
+        ctx.save_for_backward(*ins, idx, d2, velocity)
+        ctx.k, ctx.scratch = k, scratch
+        ctx.mark_non_differentiable(velocity)
+        return losses[0], losses[1], velocity
+
+    @staticmethod
+    def backward(ctx, g_rigid, g_motion, _g_velocity):
+        scaling, scaling_t, rotation, rotation_r, t, idx, d2, velocity = ctx.saved_tensors
+        dev, P = scaling.device, int(scaling.shape[0])
+        zero = torch.zeros((), dtype=torch.float32, device=dev)
+        g = torch.stack([zero if g_rigid is None else g_rigid.float().reshape(()),
+                         zero if g_motion is None else g_motion.float().reshape(())])
+        outs = [torch.zeros_like(v) for v in (scaling, scaling_t, rotation, rotation_r)]
+        with torch.cuda.device(dev):
+            rc = _capi.lib.fdgs_rigid_motion_backward(P, ctx.k, scaling.data_ptr(), scaling_t.data_ptr(), rotation.data_ptr(),
+                                                      rotation_r.data_ptr(), t.data_ptr(), idx.data_ptr(), d2.data_ptr(), velocity.data_ptr(),
+                                                      g.data_ptr(), 1.0, *[o.data_ptr() for o in outs], ctx.scratch.data_ptr(),
+                                                      _capi.current_stream_handle(dev))
+        _capi._check(rc, "fdgs_rigid_motion_backward")
+        return outs[0], outs[1], outs[2], outs[3], None, None, None
+
+
+def rigid_motion_loss(pc, k: int = 20):
+    """``(L_rigid, L_motion)`` of the reference trainer (train.py:130-159), both differentiable, on the GPU.
+
+    ``pc``: anything with the reference model's attribute names (``_xyz``, ``_scaling``, ``_scaling_t``, ``_rotation``,
+    ``_rotation_r``, ``_t``, ``rot_4d``, ``gaussian_dim``): ``GaussianParams``, ``ReferenceStyleModel`` or the reference's own
+    ``GaussianModel``.  The velocity is the 4D conditional mean shift over dt = (t + 0.1) - t; L_rigid uses the k nearest means
+    (``fdgs.knn.knn``, itself included at distance 0):  sum exp(-100 d2) |v_nbr - v_i| / k / P;  L_motion = mean |v|.
+    Gradients reach ``_scaling / _scaling_t / _rotation / _rotation_r``; the means, t and the neighbour search get none, as in the
+    reference.  Needs ``rot_4d`` and ``gaussian_dim == 4`` (the reference has no velocity otherwise)."""
+    if not getattr(pc, "rot_4d", False) or int(getattr(pc, "gaussian_dim", 3)) != 4:
+        raise ValueError("fdgs: rigid_motion_loss needs a rot_4d model with gaussian_dim == 4 (the velocity is the 4D conditional "
+                         "mean shift); got rot_4d=%s, gaussian_dim=%s" % (getattr(pc, "rot_4d", None), getattr(pc, "gaussian_dim", None)))
+    xyz = pc.get_xyz
+    if not xyz.is_cuda:
+        raise RuntimeError("fdgs: rigid_motion_loss needs GPU tensors; there is no CPU path")
+    if int(xyz.shape[0]) == 0:
+        raise ValueError("fdgs: rigid_motion_loss of a model without Gaussians")
+    l_rigid, l_motion, _ = _RigidMotion.apply(pc._scaling, pc._scaling_t, pc._rotation, pc._rotation_r, pc.get_t, xyz, int(k))
+    return l_rigid, l_motion
+
+
+class _OpaMask(torch.autograd.Function):
+    """Value and d L / d alpha in ONE pass in the forward (the gradient is linear in the upstream scalar: the backward scales it)."""
+
+    @staticmethod
+    def forward(ctx, alpha, mask):
+        if not alpha.is_cuda or not mask.is_cuda:
+            raise RuntimeError("fdgs: opa_mask_loss needs GPU tensors; there is no CPU path")
+        if alpha.numel() != mask.numel() or alpha.shape[-2:] != mask.shape[-2:]:
+            raise ValueError("fdgs: opa_mask_loss expects alpha and gt_alpha_mask of one [1, H, W] shape; got %s and %s"
+                             % (tuple(alpha.shape), tuple(mask.shape)))
+        a, m = alpha.detach().contiguous().float(), mask.detach().contiguous().float()
+        H, W, dev = int(alpha.shape[-2]), int(alpha.shape[-1]), alpha.device
+        parts = torch.empty(max(1, _capi.lib.fdgs_opa_mask_num_partials(H, W)), dtype=torch.float32, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        g = torch.empty_like(a) if alpha.requires_grad else None
+        with torch.cuda.device(dev):
+            rc = _capi.lib.fdgs_opa_mask_loss(H, W, a.data_ptr(), 0, m.data_ptr(), None, 1.0, None if g is None else g.data_ptr(), 0,
+                                              parts.data_ptr(), out.data_ptr(), _capi.current_stream_handle(dev))
+        _capi._check(rc, "fdgs_opa_mask_loss")
+        ctx.save_for_backward(g)
+        ctx.shape = alpha.shape
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        g, = ctx.saved_tensors
+        return (g * grad_out.float()).view(ctx.shape), None
+
+
+def opa_mask_loss(alpha: torch.Tensor, gt_alpha_mask: torch.Tensor) -> torch.Tensor:
+    """The reference trainer's opacity-mask loss (train.py:120-128), one kernel each way:
+    ``o = alpha.clamp(1e-6, 1 - 1e-6); mean(-(1 - gt_alpha_mask) * log(1 - o))``.  ``alpha``: ``render()``'s ``"alpha"`` [1, H, W];
+    its gradient flows back through the rasterizer's alpha path.  The mask is a constant."""
+    return _OpaMask.apply(alpha, gt_alpha_mask)

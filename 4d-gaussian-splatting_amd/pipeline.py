@@ -32,11 +32,21 @@ _LAST_STEPPER = {}    # id(model) -> weak reference to the pipeline whose step()
 class StepPipeline:
     def __init__(self, model, optimizer, world_size: int = 1, lambda_dssim: float = 0.2, overlap: bool = True,
                  fuse_sh_adam: bool = True, gather_max_views: int = 32, split_colour: bool = False, batch_views: bool = False,
-                 sh_group: int = 1, tile_cull: bool = True, lazy: bool = True, sparse_lists: bool = True, overlap_steps: bool = False):
+                 sh_group: int = 1, tile_cull: bool = True, lazy: bool = True, sparse_lists: bool = True, overlap_steps: bool = False,
+                 lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0, rigid_k: int = 20):
         """``fuse_sh_adam``: on one rank the SH coefficients are updated straight from the views'
         staged SH gradients (FlatAdam.step_sh_staged) and ``_features.grad`` is NOT materialised for the step; False keeps
         the flush into the gradient bucket followed by the plain Adam step (always the case on several ranks, where the
-        bucket is what the all-reduce sums)."""
+        bucket is what the all-reduce sums).
+        ``lambda_rigid`` / ``lambda_motion`` / ``lambda_opa_mask``: the reference trainer's other loss terms (train.py:119-159), added
+        to every view's loss with these weights (0: the term is not computed at all, the step is exactly the plain one); step() then
+        needs ``alpha_masks`` for the opacity mask, and the terms' values are in ``last_terms`` after each step."""
+        if int(world_size) > 1 and (lambda_rigid > 0 or lambda_motion > 0 or lambda_opa_mask > 0):
+            raise NotImplementedError("StepPipeline: the rigid / motion / opacity-mask terms run on one rank only")
+        self.lam_rigid, self.lam_motion, self.lam_opa = float(lambda_rigid), float(lambda_motion), float(lambda_opa_mask)
+        self.rigid_k = int(rigid_k)
+        self.regularize = self.lam_rigid > 0 or self.lam_motion > 0
+        self.last_terms = {}
         self.model, self.opt, self.world, self.lam = model, optimizer, int(world_size), float(lambda_dssim)
         self.fuse_sh_adam = bool(fuse_sh_adam)
         # several ranks, up to this many views per step over all ranks: the ranks exchange the views' SH stages (32 B per
@@ -144,11 +154,19 @@ class StepPipeline:
         """The step takes the SH backward of its views in groups (``sh_group``, see __init__): _step_batched."""
         return self.sh_group > 1 and B > 1
 
-    def step(self, cams: Sequence, gts: Sequence[torch.Tensor], pipe, bg: torch.Tensor, scaling_modifier: float = 1.0):
+    def step(self, cams: Sequence, gts: Sequence[torch.Tensor], pipe, bg: torch.Tensor, scaling_modifier: float = 1.0,
+             alpha_masks: Sequence[torch.Tensor] = None):
         """Runs forward + loss + backward of every view, the gradient all-reduce and the optimizer step.
         Returns (list of per-view results dict(render, radii, depth, alpha_T, flow, viewspace_grad, num_rendered), list
-        of losses); the tensors may be used on the caller's stream until the next call of step()."""
+        of losses); the tensors may be used on the caller's stream until the next call of step().  ``losses`` are the views'
+        L1 + SSIM values; the other terms (lambda_* > 0) are in ``last_terms``: "rigid", "motion" (device scalars) and "opa_mask"
+        (device [B]), unweighted.  ``alpha_masks``: each view's ``gt_alpha_mask`` [1, H, W] (needed with lambda_opa_mask > 0)."""
         m, ctx = self.model, (pipe, bg, scaling_modifier)
+        if self.lam_opa > 0 and (alpha_masks is None or len(alpha_masks) != len(cams)):
+            raise ValueError("StepPipeline: lambda_opa_mask > 0 needs one alpha mask per view (step(..., alpha_masks=))")
+        if self.regularize and not (m.rot_4d and m.gaussian_dim == 4):
+            raise ValueError("StepPipeline: lambda_rigid / lambda_motion need a rot_4d model with gaussian_dim == 4")
+        self._masks = alpha_masks if self.lam_opa > 0 else None
         if m.flat_grad is not self._sink_of:
             self.sink, self._sink_of = m.grad_sink(), m.flat_grad
         if self._batched(len(cams)):
@@ -190,6 +208,61 @@ class StepPipeline:
             st.gathered = self._buffer("gathered", (B, self.world, m.P, 8))
         return st
 
+    def _terms_begin(self, st):
+        """Head of a step with the rigid / motion terms: the k-NN of the means (constant within the step) and the terms' forward on
+        stream F, ahead of the first forward -- stream B waits for F after every forward, so the backward below finds them done."""
+        if not self.regularize:
+            return
+        m = self.model
+        P, k = m.P, self.rigid_k
+        with torch.cuda.stream(self.sF):
+            from .knn import knn
+            st.reg_idx, st.reg_d2 = knn(m._xyz.detach()[None], m._xyz.detach()[None], k)
+            st.reg_vel = torch.empty((P, 3), dtype=torch.float32, device=self.dev)
+            st.reg_losses = torch.empty(2, dtype=torch.float32, device=self.dev)
+            st.reg_scratch = torch.empty(_capi.lib.fdgs_rigid_motion_scratch_bytes(P, k), dtype=torch.uint8, device=self.dev)
+            st.reg_w = torch.tensor([self.lam_rigid, self.lam_motion], dtype=torch.float32, device=self.dev)
+            rc = _capi.lib.fdgs_rigid_motion_forward(P, k, m._scaling.data_ptr(), m._scaling_t.data_ptr(), m._rotation.data_ptr(),
+                                                     m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(),
+                                                     st.reg_vel.data_ptr(), st.reg_losses.data_ptr(), st.reg_scratch.data_ptr(),
+                                                     _capi.current_stream_handle(self.dev))
+        _capi._check(rc, "fdgs_rigid_motion_forward")
+        self.last_terms["rigid"], self.last_terms["motion"] = st.reg_losses[0], st.reg_losses[1]
+
+    def _terms_backward(self, st):
+        """Adds lambda_rigid dL_rigid + lambda_motion dL_motion into the bucket, on stream B right after view 0's backward (which
+        WRITES the bucket) and before anything reads the geometry gradient (the last view's fused geometry Adam, the tail).  Once per
+        step: the reference adds the terms to each of the B views' losses and divides by B (train.py:159-162)."""
+        if not self.regularize or st.reg_done:
+            return
+        m, g = self.model, self.sink
+        with torch.cuda.stream(self.sB):
+            rc = _capi.lib.fdgs_rigid_motion_backward(m.P, self.rigid_k, m._scaling.data_ptr(), m._scaling_t.data_ptr(), m._rotation.data_ptr(),
+                                                      m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(),
+                                                      st.reg_vel.data_ptr(), st.reg_w.data_ptr(), 1.0, g["dL_dscales"].data_ptr(),
+                                                      g["dL_dscales_t"].data_ptr(), g["dL_drotations"].data_ptr(), g["dL_drotations_r"].data_ptr(),
+                                                      st.reg_scratch.data_ptr(), _capi.current_stream_handle(self.dev))
+        _capi._check(rc, "fdgs_rigid_motion_backward")
+        st.reg_done = True
+
+    def _opa_grad(self, st, b, T):
+        """The opacity-mask term of view b (stream B is current): its value into last_terms["opa_mask"][b] and
+        d (lambda_opa_mask L_opa / B) / d alpha, the upstream alpha gradient of the view's backward (None without the term)."""
+        if self._masks is None:
+            return None
+        H, W = int(T.shape[-2]), int(T.shape[-1])
+        if b == 0:
+            st.opa_vals = torch.empty(st.B, dtype=torch.float32, device=self.dev)
+            st.opa_parts = torch.empty(max(1, _capi.lib.fdgs_opa_mask_num_partials(H, W)), dtype=torch.float32, device=self.dev)
+            self.last_terms["opa_mask"] = st.opa_vals
+        mask = self._masks[b].to(self.dev, torch.float32).contiguous()
+        g_alpha = torch.empty((1, H, W), dtype=torch.float32, device=self.dev)
+        rc = _capi.lib.fdgs_opa_mask_loss(H, W, T.data_ptr(), 1, mask.data_ptr(), st.up.data_ptr(), self.lam_opa, g_alpha.data_ptr(), 0,
+                                          st.opa_parts.data_ptr(), st.opa_vals[b:].data_ptr(), _capi.current_stream_handle(self.dev))
+        _capi._check(rc, "fdgs_opa_mask_loss")
+        st.keep_masks.append((mask, g_alpha))
+        return g_alpha
+
     def _colour_pass(self, cams, ctx):
         """batch_views: the SH colours of all views in one pass over the coefficients (stream F), ahead of the first view's binning."""
         with torch.cuda.stream(self.sF):
@@ -212,6 +285,7 @@ class StepPipeline:
         st = self._begin(len(cams))
         B, m = st.B, self.model
         gacc = self._buffer("gacc", (m.P, 16), torch.zeros)
+        self._terms_begin(st)
         handles = self._colour_pass(cams, ctx) if self.batch_views and B > 1 else [None] * B
         # the fused SH update behind the last view's SH backward: next to stream B's geometry backward on the idle F stream -- with
         # overlap_steps on stream A, which the next step's first view puts its colour launch on
@@ -248,7 +322,9 @@ class StepPipeline:
                             R_last = r_val
                 after_sh = partial(self._stages_final, st, [b], s_up) if st.final == "gather" or (last and st.final) else None
                 geo_adam = None
-                if last and st.final == "sh_update" and m.rot_4d and m.gaussian_dim == 4:
+                # (B = 1 with the rigid / motion terms: their gradient comes after the only view's backward, so the geometry Adam is the
+                # tail's for that step)
+                if last and st.final == "sh_update" and m.rot_4d and m.gaussian_dim == 4 and not (self.regularize and B == 1):
                     # the Adam step of the 17 geometry parameters per Gaussian INSIDE the last view's geometry backward (fdgs_backward_out.adam:
                     # the kernel has just completed their gradient) instead of by a launch of its own in the tail; bit-identical
                     def geo_adam():
@@ -258,9 +334,12 @@ class StepPipeline:
                             return None
                         st.geo_adam_done = True
                         return self.opt.geometry_adam()
-                grads = raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, None, None,
+                g_alpha = self._opa_grad(st, b, T)
+                grads = raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, g_alpha, None,
                                      self.sink, b > 0, grad_accum=gacc, after_sh=after_sh,
                                      sh_stage=st.stage[b] if st.defer_sh else None, per_view_outputs=False, geometry_adam=geo_adam)
+                if b == 0:
+                    self._terms_backward(st)
                 loss = None if self.finish_on_F else l1_ssim_loss(loss_handle)
                 pend_loss.append(loss_handle)
             # buffers allocated on F are read on B: keep them alive until F has waited for B (end of the step)
@@ -286,6 +365,7 @@ class StepPipeline:
         B, m = st.B, self.model
         G = min(self.sh_group, B)
         gacc = self._buffer("gacc_b", (B, m.P, 16), torch.zeros)
+        self._terms_begin(st)
         handles = self._colour_pass(cams, ctx) if self.batch_views else [None] * B
         results, losses, keep, pend = [], [], [], []
         for b in range(B):
@@ -295,7 +375,8 @@ class StepPipeline:
             results.append({"render": color, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow, "num_rendered": R})
             with torch.cuda.stream(self.sB):
                 g_color, loss_handle = l1_ssim_grad(color, gts[b], self.lam, st.up)
-                pend.append(raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, None, None,
+                g_alpha = self._opa_grad(st, b, T)
+                pend.append(raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, g_alpha, None,
                                          self.sink, b > 0, grad_accum=gacc[b], sh_stage=st.stage[b], begin_only=True, per_view_outputs=False))
                 losses.append(l1_ssim_loss(loss_handle))
                 if (b + 1) % G == 0 or b == B - 1:
@@ -306,6 +387,7 @@ class StepPipeline:
                     for v in range(first, b + 1):
                         keep.append(_dgr._C.backward_finish(pend[v]))
                         results[v]["viewspace_grad"] = keep[-1][0]
+                    self._terms_backward(st)   # (view 0's geometry backward has written the bucket by now)
             keep.append((geom, binb, img, out_means3D, g_color, T))
         self._optimizer_tail(st)
         self._join(st)
@@ -404,3 +486,5 @@ class _Step:
         self.geo_adam_done = False  # the geometry parameters' Adam step was taken inside the last view's backward
         self.sh_handle = None       # several ranks, dense: the all-reduce of the SH part of the bucket
         self.gathers = []           # gather: the work handles of the views' stage exchanges
+        self.reg_done = False       # the rigid / motion gradient has been added to the bucket this step
+        self.keep_masks = []        # the views' alpha masks and alpha gradients, alive until the step's end

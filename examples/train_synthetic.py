@@ -21,6 +21,7 @@ def main():
     ap.add_argument("--iterations", type=int, default=300)
     ap.add_argument("--views", type=int, default=64)
     ap.add_argument("--batch-size", type=int, default=4)
+    ap.add_argument("--lambda-rigid", type=float, default=0.0, help="the rigid term's weight (configs/dnerf/lego.yaml: 1.0; rot_4d scenes)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -46,7 +47,7 @@ def main():
     opt = train_host.make_optimizer(student)
     torch.cuda.synchronize(); t0 = time.time()
     harness.train(student, opt, cams, gts, pipe, bg, iterations=args.iterations, batch_size=args.batch_size,
-                  world_size=world, rank=rank, log_every=max(1, args.iterations // 10))
+                  world_size=world, rank=rank, log_every=max(1, args.iterations // 10), lambda_rigid=args.lambda_rigid)
     torch.cuda.synchronize()
     if rank == 0:
         dt = time.time() - t0

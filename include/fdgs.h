@@ -519,6 +519,44 @@ int fdgs_densify_split(int32_t n_children, int32_t N, int32_t rot_4d, int32_t ga
 size_t fdgs_knn_scratch_bytes(int32_t P);
 int fdgs_dist2_knn3(int32_t P, const float* points, float* mean_dist2, void* scratch, void* stream);
 
+/* ---- k nearest neighbours: pointops2's knnquery (utils/general_utils.py:170-184) ----------------------------------------
+ * For every batch bb < b and query i < n: the k sources of that batch nearest to x[bb][i] ([b,n,3] and [b,m,3] float, device),
+ * exact, each row sorted by (d2, source index) ascending, d2 = (dx*dx + dy*dy) + dz*dz in fp32.  idx [b,n,k] (batch-local source
+ * indices), dist2 [b,n,k] (SQUARED distances).  Slots no source fills (m < k) hold dist2 = 1e10, idx = 0, as the reference's
+ * initial heap; a source at d2 >= 1e10 is never taken.  1 <= k <= FDGS_KNN_MAX_K; m <= 2^24 per batch.
+ * scratch: fdgs_knn_query_scratch_bytes(n, m) bytes of device memory (reused from batch to batch). */
+#define FDGS_KNN_MAX_K 64
+size_t fdgs_knn_query_scratch_bytes(int32_t n, int32_t m);
+int fdgs_knn_query(int32_t b, int32_t n, int32_t m, int32_t k, const float* x, const float* src, int64_t* idx, float* dist2,
+                   void* scratch, void* stream);
+
+/* ---- the reference trainer's regularisers (train.py:119-159) on a rot_4d model with gaussian_dim == 4 -------------------
+ * Inputs: the RAW parameters scaling [P,3], scaling_t [P,1], rotation [P,4], rotation_r [P,4] (quaternions of any norm), t [P,1],
+ * and the k-NN of the means (fdgs_knn_query with x = src: knn_idx int64 [P,k], knn_d2 [P,k]).
+ * velocity v_i = Sigma[0:3,3] / Sigma[3,3] * dt_i, dt_i = (t_i + 0.1f) - t_i (gaussian_model.py:34-47, 247-251), written to
+ * velocity [P,3];  losses[0] = L_rigid = sum_ij exp(-100 d2_ij) |v_nbr(i,j) - v_i| / k / P,  losses[1] = L_motion = mean_i |v_i|
+ * (device memory, 2 floats; deterministic: fixed-order sums of per-workgroup partials).
+ * scratch: fdgs_rigid_motion_scratch_bytes(P, k) bytes (forward and backward; P * k < 2^31). */
+size_t fdgs_rigid_motion_scratch_bytes(int32_t P, int32_t k);
+int fdgs_rigid_motion_forward(int32_t P, int32_t k, const float* scaling, const float* scaling_t, const float* rotation,
+                              const float* rotation_r, const float* t, const int64_t* knn_idx, const float* knn_d2, float* velocity,
+                              float* losses, void* scratch, void* stream);
+/* ADDS  scale * (g_losses[0] * dL_rigid/d. + g_losses[1] * dL_motion/d.)  into d_scaling, d_scaling_t, d_rotation, d_rotation_r
+ * (g_losses: 2 floats of device memory).  The neighbour side of the rigid term is gathered through a reverse-neighbour list
+ * (a stable sort of the (neighbour, pair) table), so the result is bitwise reproducible.  |0|'s gradient is 0 (torch.norm). */
+int fdgs_rigid_motion_backward(int32_t P, int32_t k, const float* scaling, const float* scaling_t, const float* rotation,
+                               const float* rotation_r, const float* t, const int64_t* knn_idx, const float* knn_d2,
+                               const float* velocity, const float* g_losses, float scale, float* d_scaling, float* d_scaling_t,
+                               float* d_rotation, float* d_rotation_r, void* scratch, void* stream);
+
+/* ---- the opacity-mask loss (train.py:120-128): o = clamp(alpha, 1e-6, 1 - 1e-6), L = mean(-(1 - mask) log(1 - o)) -------
+ * alpha [H,W] (or T with alpha_is_T != 0: alpha = 1 - T), mask [H,W].  partials: fdgs_opa_mask_num_partials(H, W) floats;
+ * loss: 1 float; both device memory.  With grad != NULL also d L / d alpha = (1 - mask) / (1 - o) / (H W) where the clamp passes
+ * it (lo <= alpha <= hi), else 0, times scale (and times *g_upstream if that is not NULL), written (accumulate = 0) or added. */
+int fdgs_opa_mask_num_partials(int32_t H, int32_t W);
+int fdgs_opa_mask_loss(int32_t H, int32_t W, const float* alpha, int32_t alpha_is_T, const float* mask, const float* g_upstream,
+                       float scale, float* grad, int32_t accumulate, float* partials, float* loss, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
