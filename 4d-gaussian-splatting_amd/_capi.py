@@ -94,7 +94,8 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_profile_reset", "fdgs_stage_name", "fdgs_l1_ssim_forward", "fdgs_l1_ssim_backward", "fdgs_l1_ssim_loss", "fdgs_l1_ssim_loss_batch",
             "fdgs_l1_ssim_num_partials", "fdgs_l1_ssim_value_and_grad", "fdgs_adam_step", "fdgs_adam_step_sh", "fdgs_densify_classify", "fdgs_densify_gather", "fdgs_densify_split", "fdgs_densify_stats_local", "fdgs_densify_stats_apply", "fdgs_knn_scratch_bytes", "fdgs_dist2_knn3",
             "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
-            "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_last_error", "fdgs_version")
+            "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
+            "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 11
 
 
@@ -208,6 +209,12 @@ def _load():
     lib.fdgs_opa_mask_loss.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
                                        C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fdgs_opa_mask_loss.restype = C.c_int
+    lib.fdgs_env_composite.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_int32, C.c_int32,
+                                                                                            C.c_float] + [C.c_void_p] * 4
+    lib.fdgs_env_composite.restype = C.c_int
+    lib.fdgs_env_composite_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [
+        C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+    lib.fdgs_env_composite_backward.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -12,8 +12,9 @@ inputs, so there is no accumulation pass and no zero_grad.  A sink is OVERWRITTE
 ``accumulate=False`` (the first view of an optimizer step) and ADDED to with ``accumulate=True`` (the following
 views of the same step: the reference sums ``loss / batch_size`` over ``batch_size`` views, train.py:104-166).
 
-Covers the default pipeline (in-kernel covariance and SH, rot_4d or not, no env map); everything else goes
-through ``render()``.  Same result dict as ``render()``.
+Covers the default pipeline (in-kernel covariance and SH, rot_4d or not) and the environment map (``pipe.env_map_res``:
+rasterized over black, then ``fdgs.envmap.env_composite``); the Python covariance / SH branches go through ``render()``.  Same
+result dict as ``render()``.
 """
 import math
 
@@ -68,10 +69,25 @@ def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_r
                                            after_sh=after_sh, sh_stage=sh_stage, per_view_outputs=per_view_outputs, geometry_adam=geometry_adam)
 
 
+_BLACK = {}
+
+
+def _black(device):
+    """A zero background per device, made once (and waited for once: it is read on whichever stream renders)."""
+    z = _BLACK.get(device)
+    if z is None:
+        z = _BLACK[device] = torch.zeros(3, dtype=torch.float32, device=device)
+        torch.cuda.current_stream(device).synchronize()
+    return z
+
+
 def raw_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
-    """GaussianRasterizationSettings + the raw parameter tensors of ``pc`` for the default pipeline."""
-    if pipe.compute_cov3D_python or pipe.convert_SHs_python or pipe.env_map_res:
-        raise ValueError("render_raw covers the default pipeline only; use render() for the Python covariance / SH / env-map branches")
+    """GaussianRasterizationSettings + the raw parameter tensors of ``pc`` for the default pipeline (with ``pipe.env_map_res`` the
+    background is black whatever ``bg_color`` says: the environment map is composited behind the Gaussians afterwards)."""
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise ValueError("render_raw covers the default pipeline only; use render() for the Python covariance / SH branches")
+    if getattr(pipe, "env_map_res", 0):
+        bg_color = _black(pc._xyz.device)   # the environment is composited behind a black background (gaussian_renderer/__init__.py:41)
     rs = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
         tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
@@ -137,5 +153,10 @@ def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modif
     color, radii, depth, alpha, flow = _RasterizeRaw.apply(
         xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
         prefilter_var, rs, grad_sink, accumulate, tile_cull)
+    if getattr(pipe, "env_map_res", 0):
+        from .envmap import env_composite
+        if getattr(pc, "env_map", None) is None:
+            raise ValueError("render_raw: pipe.env_map_res > 0 needs the model's env_map [3, R, R]")
+        color = env_composite(color, alpha, pc.env_map, viewpoint_camera)
     return {"render": color, "viewspace_points": screenspace_points, "visibility_filter": radii > 0, "radii": radii,
             "depth": depth, "alpha": alpha, "flow": flow}

@@ -159,7 +159,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
           densify_until_num_points: int = -1, on_densify: Optional[Callable] = None, log_every: int = 0,
           log: Callable[[str], None] = print, spatial_order: bool = True,
           on_resort: Optional[Callable] = None, lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0,
-          alpha_masks: Optional[Sequence[torch.Tensor]] = None) -> Dict[str, List[float]]:
+          alpha_masks: Optional[Sequence[torch.Tensor]] = None, env_lr: float = 2.5e-3,
+          env_optimize_until: int = 10 ** 9) -> Dict[str, List[float]]:
     """The reference's training loop (train.py:82-254) over ``cameras`` / ``gts`` (all views, identical on every rank;
     each rank renders its FrameShard slice).  Returns the logged history {"iteration", "loss", "psnr"}.
     Densification (train.py:229-244) runs when ``cameras_extent`` is given: every rank takes the same decisions from the
@@ -176,7 +177,10 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     optimizer's moments are REORDERED IN PLACE (row j becomes the old row perm[j]); a caller that keeps per-Gaussian side data
     indexed like the model passes ``spatial_order=False`` or applies ``on_resort(perm)`` to it (called with every permutation).
     ``lambda_rigid`` / ``lambda_motion`` / ``lambda_opa_mask``: the reference's other loss terms (train.py:119-159; StepPipeline);
-    ``alpha_masks``: every camera's ``gt_alpha_mask`` (indexed like ``cameras``), needed with ``lambda_opa_mask`` > 0."""
+    ``alpha_masks``: every camera's ``gt_alpha_mask`` (indexed like ``cameras``), needed with ``lambda_opa_mask`` > 0.
+    ``pipe.env_map_res`` = R > 0: the environment map behind the Gaussians (train.py:71-77): ``model.env_map`` = zeros [3, R, R] unless
+    the model has one, trained by its own Adam (``fdgs.envmap.EnvMapAdam``, learning rate ``env_lr`` = the reference's feature_lr,
+    eps 1e-15) while ``iteration < env_optimize_until`` (train.py:250-252)."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -190,8 +194,15 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     if spatial_order:
         resort()
     shard = iter(FrameShard(len(cameras), batch_size, world_size, rank, seed))
+    env_opt = None
+    if getattr(pipe, "env_map_res", 0):
+        from .envmap import EnvMapAdam
+        if getattr(model, "env_map", None) is None:
+            R = int(pipe.env_map_res)
+            model.env_map = torch.zeros((3, R, R), dtype=torch.float32, device=model.flat.device).requires_grad_(True)
+        env_opt = EnvMapAdam(model.env_map, lr=env_lr, eps=1e-15)
     steppipe = StepPipeline(model, optimizer, world_size=world_size, lambda_dssim=lambda_dssim, lambda_rigid=lambda_rigid,
-                            lambda_motion=lambda_motion, lambda_opa_mask=lambda_opa_mask)
+                            lambda_motion=lambda_motion, lambda_opa_mask=lambda_opa_mask, env_optimizer=env_opt)
     stats = DensificationStats(model.P, model.flat.device, world_size)
     if sh_degree_start is not None:
         model.active_sh_degree = min(int(sh_degree_start[0]), model.max_sh_degree)
@@ -204,7 +215,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
             model.oneupSHdegree()
         idx = next(shard)
         masks = [alpha_masks[i] for i in idx] if lambda_opa_mask > 0 else None
-        results, losses = steppipe.step([cameras[i] for i in idx], [gts[i] for i in idx], pipe, bg, alpha_masks=masks)
+        results, losses = steppipe.step([cameras[i] for i in idx], [gts[i] for i in idx], pipe, bg, alpha_masks=masks,
+                                        optimize_env=iteration < env_optimize_until)
         if iteration < densify_until_iter:                                              # train.py:229-244
             t_grad = model.params["_t"].grad if model.gaussian_dim == 4 else None      # already all-reduced (mean over the batch)
             if densify_until_num_points < 0 or model.P < densify_until_num_points:

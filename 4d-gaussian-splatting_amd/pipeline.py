@@ -33,20 +33,31 @@ class StepPipeline:
     def __init__(self, model, optimizer, world_size: int = 1, lambda_dssim: float = 0.2, overlap: bool = True,
                  fuse_sh_adam: bool = True, gather_max_views: int = 32, split_colour: bool = False, batch_views: bool = False,
                  sh_group: int = 1, tile_cull: bool = True, lazy: bool = True, sparse_lists: bool = True, overlap_steps: bool = False,
-                 lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0, rigid_k: int = 20):
+                 lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0, rigid_k: int = 20,
+                 env_optimizer=None):
         """``fuse_sh_adam``: on one rank the SH coefficients are updated straight from the views'
         staged SH gradients (FlatAdam.step_sh_staged) and ``_features.grad`` is NOT materialised for the step; False keeps
         the flush into the gradient bucket followed by the plain Adam step (always the case on several ranks, where the
         bucket is what the all-reduce sums).
         ``lambda_rigid`` / ``lambda_motion`` / ``lambda_opa_mask``: the reference trainer's other loss terms (train.py:119-159), added
         to every view's loss with these weights (0: the term is not computed at all, the step is exactly the plain one); step() then
-        needs ``alpha_masks`` for the opacity mask, and the terms' values are in ``last_terms`` after each step."""
+        needs ``alpha_masks`` for the opacity mask, and the terms' values are in ``last_terms`` after each step.
+        ``env_optimizer``: the ``fdgs.envmap.EnvMapAdam`` of ``model.env_map``, used by the steps whose ``pipe.env_map_res`` > 0 (None: one
+        with the reference's defaults is made at the first such step).  Such a step rasterizes over black, composites the map behind
+        every view on stream F right behind the view's forward (``results[b]["render"]`` is the composited image), takes the
+        composite's backward on stream B between the loss gradient and the rasterizer backward (the alpha gradient; the map's gradient
+        is written by view 0 and added by the others) and steps the map's Adam in the tail (``step(..., optimize_env=)``)."""
         if int(world_size) > 1 and (lambda_rigid > 0 or lambda_motion > 0 or lambda_opa_mask > 0):
             raise NotImplementedError("StepPipeline: the rigid / motion / opacity-mask terms run on one rank only")
         self.lam_rigid, self.lam_motion, self.lam_opa = float(lambda_rigid), float(lambda_motion), float(lambda_opa_mask)
         self.rigid_k = int(rigid_k)
         self.regularize = self.lam_rigid > 0 or self.lam_motion > 0
         self.last_terms = {}
+        self.env_opt = env_optimizer
+        self._env = None        # this step's environment map (None: pipe.env_map_res == 0) and whether its Adam runs
+        self._optimize_env = False
+        # overlap_steps: recorded on stream B behind the map's Adam; the next step's first composite (stream F) waits for it
+        self._env_ev = None
         self.model, self.opt, self.world, self.lam = model, optimizer, int(world_size), float(lambda_dssim)
         self.fuse_sh_adam = bool(fuse_sh_adam)
         # several ranks, up to this many views per step over all ranks: the ranks exchange the views' SH stages (32 B per
@@ -155,18 +166,21 @@ class StepPipeline:
         return self.sh_group > 1 and B > 1
 
     def step(self, cams: Sequence, gts: Sequence[torch.Tensor], pipe, bg: torch.Tensor, scaling_modifier: float = 1.0,
-             alpha_masks: Sequence[torch.Tensor] = None):
+             alpha_masks: Sequence[torch.Tensor] = None, optimize_env: bool = True):
         """Runs forward + loss + backward of every view, the gradient all-reduce and the optimizer step.
         Returns (list of per-view results dict(render, radii, depth, alpha_T, flow, viewspace_grad, num_rendered), list
         of losses); the tensors may be used on the caller's stream until the next call of step().  ``losses`` are the views'
         L1 + SSIM values; the other terms (lambda_* > 0) are in ``last_terms``: "rigid", "motion" (device scalars) and "opa_mask"
-        (device [B]), unweighted.  ``alpha_masks``: each view's ``gt_alpha_mask`` [1, H, W] (needed with lambda_opa_mask > 0)."""
+        (device [B]), unweighted.  ``alpha_masks``: each view's ``gt_alpha_mask`` [1, H, W] (needed with lambda_opa_mask > 0).
+        ``optimize_env`` (``pipe.env_map_res`` > 0): whether the environment map's Adam runs this step (train.py:250: iteration <
+        env_optimize_until); without it the map's gradient is not computed, the Gaussians still see the map through alpha."""
         m, ctx = self.model, (pipe, bg, scaling_modifier)
         if self.lam_opa > 0 and (alpha_masks is None or len(alpha_masks) != len(cams)):
             raise ValueError("StepPipeline: lambda_opa_mask > 0 needs one alpha mask per view (step(..., alpha_masks=))")
         if self.regularize and not (m.rot_4d and m.gaussian_dim == 4):
             raise ValueError("StepPipeline: lambda_rigid / lambda_motion need a rot_4d model with gaussian_dim == 4")
         self._masks = alpha_masks if self.lam_opa > 0 else None
+        self._env_begin(pipe, optimize_env)
         if m.flat_grad is not self._sink_of:
             self.sink, self._sink_of = m.grad_sink(), m.flat_grad
         if self._batched(len(cams)):
@@ -177,6 +191,44 @@ class StepPipeline:
                 return out
             self.lazy_redone += 1
         return self._step_views(cams, gts, ctx, False)
+
+    def _env_begin(self, pipe, optimize_env):
+        """The environment map of this step (pipe.env_map_res > 0), and its optimizer."""
+        self._env = None
+        if not getattr(pipe, "env_map_res", 0):
+            return
+        if self.world > 1:
+            raise NotImplementedError("StepPipeline: the environment map runs on one rank only")
+        from .envmap import EnvMapAdam, _check_env
+        env = getattr(self.model, "env_map", None)
+        _check_env(env)
+        if self.env_opt is None:
+            self.env_opt = EnvMapAdam(env)
+        elif self.env_opt.env_map is not env:
+            raise ValueError("StepPipeline: env_optimizer steps another tensor than model.env_map")
+        self._env, self._optimize_env = env.detach(), bool(optimize_env)
+
+    def _env_composite(self, cam, color, T):
+        """Stream F is current, right behind the view's forward: the map behind the view's colours, in place.  The first composite
+        after a step whose map Adam ran waits for it (overlap_steps: stream F need not have waited for stream B)."""
+        from .envmap import composite_
+        if self._env_ev is not None:
+            self.sF.wait_event(self._env_ev)
+            self._env_ev = None
+        composite_(color, T, self._env, cam)
+
+    def _env_backward(self, st, b, cam, T, g_color, g_alpha):
+        """Stream B is current, between the view's loss gradient and its rasterizer backward: d / d alpha (written, or added to the
+        opacity-mask term's) and, with optimize_env, the map's gradient (view 0 writes, the others add).  Returns the alpha gradient."""
+        if self._env is None:
+            return g_alpha
+        from .envmap import composite_backward
+        acc = g_alpha is not None
+        if not acc:
+            g_alpha = torch.empty((1, int(T.shape[-2]), int(T.shape[-1])), dtype=torch.float32, device=self.dev)
+            st.keep_masks.append(g_alpha)
+        composite_backward(T, g_color, self._env, cam, g_alpha, acc, self.env_opt.grad if self._optimize_env else None, b > 0)
+        return g_alpha
 
     def _begin(self, B):
         """Head of every step: the streams wait for the caller's (overlap_steps: see __init__), the step's state and buffers."""
@@ -270,10 +322,13 @@ class StepPipeline:
             return raw_preprocess_batch([s[0] for s in sets], *sets[0][1], tile_cull=self.tile_cull)
 
     def _forward(self, cam, ctx, **kw):
-        """One view's forward on stream F (raw_forward options ``kw``), which stream B then waits for: (settings, tensors, outputs)."""
+        """One view's forward on stream F (raw_forward options ``kw``; with the environment map its composite behind), which stream B
+        then waits for: (settings, tensors, outputs)."""
         with torch.cuda.stream(self.sF):
             rs, tens = raw_settings(cam, self.model, *ctx)
             out = raw_forward(rs, *tens, tile_cull=self.tile_cull, **kw)
+            if self._env is not None:
+                self._env_composite(cam, out[1], out[4])
             ev = torch.cuda.Event()
             ev.record(self.sF)
         self.sB.wait_event(ev)
@@ -334,7 +389,7 @@ class StepPipeline:
                             return None
                         st.geo_adam_done = True
                         return self.opt.geometry_adam()
-                g_alpha = self._opa_grad(st, b, T)
+                g_alpha = self._env_backward(st, b, cams[b], T, g_color, self._opa_grad(st, b, T))
                 grads = raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, g_alpha, None,
                                      self.sink, b > 0, grad_accum=gacc, after_sh=after_sh,
                                      sh_stage=st.stage[b] if st.defer_sh else None, per_view_outputs=False, geometry_adam=geo_adam)
@@ -375,7 +430,7 @@ class StepPipeline:
             results.append({"render": color, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow, "num_rendered": R})
             with torch.cuda.stream(self.sB):
                 g_color, loss_handle = l1_ssim_grad(color, gts[b], self.lam, st.up)
-                g_alpha = self._opa_grad(st, b, T)
+                g_alpha = self._env_backward(st, b, cams[b], T, g_color, self._opa_grad(st, b, T))
                 pend.append(raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, g_alpha, None,
                                          self.sink, b > 0, grad_accum=gacc[b], sh_stage=st.stage[b], begin_only=True, per_view_outputs=False))
                 losses.append(l1_ssim_loss(loss_handle))
@@ -424,6 +479,10 @@ class StepPipeline:
         m = self.model
         feat = m.offsets["_features"][0]
         with torch.cuda.stream(self.sB):
+            if self._env is not None and self._optimize_env:   # (the map's gradient is complete: every view's composite backward is behind)
+                self.env_opt.step()
+                self._env_ev = torch.cuda.Event()
+                self._env_ev.record(self.sB)
             # the losses were scaled by 1 / (B * world): SUM = mean; Adam on chunk k overlaps the all-reduce of chunk k+1
             if not (st.fuse or st.gather):
                 allreduce_and_step(m, self.opt, self.world, chunks=4, average=False, sh_handle=st.sh_handle, wait_pairs=self.exchange_pairs)

@@ -6,7 +6,7 @@ a perturbed copy is trained back.  One process per GPU:
 
 Uses fdgs.harness.train (FrameShard + StepPipeline + one gradient all-reduce per step over RCCL).
 """
-import argparse, os, sys, time
+import argparse, math, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 if int(os.environ.get("WORLD_SIZE", "1")) > 1:
     # the step's own streams fill the runtime's default of 4 hardware queues; RCCL adds its own (DESIGN.md section 5a)
@@ -22,6 +22,8 @@ def main():
     ap.add_argument("--views", type=int, default=64)
     ap.add_argument("--batch-size", type=int, default=4)
     ap.add_argument("--lambda-rigid", type=float, default=0.0, help="the rigid term's weight (configs/dnerf/lego.yaml: 1.0; rot_4d scenes)")
+    ap.add_argument("--env-map-res", type=int, default=0, help="train an environment map of this resolution behind the Gaussians "
+                    "(configs/dynerf/coffee_martini.yaml: 500); the ground truth is rendered over a known smooth environment")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -36,6 +38,13 @@ def main():
     pipe, bg = train_host.PipelineFlags(), scene["bg"].to(dev)
     target = train_host.GaussianParams(scene, dev)
     cams = [train_host.SyntheticCamera(scene, dev, timestamp=(v + 0.5) / args.views * scene["time_duration"]) for v in range(args.views)]
+    if args.env_map_res:
+        pipe.env_map_res = R = args.env_map_res
+        # the known environment: a few low harmonics in longitude and latitude
+        u = (torch.arange(R, dtype=torch.float32, device=dev) + 0.5) / R
+        truth = torch.stack([0.5 + 0.3 * torch.sin(2 * math.pi * (u[None, :] + ph)) * torch.cos(math.pi * (u[:, None] - 0.5))
+                             for ph in (0.0, 0.33, 0.66)])
+        target.env_map = truth
     with torch.no_grad():
         gts = [render_raw(c, target, pipe, bg)["render"].clone() for c in cams]
     student = train_host.GaussianParams(scene, dev)
@@ -47,8 +56,18 @@ def main():
     opt = train_host.make_optimizer(student)
     torch.cuda.synchronize(); t0 = time.time()
     harness.train(student, opt, cams, gts, pipe, bg, iterations=args.iterations, batch_size=args.batch_size,
-                  world_size=world, rank=rank, log_every=max(1, args.iterations // 10), lambda_rigid=args.lambda_rigid)
+                  world_size=world, rank=rank, log_every=max(1, args.iterations // 10), lambda_rigid=args.lambda_rigid,
+                  env_lr=2e-2 if args.env_map_res else 2.5e-3)
     torch.cuda.synchronize()
+    if rank == 0 and args.env_map_res:
+        from fdgs.envmap import composite_backward
+        seen = torch.zeros_like(truth)    # the texels the cameras see
+        for c in cams[:8]:
+            composite_backward(torch.ones(c.image_height, c.image_width, device=dev), torch.ones(3, c.image_height, c.image_width, device=dev),
+                               truth, c, g_env=seen, accumulate_env=True)
+        seen = seen > 0
+        print("environment map: mean error on the %d seen texels %.4f (untrained: %.4f)" % (
+            int(seen.sum()), float((student.env_map.detach() - truth)[seen].abs().mean()), float(truth[seen].abs().mean())))
     if rank == 0:
         dt = time.time() - t0
         print("%d iterations x %d views x %d ranks in %.2f s: %.0f images/s" % (args.iterations, args.batch_size, world, dt,

@@ -557,6 +557,32 @@ int fdgs_opa_mask_num_partials(int32_t H, int32_t W);
 int fdgs_opa_mask_loss(int32_t H, int32_t W, const float* alpha, int32_t alpha_is_T, const float* mask, const float* g_upstream,
                        float scale, float* grad, int32_t accumulate, float* partials, float* loss, void* stream);
 
+/* ---- the environment map behind the Gaussians (gaussian_renderer/__init__.py:165-177 of the reference) --------------------
+ * Per pixel (i, j): the ray of the pixel centre, d = normalize((inv(viewmatrix^T) ((i + .5 - cx) / fl_x, (j + .5 - cy) / fl_y, 1, 1))[:3]
+ * - campos) with origin campos (scene/cameras.py:75-82), meets the sphere of `radius` about the origin at
+ * t = -(o.d) + sqrt(delta) / (d.d) (the reference's operator precedence); the point (x, y, z) there is looked up at
+ * u = atan2(y, x) / 2pi + 0.5, v = acos(z / radius) / pi by a bilinear grid_sample (align_corners = False, zero padding: the seam
+ * at u = 0 / 1 does not wrap) of env [3, env_h, env_w].  One deliberate difference: ray and texture coordinates are computed in
+ * float64 and v as atan2(sqrt(x^2 + y^2), z), which is acos(clamp(z / radius, -1, 1)) on the sphere: no NaN looking at the pole (fp32
+ * gives z / radius = 1.0000001 there, and the reference's acos a NaN), and no loss of v to fp32's acos near the poles.  The bilinear
+ * weights are rounded to fp32.  The camera must lie inside the sphere (the reference
+ * asserts delta > 0; the library does not check it).  viewmatrix / campos: the camera's world_view_transform [16] (row-major, as the
+ * rasterizer takes it) and camera_center [3]; the 4x4 inverse is taken on the device.  All arrays are device memory; images planar
+ * [3, H, W], T [H, W] the rasterizer's final transmittance.
+ *
+ * colour_out = colour_in + T * env(ray(pixel)); colour_out may alias colour_in. */
+int fdgs_env_composite(int32_t H, int32_t W, const float* viewmatrix, const float* campos, float fl_x, float fl_y,
+                       float cx, float cy, const float* env, int32_t env_h, int32_t env_w, float radius,
+                       const float* T, const float* colour_in, float* colour_out, void* stream);
+/* g_alpha (+)= -sum_c g_colour_c * env_c   (the gradient w.r.t. alpha = 1 - T, as fdgs_backward_in.dL_dout_alpha; NULL: not computed)
+ * g_env   (+)= sum over pixels of g_colour * T * bilinear weights   (NULL: not computed)
+ * "(+)=": written, or added with accumulate_* != 0.  g_env is summed with float atomics (per 16 x 16 pixel tile in LDS first): like
+ * the reference's grid_sample backward and fdgs_rasterize_backward, it is reproducible to the order of arrival only. */
+int fdgs_env_composite_backward(int32_t H, int32_t W, const float* viewmatrix, const float* campos, float fl_x, float fl_y,
+                                float cx, float cy, const float* env, int32_t env_h, int32_t env_w, float radius,
+                                const float* T, const float* g_colour, float* g_alpha, int32_t accumulate_alpha,
+                                float* g_env, int32_t accumulate_env, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
