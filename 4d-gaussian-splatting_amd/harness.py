@@ -160,9 +160,12 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
           log: Callable[[str], None] = print, spatial_order: bool = True,
           on_resort: Optional[Callable] = None, lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0,
           alpha_masks: Optional[Sequence[torch.Tensor]] = None, env_lr: float = 2.5e-3,
-          env_optimize_until: int = 10 ** 9) -> Dict[str, List[float]]:
+          env_optimize_until: int = 10 ** 9, test_cameras: Optional[Sequence] = None, test_gts: Optional[Sequence[torch.Tensor]] = None,
+          test_iterations: Sequence[int] = (), eval_train_views: bool = True,
+          on_evaluate: Optional[Callable] = None) -> Dict[str, list]:
     """The reference's training loop (train.py:82-254) over ``cameras`` / ``gts`` (all views, identical on every rank;
-    each rank renders its FrameShard slice).  Returns the logged history {"iteration", "loss", "psnr"}.
+    each rank renders its FrameShard slice).  Returns the logged history {"iteration", "loss", "psnr"} (lists of numbers) and, when
+    ``test_iterations`` is given, "eval" (a list of dicts, one per evaluated set: see below).
     Densification (train.py:229-244) runs when ``cameras_extent`` is given: every rank takes the same decisions from the
     all-reduced statistics and draws the split samples from a generator seeded with (seed, iteration), so the replicas
     stay identical without a broadcast.  ``on_densify(model, optimizer, stats, iteration)`` replaces that default.
@@ -180,7 +183,13 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     ``alpha_masks``: every camera's ``gt_alpha_mask`` (indexed like ``cameras``), needed with ``lambda_opa_mask`` > 0.
     ``pipe.env_map_res`` = R > 0: the environment map behind the Gaussians (train.py:71-77): ``model.env_map`` = zeros [3, R, R] unless
     the model has one, trained by its own Adam (``fdgs.envmap.EnvMapAdam``, learning rate ``env_lr`` = the reference's feature_lr,
-    eps 1e-15) while ``iteration < env_optimize_until`` (train.py:250-252)."""
+    eps 1e-15) while ``iteration < env_optimize_until`` (train.py:250-252).
+    Evaluation (training_report, train.py:276-345): after the step of every iteration in ``test_iterations``, rank 0 evaluates
+    ``test_cameras`` / ``test_gts`` ("test") and, with ``eval_train_views``, the training views 5, 10, 15, 20, 25 modulo
+    len(cameras) ("train") with ``fdgs.metrics.evaluate`` (L1, PSNR, SSIM, MS-SSIM; MS-SSIM needs both image sides >= 176 and is
+    NaN below that), appends {"iteration", "set", "l1", "psnr", "ssim", "msssim", "views"} to ``hist["eval"]`` and calls
+    ``on_evaluate(iteration, set_name, metrics)`` (the hook for keeping the best checkpoint, train.py:219-224).  No collective:
+    the other ranks skip it.  ``hist["eval"]`` exists only when ``test_iterations`` is given."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -207,7 +216,10 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     if sh_degree_start is not None:
         model.active_sh_degree = min(int(sh_degree_start[0]), model.max_sh_degree)
         model.active_sh_degree_t = min(int(sh_degree_start[1]), model.max_sh_degree_t)
-    hist: Dict[str, List[float]] = {"iteration": [], "loss": [], "psnr": []}
+    hist: Dict[str, list] = {"iteration": [], "loss": [], "psnr": []}
+    test_iterations = set(int(i) for i in test_iterations)
+    if test_iterations:
+        hist["eval"] = []
     for iteration in range(1, iterations + 1):
         optimizer.set_lr("_xyz", expon_lr(iteration, position_lr_init, position_lr_final, 0, position_lr_delay_mult,
                                           position_lr_max_steps))                       # gaussian_model.py:359-365
@@ -246,4 +258,28 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
             if rank == 0:
                 log("[it %5d] loss %.5f  psnr %.2f dB  (%d Gaussians, SH degree %d / time %d)" % (iteration, loss, p, model.P,
                                                                                                  model.active_sh_degree, model.active_sh_degree_t))
+        if iteration in test_iterations and rank == 0:
+            _evaluate_sets(model, cameras, gts, test_cameras, test_gts, eval_train_views, pipe, bg, iteration, hist["eval"], on_evaluate,
+                           log if log_every else None)
     return hist
+
+
+def _evaluate_sets(model, cameras, gts, test_cameras, test_gts, eval_train_views, pipe, bg, iteration, out, on_evaluate, log):
+    """train.py:300-340: the training views 5, 10, ..., 25 (modulo the number of views), then the test views."""
+    from .metrics import MIN_SIDE, evaluate
+    sets = []
+    if eval_train_views and len(cameras):
+        idx = [i % len(cameras) for i in range(5, 30, 5)]
+        sets.append(("train", [cameras[i] for i in idx], [gts[i] for i in idx]))
+    if test_cameras:
+        sets.append(("test", list(test_cameras), list(test_gts)))
+    for name, cams, ims in sets:
+        ms = all(int(c.image_height) >= MIN_SIDE and int(c.image_width) >= MIN_SIDE for c in cams)
+        m = evaluate(model, cams, ims, pipe, bg, msssim=ms)
+        out.append({"iteration": iteration, "set": name, "l1": m["l1"], "psnr": m["psnr"], "ssim": m["ssim"], "msssim": m["msssim"],
+                    "views": len(cams)})
+        if log is not None:
+            log("[it %5d] evaluating %s (%d views): L1 %.5f PSNR %.3f SSIM %.5f MS-SSIM %.5f" % (
+                iteration, name, len(cams), m["l1"], m["psnr"], m["ssim"], m["msssim"]))
+        if on_evaluate is not None:
+            on_evaluate(iteration, name, m)

@@ -24,6 +24,10 @@ def main():
     ap.add_argument("--lambda-rigid", type=float, default=0.0, help="the rigid term's weight (configs/dnerf/lego.yaml: 1.0; rot_4d scenes)")
     ap.add_argument("--env-map-res", type=int, default=0, help="train an environment map of this resolution behind the Gaussians "
                     "(configs/dynerf/coffee_martini.yaml: 500); the ground truth is rendered over a known smooth environment")
+    ap.add_argument("--test-views", type=int, default=0, help="hold out this many cameras at timestamps half-way between two training "
+                    "ones and evaluate them and five training views (L1, PSNR, SSIM, MS-SSIM) at 7000, 30000 and the last iteration")
+    ap.add_argument("--exhaust-test", action="store_true", help="also evaluate every 500 iterations (train.py:392-393); without "
+                    "--test-views only the five training views are evaluated")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -45,8 +49,20 @@ def main():
         truth = torch.stack([0.5 + 0.3 * torch.sin(2 * math.pi * (u[None, :] + ph)) * torch.cos(math.pi * (u[:, None] - 0.5))
                              for ph in (0.0, 0.33, 0.66)])
         target.env_map = truth
+    # held-out views: training view j sits at (j + 0.5) / views of the time span; test view v half-way between training views j and j + 1,
+    # at (j + 1) / views, with the j spread evenly over 0 .. views - 2
+    if args.test_views > args.views - 1:
+        ap.error("--test-views must be at most --views - 1 (one held-out timestamp between two training ones)")
+    tcams = [train_host.SyntheticCamera(scene, dev, timestamp=((2 * v + 1) * (args.views - 1) // (2 * args.test_views) + 1) / args.views
+                                        * scene["time_duration"]) for v in range(args.test_views)]
     with torch.no_grad():
         gts = [render_raw(c, target, pipe, bg)["render"].clone() for c in cams]
+        tgts = [render_raw(c, target, pipe, bg)["render"].clone() for c in tcams]
+    test_iterations = ()   # training_report's five training views, plus the held-out ones if there are any
+    if args.test_views or args.exhaust_test:
+        test_iterations = [7000, 30000, args.iterations]
+        if args.exhaust_test:
+            test_iterations += list(range(0, args.iterations + 1, 500))
     student = train_host.GaussianParams(scene, dev)
     g = torch.Generator(device="cpu").manual_seed(1)   # same perturbation on every rank: replicas start identical
     with torch.no_grad():
@@ -57,7 +73,8 @@ def main():
     torch.cuda.synchronize(); t0 = time.time()
     harness.train(student, opt, cams, gts, pipe, bg, iterations=args.iterations, batch_size=args.batch_size,
                   world_size=world, rank=rank, log_every=max(1, args.iterations // 10), lambda_rigid=args.lambda_rigid,
-                  env_lr=2e-2 if args.env_map_res else 2.5e-3)
+                  env_lr=2e-2 if args.env_map_res else 2.5e-3, test_cameras=tcams or None, test_gts=tgts or None,
+                  test_iterations=test_iterations)   # harness.train logs one line per evaluated set
     torch.cuda.synchronize()
     if rank == 0 and args.env_map_res:
         from fdgs.envmap import composite_backward

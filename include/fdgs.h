@@ -583,6 +583,24 @@ int fdgs_env_composite_backward(int32_t H, int32_t W, const float* viewmatrix, c
                                 const float* T, const float* g_colour, float* g_alpha, int32_t accumulate_alpha,
                                 float* g_env, int32_t accumulate_env, void* stream);
 
+/* ---- evaluation metrics of one view (train.py:276-345, training_report) ----------------------------------------------------
+ * img (the render) and gt [C, H, W] float, device memory.  out4 (device memory, 4 floats) = [l1, psnr, ssim, msssim]:
+ *   l1     mean |img - gt|                                                  (utils/loss_utils.py:18)
+ *   psnr   mean over channels of 20 log10(1 / sqrt(mse_c)), +inf where mse_c = 0 (utils/image_utils.py:17-19)
+ *   ssim   the training loss's SSIM: 11x11 Gaussian window, sigma 1.5, zero padding, mean over all pixels and channels
+ *   msssim torchmetrics' MultiScaleStructuralSimilarityIndexMeasure(data_range = 1): five scales of 2x2 average pooling; per scale
+ *          the means of SSIM and CS = (2 s_xy + C2) / (s_x^2 + s_y^2 + C2) over the valid (H - 10) x (W - 10) window positions,
+ *          relu'd; prod_{s<4} cs_s^beta_s * sim_4^beta_4, beta = (0.0448, 0.2856, 0.3001, 0.2363, 0.1333)
+ * flags: FDGS_METRICS_CLAMP clamps img to [0, 1] first (the reference's evaluation; gt is never clamped); FDGS_METRICS_NO_MSSSIM
+ * skips MS-SSIM (out4[3] = NaN) and allows any size.  Without it both sides must be >= 176 (H // 16 > 10, W // 16 > 10, as
+ * torchmetrics), else FDGS_ERR_INVALID_ARG.  Fixed-order sums: the row is bitwise reproducible.  scratch: device memory of
+ * fdgs_eval_metrics_scratch_bytes(C, H, W) bytes (-1: invalid sizes), reusable by the next call on the same stream. */
+#define FDGS_METRICS_CLAMP 1
+#define FDGS_METRICS_NO_MSSSIM 2
+int fdgs_eval_metrics_scratch_bytes(int32_t C, int32_t H, int32_t W);
+int fdgs_eval_metrics(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, void* scratch,
+                      float* out4, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
