@@ -189,7 +189,12 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     len(cameras) ("train") with ``fdgs.metrics.evaluate`` (L1, PSNR, SSIM, MS-SSIM; MS-SSIM needs both image sides >= 176 and is
     NaN below that), appends {"iteration", "set", "l1", "psnr", "ssim", "msssim", "views"} to ``hist["eval"]`` and calls
     ``on_evaluate(iteration, set_name, metrics)`` (the hook for keeping the best checkpoint, train.py:219-224).  No collective:
-    the other ranks skip it.  ``hist["eval"]`` exists only when ``test_iterations`` is given."""
+    the other ranks skip it.  ``hist["eval"]`` exists only when ``test_iterations`` is given.
+    ``gts`` (and ``test_gts``) may be a ``fdgs.frames.FrameStore``: the frames stay uint8 (on the device or in pinned host memory) and
+    every step's ground truth is decoded by one launch into the store's ring (``store.batch``; the ring is at least 2 * batch_size
+    slots long).  The shard's batches are then drawn one step ahead -- same batches in the same order -- so that a host-resident store
+    uploads the next step's frames (``store.prefetch``) while this step runs.  With ``lambda_opa_mask`` > 0, ``alpha_masks`` None
+    and an RGBA store, the masks are the store's alpha planes, decoded by the same launch."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -203,6 +208,14 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     if spatial_order:
         resort()
     shard = iter(FrameShard(len(cameras), batch_size, world_size, rank, seed))
+    from .frames import FrameStore
+    store = gts if isinstance(gts, FrameStore) else None
+    if store is not None:
+        if len(store) != len(cameras):
+            raise ValueError("harness.train: need one frame per camera (got %d cameras, %d frames)" % (len(cameras), len(store)))
+        store.reserve(batch_size)
+        store_masks = lambda_opa_mask > 0 and alpha_masks is None and store.has_alpha
+        idx_next = next(shard)
     env_opt = None
     if getattr(pipe, "env_map_res", 0):
         from .envmap import EnvMapAdam
@@ -225,9 +238,18 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
                                           position_lr_max_steps))                       # gaussian_model.py:359-365
         if iteration % sh_increase_interval == 0:                                       # train.py:93-94
             model.oneupSHdegree()
-        idx = next(shard)
-        masks = [alpha_masks[i] for i in idx] if lambda_opa_mask > 0 else None
-        results, losses = steppipe.step([cameras[i] for i in idx], [gts[i] for i in idx], pipe, bg, alpha_masks=masks,
+        if store is None:
+            idx = next(shard)
+            masks = [alpha_masks[i] for i in idx] if lambda_opa_mask > 0 else None
+            gt_batch = [gts[i] for i in idx]
+        else:
+            idx, idx_next = idx_next, next(shard)
+            if store_masks:
+                gt_batch, masks = store.batch(idx, masks=True)
+            else:
+                gt_batch, masks = store.batch(idx), ([alpha_masks[i] for i in idx] if lambda_opa_mask > 0 else None)
+            store.prefetch(idx_next)
+        results, losses = steppipe.step([cameras[i] for i in idx], gt_batch, pipe, bg, alpha_masks=masks,
                                         optimize_env=iteration < env_optimize_until)
         if iteration < densify_until_iter:                                              # train.py:229-244
             t_grad = model.params["_t"].grad if model.gaussian_dim == 4 else None      # already all-reduced (mean over the batch)
@@ -253,7 +275,7 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
         if log_every and (iteration % log_every == 0 or iteration == 1 or iteration == iterations):
             with torch.no_grad():
                 loss = float(torch.stack(losses).mean())
-                p = float(psnr(results[-1]["render"], gts[idx[-1]]).mean())
+                p = float(psnr(results[-1]["render"], gt_batch[-1]).mean())
             hist["iteration"].append(iteration); hist["loss"].append(loss); hist["psnr"].append(p)
             if rank == 0:
                 log("[it %5d] loss %.5f  psnr %.2f dB  (%d Gaussians, SH degree %d / time %d)" % (iteration, loss, p, model.P,
@@ -270,9 +292,9 @@ def _evaluate_sets(model, cameras, gts, test_cameras, test_gts, eval_train_views
     sets = []
     if eval_train_views and len(cameras):
         idx = [i % len(cameras) for i in range(5, 30, 5)]
-        sets.append(("train", [cameras[i] for i in idx], [gts[i] for i in idx]))
+        sets.append(("train", [cameras[i] for i in idx], _Picked(gts, idx)))
     if test_cameras:
-        sets.append(("test", list(test_cameras), list(test_gts)))
+        sets.append(("test", list(test_cameras), test_gts))
     for name, cams, ims in sets:
         ms = all(int(c.image_height) >= MIN_SIDE and int(c.image_width) >= MIN_SIDE for c in cams)
         m = evaluate(model, cams, ims, pipe, bg, msssim=ms)
@@ -283,3 +305,17 @@ def _evaluate_sets(model, cameras, gts, test_cameras, test_gts, eval_train_views
                 iteration, name, len(cams), m["l1"], m["psnr"], m["ssim"], m["msssim"]))
         if on_evaluate is not None:
             on_evaluate(iteration, name, m)
+
+
+class _Picked:
+    """``[gts[i] for i in idx]`` taken one at a time: a FrameStore hands out views of a ring, so a list of more frames than it has
+    slots would hold frames that have been overwritten."""
+
+    def __init__(self, gts, idx):
+        self.gts, self.idx = gts, list(idx)
+
+    def __len__(self):
+        return len(self.idx)
+
+    def __getitem__(self, k):
+        return self.gts[self.idx[k]]

@@ -28,6 +28,8 @@ def main():
                     "ones and evaluate them and five training views (L1, PSNR, SSIM, MS-SSIM) at 7000, 30000 and the last iteration")
     ap.add_argument("--exhaust-test", action="store_true", help="also evaluate every 500 iterations (train.py:392-393); without "
                     "--test-views only the five training views are evaluated")
+    ap.add_argument("--u8-frames", choices=("device", "host"), default=None, help="quantise the rendered ground truth to 8-bit images, as a "
+                    "dataset's are, and train from a FrameStore of them kept on the device or in pinned host memory (fdgs.frames)")
     args = ap.parse_args()
     world, rank, local = int(os.environ.get("WORLD_SIZE", "1")), int(os.environ.get("RANK", "0")), int(os.environ.get("LOCAL_RANK", "0"))
     torch.cuda.set_device(local)
@@ -58,6 +60,11 @@ def main():
     with torch.no_grad():
         gts = [render_raw(c, target, pipe, bg)["render"].clone() for c in cams]
         tgts = [render_raw(c, target, pipe, bg)["render"].clone() for c in tcams]
+    if args.u8_frames:
+        from fdgs.frames import FrameStore
+        quantise = lambda ims: torch.stack([(x.clamp(0, 1) * 255 + 0.5).to(torch.uint8).permute(1, 2, 0) for x in ims])   # [N, H, W, 3]
+        gts = FrameStore(quantise(gts), residency=args.u8_frames, device=dev)
+        tgts = FrameStore(quantise(tgts), residency=args.u8_frames, device=dev) if tgts else tgts
     test_iterations = ()   # training_report's five training views, plus the held-out ones if there are any
     if args.test_views or args.exhaust_test:
         test_iterations = [7000, 30000, args.iterations]

@@ -601,6 +601,25 @@ int fdgs_eval_metrics_scratch_bytes(int32_t C, int32_t H, int32_t W);
 int fdgs_eval_metrics(const float* img, const float* gt, int32_t C, int32_t H, int32_t W, int32_t flags, void* scratch,
                       float* out4, void* stream);
 
+/* ---- ground-truth frames kept as 8-bit images, decoded on the device -----------------------------------------------------------
+ * What the reference's loader computes on the host for every image (utils/general_utils.py:22-28 PILtoTorch: np.array(pil) / 255.0,
+ * permuted to [C, H, W]; scene/cameras.py:53-57: image *= gt_alpha_mask; utils/data_utils.py:16-34 the same per batch) and then
+ * moves to the device as float32 inside the step (train.py:106), done here from the 8-bit data: a quarter of the memory or of the
+ * bus traffic.  frames: N images uint8 [H, W, C], interleaved, C = 3 or 4, one behind the other (frame n at n*H*W*C bytes).
+ * index: B int32 frame numbers in DEVICE memory (no host-side table, no synchronisation to enqueue the call); the B frames of the
+ * batch are decoded by ONE launch.  Image b of the batch goes to out + b * out_stride as float32 [3, H, W] and, with C = 4 and
+ * mask_out != NULL, its alpha plane to mask_out + b * mask_stride as [1, H, W] (strides in floats, at least 3 H W and H W).
+ * fp32, exactly these IEEE operations in this order, bit for bit what the reference's loader produces:
+ *   v = float(u8) / 255.0f  for every channel (a division, not a product with 1/255.f);
+ *   C = 4:  mask = a / 255.0f,  rgb = v * mask.
+ * No clamp: the values are in [0, 1] by construction.  A frame number outside [0, N) writes nothing for that image of the batch.
+ * Shapes: a lane takes 4 consecutive pixels with dword / 16-byte accesses when every frame starts on a dword (H*W*C a multiple of
+ * 4: every RGBA shape, RGB with H*W a multiple of 4; the last H*W mod 4 pixels one by one); other RGB shapes, and pointers that are
+ * not dword-aligned, take a byte-wise path with one pixel per lane.  FDGS_ERR_INVALID_ARG: C outside {3, 4}, non-positive N, H, W
+ * or B, B > 65535, H*W > 2^31 - 4096, a NULL frames / index / out, a stride below the image's size. */
+int fdgs_frames_decode(const uint8_t* frames, int32_t N, int32_t H, int32_t W, int32_t C, const int32_t* index, int32_t B,
+                       float* out, int64_t out_stride, float* mask_out, int64_t mask_stride, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
