@@ -95,7 +95,8 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_l1_ssim_num_partials", "fdgs_l1_ssim_value_and_grad", "fdgs_adam_step", "fdgs_adam_step_sh", "fdgs_densify_classify", "fdgs_densify_gather", "fdgs_densify_split", "fdgs_densify_stats_local", "fdgs_densify_stats_apply", "fdgs_knn_scratch_bytes", "fdgs_dist2_knn3",
             "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
-            "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_last_error", "fdgs_version")
+            "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
+            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 11
 
 
@@ -221,6 +222,12 @@ def _load():
     lib.fdgs_eval_metrics.restype = C.c_int
     lib.fdgs_frames_decode.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     lib.fdgs_frames_decode.restype = C.c_int
+    lib.fdgs_frames_encode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.fdgs_frames_encode.restype = C.c_int
+    lib.fdgs_frames_encode_gray_scratch_bytes.argtypes = [C.c_int32] * 3
+    lib.fdgs_frames_encode_gray_scratch_bytes.restype = C.c_int64
+    lib.fdgs_frames_encode_gray.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fdgs_frames_encode_gray.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

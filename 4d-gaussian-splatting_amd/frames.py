@@ -10,6 +10,14 @@ float tensors, bit for bit: ``v = float(u8) / 255.0f``, and with an alpha channe
 * ``FrameStore`` -- N frames, a ring of float slots, ``store.batch(idx)`` / ``store[i]``; usable wherever a sequence of ground-truth
   tensors is (``harness.train(..., gts=store)``, ``metrics.evaluate(model, cams, store, ...)``).
 
+And the way back (csrc/frame_encode.hip): float images out as uint8 frames, torchvision ``save_image``'s rule
+``img.mul(255).add(0.5).clamp(0, 255).to(uint8)`` bit for bit (NaN -> 0), the exact inverse of the decode for all 256 bytes.
+
+* ``encode_frames(images, index, frames_u8, alphas=None)`` / ``encode_gray(planes, index, frames_u8)`` -- the checked wrappers of
+  ``fdgs_frames_encode`` / ``fdgs_frames_encode_gray`` (the reference's grey depth image, utils/image_utils.py:21-28).
+* ``FrameWriter`` -- the counterpart of ``FrameStore``: N frames written one launch at a time, on the device or through a ring of
+  device slots into pinned host memory.
+
 There is no CPU path: the frames may live on the host, the decode runs on the GPU.
 """
 from typing import List, Optional, Sequence
@@ -338,3 +346,234 @@ class FrameStore:
         if not -self.N <= j < self.N:
             raise IndexError("fdgs.frames: frame index %d out of range for %d frames" % (j, self.N))
         return self.batch([j])[0]
+
+
+# ---- the way back: float images -> uint8 frames ---------------------------------------------------------------------------------
+def _check_encode(images, index, frames_u8, planes, what):
+    """Shared argument checks of the two encoders; returns (N, H, W, C, B, stride of ``images`` in floats)."""
+    for name, t in ((what, images), ("index", index), ("frames", frames_u8)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            raise ValueError("fdgs.frames: %s must be a GPU tensor; there is no CPU path" % name)
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or not frames_u8.is_contiguous() or 0 in frames_u8.shape:
+        raise ValueError("fdgs.frames: frames must be a contiguous uint8 tensor [N, H, W, C], got %s %s" % (tuple(frames_u8.shape), frames_u8.dtype))
+    N, H, W, C = (int(s) for s in frames_u8.shape)
+    dev = frames_u8.device
+    if index.dtype != torch.int32 or index.dim() != 1 or not index.is_contiguous() or index.numel() == 0 or index.device != dev:
+        raise ValueError("fdgs.frames: index must be a contiguous int32 tensor [B] (B >= 1) on %s, got %s %s" % (dev, tuple(index.shape), index.dtype))
+    B = int(index.numel())
+    return N, H, W, C, B, _batch_stride(images, what, B, planes, H, W, dev)
+
+
+def _batch_stride(t, name, B, planes, H, W, dev):
+    if (not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or tuple(t.shape) != (B, planes, H, W)
+            or not t[0].is_contiguous() or (B > 1 and t.stride(0) < planes * H * W)):
+        raise ValueError("fdgs.frames: %s must be float32 [%d, %d, %d, %d] on %s with contiguous images, got %s %s" % (
+            name, B, planes, H, W, dev, tuple(getattr(t, "shape", ())), getattr(t, "dtype", type(t))))
+    return int(t.stride(0)) if B > 1 else planes * H * W
+
+
+def encode_frames(images: torch.Tensor, index: torch.Tensor, frames_u8: torch.Tensor, alphas: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``frames_u8[index[b]] = (images[b] * 255 + 0.5).clamp(0, 255).to(uint8)`` in [H, W, C] order for the B entries of ``index``, in
+    one launch on the current stream, without a host synchronisation (NaN -> 0; the product and the sum are rounded separately).
+    ``images``: float32 [B, 3, H, W]; ``frames_u8``: contiguous uint8 [N, H, W, C], C = 3 or 4; with C = 4 ``alphas``: float32
+    [B, 1, H, W] for the fourth byte -- both may be strided along the first dimension and contiguous within an image; ``index``:
+    int32 [B] on the same GPU (an entry outside [0, N) writes nothing).  Gradients are not tracked.  Returns ``frames_u8``."""
+    images = images.detach() if isinstance(images, torch.Tensor) else images
+    N, H, W, C, B, stride = _check_encode(images, index, frames_u8, 3, "images")
+    if C not in (3, 4):
+        raise ValueError("fdgs.frames: frames must have 3 (RGB) or 4 (RGBA) channels, got C = %d" % C)
+    if (alphas is not None) != (C == 4):
+        raise ValueError("fdgs.frames: alphas go with RGBA frames (C = 4) and only with them, got C = %d and alphas %s" % (
+            C, "given" if alphas is not None else "missing"))
+    astride = 0
+    if alphas is not None:
+        alphas = alphas.detach() if isinstance(alphas, torch.Tensor) else alphas
+        astride = _batch_stride(alphas, "alphas", B, 1, H, W, frames_u8.device)
+    dev = frames_u8.device
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_frames_encode(images.data_ptr(), stride, None if alphas is None else alphas.data_ptr(), astride, B, H, W, C,
+                                          frames_u8.data_ptr(), N, index.data_ptr(), _capi.current_stream_handle(dev))
+    if rc == 1:
+        raise ValueError(_capi.last_error())
+    _capi._check(rc, "fdgs_frames_encode")
+    return frames_u8
+
+
+def gray_scratch(B: int, H: int, W: int, device) -> torch.Tensor:
+    """Device scratch of ``encode_gray`` for batches of up to B planes [H, W] (the min / max partials)."""
+    nbytes = _capi.lib.fdgs_frames_encode_gray_scratch_bytes(int(B), int(H), int(W))
+    if nbytes < 0:
+        raise ValueError("fdgs.frames: invalid plane shape %s" % ((B, H, W),))
+    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+
+
+def encode_gray(planes: torch.Tensor, index: torch.Tensor, frames_u8: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The reference's grey depth image (``easy_cmap``, utils/image_utils.py:21-28): ``g = clamp((d - d.min()) / (d.max() - d.min()),
+    0, 1)`` per plane, then the quantisation of ``encode_frames``, into ``frames_u8[index[b]]``: contiguous uint8 [N, H, W, 1] -- ONE
+    channel (``easy_cmap`` writes the same value three times; ``frames.expand(-1, -1, -1, 3)`` is that image).  A constant plane gives
+    0 / 0 = NaN in the reference and 0 here.  ``planes``: float32 [B, 1, H, W], may be strided along the first dimension.  Two
+    launches on the current stream (min / max, encode); ``scratch``: ``gray_scratch(B, H, W, device)``, allocated if not given."""
+    planes = planes.detach() if isinstance(planes, torch.Tensor) else planes
+    N, H, W, C, B, stride = _check_encode(planes, index, frames_u8, 1, "planes")
+    if C != 1:
+        raise ValueError("fdgs.frames: grey frames have one channel [N, H, W, 1], got C = %d" % C)
+    dev = frames_u8.device
+    need = _capi.lib.fdgs_frames_encode_gray_scratch_bytes(B, H, W)
+    if need < 0:
+        raise ValueError("fdgs.frames: invalid plane shape %s" % ((B, H, W),))
+    if scratch is None:
+        scratch = gray_scratch(B, H, W, dev)
+    elif scratch.device != dev or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+        raise ValueError("fdgs.frames: scratch must be a contiguous tensor of at least %d bytes on %s" % (need, dev))
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_frames_encode_gray(planes.data_ptr(), stride, B, H, W, frames_u8.data_ptr(), N, index.data_ptr(),
+                                               scratch.data_ptr(), _capi.current_stream_handle(dev))
+    if rc == 1:
+        raise ValueError(_capi.last_error())
+    _capi._check(rc, "fdgs_frames_encode_gray")
+    return frames_u8
+
+
+class FrameWriter:
+    """``n_frames`` frames of one shape collected as uint8 [N, H, W, C] -- what ``FrameStore`` accepts -- from float images on the
+    GPU, encoded by one launch per ``write`` / ``write_batch`` on the caller's current stream (``encode_frames``; ``channels`` = 3,
+    4 with an alpha plane as the fourth byte, or 1: grey planes through ``write_gray`` / ``encode_gray``).
+
+    ``residency="device"``: the launch writes straight into the [N, H, W, C] device tensor.  ``residency="host"``: into a ring of
+    ``slots`` device frames (default 2); each slot is then copied into a pinned [N, H, W, C] host tensor on a copy stream of the
+    writer's own, which waits for the encode's event; the copy leaves an event per slot, and the encode that takes the slot again
+    is ordered behind it ON THE STREAM (``wait_event``): the host never waits in ``write``, the render of the next view is enqueued
+    while this one's copy travels.  ``finish()`` waits for the outstanding copies and returns the tensor; ``.frames`` before
+    ``finish()`` raises.  The inputs are read by the encode only, on the caller's stream: they may be reused as soon as ``write``
+    returned, stream-ordered."""
+
+    def __init__(self, n_frames: int, H: int, W: int, channels: int = 3, residency: str = "host", slots: Optional[int] = None, device=None):
+        if residency not in ("device", "host"):
+            raise ValueError("fdgs.frames: residency must be \"device\" or \"host\", got %r" % (residency,))
+        if channels not in (1, 3, 4):
+            raise ValueError("fdgs.frames: a writer has 1 (grey), 3 (RGB) or 4 (RGBA) channels, got %r" % (channels,))
+        N, H, W = int(n_frames), int(H), int(W)
+        if N <= 0 or H <= 0 or W <= 0:
+            raise ValueError("fdgs.frames: empty frame array %s" % ((N, H, W, channels),))
+        if slots is not None and int(slots) < 1:
+            raise ValueError("fdgs.frames: a writer needs at least 1 slot, got %r" % (slots,))
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError("fdgs.frames: the encode runs on the GPU; device must be a GPU, got %s" % self.device)
+        self.N, self.H, self.W, self.C = N, H, W, int(channels)
+        self.residency = residency
+        self.launches = 0          # encode launches so far (a grey batch: one reduction + one encode = 1)
+        self._finished = False
+        self._scratch = None
+        if residency == "device":
+            self.slots = N
+            self._frames = self._target = torch.empty((N, H, W, self.C), dtype=torch.uint8, device=self.device)
+            self._numbers = torch.arange(N, dtype=torch.int32, device=self.device)
+        else:
+            self.slots = min(N, 2 if slots is None else int(slots))
+            self._frames = torch.empty((N, H, W, self.C), dtype=torch.uint8).pin_memory()
+            self._target = torch.empty((self.slots, H, W, self.C), dtype=torch.uint8, device=self.device)
+            # slot numbers of a run that starts anywhere in the ring and wraps: one launch for any run of up to `slots` frames
+            self._numbers = (torch.arange(2 * self.slots, dtype=torch.int32, device=self.device) % self.slots).contiguous()
+            self._copied = [None] * self.slots      # per slot: the event behind the copy that last read it
+            self._cursor = 0
+            self._copy_stream = torch.cuda.Stream(self.device)
+
+    def __len__(self):
+        return self.N
+
+    @property
+    def shape(self):
+        return (self.H, self.W, self.C)
+
+    @property
+    def frames(self) -> torch.Tensor:
+        if not self._finished:
+            raise RuntimeError("fdgs.frames: FrameWriter.frames before finish(): copies may still be travelling")
+        return self._frames
+
+    def finish(self) -> torch.Tensor:
+        """Waits for the outstanding copies (host residency; a device-resident result is stream-ordered like any tensor) and
+        returns uint8 [N, H, W, C]."""
+        if self.residency == "host":
+            for ev in self._copied:
+                if ev is not None:
+                    ev.synchronize()
+        self._finished = True
+        return self._frames
+
+    def _run(self, first, B, encode):
+        """Frames first .. first + B - 1 (B <= slots): ``encode(index, target)`` once, then the copies of host residency."""
+        if self.residency == "device":
+            encode(self._numbers[first:first + B], self._target)
+            self._finished = False
+            self.launches += 1
+            return
+        main = torch.cuda.current_stream(self.device)
+        c = self._cursor % self.slots
+        used = [(c + j) % self.slots for j in range(B)]
+        for s in used:
+            if self._copied[s] is not None:
+                main.wait_event(self._copied[s])
+        encode(self._numbers[c:c + B], self._target)
+        self._finished = False
+        self.launches += 1
+        self._cursor += B
+        done = torch.cuda.Event()
+        done.record(main)
+        cs = self._copy_stream
+        cs.wait_event(done)
+        with torch.cuda.stream(cs):
+            k = 0
+            for s0, count in ring_runs(c, B, self.slots):
+                self._frames[first + k:first + k + count].copy_(self._target[s0:s0 + count], non_blocking=True)
+                k += count
+            ev = torch.cuda.Event()
+            ev.record(cs)
+        for s in used:
+            self._copied[s] = ev
+
+    def _batches(self, first, images, planes, name, extra=None):
+        first = int(first)
+        if not isinstance(images, torch.Tensor) or images.dim() != 4 or tuple(images.shape[1:]) != (planes, self.H, self.W):
+            raise ValueError("fdgs.frames: %s must be float32 [B, %d, %d, %d], got %s" % (name, planes, self.H, self.W, tuple(getattr(images, "shape", ()))))
+        B = int(images.shape[0])
+        if B < 1 or not 0 <= first <= self.N - B:
+            raise ValueError("fdgs.frames: frames %d .. %d out of range for %d frames" % (first, first + B - 1, self.N))
+        if extra is not None and (not isinstance(extra, torch.Tensor) or tuple(extra.shape) != (B, 1, self.H, self.W)):
+            raise ValueError("fdgs.frames: alphas must be float32 [%d, 1, %d, %d], got %s" % (B, self.H, self.W, tuple(getattr(extra, "shape", ()))))
+        step = min(self.slots, 65535)   # a launch takes at most 65535 images, a run of host residency at most the ring
+        for k in range(0, B, step):
+            yield first + k, images[k:k + step], (None if extra is None else extra[k:k + step])
+
+    def write_batch(self, first: int, images: torch.Tensor, alphas: Optional[torch.Tensor] = None):
+        """Frames ``first`` .. ``first + B - 1`` from ``images`` float32 [B, 3, H, W] (and ``alphas`` [B, 1, H, W] with 4 channels): one
+        launch (host residency: one per ``slots`` frames)."""
+        if self.C == 1:
+            raise ValueError("fdgs.frames: a grey writer (channels = 1) takes write_gray")
+        if (alphas is not None) != (self.C == 4):
+            raise ValueError("fdgs.frames: alphas go with 4 channels and only with them (channels = %d)" % self.C)
+        for f, im, al in list(self._batches(first, images, 3, "images", alphas)):
+            self._run(f, int(im.shape[0]), lambda index, target, im=im, al=al: encode_frames(im, index, target, al))
+
+    def write(self, i: int, image: torch.Tensor, alpha: Optional[torch.Tensor] = None):
+        """Frame ``i`` from ``image`` float32 [3, H, W] (and ``alpha`` [1, H, W] with 4 channels): one launch."""
+        if not isinstance(image, torch.Tensor) or image.dim() != 3:
+            raise ValueError("fdgs.frames: image must be float32 [3, %d, %d], got %s" % (self.H, self.W, tuple(getattr(image, "shape", ()))))
+        if alpha is not None and (not isinstance(alpha, torch.Tensor) or alpha.dim() != 3):
+            raise ValueError("fdgs.frames: alpha must be float32 [1, %d, %d], got %s" % (self.H, self.W, tuple(getattr(alpha, "shape", ()))))
+        self.write_batch(i, image[None], None if alpha is None else alpha[None])
+
+    def write_gray(self, first: int, planes: torch.Tensor):
+        """Grey frames (``encode_gray``) ``first`` .. from ``planes`` float32 [B, 1, H, W] or one plane [1, H, W] / [H, W]."""
+        if self.C != 1:
+            raise ValueError("fdgs.frames: write_gray needs a grey writer (channels = 1), this one has %d channels" % self.C)
+        if isinstance(planes, torch.Tensor) and planes.dim() in (2, 3):
+            planes = planes.reshape(1, 1, self.H, self.W) if planes.numel() == self.H * self.W and planes.is_contiguous() else planes
+        for f, pl, _ in list(self._batches(first, planes, 1, "planes")):
+            B = int(pl.shape[0])
+            if self._scratch is None:
+                self._scratch = gray_scratch(min(self.slots, 65535), self.H, self.W, self.device)
+            self._run(f, B, lambda index, target, pl=pl: encode_gray(pl, index, target, self._scratch))

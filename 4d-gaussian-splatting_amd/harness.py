@@ -58,11 +58,20 @@ class FrameShard:
         return [perm[k * G + self.rank * self.B: k * G + (self.rank + 1) * self.B] for k in range(self.batches_per_epoch())]
 
     def __iter__(self) -> Iterator[List[int]]:
-        e = 0
+        return self.iter_from(0)
+
+    def iter_from(self, start: int) -> Iterator[List[int]]:
+        """The sequence of ``iter(shard)`` from its batch number ``start`` on (0 = the whole sequence): what a run resumed after
+        ``start`` iterations draws -- the batches the uninterrupted run would have drawn.  Nothing is replayed: the permutation
+        of an epoch is a pure function of (seed, epoch)."""
+        start = int(start)
+        if start < 0:
+            raise ValueError("FrameShard.iter_from: start must be >= 0, got %d" % start)
+        e, skip = divmod(start, self.batches_per_epoch())
         while True:
-            for b in self.epoch(e):
+            for b in self.epoch(e)[skip:]:
                 yield b
-            e += 1
+            e, skip = e + 1, 0
 
 
 class DensificationStats:
@@ -162,7 +171,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
           alpha_masks: Optional[Sequence[torch.Tensor]] = None, env_lr: float = 2.5e-3,
           env_optimize_until: int = 10 ** 9, test_cameras: Optional[Sequence] = None, test_gts: Optional[Sequence[torch.Tensor]] = None,
           test_iterations: Sequence[int] = (), eval_train_views: bool = True,
-          on_evaluate: Optional[Callable] = None) -> Dict[str, list]:
+          on_evaluate: Optional[Callable] = None, start_iteration: int = 0, stats: Optional["DensificationStats"] = None,
+          save_iterations: Sequence[int] = (), on_save: Optional[Callable] = None) -> Dict[str, list]:
     """The reference's training loop (train.py:82-254) over ``cameras`` / ``gts`` (all views, identical on every rank;
     each rank renders its FrameShard slice).  Returns the logged history {"iteration", "loss", "psnr"} (lists of numbers) and, when
     ``test_iterations`` is given, "eval" (a list of dicts, one per evaluated set: see below).
@@ -194,7 +204,13 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     every step's ground truth is decoded by one launch into the store's ring (``store.batch``; the ring is at least 2 * batch_size
     slots long).  The shard's batches are then drawn one step ahead -- same batches in the same order -- so that a host-resident store
     uploads the next step's frames (``store.prefetch``) while this step runs.  With ``lambda_opa_mask`` > 0, ``alpha_masks`` None
-    and an RGBA store, the masks are the store's alpha planes, decoded by the same launch."""
+    and an RGBA store, the masks are the store's alpha planes, decoded by the same launch.
+    Saving and resuming (train.py:50-52, 224-228): after the step (and the evaluation) of every iteration in ``save_iterations``,
+    rank 0 calls ``on_save(iteration, model, optimizer, stats)`` -- e.g. ``fdgs.checkpoint.save(path, model, optimizer, iteration,
+    stats)``; ``on_evaluate`` with the same function is the reference's best-PSNR checkpoint.  ``start_iteration`` = n resumes a run
+    that was saved after n iterations: the loop runs from n + 1 to ``iterations``, the shard starts at its batch number n, and
+    ``stats`` (the loaded ``DensificationStats``) replaces the fresh ones.  ``spatial_order`` re-derives its permutation from the
+    loaded parameters (the identity for a model that was saved in Morton order and has not moved since); ``stats`` follows it."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -205,9 +221,14 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
             stats.xyz_gradient_accum, stats.t_gradient_accum = stats.xyz_gradient_accum[perm], stats.t_gradient_accum[perm]
             stats.denom, stats.max_radii2D = stats.denom[perm], stats.max_radii2D[perm]
 
+    start_iteration = int(start_iteration)
+    if start_iteration < 0:
+        raise ValueError("harness.train: start_iteration must be >= 0, got %d" % start_iteration)
+    if stats is not None and int(stats.denom.shape[0]) != model.P:
+        raise ValueError("harness.train: stats are for %d Gaussians, the model has %d" % (int(stats.denom.shape[0]), model.P))
     if spatial_order:
-        resort()
-    shard = iter(FrameShard(len(cameras), batch_size, world_size, rank, seed))
+        resort(stats)
+    shard = FrameShard(len(cameras), batch_size, world_size, rank, seed).iter_from(start_iteration)
     from .frames import FrameStore
     store = gts if isinstance(gts, FrameStore) else None
     if store is not None:
@@ -225,15 +246,19 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
         env_opt = EnvMapAdam(model.env_map, lr=env_lr, eps=1e-15)
     steppipe = StepPipeline(model, optimizer, world_size=world_size, lambda_dssim=lambda_dssim, lambda_rigid=lambda_rigid,
                             lambda_motion=lambda_motion, lambda_opa_mask=lambda_opa_mask, env_optimizer=env_opt)
-    stats = DensificationStats(model.P, model.flat.device, world_size)
+    if stats is None:
+        stats = DensificationStats(model.P, model.flat.device, world_size)
+    else:
+        stats.world = int(world_size)
     if sh_degree_start is not None:
         model.active_sh_degree = min(int(sh_degree_start[0]), model.max_sh_degree)
         model.active_sh_degree_t = min(int(sh_degree_start[1]), model.max_sh_degree_t)
     hist: Dict[str, list] = {"iteration": [], "loss": [], "psnr": []}
     test_iterations = set(int(i) for i in test_iterations)
+    save_iterations = set(int(i) for i in save_iterations)
     if test_iterations:
         hist["eval"] = []
-    for iteration in range(1, iterations + 1):
+    for iteration in range(start_iteration + 1, iterations + 1):
         optimizer.set_lr("_xyz", expon_lr(iteration, position_lr_init, position_lr_final, 0, position_lr_delay_mult,
                                           position_lr_max_steps))                       # gaussian_model.py:359-365
         if iteration % sh_increase_interval == 0:                                       # train.py:93-94
@@ -283,6 +308,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
         if iteration in test_iterations and rank == 0:
             _evaluate_sets(model, cameras, gts, test_cameras, test_gts, eval_train_views, pipe, bg, iteration, hist["eval"], on_evaluate,
                            log if log_every else None)
+        if iteration in save_iterations and rank == 0 and on_save is not None:
+            on_save(iteration, model, optimizer, stats)
     return hist
 
 

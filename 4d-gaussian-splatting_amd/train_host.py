@@ -72,6 +72,42 @@ class GaussianParams:
         self.env_map = None
         self.get_max_sh_channels = M
 
+    @classmethod
+    def from_raw(cls, tensors: Dict[str, torch.Tensor], device, *, max_sh_degree: int, max_sh_degree_t: int = 0, active_sh_degree: int = None,
+                 active_sh_degree_t: int = None, time_duration=(0.0, 1.0), rot_4d: bool = False, gaussian_dim: int = 3,
+                 force_sh_3d: bool = False, prefilter_var: float = -1.0) -> "GaussianParams":
+        """A model from RAW (pre-activation) tensors -- what a checkpoint holds (fdgs.checkpoint.restore): ``tensors`` maps the names
+        of ``NAMES`` to ``_xyz`` [P, 3], ``_features`` [P, M, 3], ``_opacity`` [P, 1], ``_scaling`` [P, 3], ``_rotation`` [P, 4] and,
+        where the model has them, ``_t`` [P, 1], ``_scaling_t`` [P, 1], ``_rotation_r`` [P, 4].  They are COPIED into the flat bucket
+        bit for bit.  The bucket always holds all eight segments: a tensor that is missing or empty (a 3D model's ``_t`` /
+        ``_scaling_t``, ``_rotation_r`` without ``rot_4d``) is filled with what ``create_from_pcd`` starts from -- t = 0,
+        log-scale 0, the identity quaternion; the kernels do not read it.  ``time_duration``: the reference's [t0, t1] pair."""
+        P, M = int(tensors["_xyz"].shape[0]), int(tensors["_features"].shape[1])
+        self = cls.__new__(cls)
+        self.M = M
+        total = P * self.floats_per_gaussian()
+        self._bind(torch.empty(total, dtype=torch.float32, device=device), torch.zeros(total, dtype=torch.float32, device=device), P)
+        with torch.no_grad():
+            for name in self.NAMES:
+                dst, src = self.params[name], tensors.get(name, None)
+                if src is None or src.numel() == 0:
+                    dst.zero_()
+                    if name == "_rotation_r":
+                        dst[:, 0] = 1.0
+                elif tuple(src.shape) != tuple(dst.shape):
+                    raise ValueError("GaussianParams.from_raw: %s must be %s, got %s" % (name, tuple(dst.shape), tuple(src.shape)))
+                else:
+                    dst.copy_(src.detach().to(device=device, dtype=torch.float32))
+        self.max_sh_degree, self.max_sh_degree_t = int(max_sh_degree), int(max_sh_degree_t)
+        self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else int(active_sh_degree)
+        self.active_sh_degree_t = self.max_sh_degree_t if active_sh_degree_t is None else int(active_sh_degree_t)
+        self.time_duration = [float(time_duration[0]), float(time_duration[1])]
+        self.rot_4d, self.gaussian_dim, self.force_sh_3d = bool(rot_4d), int(gaussian_dim), bool(force_sh_3d)
+        self.prefilter_var = float(prefilter_var)
+        self.env_map = None
+        self.get_max_sh_channels = M
+        return self
+
     def oneupSHdegree(self):
         """scene/gaussian_model.py:253-257: the spatial degree climbs to its maximum first, then the time degree."""
         if self.active_sh_degree < self.max_sh_degree:

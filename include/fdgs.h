@@ -620,6 +620,31 @@ int fdgs_eval_metrics(const float* img, const float* gt, int32_t C, int32_t H, i
 int fdgs_frames_decode(const uint8_t* frames, int32_t N, int32_t H, int32_t W, int32_t C, const int32_t* index, int32_t B,
                        float* out, int64_t out_stride, float* mask_out, int64_t mask_stride, void* stream);
 
+/* ---- float images written out as 8-bit frames: the inverse of fdgs_frames_decode ----------------------------------------------------
+ * images: B float32 images [3, H, W], image b at images + b * image_stride (floats, at least 3 H W); with C = 4 also alphas: B planes
+ * [1, H, W] at alphas + b * alpha_stride (at least H W) for the fourth byte.  frames: N images uint8 [H, W, C], interleaved, C = 3
+ * or 4, one behind the other; index: B int32 frame numbers in DEVICE memory: image b is written to frame index[b]; a number outside
+ * [0, N) writes nothing.  ONE launch for the batch.  fp32, exactly these IEEE operations in this order per value (torchvision's
+ * save_image: img.mul(255).add_(0.5).clamp_(0, 255).to(uint8)), no fused multiply-add:
+ *   t = v * 255.0f;  t = t + 0.5f;  q = (uint8) min(max(t, 0.0f), 255.0f)  (truncating);  NaN -> 0.
+ * fdgs_frames_encode(fdgs_frames_decode(q)) == q for all 256 bytes.  Shapes: a lane takes 4 consecutive pixels with 16-byte loads
+ * and dword stores when every frame starts on a dword (H*W*C a multiple of 4); other shapes, and pointers that are not
+ * dword-aligned, take a byte-wise path with one pixel per lane.  FDGS_ERR_INVALID_ARG: C outside {3, 4}, non-positive N, H, W or B,
+ * B > 65535, H*W > 2^31 - 4096, a NULL images / index / frames (or alphas with C = 4), a stride below the image's size. */
+int fdgs_frames_encode(const float* images, int64_t image_stride, const float* alphas, int64_t alpha_stride, int32_t B,
+                       int32_t H, int32_t W, int32_t C, uint8_t* frames, int32_t N, const int32_t* index, void* stream);
+
+/* The reference's grey depth image (utils/image_utils.py:21-28 easy_cmap, what training_report logs): B float32 planes [H, W] at
+ * planes + b * plane_stride -> frames uint8 [N, H, W, 1] (ONE channel; a viewer replicates it), frame index[b] as above.
+ *   g = clamp((d - min) / (max - min), 0, 1)  -- one IEEE subtraction, one IEEE division, min / max over the plane (a NaN in the
+ * plane makes both NaN, as torch.min / torch.max) -- then the quantisation above.  max == min gives 0 / 0 = NaN -> 0.
+ * Two launches on `stream`: a wave64 min / max reduction that leaves one (min, max) pair per workgroup in `scratch`, and the encode,
+ * whose workgroups finish the pairs of their plane.  No atomics.  scratch: device memory of fdgs_frames_encode_gray_scratch_bytes(B,
+ * H, W) bytes (-1: invalid sizes), dword-aligned, reusable by the next call on the same stream. */
+int64_t fdgs_frames_encode_gray_scratch_bytes(int32_t B, int32_t H, int32_t W);
+int fdgs_frames_encode_gray(const float* planes, int64_t plane_stride, int32_t B, int32_t H, int32_t W, uint8_t* frames, int32_t N,
+                            const int32_t* index, void* scratch, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
