@@ -145,13 +145,18 @@ static const unsigned g_probe_skip = []() { const char* e = getenv("FDGS_TIMING_
 #define FDGS_STAGE_SKIPPED(id) false
 #endif
 
-// debug mode == the reference's CHECK_CUDA(..., debug): synchronise and check after each stage
-#define STAGE(id, expr, what)                                                                       \
+// where a stage is enqueued; debug mode == the reference's CHECK_CUDA(..., debug): synchronise and check after each stage
+struct StageCtx { hipStream_t stream; bool debug; };
+#define STAGE(ctx, id, expr, what)                                                                  \
 	do {                                                                                            \
-		StageTimer timer__(id, stream);                                                             \
+		StageTimer timer__(id, (ctx).stream);                                                       \
 		if (!FDGS_STAGE_SKIPPED(id)) HIP_TRY((expr), what);                                         \
-		if (debug) HIP_TRY(hipStreamSynchronize(stream), what);                                     \
+		if ((ctx).debug) HIP_TRY(hipStreamSynchronize((ctx).stream), what);                         \
 	} while (0)
+
+// tile order of the blend kernels (written by the forward's scan or sparse sort, read again by the backward); FDGS_TILE_ORDER=0 in the
+// environment: index order (A/B timing)
+static const bool g_use_tile_order = []() { const char* e = getenv("FDGS_TILE_ORDER"); return !(e && e[0] == '0'); }();
 
 // every struct of the ABI starts with its own size as the caller's header defined it: a caller built against another fdgs.h
 // is turned away here instead of the library reading past the end of a shorter struct
@@ -162,10 +167,10 @@ static const unsigned g_probe_skip = []() { const char* e = getenv("FDGS_TIMING_
 			            (unsigned)(ptr)->struct_size, FDGS_VERSION, sizeof(type));                                        \
 	} while (0)
 
+// (the caller has checked s->struct_size)
 static int check_scene(const fdgs_scene* s)
 {
 	if (!s) return fail(FDGS_ERR_INVALID_ARG, "scene is NULL");
-	CHECK_STRUCT(s, fdgs_scene);
 	if (s->P < 0 || s->W <= 0 || s->H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", s->P, s->W, s->H);
 	if (div_up(s->W, TILE_X) > 65535 || div_up(s->H, TILE_Y) > 65535) return fail(FDGS_ERR_INVALID_ARG, "image too large for 16-bit tile rectangles");
 	// (the tile order packs a rank into 24 bits, and T = gx * gy is an int everywhere: 2^24 tiles = 4.3 gigapixels)
@@ -211,8 +216,6 @@ extern "C" int fdgs_version(void) { return FDGS_VERSION; }
 // again (longer lists than guessed), [2] exact sizes (first call of a thread, debug mode, or more instances than guessed)
 static std::atomic<long long> g_run_ahead[3];
 static std::atomic<bool> g_run_ahead_enabled{[]() { const char* e = getenv("FDGS_RUN_AHEAD"); return !(e && e[0] == '0'); }()};   // FDGS_RUN_AHEAD=0: as fdgs_set_run_ahead(0)
-constexpr int FDGS_MAX_DEVICES = 64;   // = the size of g_box_of
-constexpr int FDGS_GUESS_SLOTS = 8;    // = the size of g_guesses
 extern "C" void fdgs_set_run_ahead(int32_t enable) { g_run_ahead_enabled.store(enable != 0); }
 // Byte budget of fdgs_forward_out.sparse_lists (include/fdgs.h): a forward takes the sparse layout only when its binning buffer --
 // T * cap entries -- stays within max(g_sparse_min_bytes, g_sparse_factor x the compact buffer the same guess would get).
@@ -234,12 +237,18 @@ extern "C" void fdgs_debug_run_ahead_stats(int64_t* counts3)
 	for (int k = 0; k < 3; k++) counts3[k] = (int64_t)g_run_ahead[k].load();
 }
 
-// ---- per host thread and device: the pinned mailbox ring the tile scans report into, the run-ahead guesses, the lazy forwards ----
+// ---- per host thread and device (a host thread may drive several GPUs): the pinned mailbox ring the forwards report into, the second
+// stream of split_colour, the run-ahead guesses ----
 namespace
 {
-	constexpr int MAIL_SLOTS = 64;   // forwards of one thread that may be unreported at a time (fdgs_forward_out.lazy); 16 bytes each
-	struct RunAhead { int dev = -1, W = 0, H = 0, P = 0; long long capacity = 0; int longest = 0; long long r_hist[4] = { 0, 0, 0, 0 }; int l_hist[4] = { 0, 0, 0, 0 }; int hist_at = 0; };
-	struct MailRec { unsigned long long seq = 0; long long cap = 0; int longest_cap = 0; RunAhead* guess = nullptr; int gdev = 0, gW = 0, gH = 0, gP = 0; bool pending = false, lazy = false; hipStream_t stream = nullptr; /* the stream the forward (its tile scan) was enqueued on */ };
+	constexpr int FDGS_MAX_DEVICES = 64;   // device ordinals a thread's state is kept for
+	constexpr int FDGS_GUESS_SLOTS = 8;    // (W, H, P) configurations a thread alternates between without losing a guess
+	constexpr int MAIL_SLOTS = 64;         // forwards of one thread that may be unreported at a time (fdgs_forward_out.lazy); 16 bytes each
+	struct RunAhead { int W = 0, H = 0, P = 0; long long capacity = 0; int longest = 0; long long r_hist[4] = { 0, 0, 0, 0 }; int l_hist[4] = { 0, 0, 0, 0 }; int hist_at = 0; };
+	// INVARIANT: `pending` is set only once a launch that writes the record's ticket has been enqueued (the tile scan; with sparse
+	// lists the tile sort), so a pending record is reported unless its stream fails.  A forward that returns before that launch leaves
+	// its record unmarked, and harvest steps over it.
+	struct MailRec { unsigned long long seq = 0; long long cap = 0; int longest_cap = 0; RunAhead* guess = nullptr; int gW = 0, gH = 0, gP = 0; bool pending = false, lazy = false; hipStream_t stream = nullptr; /* the stream the forward (its tile scan) was enqueued on */ };
 	struct Mailbox
 	{
 		volatile uint32_t* host = nullptr; uint32_t* dev = nullptr;
@@ -248,9 +257,28 @@ namespace
 		int failed = 0;                         // lazy forwards whose lists did not fit, since the last fdgs_forward_lazy_status
 		int done_R[MAIL_SLOTS]; int done_n = 0; // num_rendered of the lazy forwards reported since then (oldest first)
 	};
-	thread_local Mailbox* g_box_of[64];   // allocated on a thread's first forward on the device
-	thread_local RunAhead g_guesses[8];
-	thread_local int g_guess_next = 0;
+	struct ThreadState
+	{
+		Mailbox box;
+		// split_colour: the SH colours are only needed by the blend -- they are evaluated on a second stream of this thread's while
+		// the binning runs on the caller's (event after the geometry launch, event back before the blend)
+		hipStream_t aux_stream = nullptr; hipEvent_t fork = nullptr, join = nullptr;
+		// the guess is kept per (image size, P): a thread that alternates between scenes or resolutions keeps one per configuration
+		// (a few slots, replaced round-robin)
+		RunAhead guesses[FDGS_GUESS_SLOTS]; int guess_next = 0;
+	};
+	thread_local ThreadState* g_state_of[FDGS_MAX_DEVICES];   // allocated on a thread's first call on the device
+
+	// the calling thread's state for the current device
+	int thread_state(ThreadState** st)
+	{
+		int dev_id = 0;
+		HIP_TRY(hipGetDevice(&dev_id), "hipGetDevice");
+		if (dev_id < 0 || dev_id >= FDGS_MAX_DEVICES) return fail(FDGS_ERR_UNSUPPORTED, "device ordinal %d beyond %d", dev_id, FDGS_MAX_DEVICES);
+		if (!g_state_of[dev_id]) g_state_of[dev_id] = new ThreadState();
+		*st = g_state_of[dev_id];
+		return FDGS_OK;
+	}
 	inline uint32_t ticket_of(unsigned long long seq) { return (uint32_t)(seq % 0xFFFFFFFFull) + 1u; }   // never 0
 
 	void note_result(RunAhead& g, long long R, int longest)
@@ -290,7 +318,7 @@ namespace
 			if (!arrived) return false;
 			const long long R = (long long)(int)m[0];
 			const int longest = (int)m[1];
-			if (r.guess && r.guess->dev == r.gdev && r.guess->W == r.gW && r.guess->H == r.gH && r.guess->P == r.gP) note_result(*r.guess, R, longest);
+			if (r.guess && r.guess->W == r.gW && r.guess->H == r.gH && r.guess->P == r.gP) note_result(*r.guess, R, longest);
 			if (r.lazy)
 			{
 				if (R < 0 || R > r.cap || longest > r.longest_cap) box.failed++;
@@ -301,22 +329,117 @@ namespace
 		}
 		return true;
 	}
+
+	// How a forward sizes and lays out its tile lists, decided before anything behind the scan is enqueued.
+	//   Exact:  wait for num_rendered, then size the buffer with it (capacity / sort_longest are filled in from the report).
+	//   Ahead:  everything is enqueued with buffers sized by the guess; the host reads the report afterwards and starts over where it did not fit.
+	//   Lazy:   as Ahead with generous headroom, nobody waits; a forward that does not fit is reported by fdgs_forward_lazy_status.
+	//   Sparse: a lazy forward whose tile t owns the fixed slots [t * tile_cap, (t + 1) * tile_cap) of the buffer (no count pass, no scan).
+	enum class Mode { Exact, Ahead, Lazy, Sparse };
+	struct Plan
+	{
+		Mode mode;
+		long long capacity;   // instances the binning buffer holds (Sparse: T * tile_cap)
+		int sort_longest;     // longest list the sort instances launched take (Sparse: tile_cap)
+		uint32_t tile_cap;    // Sparse: slots per tile, a multiple of 64 (the cull planes' words); otherwise 0
+		bool scratch;         // the buffer includes the global sort scratch (lists longer than the LDS takes)
+	};
+	Plan exact_plan(long long R, int longest, int lds_cap) { return Plan{ Mode::Exact, R, longest, 0u, longest > lds_cap }; }
+
+	// run_ahead: not debug mode, not switched off; lazy / sparse: what the call asks for (fdgs_forward_out; sparse needs the tile order)
+	Plan plan_forward(const RunAhead& guess, bool run_ahead, bool lazy, bool sparse, int T, int lds_cap, long long sparse_min_bytes, int sparse_factor)
+	{
+		if (!run_ahead || guess.capacity <= 0) return exact_plan(0, 0, lds_cap);
+		if (!lazy) return Plan{ Mode::Ahead, guess.capacity, guess.longest, 0u, guess.longest > lds_cap };
+		// lazy: nobody is there to start over, so the headroom is generous -- 1.5 x the largest of the last four reports (+ 64 Ki
+		// instances, in steps of 256 Ki so that the allocator sees few distinct sizes), and the sort instances are chosen for lists
+		// 1.5 x the longest one seen; a forward that still does not fit is reported by fdgs_forward_lazy_status
+		long long rmax = 0; int lmax = 0;
+		for (int k = 0; k < 4; k++) { rmax = std::max(rmax, guess.r_hist[k]); lmax = std::max(lmax, guess.l_hist[k]); }
+		// (geometric steps -- 1/16 octave, at least 256 Ki -- because a scene that grows a little every step must not present the
+		// caller's allocator with a new, slightly larger size every few steps: a device allocation of hundreds of MB in the middle
+		// of a running pipeline stalls it for milliseconds; measured on the C5 leg of bench.py, profiles/HISTORY.md round 5)
+		const long long want = rmax + rmax / 2 + 65536;
+		long long q = 1ll << 18;
+		while (q * 32 <= want) q <<= 1;
+		const long long cap = std::min<long long>((want / q + 1) * q, 0x7fffffffLL);
+		const int longest = lmax + lmax / 2 + 64;
+		const Plan compact{ Mode::Lazy, cap, longest, 0u, longest > lds_cap };
+		if (!sparse) return compact;
+		// SPARSE lists (fdgs_forward_out.sparse_lists, lazy forwards only): tile t's list gets the fixed slots [t * cap, (t + 1) * cap) of the
+		// binning buffer, cap = the longest list provided for (a multiple of 64: the cull planes' words).  Then nobody needs the lists'
+		// starts before the scatter pass -- no count pass, no scan: the scatter counts as it goes (the tile counters start from zero),
+		// the per-tile sort reads each tile's count, and one extra workgroup of its launch reports num_rendered / the longest list and
+		// writes the blend kernels' tile order.  Two launches (~16 us at C3) off the forward's critical chain for address space:
+		// T * cap instead of num_rendered entries (C3: 8.5 M instead of 2.0 M; 288 GB of HBM: DESIGN.md section 4.3).
+		// a multiple of 64, in steps of 1/8 octave for the same reason as the capacity above (one step of 64 is T * 64 entries: 16 MB at C5)
+		q = 64;
+		while (q * 16 <= longest) q <<= 1;
+		const long long cap_tile = ((long long)longest + q - 1) / q * q;
+		// The price is address space, and it has a budget: ONE long list (a real capture has hot tiles: 16 k entries in one tile of a
+		// 2704 x 2028 image would make T * cap = 4.2 GB per forward in flight) must not turn a 200 MB buffer into gigabytes.  Beyond
+		// max(1 GiB, 4 x the compact buffer of the same guess) -- fdgs_set_sparse_lists_budget -- the forward keeps compact lists.
+		if (cap_tile * (long long)T > 0x7fffffffLL) return compact;
+		const Plan slots{ Mode::Sparse, cap_tile * T, (int)cap_tile, (uint32_t)cap_tile, (int)cap_tile > lds_cap };
+		const size_t sparse_bytes = bin_layout((int)slots.capacity, slots.scratch, T).total;
+		const size_t compact_bytes = bin_layout((int)compact.capacity, compact.scratch, T).total;
+		const long long budget = std::max<long long>(sparse_min_bytes, (long long)sparse_factor * (long long)compact_bytes);
+		return (long long)sparse_bytes <= budget ? slots : compact;
+	}
+
+	// what the launches of one forward call share
+	struct FwdCall
+	{
+		const fdgs_scene& s; const fdgs_forward_out& out; StageCtx q;
+		int gx, T;
+		const uint16_t* rect; const float* depths; const float* records;                   // geometry buffer
+		uint32_t *counters, *ctl, *tile_order, *ranges, *n_contrib; float* final_T;          // image buffer
+		uint32_t* mail_dev; uint32_t ticket;                                                // this call's mailbox slot, as the device sees it
+		// the colour stream's event the blend must wait for, or NULL (nothing on the second stream, or joined already).  Whichever way
+		// the call returns: work on the second stream writes into this call's geometry buffer, so the caller's stream waits for it
+		// (the buffer may be released in stream order right after an error return)
+		hipEvent_t join;
+		~FwdCall() { if (join) (void)hipStreamWaitEvent(q.stream, join, 0); }
+	};
+	// the binning buffer of a plan, as the caller's allocator gave it
+	struct Lists { char* bin; BinLayout L; };
+	int alloc_lists(const Plan& plan, int T, fdgs_alloc_fn alloc, void* alloc_user, Lists* lists)
+	{
+		lists->L = bin_layout((int)plan.capacity, plan.scratch, T);
+		lists->bin = (char*)alloc(alloc_user, FDGS_BUF_BINNING, lists->L.total);
+		if (!lists->bin) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL (binning)");
+		if (plan.mode != Mode::Exact) g_sparse_stats[2].store((long long)lists->L.total);
+		return FDGS_OK;
+	}
+	// [scatter ->] sort -> join the colour stream -> blend.  borrowed: a global sort scratch to use instead of the buffer's own.
+	int enqueue_lists(FwdCall& f, const Plan& plan, const Lists& lists, bool scatter, void* borrowed = nullptr)
+	{
+		const bool sparse = plan.mode == Mode::Sparse;   // the sort launch then reports num_rendered and writes the tile order, as the scan does otherwise
+		const hipStream_t stream = f.q.stream;
+		const BinLayout& BL = lists.L;
+		uint32_t* point_list = (uint32_t*)(lists.bin + BL.point_list);
+		uint32_t* pairs = (uint32_t*)(lists.bin + BL.pairs);
+		void* sort_scratch = borrowed ? borrowed : (plan.scratch ? (void*)(lists.bin + BL.big_scratch) : nullptr);
+		if (scatter)
+			STAGE(f.q, FDGS_STAGE_TILE_SCATTER, launch_tile_scatter(f.rect, f.depths, f.s.P, f.gx, f.T, f.counters, pairs, f.ctl, (uint32_t)plan.capacity,
+			                          sparse ? nullptr : f.tile_order, stream, plan.tile_cap), "tile scatter");
+		STAGE(f.q, FDGS_STAGE_TILE_SORT, launch_tile_sort(f.counters, f.T, plan.sort_longest, pairs, point_list, f.ranges, sort_scratch, f.ctl, (uint32_t)plan.capacity,
+		                       sparse ? nullptr : f.tile_order, stream, plan.tile_cap, sparse ? f.ctl : nullptr, sparse ? f.mail_dev : nullptr,
+		                       sparse ? f.ticket : 0u, sparse ? f.tile_order : nullptr), "tile sort");
+		if (f.join) { HIP_TRY(hipStreamWaitEvent(stream, f.join, 0), "hipStreamWaitEvent"); f.join = nullptr; }   // the blend must not start before the colours are there
+		STAGE(f.q, FDGS_STAGE_BLEND_FWD, launch_blend_fwd(f.s, f.out, f.records, point_list, f.ranges, f.tile_order, f.final_T, f.n_contrib,
+		                       (unsigned long long*)(lists.bin + BL.cull_bits), BL.cull_stride, (uint32_t)(BL.cull_bits / 8), f.ctl, stream), "blend_fwd");
+		return FDGS_OK;
+	}
 }
 
 extern "C" int fdgs_forward_lazy_status(int32_t wait, void* stream_v, int32_t* pending, int32_t* failed, int32_t* num_rendered, int32_t max_out, int32_t* n_out)
 {
 	g_err[0] = 0;
-	int dev_id = 0;
-	HIP_TRY(hipGetDevice(&dev_id), "hipGetDevice");
-	if (dev_id < 0 || dev_id >= 64) return fail(FDGS_ERR_UNSUPPORTED, "device ordinal %d beyond 64", dev_id);
-	if (!g_box_of[dev_id])
-	{
-		if (pending) *pending = 0;
-		if (failed) *failed = 0;
-		if (n_out) *n_out = 0;
-		return FDGS_OK;
-	}
-	Mailbox& box = *g_box_of[dev_id];
+	ThreadState* st = nullptr;
+	const int rc = thread_state(&st);
+	if (rc != FDGS_OK) return rc;
+	Mailbox& box = st->box;   // (no forward yet: nothing pending, nothing to report)
 	(void)stream_v;   // (kept in the signature: every pending forward is waited for on ITS stream)
 	if (box.host && !harvest(box, wait != 0, HARVEST_ALL))
 		return fail(FDGS_ERR_HIP, "a lazy forward never reported num_rendered (failed launch?)");
@@ -355,78 +478,54 @@ extern "C" int fdgs_rasterize_forward(const fdgs_scene* scene, const fdgs_forwar
 	char* geom = (char*)alloc(alloc_user, FDGS_BUF_GEOMETRY, GL.total);
 	char* img = (char*)alloc(alloc_user, FDGS_BUF_IMAGE, IL.total);
 	if (!geom || !img) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL");
-	float* final_T = (float*)(img + IL.final_T);
-	uint32_t* n_contrib = (uint32_t*)(img + IL.n_contrib);
-	uint32_t* ranges = (uint32_t*)(img + IL.ranges);
-
-	uint32_t* counters = (uint32_t*)(img + IL.tile_counters);
-	uint32_t* ctl = (uint32_t*)(img + IL.bin_ctl);
-	// tile order of the blend kernels (written by the scan); FDGS_TILE_ORDER=0 in the environment: index order (A/B timing)
-	static const bool use_order = []() { const char* e = getenv("FDGS_TILE_ORDER"); return !(e && e[0] == '0'); }();
-	uint32_t* tile_order = use_order ? (uint32_t*)(img + IL.tile_order) : nullptr;
-	const float* records = (const float*)(geom + GL.records);
+	FwdCall f{ s, *out, StageCtx{ stream, debug }, gx, T,
+	           (const uint16_t*)(geom + GL.rect), (const float*)(geom + GL.depths), (const float*)(geom + GL.records),
+	           (uint32_t*)(img + IL.tile_counters), (uint32_t*)(img + IL.bin_ctl), g_use_tile_order ? (uint32_t*)(img + IL.tile_order) : nullptr,
+	           (uint32_t*)(img + IL.ranges), (uint32_t*)(img + IL.n_contrib), (float*)(img + IL.final_T), nullptr, 0u, nullptr };
 	if (P == 0)
 	{
 		// nothing to bin; the blend kernel still writes background colour / T = 1 everywhere
 		if (!alloc(alloc_user, FDGS_BUF_BINNING, bin_layout(0, false, T).total)) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL (binning)");
-		STAGE(FDGS_STAGE_TILE_SORT, hipMemsetAsync(ranges, 0, (size_t)T * 8, stream), "ranges memset");
-		STAGE(FDGS_STAGE_BLEND_FWD, launch_blend_fwd(s, *out, records, nullptr, ranges, nullptr, final_T, n_contrib, nullptr, 0u, 0u, ctl, stream), "blend_fwd");
+		STAGE(f.q, FDGS_STAGE_TILE_SORT, hipMemsetAsync(f.ranges, 0, (size_t)T * 8, stream), "ranges memset");
+		STAGE(f.q, FDGS_STAGE_BLEND_FWD, launch_blend_fwd(s, *out, f.records, nullptr, f.ranges, nullptr, f.final_T, f.n_contrib, nullptr, 0u, 0u, f.ctl, stream), "blend_fwd");
 		return FDGS_OK;
 	}
 
-	// Per-thread forward state, keyed by the device the call runs on (a host thread may drive several GPUs): the second stream
-	// and its events (split_colour), the pinned mailbox, the run-ahead guesses.
-	int dev_id = 0;
-	HIP_TRY(hipGetDevice(&dev_id), "hipGetDevice");
-	if (dev_id < 0 || dev_id >= FDGS_MAX_DEVICES) return fail(FDGS_ERR_UNSUPPORTED, "device ordinal %d beyond %d", dev_id, FDGS_MAX_DEVICES);
-	// split_colour: the SH colours are only needed by the blend -- they are evaluated on a second stream of this thread's while
-	// the binning runs on the caller's (event after the geometry launch, event back before the blend)
-	struct Aux { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-	static thread_local Aux aux_of[FDGS_MAX_DEVICES];
-	Aux& aux = aux_of[dev_id];
+	ThreadState* st = nullptr;
+	if ((rc = thread_state(&st)) != FDGS_OK) return rc;
 	const bool pre = out->preprocessed != 0;   // fdgs_preprocess_batch ran the preprocess of this view (same stream, same buffers)
 	const bool split = out->split_colour != 0 && s.shs != nullptr && !debug && !pre;
 	if (pre) { /* nothing to launch */ }
 	else if (split)
 	{
-		if (!aux.stream)
+		if (!st->aux_stream)
 		{
-			HIP_TRY(hipStreamCreateWithFlags(&aux.stream, hipStreamNonBlocking), "hipStreamCreate");
-			HIP_TRY(hipEventCreateWithFlags(&aux.fork, hipEventDisableTiming), "hipEventCreate");
-			HIP_TRY(hipEventCreateWithFlags(&aux.join, hipEventDisableTiming), "hipEventCreate");
+			HIP_TRY(hipStreamCreateWithFlags(&st->aux_stream, hipStreamNonBlocking), "hipStreamCreate");
+			HIP_TRY(hipEventCreateWithFlags(&st->fork, hipEventDisableTiming), "hipEventCreate");
+			HIP_TRY(hipEventCreateWithFlags(&st->join, hipEventDisableTiming), "hipEventCreate");
 		}
 		// (fdgs_forward_out.colour_stream: the caller's choice of that second stream -- whatever it has enqueued there, e.g. the update
 		// of the SH coefficients, comes before the colours, while geometry and binning on `stream` do not wait for it)
-		hipStream_t const cstream = out->colour_stream ? (hipStream_t)out->colour_stream : aux.stream;
-		STAGE(FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(s, *out, geom, counters, 1, stream), "preprocess_fwd (geometry)");
-		HIP_TRY(hipEventRecord(aux.fork, stream), "hipEventRecord");
-		HIP_TRY(hipStreamWaitEvent(cstream, aux.fork, 0), "hipStreamWaitEvent");
+		hipStream_t const cstream = out->colour_stream ? (hipStream_t)out->colour_stream : st->aux_stream;
+		STAGE(f.q, FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(s, *out, geom, f.counters, 1, stream), "preprocess_fwd (geometry)");
+		HIP_TRY(hipEventRecord(st->fork, stream), "hipEventRecord");
+		HIP_TRY(hipStreamWaitEvent(cstream, st->fork, 0), "hipStreamWaitEvent");
 		{
 			StageTimer timer__(FDGS_STAGE_COLOUR_FWD, cstream);
-			HIP_TRY(launch_preprocess_fwd(s, *out, geom, counters, 2, cstream), "preprocess_fwd (colour)");
+			HIP_TRY(launch_preprocess_fwd(s, *out, geom, f.counters, 2, cstream), "preprocess_fwd (colour)");
 		}
-		HIP_TRY(hipEventRecord(aux.join, cstream), "hipEventRecord");
+		HIP_TRY(hipEventRecord(st->join, cstream), "hipEventRecord");
+		f.join = st->join;
 	}
 	else
-		STAGE(FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(s, *out, geom, counters, 0, stream), "preprocess_fwd");
-	bool joined = !split;   // the blend must not start before the colours are there
-	// whichever way this call returns from here on: work on the second stream writes into this call's geometry buffer, so the
-	// caller's stream waits for it (the buffer may be released in stream order right after an error return)
-	struct JoinGuard
-	{
-		hipStream_t stream; Aux& aux; bool& joined;
-		~JoinGuard() { if (!joined && aux.join) (void)hipStreamWaitEvent(stream, aux.join, 0); }
-	} join_guard{ stream, aux, joined };
-	const uint16_t* rect = (const uint16_t*)(geom + GL.rect);
-	const float* depths = (const float*)(geom + GL.depths);
+		STAGE(f.q, FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(s, *out, geom, f.counters, 0, stream), "preprocess_fwd");
 	// (the count pass is enqueued further down, once it is known whether this forward needs one: sparse lists do not)
 	// num_rendered (and the longest tile list) come back through a pinned, device-mapped mailbox that the scan kernel
 	// writes itself: {R, longest, ticket}, one slot of a small ring per forward.  The host spins on the ticket -- the forward's
 	// one wait for the device, as rasterizer_impl.cu:302, without a copy kernel and a stream synchronisation (~10 us); if the
 	// ticket does not show up (a failed launch), the stream is synchronised and the error reported.  A LAZY forward
 	// (fdgs_forward_out.lazy) does not wait at all: its report is read by a later call (fdgs_forward_lazy_status, or the next forward).
-	if (!g_box_of[dev_id]) g_box_of[dev_id] = new Mailbox();
-	Mailbox& box = *g_box_of[dev_id];
+	Mailbox& box = st->box;
 	if (!box.host)
 	{
 		void* h = nullptr;
@@ -443,8 +542,9 @@ extern "C" int fdgs_rasterize_forward(const fdgs_scene* scene, const fdgs_forwar
 	// to older numbers)
 	if (seq > MAIL_SLOTS && !harvest(box, true, seq - MAIL_SLOTS)) return fail(FDGS_ERR_HIP, "a previous forward did not report num_rendered");
 	const int slot = (int)(seq % MAIL_SLOTS);
-	const uint32_t ticket = ticket_of(seq);
 	volatile uint32_t* const mail = box.host + 4 * slot;
+	f.mail_dev = box.dev + 4 * slot;
+	f.ticket = ticket_of(seq);
 
 	// Run-ahead.  The reference stops here until num_rendered has come back and sizes the binning buffers with it
 	// (rasterizer_impl.cu:302-306): the device idles for a host round trip in the middle of the forward.  Views follow each
@@ -453,168 +553,73 @@ extern "C" int fdgs_rasterize_forward(const fdgs_scene* scene, const fdgs_forwar
 	// everything alone when it does not fit (the sort then reports every tile empty, so the blend behind it reads nothing).
 	// The host picks up the mailbox afterwards (written long before) and, when the guess was too small, starts over from
 	// the scatter pass with exact sizes.
-	// the guess is kept per (device, image size, P): a thread that alternates between scenes or resolutions keeps one per
-	// configuration (a few slots, replaced round-robin)
 	RunAhead* gp = nullptr;
-	for (auto& g : g_guesses) if (g.dev == dev_id && g.W == W && g.H == H && g.P == P) gp = &g;
+	for (auto& g : st->guesses) if (g.W == W && g.H == H && g.P == P) gp = &g;
 	if (!gp)
 	{
-		gp = &g_guesses[g_guess_next];
-		g_guess_next = (g_guess_next + 1) % FDGS_GUESS_SLOTS;
+		gp = &st->guesses[st->guess_next];
+		st->guess_next = (st->guess_next + 1) % FDGS_GUESS_SLOTS;
 		*gp = RunAhead();
-		gp->dev = dev_id; gp->W = W; gp->H = H; gp->P = P;
+		gp->W = W; gp->H = H; gp->P = P;
 	}
-	RunAhead& guess = *gp;
 	MailRec& rec = box.rec[slot];
 	rec = MailRec();
-	rec.seq = seq; rec.guess = gp; rec.gdev = dev_id; rec.gW = W; rec.gH = H; rec.gP = P; rec.pending = true; rec.stream = stream;
+	rec.seq = seq; rec.guess = gp; rec.gW = W; rec.gH = H; rec.gP = P; rec.stream = stream;
 	const int lds_cap = tile_sort_lds_cap();
-	const bool ahead = guess.capacity > 0 && !debug && g_run_ahead_enabled.load(std::memory_order_relaxed);
-	// lazy: nobody is there to start over, so the headroom is generous -- 1.5 x the largest of the last four reports (+ 64 Ki
-	// instances, in steps of 256 Ki so that the allocator sees few distinct sizes), and the sort instances are chosen for lists
-	// 1.5 x the longest one seen; a forward that still does not fit is reported by fdgs_forward_lazy_status
-	const bool lazy = ahead && out->lazy != 0;
-	long long ahead_cap = guess.capacity;
-	int ahead_longest = guess.longest;
-	if (lazy)
+	const bool want_sparse = out->lazy != 0 && out->sparse_lists != 0 && f.tile_order != nullptr;
+	Plan plan = plan_forward(*gp, !debug && g_run_ahead_enabled.load(std::memory_order_relaxed), out->lazy != 0, want_sparse, T, lds_cap,
+	                         g_sparse_min_bytes.load(std::memory_order_relaxed), g_sparse_factor.load(std::memory_order_relaxed));
+	const bool lazy = plan.mode == Mode::Lazy || plan.mode == Mode::Sparse;
+	if (lazy && want_sparse) g_sparse_stats[plan.mode == Mode::Sparse ? 0 : 1]++;
+	if (plan.mode != Mode::Sparse)
 	{
-		long long rmax = 0; int lmax = 0;
-		for (int k = 0; k < 4; k++) { rmax = std::max(rmax, guess.r_hist[k]); lmax = std::max(lmax, guess.l_hist[k]); }
-		// (geometric steps -- 1/16 octave, at least 256 Ki -- because a scene that grows a little every step must not present the
-		// caller's allocator with a new, slightly larger size every few steps: a device allocation of hundreds of MB in the middle
-		// of a running pipeline stalls it for milliseconds; measured on the C5 leg of bench.py, profiles/HISTORY.md round 5)
-		const long long want = rmax + rmax / 2 + 65536;
-		long long q = 1ll << 18;
-		while (q * 32 <= want) q <<= 1;
-		ahead_cap = std::min<long long>((want / q + 1) * q, 0x7fffffffLL);
-		ahead_longest = lmax + lmax / 2 + 64;
+		STAGE(f.q, FDGS_STAGE_TILE_COUNT, launch_tile_count(f.rect, P, gx, T, f.counters, stream), "tile count");
+		STAGE(f.q, FDGS_STAGE_TILE_SCAN, launch_tile_scan(f.counters, T, f.ctl, f.mail_dev, f.ticket, f.tile_order, stream), "tile scan");
+		rec.pending = true;
 	}
-	// SPARSE lists (fdgs_forward_out.sparse_lists, lazy forwards only): tile t's list gets the fixed slots [t * cap, (t + 1) * cap) of the
-	// binning buffer, cap = the longest list provided for (a multiple of 64: the cull planes' words).  Then nobody needs the lists'
-	// starts before the scatter pass -- no count pass, no scan: the scatter counts as it goes (the tile counters start from zero),
-	// the per-tile sort reads each tile's count, and one extra workgroup of its launch reports num_rendered / the longest list and
-	// writes the blend kernels' tile order.  Two launches (~16 us at C3) off the forward's critical chain for address space:
-	// T * cap instead of num_rendered entries (C3: 8.5 M instead of 2.0 M; 288 GB of HBM: DESIGN.md section 4.3).
-	uint32_t sparse_cap = 0u;
-	if (lazy && out->sparse_lists != 0 && tile_order != nullptr && ahead_longest > 0)
+	Lists lists{};
+	if (plan.mode != Mode::Exact)
 	{
-		// a multiple of 64, in steps of 1/8 octave for the same reason as ahead_cap above (one step of 64 is T * 64 entries: 16 MB at C5)
-		long long q = 64;
-		while (q * 16 <= ahead_longest) q <<= 1;
-		const long long cap_tile = ((long long)ahead_longest + q - 1) / q * q;
-		// The price is address space, and it has a budget: ONE long list (a real capture has hot tiles: 16 k entries in one tile of a
-		// 2704 x 2028 image would make T * cap = 4.2 GB per forward in flight) must not turn a 200 MB buffer into gigabytes.  Beyond
-		// max(1 GiB, 4 x the compact buffer of the same guess) -- fdgs_set_sparse_lists_budget -- the forward keeps compact lists.
-		if (cap_tile * (long long)T <= 0x7fffffffLL)
-		{
-			const size_t sparse_bytes = bin_layout((int)(cap_tile * T), (int)cap_tile > lds_cap, T).total;
-			const size_t compact_bytes = bin_layout((int)ahead_cap, ahead_longest > lds_cap, T).total;
-			const long long budget = std::max<long long>(g_sparse_min_bytes.load(std::memory_order_relaxed),
-			                                             (long long)g_sparse_factor.load(std::memory_order_relaxed) * (long long)compact_bytes);
-			if ((long long)sparse_bytes <= budget) sparse_cap = (uint32_t)cap_tile;
-		}
-		g_sparse_stats[sparse_cap != 0u ? 0 : 1]++;
+		if ((rc = alloc_lists(plan, T, alloc, alloc_user, &lists)) != FDGS_OK) return rc;
+		if ((rc = enqueue_lists(f, plan, lists, true)) != FDGS_OK) return rc;
+		rec.pending = true;   // (with sparse lists the sort launch, enqueued just now, is the one that reports)
 	}
-	if (sparse_cap == 0u)
-	{
-		STAGE(FDGS_STAGE_TILE_COUNT, launch_tile_count(rect, P, gx, T, counters, stream), "tile count");
-		STAGE(FDGS_STAGE_TILE_SCAN, launch_tile_scan(counters, T, ctl, box.dev + 4 * slot, ticket, tile_order, stream), "tile scan");
-	}
-	char* bin = nullptr;
-	BinLayout BL = bin_layout(0, false, T);
-	bool has_scratch = false;   // BL includes the global sort scratch
-	if (sparse_cap != 0u)
-	{
-		const long long total = (long long)sparse_cap * T;
-		has_scratch = (int)sparse_cap > lds_cap;
-		BL = bin_layout((int)total, has_scratch, T);
-		bin = (char*)alloc(alloc_user, FDGS_BUF_BINNING, BL.total);
-		if (!bin) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL (binning)");
-		g_sparse_stats[2].store((long long)BL.total);
-		uint32_t* point_list = (uint32_t*)(bin + BL.point_list);
-		uint32_t* pairs = (uint32_t*)(bin + BL.pairs);
-		STAGE(FDGS_STAGE_TILE_SCATTER, launch_tile_scatter(rect, depths, P, gx, T, counters, pairs, ctl, (uint32_t)total, nullptr, stream, sparse_cap), "tile scatter (sparse)");
-		STAGE(FDGS_STAGE_TILE_SORT, launch_tile_sort(counters, T, (int)sparse_cap, pairs, point_list, ranges, has_scratch ? (void*)(bin + BL.big_scratch) : nullptr,
-		                       ctl, (uint32_t)total, nullptr, stream, sparse_cap, ctl, box.dev + 4 * slot, ticket, tile_order), "tile sort (sparse)");
-		if (!joined) { HIP_TRY(hipStreamWaitEvent(stream, aux.join, 0), "hipStreamWaitEvent"); joined = true; }
-		STAGE(FDGS_STAGE_BLEND_FWD, launch_blend_fwd(s, *out, records, point_list, ranges, tile_order, final_T, n_contrib, (unsigned long long*)(bin + BL.cull_bits),
-		                                                   BL.cull_stride, (uint32_t)(BL.cull_bits / 8), ctl, stream), "blend_fwd");
-		rec.lazy = true; rec.cap = total; rec.longest_cap = (int)sparse_cap;
-		*num_rendered = -1;
-		g_run_ahead[0]++;
-		return FDGS_OK;
-	}
-	const auto enqueue_rest = [&](long long capacity, int sort_longest, bool scatter) -> int
-	{
-		uint32_t* point_list = (uint32_t*)(bin + BL.point_list);
-		uint32_t* pairs = (uint32_t*)(bin + BL.pairs);
-		if (scatter)
-			STAGE(FDGS_STAGE_TILE_SCATTER, launch_tile_scatter(rect, depths, P, gx, T, counters, pairs, ctl, (uint32_t)capacity, tile_order, stream), "tile scatter");
-		STAGE(FDGS_STAGE_TILE_SORT, launch_tile_sort(counters, T, sort_longest, pairs, point_list, ranges,
-		                       has_scratch ? (void*)(bin + BL.big_scratch) : nullptr, ctl, (uint32_t)capacity, tile_order, stream), "tile sort");
-		if (!joined) { HIP_TRY(hipStreamWaitEvent(stream, aux.join, 0), "hipStreamWaitEvent"); joined = true; }
-		STAGE(FDGS_STAGE_BLEND_FWD, launch_blend_fwd(s, *out, records, point_list, ranges, tile_order, final_T, n_contrib, (unsigned long long*)(bin + BL.cull_bits),
-		                                                   BL.cull_stride, (uint32_t)(BL.cull_bits / 8), ctl, stream), "blend_fwd");
-		return FDGS_OK;
-	};
-	if (ahead)
-	{
-		has_scratch = ahead_longest > lds_cap;
-		BL = bin_layout((int)ahead_cap, has_scratch, T);
-		bin = (char*)alloc(alloc_user, FDGS_BUF_BINNING, BL.total);
-		if (!bin) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL (binning)");
-		g_sparse_stats[2].store((long long)BL.total);
-		if ((rc = enqueue_rest(ahead_cap, ahead_longest, true)) != FDGS_OK) return rc;
-	}
-
 	if (lazy)
 	{
 		// everything is on its way; the report is read later (the slot stays pending)
-		rec.lazy = true; rec.cap = ahead_cap; rec.longest_cap = ahead_longest;
+		rec.lazy = true; rec.cap = plan.capacity; rec.longest_cap = plan.sort_longest;
 		*num_rendered = -1;
 		g_run_ahead[0]++;
 		return FDGS_OK;
 	}
 	// this call's own report (older pending ones -- lazy forwards -- are read on the way)
 	if (!harvest(box, true, seq)) return fail(FDGS_ERR_HIP, "the tile scan did not report num_rendered (failed launch?)");
-	if (rec.pending || __atomic_load_n(&mail[2], __ATOMIC_ACQUIRE) != ticket) return fail(FDGS_ERR_HIP, "internal: the forward's own report was not read");
+	if (rec.pending || __atomic_load_n(&mail[2], __ATOMIC_ACQUIRE) != f.ticket) return fail(FDGS_ERR_HIP, "internal: the forward's own report was not read");
 	const int R = (int)mail[0], longest = (int)mail[1];
 	if (R < 0) return fail(FDGS_ERR_INVALID_ARG, "num_rendered overflow");
 	*num_rendered = R;
 
-	if (ahead && R <= ahead_cap && longest <= ahead_longest) { g_run_ahead[0]++; return FDGS_OK; }   // the usual case: everything is already on its way
-	if (ahead && R <= ahead_cap)
+	if (plan.mode == Mode::Ahead && R <= plan.capacity)
 	{
+		if (longest <= plan.sort_longest) { g_run_ahead[0]++; return FDGS_OK; }   // the usual case: everything is already on its way
 		g_run_ahead[1]++;
 		// the lists were scattered, but some are longer than the sort instances that were launched take (they were left
 		// unsorted): sort again with the right instances.  Lists beyond the LDS need 8 bytes per instance of scratch; if the
 		// buffer was sized without it, the scratch is borrowed from the stream-ordered allocator for this one call.
 		void* extra = nullptr;
-		if (longest > lds_cap && !has_scratch)
-		{
-			HIP_TRY(hipMallocAsync(&extra, (size_t)ahead_cap * 8 + 256, stream), "hipMallocAsync (sort scratch)");
-		}
-		uint32_t* point_list = (uint32_t*)(bin + BL.point_list);
-		hipError_t sorted;
-		{
-			StageTimer timer__(FDGS_STAGE_TILE_SORT, stream);
-			sorted = launch_tile_sort(counters, T, longest, (const uint32_t*)(bin + BL.pairs), point_list, ranges,
-			                          extra ? extra : (has_scratch ? (void*)(bin + BL.big_scratch) : nullptr), ctl, (uint32_t)ahead_cap, tile_order, stream);
-		}
-		if (extra) HIP_TRY(hipFreeAsync(extra, stream), "hipFreeAsync (sort scratch)");   // stream-ordered: after the sort, whether it was launched or not
-		HIP_TRY(sorted, "tile sort");
-		if (!joined) { HIP_TRY(hipStreamWaitEvent(stream, aux.join, 0), "hipStreamWaitEvent"); joined = true; }
-		STAGE(FDGS_STAGE_BLEND_FWD, launch_blend_fwd(s, *out, records, point_list, ranges, tile_order, final_T, n_contrib, (unsigned long long*)(bin + BL.cull_bits),
-		                                                   BL.cull_stride, (uint32_t)(BL.cull_bits / 8), ctl, stream), "blend_fwd");
-		return FDGS_OK;
+		if (longest > lds_cap && !plan.scratch)
+			HIP_TRY(hipMallocAsync(&extra, (size_t)plan.capacity * 8 + 256, stream), "hipMallocAsync (sort scratch)");
+		plan.sort_longest = longest;
+		rc = enqueue_lists(f, plan, lists, false, extra);
+		const hipError_t freed = extra ? hipFreeAsync(extra, stream) : hipSuccess;   // stream-ordered: after the sort, whether it was launched or not
+		if (rc == FDGS_OK) HIP_TRY(freed, "hipFreeAsync (sort scratch)");
+		return rc;
 	}
 	// first call of this thread, debug mode, or more instances than guessed (nothing was scattered): exact sizes
 	g_run_ahead[2]++;
-	has_scratch = longest > lds_cap;
-	BL = bin_layout(R, has_scratch, T);
-	bin = (char*)alloc(alloc_user, FDGS_BUF_BINNING, BL.total);
-	if (!bin) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL (binning)");
-	return enqueue_rest(R, longest, true);
+	plan = exact_plan(R, longest, lds_cap);
+	if ((rc = alloc_lists(plan, T, alloc, alloc_user, &lists)) != FDGS_OK) return rc;
+	return enqueue_lists(f, plan, lists, true);
 }
 
 extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backward_in* in,
@@ -628,7 +633,7 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	if (out->adam != nullptr)
 	{
 		const fdgs_geometry_adam* g = out->adam;
-		if (g->struct_size != sizeof(fdgs_geometry_adam)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_geometry_adam.struct_size is %u, expected %zu", (unsigned)g->struct_size, sizeof(fdgs_geometry_adam));
+		CHECK_STRUCT(g, fdgs_geometry_adam);
 		if (!scene->raw_params || scene->cov3D_precomp || !scene->scales || !scene->rotations || !scene->ts || !scene->scales_t || !scene->rotations_r)
 			return fail(FDGS_ERR_INVALID_ARG, "fdgs_backward_out.adam needs a raw_params scene that holds all seven geometry tensors (rot_4d): an optimizer steps the "
 			                                  "parameters a 3D scene leaves out as well, this call could not");
@@ -641,7 +646,7 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	if (rc != FDGS_OK) return rc;
 	const fdgs_scene& s = *scene;
 	hipStream_t stream = (hipStream_t)stream_v;
-	const bool debug = s.debug != 0;
+	const StageCtx q{ stream, s.debug != 0 };
 	const int P = s.P, W = s.W, H = s.H;
 	if (P == 0) return FDGS_OK;
 	if ((!in->dL_dout_color && !in->dL_dout_depth && !in->dL_dout_alpha && !in->dL_dout_flow) ||
@@ -666,7 +671,7 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	const uint32_t* point_list = (const uint32_t*)(bin + BL.point_list);
 
 	// the forward's tile order (left in the image buffer by the scan); not there for P == 0 (returned above) or with FDGS_TILE_ORDER=0
-	static const bool bwd_order = []() { const char* e = getenv("FDGS_TILE_ORDER"); return !(e && e[0] == '0'); }();
+	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;
 	if (out->stage_mask < 0 || out->stage_mask > 5 || ((out->stage_mask & 4) && out->stage_mask != 5))
 		return fail(FDGS_ERR_INVALID_ARG, "stage_mask %d: 0 / 3 (whole backward), 1 (blend + SH backward), 2 (geometry backward) or 5 (blend backward only; "
 		            "the SH backward is left to fdgs_sh_backward_batch, then 2)", out->stage_mask);
@@ -677,15 +682,15 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	{
 		// the packed accumulator records of the blend backward start from zero
 		if (!out->grad_accum_clean)
-			STAGE(FDGS_STAGE_GRAD_ZERO, hipMemsetAsync(out->grad_accum, 0, (size_t)P * GRAD_ACC_WORDS * 4, stream), "memset");
+			STAGE(q, FDGS_STAGE_GRAD_ZERO, hipMemsetAsync(out->grad_accum, 0, (size_t)P * GRAD_ACC_WORDS * 4, stream), "memset");
 		if (R != 0)
-			STAGE(FDGS_STAGE_BLEND_BWD, launch_blend_bwd(s, *in, *out, (const float*)(geom + GL.records), point_list, (const uint32_t*)(img + IL.ranges),
-			                       bwd_order ? (const uint32_t*)(img + IL.tile_order) : nullptr, (const float*)(img + IL.final_T), (const uint32_t*)(img + IL.n_contrib),
+			STAGE(q, FDGS_STAGE_BLEND_BWD, launch_blend_bwd(s, *in, *out, (const float*)(geom + GL.records), point_list, (const uint32_t*)(img + IL.ranges),
+			                       tile_order, (const float*)(img + IL.final_T), (const uint32_t*)(img + IL.n_contrib),
 			                       (const uint32_t*)(img + IL.bin_ctl), stream), "blend_bwd");
-		if (!(out->stage_mask & 4)) STAGE(FDGS_STAGE_SH_BWD, launch_sh_bwd(s, *in, *out, geom, stream), "sh_bwd");
+		if (!(out->stage_mask & 4)) STAGE(q, FDGS_STAGE_SH_BWD, launch_sh_bwd(s, *in, *out, geom, stream), "sh_bwd");
 	}
 	if (stages & 2)
-		STAGE(FDGS_STAGE_PREPROCESS_BWD, launch_preprocess_bwd(s, *in, *out, geom, stream), "preprocess_bwd");
+		STAGE(q, FDGS_STAGE_PREPROCESS_BWD, launch_preprocess_bwd(s, *in, *out, geom, stream), "preprocess_bwd");
 	return FDGS_OK;
 }
 
@@ -700,26 +705,41 @@ static int check_same_gaussians(const fdgs_scene& a, const fdgs_scene& b, int v)
 	return FDGS_OK;
 }
 
+constexpr int FDGS_MAX_BATCH_VIEWS = 64;   // views one batched call takes
+
+// the scenes of a batched call `fn`: a supported number of views, each scene valid by itself, all describing the same Gaussians
+static int check_batch_scenes(const char* fn, int num_views, const fdgs_scene* const* scenes)
+{
+	if (num_views < 1 || num_views > FDGS_MAX_BATCH_VIEWS || !scenes) return fail(FDGS_ERR_INVALID_ARG, "%s: bad arguments", fn);
+	for (int v = 0; v < num_views; v++)
+	{
+		if (!scenes[v]) return fail(FDGS_ERR_INVALID_ARG, "%s: view %d is NULL", fn, v);
+		CHECK_STRUCT(scenes[v], fdgs_scene);
+		int rc = check_scene(scenes[v]);
+		if (rc != FDGS_OK) return rc;
+		if ((rc = check_same_gaussians(*scenes[0], *scenes[v], v)) != FDGS_OK) return rc;
+	}
+	return FDGS_OK;
+}
+
 extern "C" int fdgs_preprocess_batch(int32_t num_views, const fdgs_scene* const* scenes, const fdgs_forward_out* const* outs,
                                      fdgs_alloc_fn alloc, void* const* alloc_users, void* stream_v)
 {
 	g_err[0] = 0;
-	if (num_views < 1 || num_views > 64 || !scenes || !outs || !alloc || !alloc_users) return fail(FDGS_ERR_INVALID_ARG, "fdgs_preprocess_batch: bad arguments");
+	if (!outs || !alloc || !alloc_users) return fail(FDGS_ERR_INVALID_ARG, "fdgs_preprocess_batch: bad arguments");
+	const int rc = check_batch_scenes("fdgs_preprocess_batch", num_views, scenes);
+	if (rc != FDGS_OK) return rc;
 	hipStream_t stream = (hipStream_t)stream_v;
-	char* geoms[64];
+	char* geoms[FDGS_MAX_BATCH_VIEWS];
 	for (int v = 0; v < num_views; v++)
 	{
-		if (!scenes[v] || !outs[v]) return fail(FDGS_ERR_INVALID_ARG, "fdgs_preprocess_batch: view %d is NULL", v);
-		CHECK_STRUCT(scenes[v], fdgs_scene);
+		if (!outs[v]) return fail(FDGS_ERR_INVALID_ARG, "fdgs_preprocess_batch: view %d is NULL", v);
 		CHECK_STRUCT(outs[v], fdgs_forward_out);
-		int rc = check_scene(scenes[v]);
-		if (rc != FDGS_OK) return rc;
-		if ((rc = check_same_gaussians(*scenes[0], *scenes[v], v)) != FDGS_OK) return rc;
 		if (scenes[v]->P > 0 && (!outs[v]->radii || !outs[v]->out_means3D)) return fail(FDGS_ERR_INVALID_ARG, "forward outputs must not be NULL");
 	}
 	const fdgs_scene& s0 = *scenes[0];
 	if (s0.P == 0) return FDGS_OK;   // the views' forward calls handle the empty model themselves
-	const bool debug = s0.debug != 0;
+	const StageCtx q{ stream, s0.debug != 0 };
 	const GeomLayout GL = geom_layout(s0.P);
 	const ImageLayout IL = image_layout(s0.W, s0.H);
 	for (int v = 0; v < num_views; v++)
@@ -729,9 +749,9 @@ extern "C" int fdgs_preprocess_batch(int32_t num_views, const fdgs_scene* const*
 		if (!geoms[v] || !img) return fail(FDGS_ERR_ALLOC, "scratch allocator returned NULL");
 		uint32_t* counters = (uint32_t*)(img + IL.tile_counters);
 		// with SH: geometry now, colours for all views below; precomputed colours: the whole preprocess per view
-		STAGE(FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(*scenes[v], *outs[v], geoms[v], counters, s0.shs ? 1 : 0, stream), "preprocess_fwd (geometry)");
+		STAGE(q, FDGS_STAGE_PREPROCESS_FWD, launch_preprocess_fwd(*scenes[v], *outs[v], geoms[v], counters, s0.shs ? 1 : 0, stream), "preprocess_fwd (geometry)");
 	}
-	if (s0.shs) STAGE(FDGS_STAGE_COLOUR_FWD, launch_colour_batch(num_views, scenes, outs, geoms, stream), "colour batch");
+	if (s0.shs) STAGE(q, FDGS_STAGE_COLOUR_FWD, launch_colour_batch(num_views, scenes, outs, geoms, stream), "colour batch");
 	return FDGS_OK;
 }
 
@@ -739,25 +759,22 @@ extern "C" int fdgs_sh_backward_batch(int32_t num_views, const fdgs_scene* const
                                       const fdgs_backward_out* const* outs, void* stream_v)
 {
 	g_err[0] = 0;
-	if (num_views < 1 || num_views > 64 || !scenes || !ins || !outs) return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: bad arguments");
-	hipStream_t stream = (hipStream_t)stream_v;
+	if (!ins || !outs) return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: bad arguments");
+	const int rc = check_batch_scenes("fdgs_sh_backward_batch", num_views, scenes);
+	if (rc != FDGS_OK) return rc;
 	for (int v = 0; v < num_views; v++)
 	{
-		if (!scenes[v] || !ins[v] || !outs[v]) return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: view %d is NULL", v);
-		CHECK_STRUCT(scenes[v], fdgs_scene);
+		if (!ins[v] || !outs[v]) return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: view %d is NULL", v);
 		CHECK_STRUCT(ins[v], fdgs_backward_in);
 		CHECK_STRUCT(outs[v], fdgs_backward_out);
-		int rc = check_scene(scenes[v]);
-		if (rc != FDGS_OK) return rc;
-		if ((rc = check_same_gaussians(*scenes[0], *scenes[v], v)) != FDGS_OK) return rc;
 		if (scenes[v]->P > 0 && scenes[v]->shs && (!ins[v]->radii || !ins[v]->out_means3D || !ins[v]->geom_buffer || !outs[v]->grad_accum || !outs[v]->sh_stage))
 			return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: view %d needs radii, out_means3D, geom_buffer, grad_accum and sh_stage", v);
 		for (int w = 0; w < v; w++)
 			if (scenes[v]->P > 0 && (outs[w]->grad_accum == outs[v]->grad_accum || outs[w]->sh_stage == outs[v]->sh_stage))
 				return fail(FDGS_ERR_INVALID_ARG, "fdgs_sh_backward_batch: views %d and %d share grad_accum / sh_stage", w, v);
 	}
-	const bool debug = scenes[0]->debug != 0;
-	STAGE(FDGS_STAGE_SH_BWD, launch_sh_bwd_batch(num_views, scenes, ins, outs, stream), "sh_bwd batch");
+	const StageCtx q{ (hipStream_t)stream_v, scenes[0]->debug != 0 };
+	STAGE(q, FDGS_STAGE_SH_BWD, launch_sh_bwd_batch(num_views, scenes, ins, outs, q.stream), "sh_bwd batch");
 	return FDGS_OK;
 }
 

@@ -565,6 +565,43 @@ def test_forward_run_ahead_matches_exact_path(gpu_device):
     assert longest[3] > 4096 > longest[2] + longest[2] // 4 and longest[2] > longest[1] + longest[1] // 4 and Rs[1] > 2 * Rs[0]
 
 
+def test_sort_again_borrows_scratch_for_lists_beyond_the_lds(gpu_device):
+    """The run-ahead forward that has to sort again, with lists longer than the LDS takes in a binning buffer that was sized without
+    the global sort scratch (the guess knew only lists that fit): the scratch is borrowed from the stream-ordered allocator for that one
+    call.  The LDS limit is lowered (fdgs_debug_tile_sort_limits) to lie between the guessed longest list and the real one; every output
+    equals the exact path's bit for bit."""
+    from fdgs import _capi
+    cfg = SC("ra2", 30029, 320, 240, 0, 0, 0.03, 1.0, True, 4, True)   # a P no other test uses: the guess is this test's own
+
+    def variant(k_mean, k_scale):
+        sc = synth.make_scene(cfg, seed=40)
+        sc["means3D"] = (sc["means3D"] * torch.tensor([k_mean, k_mean, 1.0])).contiguous()
+        sc["scales"] = (sc["scales"] * k_scale).contiguous()
+        return sc
+
+    def longest_of(res):
+        return int((res["ranges"][:, 1].astype(np.int64) - res["ranges"][:, 0]).max())
+
+    b, c = variant(1.0, 1.0), variant(0.5, 0.45)   # steps "b" and "c" of test_forward_run_ahead_matches_exact_path
+    exact, _ = run_hip(dict(c, debug=True), gpu_device, None)
+    L_c = longest_of(exact)
+    guess, _ = run_hip(b, gpu_device, None)        # leaves the guess behind: capacity from R_b, sort instances for L_b + L_b // 4
+    L_b = longest_of(guess)
+    cap = L_b + L_b // 4
+    print("sort again with borrowed scratch: R", guess["R"], exact["R"], "longest", L_b, L_c, "LDS limit", cap)
+    assert L_c > cap, (L_b, L_c)
+    try:
+        _capi.lib.fdgs_debug_tile_sort_limits(cap, 0)
+        before = _capi.run_ahead_stats()
+        fast, _ = run_hip(c, gpu_device, None)
+        assert tuple(y - x for x, y in zip(before, _capi.run_ahead_stats())) == (0, 1, 0)
+    finally:
+        _capi.lib.fdgs_debug_tile_sort_limits(0, 0)
+    assert fast["R"] == exact["R"]
+    for key in ("point_list", "ranges", "n_contrib", "final_T", "out_color", "out_depth", "out_flow", "radii"):
+        np.testing.assert_array_equal(fast[key], exact[key], err_msg="sort again, borrowed scratch: " + key)
+
+
 def test_run_ahead_can_be_switched_off(gpu_device):
     """fdgs_set_run_ahead(0): every forward waits for num_rendered and sizes the binning buffer exactly (the reference's contract)."""
     from fdgs import _capi

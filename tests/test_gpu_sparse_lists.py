@@ -229,3 +229,33 @@ def test_one_hot_tile_does_not_buy_gigabytes(gpu_device):
     assert s1[2] < 64 << 20 and res[7].numel() == s1[2] and peak < 512 << 20 and would_be > 4 * 2**30
     for i in (1, 3, 4, 5):
         assert torch.equal(res[i], first[i])
+
+
+def test_failed_binning_allocation_leaves_the_thread_usable(gpu_device, monkeypatch):
+    """A sparse forward whose binning allocation fails (the scratch allocator returns NULL on out-of-memory) returns FDGS_ERR_ALLOC
+    before anything that would report for it is enqueued: its mailbox record must not stay pending, or the thread's later status calls
+    and forwards would wait for a report that never comes."""
+    from fdgs import _capi
+    from fdgs.gaussian_renderer import diff_gaussian_rasterization as dgr
+    cfg = SC("spa", 24007, 320, 240, 1, 0, 0.03, 1.0, True, 4, True)
+    scene = synth.make_scene(cfg, seed=12, pose="rig1")
+    sc = scene_to_device(scene, gpu_device)
+    _capi.forward_lazy_status(gpu_device, wait=True)
+    first = _fwd(sc)
+    warm = _fwd(sc, lazy=True, sparse_lists=True)
+    assert warm[0] == -1 and _capi.forward_lazy_status(gpu_device, wait=True) == (0, 0, [first[0]])
+    real_alloc = dgr._Scratch._alloc
+
+    def no_binning(self, user, which, nbytes):
+        return None if int(which) == _capi.FDGS_BUF_BINNING else real_alloc(self, user, which, nbytes)
+
+    s0 = _capi.sparse_lists_stats()
+    with monkeypatch.context() as m:
+        m.setattr(dgr._Scratch, "_alloc", no_binning)
+        with pytest.raises(RuntimeError, match=r"\(code 3\)"):
+            _fwd(sc, lazy=True, sparse_lists=True)
+    assert _capi.sparse_lists_stats()[0] - s0[0] == 1, "the failed forward was not on the sparse path"
+    assert _capi.forward_lazy_status(gpu_device, wait=True) == (0, 0, [])
+    again = _fwd(sc, lazy=True, sparse_lists=True)
+    assert again[0] == -1 and _capi.forward_lazy_status(gpu_device, wait=True) == (0, 0, [first[0]])
+    assert torch.equal(again[1], first[1])
