@@ -634,11 +634,11 @@ def l1_loss(network_output, gt):
     return torch.abs(network_output - gt).mean()
 
 
-_WINDOWS: Dict[Tuple[int, int, str], torch.Tensor] = {}
+_WINDOWS: Dict[Tuple[int, int, str, torch.dtype], torch.Tensor] = {}
 
 
 def _window(window_size: int, channel: int, like: torch.Tensor) -> torch.Tensor:
-    key = (window_size, channel, str(like.device))
+    key = (window_size, channel, str(like.device), like.dtype)   # (the dtype too: a float64 and a float32 evaluation in one process)
     w = _WINDOWS.get(key)
     if w is None:
         g = torch.tensor([math.exp(-(x - window_size // 2) ** 2 / float(2 * 1.5 ** 2)) for x in range(window_size)])

@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 import torch
 
+import loss_cases
+
 pytestmark = pytest.mark.gpu
 
 GOLDEN = sorted(glob.glob(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "ssim_*.npz")))
@@ -42,12 +44,8 @@ def test_fused_l1_ssim_matches_reference_fixtures(path, gpu_device):
 def test_fused_l1_ssim_matches_reference_loss(shape, lam, gpu_device):
     from fdgs import train_host
     from fdgs.loss import fused_l1_ssim
-    g = torch.Generator().manual_seed(5)
     # smooth-ish images in [0, 1] plus noise, like a render vs a photo
-    base = torch.rand(shape[0], shape[1] // 4 + 2, shape[2] // 4 + 2, generator=g)
-    up = torch.nn.functional.interpolate(base[None], size=shape[1:], mode="bilinear", align_corners=False)[0]
-    img = (up + 0.1 * torch.randn(shape, generator=g)).clamp(0, 1)
-    gt = (up.flip(-1) * 0.5 + 0.5 * torch.rand(shape, generator=g)).clamp(0, 1)
+    img, gt = loss_cases.smooth(shape, 5)
 
     x64 = img.double().requires_grad_(True)
     ref = train_host.photometric_loss(x64, gt.double(), lam)
