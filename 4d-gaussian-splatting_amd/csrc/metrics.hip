@@ -16,7 +16,7 @@
 //   finish kernel: one workgroup, fixed summation order (double), writes out4 = [l1, psnr, ssim, msssim]: bitwise reproducible, one
 //                  view's row depends on nothing but that view.
 #include <math.h>
-#include "fdgs_common.h"
+#include "ssim_window.h"
 
 namespace fdgs
 {
@@ -24,40 +24,14 @@ namespace metrics
 {
 	constexpr int TX = 32, TY = 32;     // output tile
 	constexpr int ROWS = TY / 8;        // adjacent output rows a thread finishes in the vertical pass (32 columns x 8 row groups)
-	constexpr int R = 5;                // window radius (11 taps)
-	constexpr int HW_ = TX + 2 * R;     // 42: tile + halo, columns
-	constexpr int HH = TY + 2 * R;      // 42: rows
+	constexpr int R = SR;               // window radius
+	constexpr int HH = TY + 2 * R;      // 42: rows of tile + halo (and columns: TX + 2 * R)
 	constexpr int SSTR = 46;            // LDS row strides in (u, v) pairs (the bank-conflict choice of ssim.hip)
 	constexpr int HSTR = 38;
-	constexpr int THREADS = 256;
+	constexpr int THREADS = STHREADS;
 	constexpr int NPART = 5;            // partial sums per tile: |x-y|, (x-y)^2, ssim (all own pixels), S, CS (valid region)
 	constexpr int SCALES = 5;
 	constexpr int MIN_SIDE = 176;       // torchmetrics: H // 16 > 10 and W // 16 > 10 for five scales and an 11-tap window
-	typedef float v2f __attribute__((ext_vector_type(2)));
-	typedef float v4f __attribute__((ext_vector_type(4)));
-
-	// gaussian(11, 1.5) normalised, as utils/loss_utils.py:23-25 (the same constants as ssim.hip)
-	__device__ constexpr float GW[11] = {
-		0.0010283801f, 0.0075987582f, 0.0360007733f, 0.1093606874f, 0.2130055279f, 0.2660117149f,
-		0.2130055279f, 0.1093606874f, 0.0360007733f, 0.0075987582f, 0.0010283801f };
-
-	// workgroup -> tile: XCD j takes the j-th eighth of the tiles in row-major order (ssim.hip: halo neighbours share one L2).
-	// Tiles are numbered channel by channel, so channel c's partials are the contiguous range [c * gx * gy, (c + 1) * gx * gy).
-	struct Tile { int tx, ty, c, index; bool valid; };
-	__device__ __forceinline__ Tile tile_of(int gx, int gy, int C)
-	{
-		const int total = gx * gy * C, chunk = (total + 7) / 8;
-		const int wg = (int)blockIdx.x, xcd = wg & 7, k = wg >> 3;
-		Tile t;
-		t.index = xcd * chunk + k;
-		t.valid = k < chunk && t.index < total;
-		const int i = t.valid ? t.index : 0;
-		t.c = i / (gx * gy);
-		const int r = i - t.c * (gx * gy);
-		t.ty = r / gx; t.tx = r - t.ty * gx;
-		return t;
-	}
-	static inline int grid_of(int ntiles) { return ((ntiles + 7) / 8) * 8; }
 	static inline int tiles_of(int C, int H, int W) { return div_up(W, TX) * div_up(H, TY) * C; }
 
 	__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
@@ -76,42 +50,23 @@ namespace metrics
 		v2f (*h_s)[HSTR] = reinterpret_cast<v2f (*)[HSTR]>(s_raw + HM_BYTES);     // (u^2, v^2): over the input tile once it is read
 		__shared__ float red[NPART][THREADS / WAVE];
 
-		const Tile tile = tile_of((W + TX - 1) / TX, (H + TY - 1) / TY, C);
+		const TileId tile = tile_of((W + TX - 1) / TX, (H + TY - 1) / TY, C);
 		if (!tile.valid) return;
 		const int c = tile.c;
 		const int x0 = tile.tx * TX, y0 = tile.ty * TY;
 		const int tid = threadIdx.x;
 		const size_t plane = (size_t)c * H * W;
 
-		// halo: thread -> one column of the 42 and rows tid / 42, + 6, + 12, ... (252 of the 256 threads), every load in flight at once
-		float l1 = 0.f, sq = 0.f;
-		{
-			constexpr int RPT = THREADS / HW_, TRIPS = (HH + RPT - 1) / RPT;
-			const int lyb = tid / HW_, hx = tid - lyb * HW_;
-			const int gxh = x0 + hx - R;
-			const bool col_in = tid < RPT * HW_ && (unsigned)gxh < (unsigned)W;
-			const bool col_own = (unsigned)(hx - R) < (unsigned)TX;
-			v2f p[TRIPS];
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT, gy = y0 + ly - R;
-				const bool in = col_in && ly < HH && (unsigned)gy < (unsigned)H;
-				const size_t o = in ? plane + (size_t)gy * W + gxh : plane;   // branch-free: outside lanes read a valid address
+		// halo; the render clamped on load; |x - y| and (x - y)^2 summed over the own pixels
+		float sums[NPART] = { 0.f, 0.f, 0.f, 0.f, 0.f };   // |x-y|, (x-y)^2, ssim, S, CS
+		load_halo<TX, TY, R>(tid, x0, y0, H, W, plane,
+			[&](size_t o, bool in) {
 				const float va = a[o], vb = b[o];
 				const float vx = clamp_a ? clamp01(va) : va;
-				p[t] = in ? v2f{ vx + vb, vx - vb } : v2f{ 0.0f, 0.0f };      // zero padding outside the image
-			}
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT;
-				if (tid < RPT * HW_ && ly < HH) s_in[ly][hx] = p[t];
-				const bool own = col_own && (unsigned)(ly - R) < (unsigned)TY;   // (outside the image: 0 - 0)
-				l1 += own ? fabsf(p[t].y) : 0.0f;
-				sq += own ? p[t].y * p[t].y : 0.0f;
-			}
-		}
+				return in ? v2f{ vx + vb, vx - vb } : v2f{ 0.0f, 0.0f };
+			},
+			[&](int ly, int hx, v2f p) { s_in[ly][hx] = p; },
+			[&](v2f p, bool own) { sums[0] += own ? fabsf(p.y) : 0.0f; sums[1] += own ? p.y * p.y : 0.0f; });
 		// the pooled pair of the own 32x32 pixels: thread -> one of the 16x16 outputs (avg_pool2d(2, 2): an odd last row / column is
 		// dropped).  Its four source pixels were just loaded by this workgroup: L2 / L1 hits.
 		if (pa)
@@ -131,92 +86,32 @@ namespace metrics
 		}
 		__syncthreads();
 
-		// horizontal pass: task -> (row, 4 adjacent columns); results wait in registers until every task has read its inputs
-		constexpr int HR = (HH * (TX / 4) + THREADS - 1) / THREADS;
-		v2f as[HR][4];
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * THREADS;
-			if (task < HH * (TX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v2f p[16], s2[14];
-				const v4f* src = reinterpret_cast<const v4f*>(&s_in[ly][cx]);
-#pragma unroll
-				for (int i = 0; i < 7; i++) { const v4f q = src[i]; p[2 * i] = v2f{ q.x, q.y }; p[2 * i + 1] = v2f{ q.z, q.w }; }
-#pragma unroll
-				for (int i = 0; i < 14; i++) s2[i] = p[i] * p[i];
-				v2f am[4];
-#pragma unroll
-				for (int j = 0; j < 4; j++)
-				{
-					am[j] = GW[0] * p[j]; as[r][j] = GW[0] * s2[j];
-#pragma unroll
-					for (int k = 1; k < 11; k++) { am[j] += GW[k] * p[j + k]; as[r][j] += GW[k] * s2[j + k]; }
-				}
-				v4f* dm = reinterpret_cast<v4f*>(&h_m[ly][cx]);
-				dm[0] = v4f{ am[0].x, am[0].y, am[1].x, am[1].y }; dm[1] = v4f{ am[2].x, am[2].y, am[3].x, am[3].y };
-			}
-			__builtin_amdgcn_sched_barrier(0);
-		}
+		// horizontal pass: the (u^2, v^2) results wait in registers until every task has read its inputs
+		v2f as[hpass_rounds(HH, TX / 4)][4];
+		hpass_tasks<HH, TX / 4, true>(tid, [&](int r, int ly, int cx) {
+			v2f am[4];
+			hwin4_sq(&s_in[ly][cx], am, as[r]);
+			store4(&h_m[ly][cx], am);
+		});
 		__syncthreads();   // the input tile has been read: its bytes become h_s
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * THREADS;
-			if (task < HH * (TX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v4f* ds = reinterpret_cast<v4f*>(&h_s[ly][cx]);
-				ds[0] = v4f{ as[r][0].x, as[r][0].y, as[r][1].x, as[r][1].y }; ds[1] = v4f{ as[r][2].x, as[r][2].y, as[r][3].x, as[r][3].y };
-			}
-		}
+		hpass_tasks<HH, TX / 4, false>(tid, [&](int r, int ly, int cx) { store4(&h_s[ly][cx], as[r]); });
 		__syncthreads();
 
 		// vertical pass: thread -> (column, ROWS adjacent rows); SSIM as ssim_fwd_kernel computes it, plus CS on the valid region
 		const int lx = tid & (TX - 1), ly0 = (tid >> 5) * ROWS;
-		v2f vm[10 + ROWS], vs[10 + ROWS];
-#pragma unroll
-		for (int r = 0; r < 10 + ROWS; r++) { vm[r] = h_m[ly0 + r][lx]; vs[r] = h_s[ly0 + r][lx]; }
-		float sv = 0.f, svv = 0.f, csv = 0.f;
 		const int gx = x0 + lx;
 		const bool col_valid = gx >= R && gx < W - R;
-#pragma unroll
-		for (int j = 0; j < ROWS; j++)
-		{
-			v2f mu = GW[0] * vm[j], e2 = GW[0] * vs[j];
-#pragma unroll
-			for (int k = 1; k < 11; k++) { mu += GW[k] * vm[j + k]; e2 += GW[k] * vs[j + k]; }
+		vpass2<ROWS>(h_m, h_s, ly0, lx, [&](int j, v2f mu, v2f e2) {
 			const int gy = y0 + ly0 + j;
 			if (gx < W && gy < H)
 			{
-				const float mu1 = 0.5f * (mu.x + mu.y), mu2 = 0.5f * (mu.x - mu.y);
-				const float e_sum = 0.5f * (e2.x + e2.y), e12 = 0.25f * (e2.x - e2.y);
-				const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-				const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-				const float sg12 = e12 - mu12;
-				const float A = 2.f * mu12 + C1, B = 2.f * sg12 + C2, Cc = mu1_sq + mu2_sq + C1, D = (e_sum - (mu1_sq + mu2_sq)) + C2;
-				const float rC = __builtin_amdgcn_rcpf(Cc), rD = __builtin_amdgcn_rcpf(D);
-				const float m = A * B * (rC * rD);
-				sv += m;
-				if (col_valid && gy >= R && gy < H - R) { svv += m; csv += B * rD; }
+				const Ssim s = ssim_from_uv(mu, e2);
+				sums[2] += s.m;
+				if (col_valid && gy >= R && gy < H - R) { sums[3] += s.m; sums[4] += s.B * s.rD; }
 			}
-		}
-		float v[NPART] = { l1, sq, sv, svv, csv };
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1)
-		{
-#pragma unroll
-			for (int k = 0; k < NPART; k++) v[k] += __shfl_down(v[k], o);
-		}
-		if ((tid & 63) == 0)
-		{
-#pragma unroll
-			for (int k = 0; k < NPART; k++) red[k][tid >> 6] = v[k];
-		}
-		__syncthreads();
-		if (tid < NPART) part[(size_t)tid * ntiles + tile.index] = (red[tid][0] + red[tid][1]) + (red[tid][2] + red[tid][3]);
+		});
+		tile_reduce(sums, red, tid);
+		if (tid < NPART) part[(size_t)tid * ntiles + tile.index] = sum4<true>(red[tid]);
 	}
 
 	struct Plan

@@ -20,19 +20,15 @@
 //   backward: dL/dx(p) = w_l1 sign(x-y) + w_ssim [ (W * dmu1)(p) + 2 x(p) (W * dE11)(p) + y(p) (W * dE12)(p) ]
 //             -- three more separable windows over the stored derivative maps (W symmetric).
 // fp32, ~200 VALU instructions per pixel-channel forward, ~100 backward; no MFMA (11-tap separable stencil).
+// The window machinery itself -- halo load, horizontal and vertical passes, SSIM algebra, tile sums -- is ssim_window.h, shared with metrics.hip.
 #include <cstdlib>
-#include "fdgs_common.h"
+#include "ssim_window.h"
 
 namespace fdgs
 {
-#ifndef FDGS_SSIM_STY
-#define FDGS_SSIM_STY 32   // 16: the tile of rounds 1-3 (A/B: FDGS_EXTRA_FLAGS=-DFDGS_SSIM_STY=16 csrc/build.sh)
-#endif
-	constexpr int STX = 32, STY = FDGS_SSIM_STY;    // output tile (rows: 16 or 32)
+	constexpr int STX = 32, STY = 32;    // output tile
 	constexpr int SROWS = STY / 8;       // adjacent output rows a thread finishes in the vertical pass (256 threads = 32 columns x 8 row groups)
-	constexpr int SR = 5;                // window radius (11 taps)
-	constexpr int SW = STX + 2 * SR;     // 42: tile + halo, columns
-	constexpr int SHH = STY + 2 * SR;    // 26: rows
+	constexpr int SHH = STY + 2 * SR;    // 42: rows of tile + halo (and columns: STX + 2 * SR)
 	// LDS row strides (16-byte aligned rows for the b128 accesses), chosen for the banks.  In the horizontal pass 8 threads take a
 	// row and a wave 8 rows; a thread's b128 touches 4 of every 8 dwords of a pair-array row, so consecutive rows must be offset by
 	// 4 (mod 8) dwords or all 8 rows fall on the same half of the banks (measured with strides 44 / 36: 41 % of the backward's LDS
@@ -43,34 +39,6 @@ namespace fdgs
 	constexpr int SSTR1 = 48;            // input tile of the backward's scalar map
 	constexpr int HSTR = 38;             // horizontally filtered moments, pair arrays
 	constexpr int HSTR1B = 36;           // ... of the backward (48 would cost its sixth workgroup per CU)
-	constexpr int STHREADS = 256;
-	typedef float v2f __attribute__((ext_vector_type(2)));
-	typedef float v4f __attribute__((ext_vector_type(4)));
-
-	// Workgroup -> tile.  The hardware deals consecutive workgroup ids round-robin to the 8 XCDs, each with its own L2: with the
-	// plain (x, y, channel) grid the tiles that share a halo -- horizontal neighbours -- always sit on DIFFERENT XCDs and every halo
-	// byte is fetched from memory once per tile that needs it (FETCH_SIZE: 1.6 x the tile bytes).  Here XCD j takes the j-th eighth of
-	// the tiles in row-major order -- a band of tile rows of one channel -- so that neighbours meet in one L2.
-	struct TileId { int tx, ty, c, index; bool valid; };
-	__device__ __forceinline__ TileId ssim_tile_of(int gx, int gy, int C)
-	{
-		const int total = gx * gy * C, chunk = (total + 7) / 8;
-		const int wg = (int)blockIdx.x, xcd = wg & 7, k = wg >> 3;
-		TileId t;
-		t.index = xcd * chunk + k;
-		t.valid = k < chunk && t.index < total;
-		const int i = t.valid ? t.index : 0;
-		t.c = i / (gx * gy);
-		const int r = i - t.c * (gx * gy);
-		t.ty = r / gx; t.tx = r - t.ty * gx;
-		return t;
-	}
-	static inline int ssim_grid(int gx, int gy, int C) { return ((gx * gy * C + 7) / 8) * 8; }
-
-	// gaussian(11, 1.5) normalised, as utils/loss_utils.py:23-25
-	__device__ constexpr float GW[11] = {
-		0.0010283801f, 0.0075987582f, 0.0360007733f, 0.1093606874f, 0.2130055279f, 0.2660117149f,
-		0.2130055279f, 0.1093606874f, 0.0360007733f, 0.0075987582f, 0.0010283801f };
 
 	__global__ void __launch_bounds__(STHREADS) ssim_fwd_kernel(
 		const float* __restrict__ img1, const float* __restrict__ img2, int C, int H, int W,
@@ -82,10 +50,9 @@ namespace fdgs
 		// (32-row tile): four workgroups per CU instead of three.  (All three behind the barrier: 16 more VGPRs for nothing -- the
 		// results are larger than the inputs.)
 		// Round 6: FOUR moment channels instead of five, all of them packed pairs.  With u = x + y, v = x - y the window statistics SSIM
-		// needs are E[u], E[v], E[u^2], E[v^2]:  mu1, mu2 = (E[u] +- E[v]) / 2,  E[x^2] + E[y^2] = (E[u^2] + E[v^2]) / 2,  E[xy] = (E[u^2] -
-		// E[v^2]) / 4 -- the scalar fifth channel x y (a plain FMA per tap next to two packed ones, and per pair of outputs four register moves
-		// the compiler needed to feed it to a packed multiply) is gone: 3 -> 2 instructions per tap, one LDS array less (28 instead of 34 KB:
-		// five workgroups per CU instead of four).  sigma_1^2 and sigma_2^2 only ever enter SSIM as their sum.
+		// needs are E[u], E[v], E[u^2], E[v^2] (ssim_from_uv) -- the scalar fifth channel x y (a plain FMA per tap next to two packed ones,
+		// and per pair of outputs four register moves the compiler needed to feed it to a packed multiply) is gone: 3 -> 2 instructions per
+		// tap, one LDS array less (28 instead of 34 KB: five workgroups per CU instead of four).
 		constexpr int IN_BYTES = SHH * SSTR * 8, HM_BYTES = SHH * HSTR * 8;
 		constexpr int SH_BYTES = IN_BYTES > HM_BYTES ? IN_BYTES : HM_BYTES;
 		__shared__ __attribute__((aligned(16))) char s_raw[HM_BYTES + SH_BYTES];
@@ -94,134 +61,43 @@ namespace fdgs
 		v2f (*h_s)[HSTR] = reinterpret_cast<v2f (*)[HSTR]>(s_raw + HM_BYTES);                        // (u^2, v^2): over the input tile
 		__shared__ float red[2][STHREADS / WAVE];
 
-		const TileId tile = ssim_tile_of((W + STX - 1) / STX, (H + STY - 1) / STY, C);
+		const TileId tile = tile_of((W + STX - 1) / STX, (H + STY - 1) / STY, C);
 		if (!tile.valid) return;
-		const int c = tile.c;
 		const int x0 = tile.tx * STX, y0 = tile.ty * STY;
 		const int tid = threadIdx.x;
-		const size_t plane = (size_t)c * H * W;
+		const size_t plane = (size_t)tile.c * H * W;
 
-		// halo: thread -> one column of the 42 and rows tid / 42, + 6, + 12, ... (252 of the 256 threads; the column, its bounds test
-		// and the address are computed once, a trip only moves down six rows).  All loads of the thread are issued before the first
-		// one is waited for (a rolled loop paid one global round trip per trip)
-		float l1 = 0.f;   // |x - y| over the tile's own pixels: summed where they are loaded (the input tile is gone after the horizontal pass)
-		{
-			constexpr int RPT = STHREADS / SW, TRIPS = (SHH + RPT - 1) / RPT;
-			const int lyb = tid / SW, hx = tid - lyb * SW;
-			const int gxh = x0 + hx - SR;
-			const bool col_in = tid < RPT * SW && (unsigned)gxh < (unsigned)W;
-			const bool col_own = (unsigned)(hx - SR) < (unsigned)STX;
-			v2f p[TRIPS];
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT, gy = y0 + ly - SR;
-				const bool in = col_in && ly < SHH && (unsigned)gy < (unsigned)H;
-				const size_t o = in ? plane + (size_t)gy * W + gxh : plane;   // branch-free: outside lanes read a valid address
-				const float vx = img1[o], vy = img2[o];
-				p[t] = in ? v2f{ vx + vy, vx - vy } : v2f{ 0.0f, 0.0f };     // (u, v); zero padding (F.conv2d padding = 5)
-			}
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT;
-				if (tid < RPT * SW && ly < SHH) s_in[ly][hx] = p[t];
-				const bool own = col_own && (unsigned)(ly - SR) < (unsigned)STY;   // (outside the image: 0 - 0)
-				l1 += own ? fabsf(p[t].y) : 0.0f;                                  // |x - y|
-			}
-		}
+		float sums[2] = { 0.f, 0.f };   // |x - y| and ssim over the tile's own pixels
+		load_halo<STX, STY, SR>(tid, x0, y0, H, W, plane,
+			[&](size_t o, bool in) { const float vx = img1[o], vy = img2[o]; return in ? v2f{ vx + vy, vx - vy } : v2f{ 0.0f, 0.0f }; },
+			[&](int ly, int hx, v2f p) { s_in[ly][hx] = p; },
+			[&](v2f p, bool own) { sums[0] += own ? fabsf(p.y) : 0.0f; });
 		__syncthreads();
 
-		// horizontal pass: task -> (row, 4 adjacent columns); SHH * 8 tasks over the 256 threads in HR rounds; results stay in
-		// registers until every task has read its inputs
-		constexpr int HR = (SHH * (STX / 4) + STHREADS - 1) / STHREADS;
-		v2f as[HR][4];
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * STHREADS;
-			if (task < SHH * (STX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v2f p[16], sq[14];
-				const v4f* src = reinterpret_cast<const v4f*>(&s_in[ly][cx]);
-#pragma unroll
-				for (int i = 0; i < 7; i++) { const v4f q = src[i]; p[2 * i] = v2f{ q.x, q.y }; p[2 * i + 1] = v2f{ q.z, q.w }; }
-#pragma unroll
-				for (int i = 0; i < 14; i++) sq[i] = p[i] * p[i];
-				v2f am[4];
-#pragma unroll
-				for (int j = 0; j < 4; j++)
-				{
-					am[j] = GW[0] * p[j]; as[r][j] = GW[0] * sq[j];
-#pragma unroll
-					for (int k = 1; k < 11; k++) { am[j] += GW[k] * p[j + k]; as[r][j] += GW[k] * sq[j + k]; }
-				}
-				v4f* dm = reinterpret_cast<v4f*>(&h_m[ly][cx]);   // (its own bytes: written at once)
-				dm[0] = v4f{ am[0].x, am[0].y, am[1].x, am[1].y }; dm[1] = v4f{ am[2].x, am[2].y, am[3].x, am[3].y };
-			}
-			__builtin_amdgcn_sched_barrier(0);   // one round's inputs at a time in registers
-		}
+		v2f as[hpass_rounds(SHH, STX / 4)][4];
+		hpass_tasks<SHH, STX / 4, true>(tid, [&](int r, int ly, int cx) {
+			v2f am[4];
+			hwin4_sq(&s_in[ly][cx], am, as[r]);
+			store4(&h_m[ly][cx], am);   // (its own bytes: written at once)
+		});
 		__syncthreads();   // the input tile has been read: its bytes become the filtered arrays
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * STHREADS;
-			if (task < SHH * (STX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v4f* ds = reinterpret_cast<v4f*>(&h_s[ly][cx]);
-				ds[0] = v4f{ as[r][0].x, as[r][0].y, as[r][1].x, as[r][1].y }; ds[1] = v4f{ as[r][2].x, as[r][2].y, as[r][3].x, as[r][3].y };
-			}
-		}
+		hpass_tasks<SHH, STX / 4, false>(tid, [&](int r, int ly, int cx) { store4(&h_s[ly][cx], as[r]); });
 		__syncthreads();
 
-		// vertical pass: thread -> (column, SROWS adjacent rows)
 		const int lx = tid & (STX - 1), ly0 = (tid >> 5) * SROWS;
-		v2f vm[10 + SROWS], vs[10 + SROWS];
-#pragma unroll
-		for (int r = 0; r < 10 + SROWS; r++) { vm[r] = h_m[ly0 + r][lx]; vs[r] = h_s[ly0 + r][lx]; }
-		float sv = 0.f;
 		const int gx = x0 + lx;
-#pragma unroll
-		for (int j = 0; j < SROWS; j++)
-		{
-			v2f mu = GW[0] * vm[j], e2 = GW[0] * vs[j];
-#pragma unroll
-			for (int k = 1; k < 11; k++) { mu += GW[k] * vm[j + k]; e2 += GW[k] * vs[j + k]; }
+		vpass2<SROWS>(h_m, h_s, ly0, lx, [&](int j, v2f mu, v2f e2) {
 			const int gy = y0 + ly0 + j;
 			if (gx < W && gy < H)
 			{
-				const float mu1 = 0.5f * (mu.x + mu.y), mu2 = 0.5f * (mu.x - mu.y);   // from E[u], E[v]
-				const float e_sum = 0.5f * (e2.x + e2.y), e12 = 0.25f * (e2.x - e2.y);   // E[x^2] + E[y^2], E[xy] from E[u^2], E[v^2]
-				const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-				const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-				const float sg12 = e12 - mu12;
-				const float A = 2.f * mu12 + C1, B = 2.f * sg12 + C2, Cc = mu1_sq + mu2_sq + C1, D = (e_sum - (mu1_sq + mu2_sq)) + C2;
-				// 1 / Cc and 1 / D by v_rcp_f32 (1 ulp): three IEEE divisions were a seventh of the kernel's instructions
-				const float rC = __builtin_amdgcn_rcpf(Cc), rD = __builtin_amdgcn_rcpf(D);
-				const float inv = rC * rD;
-				const float m = A * B * inv;
-				// total derivative w.r.t. mu1 (through A, B, Cc, D), and w.r.t. the raw moments E[x^2], E[xy]
-				const float dm_dA = B * inv, dm_dB = A * inv, dm_dC = -m * rC, dm_dD = -m * rD;
+				const Ssim s = ssim_from_uv(mu, e2);
 				const size_t o = plane + (size_t)gy * W + gx;
-				dm_dmu1[o] = dm_dA * 2.f * mu2 - dm_dB * 2.f * mu2 + dm_dC * 2.f * mu1 - dm_dD * 2.f * mu1;
-				dm_de11[o] = dm_dD;
-				dm_de12[o] = 2.f * dm_dB;
-				sv += m;
+				ssim_derivs(s, dm_dmu1[o], dm_de11[o], dm_de12[o]);
+				sums[1] += s.m;
 			}
-		}
-		// per-tile partial sums (wave shuffle + 4 partials)
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) { l1 += __shfl_down(l1, o); sv += __shfl_down(sv, o); }
-		if ((tid & 63) == 0) { red[0][tid >> 6] = l1; red[1][tid >> 6] = sv; }
-		__syncthreads();
-		if (tid == 0)
-		{
-			const int b = tile.index;
-			partial_l1[b] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-			partial_ssim[b] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-		}
+		});
+		tile_reduce(sums, red, tid);
+		if (tid == 0) { partial_l1[tile.index] = sum4<false>(red[0]); partial_ssim[tile.index] = sum4<false>(red[1]); }
 	}
 
 	__global__ void __launch_bounds__(STHREADS) ssim_bwd_kernel(
@@ -238,113 +114,34 @@ namespace fdgs
 		v2f (*h_p)[HSTR] = reinterpret_cast<v2f (*)[HSTR]>(s_raw);
 		float (*h_q)[HSTR1B] = reinterpret_cast<float (*)[HSTR1B]>(s_raw + HP_BYTES);
 
-		const TileId tile = ssim_tile_of((W + STX - 1) / STX, (H + STY - 1) / STY, C);
+		const TileId tile = tile_of((W + STX - 1) / STX, (H + STY - 1) / STY, C);
 		if (!tile.valid) return;
-		const int c = tile.c;
 		const int x0 = tile.tx * STX, y0 = tile.ty * STY;
 		const int tid = threadIdx.x;
-		const size_t plane = (size_t)c * H * W;
+		const size_t plane = (size_t)tile.c * H * W;
 
-		{
-			constexpr int RPT = STHREADS / SW, TRIPS = (SHH + RPT - 1) / RPT;   // (thread -> column + every sixth row, as in the forward kernel)
-			const int lyb = tid / SW, hx = tid - lyb * SW;
-			const int gxh = x0 + hx - SR;
-			const bool col_in = tid < RPT * SW && (unsigned)gxh < (unsigned)W;
-			v2f p[TRIPS];
-			float q[TRIPS];
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)       // every load in flight before the first wait
-			{
-				const int ly = lyb + t * RPT, gy = y0 + ly - SR;
-				const bool in = col_in && ly < SHH && (unsigned)gy < (unsigned)H;
-				const size_t o = in ? plane + (size_t)gy * W + gxh : plane;   // branch-free: outside lanes read a valid address
+		struct PQ { v2f p; float q; };
+		load_halo<STX, STY, SR>(tid, x0, y0, H, W, plane,
+			[&](size_t o, bool in) {
 				const float va = dm_dmu1[o], vb = dm_de11[o], vc = dm_de12[o];
-				p[t] = in ? v2f{ va, vb } : v2f{ 0.0f, 0.0f };
-				q[t] = in ? vc : 0.0f;
-			}
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT;
-				if (tid < RPT * SW && ly < SHH) { s_p[ly][hx] = p[t]; s_q[ly][hx] = q[t]; }
-			}
-		}
-		// the pixels this thread finishes below: their image values travel while the windows are computed
+				return PQ{ in ? v2f{ va, vb } : v2f{ 0.0f, 0.0f }, in ? vc : 0.0f };
+			},
+			[&](int ly, int hx, PQ v) { s_p[ly][hx] = v.p; s_q[ly][hx] = v.q; },
+			[](PQ, bool) {});
 		const int lx = tid & (STX - 1), ly0 = (tid >> 5) * SROWS;
 		const int gx = x0 + lx;
 		float px[SROWS], py[SROWS];
-#pragma unroll
-		for (int j = 0; j < SROWS; j++)
-		{
-			const int gy = y0 + ly0 + j;
-			const size_t o = (gx < W && gy < H) ? plane + (size_t)gy * W + gx : plane;
-			px[j] = img1[o]; py[j] = img2[o];
-		}
+		load_own(img1, img2, gx, y0 + ly0, H, W, plane, px, py);
 		__syncthreads();
-		constexpr int HR = (SHH * (STX / 4) + STHREADS - 1) / STHREADS;
+
+		constexpr int HR = hpass_rounds(SHH, STX / 4);
 		v2f ap[HR][4];
 		float aq[HR][4];
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * STHREADS;
-			if (task < SHH * (STX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v2f p[16];
-				float q[16];
-				const v4f* sp = reinterpret_cast<const v4f*>(&s_p[ly][cx]);
-				const v4f* sq = reinterpret_cast<const v4f*>(&s_q[ly][cx]);
-#pragma unroll
-				for (int i = 0; i < 7; i++) { const v4f t = sp[i]; p[2 * i] = v2f{ t.x, t.y }; p[2 * i + 1] = v2f{ t.z, t.w }; }
-#pragma unroll
-				for (int i = 0; i < 4; i++) { const v4f t = sq[i]; q[4 * i] = t.x; q[4 * i + 1] = t.y; q[4 * i + 2] = t.z; q[4 * i + 3] = t.w; }
-#pragma unroll
-				for (int j = 0; j < 4; j++)
-				{
-					ap[r][j] = GW[0] * p[j]; aq[r][j] = GW[0] * q[j];
-#pragma unroll
-					for (int k = 1; k < 11; k++) { ap[r][j] += GW[k] * p[j + k]; aq[r][j] += GW[k] * q[j + k]; }
-				}
-			}
-			__builtin_amdgcn_sched_barrier(0);   // one round's inputs at a time in registers
-		}
+		hpass_tasks<SHH, STX / 4, true>(tid, [&](int r, int ly, int cx) { hwin4_pq(&s_p[ly][cx], &s_q[ly][cx], ap[r], aq[r]); });
 		__syncthreads();   // the inputs have been read: their bytes become the filtered arrays
-#pragma unroll
-		for (int r = 0; r < HR; r++)
-		{
-			const int task = tid + r * STHREADS;
-			if (task < SHH * (STX / 4))
-			{
-				const int ly = task >> 3, cx = (task & 7) * 4;
-				v4f* dp = reinterpret_cast<v4f*>(&h_p[ly][cx]);
-				dp[0] = v4f{ ap[r][0].x, ap[r][0].y, ap[r][1].x, ap[r][1].y }; dp[1] = v4f{ ap[r][2].x, ap[r][2].y, ap[r][3].x, ap[r][3].y };
-				*reinterpret_cast<v4f*>(&h_q[ly][cx]) = v4f{ aq[r][0], aq[r][1], aq[r][2], aq[r][3] };
-			}
-		}
+		hpass_tasks<SHH, STX / 4, false>(tid, [&](int r, int ly, int cx) { store4(&h_p[ly][cx], ap[r]); store4(&h_q[ly][cx], aq[r]); });
 		__syncthreads();
-		v2f vp[10 + SROWS];
-		float vq[10 + SROWS];
-#pragma unroll
-		for (int r = 0; r < 10 + SROWS; r++) { vp[r] = h_p[ly0 + r][lx]; vq[r] = h_q[ly0 + r][lx]; }
-		const float up = upstream[0];
-#pragma unroll
-		for (int j = 0; j < SROWS; j++)
-		{
-			v2f ab = GW[0] * vp[j];
-			float d = GW[0] * vq[j];
-#pragma unroll
-			for (int k = 1; k < 11; k++) { ab += GW[k] * vp[j + k]; d += GW[k] * vq[j + k]; }
-			const int gy = y0 + ly0 + j;
-			if (gx < W && gy < H)
-			{
-				const size_t o = plane + (size_t)gy * W + gx;
-				const float x = px[j], y = py[j];
-				const float diff = x - y;
-				const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-				dL_dimg1[o] = up * (w_l1 * sgn + w_ssim * (ab.x + 2.f * x * ab.y + y * d));
-			}
-		}
+		vgrad_pass<SROWS>(h_p, h_q, ly0, lx, upstream, w_l1, w_ssim, px, py, gx, y0 + ly0, H, W, plane, dL_dimg1);
 	}
 }
 
@@ -358,8 +155,11 @@ namespace fdgs
 	// derivative maps on the 42x42 pixels around it (window radius 5), from the moments of the 52x52 input pixels around those --
 	// nothing but the two images is read, nothing but the gradient and two partial sums per tile is written.  The price is
 	// arithmetic: the forward's windows and SSIM algebra run on 1.72 x the pixels (every derivative pixel is computed by the up to
-	// four tiles whose halo it lies in).  Same arithmetic per pixel, operation by operation, as ssim_fwd_kernel / ssim_bwd_kernel:
-	// the results are bit-identical to the two-kernel path.
+	// four tiles whose halo it lies in).  Phases 3 and 4 are ssim_bwd_kernel's arithmetic operation by operation.  Phases 1 and 2
+	// are NOT ssim_fwd_kernel's: they still filter the five moments x, y, x^2, y^2, xy of rounds 1-5, the forward kernel the four of
+	// (u, v) = (x + y, x - y), so the derivative maps -- and with them gradient and ssim sum -- agree with the two-kernel path to
+	// rounding, not bit for bit (both are held to the same float64 reference and error bars by the tests); the L1 sums are |x - y|
+	// in both and equal.
 	//   phase 0  A = 52x52 inputs (x, y) -> LDS (zero padding outside the image); |x - y| over the own 32x32
 	//   phase 1  horizontal windows of (x, y), (x^2, y^2), xy on the 52 rows x 44 columns (42 used)
 	//   phase 2  vertical windows + SSIM algebra on B = 42x42: ssim (summed over the own 32x32) and d ssim / d mu1, d E[x^2], d E[xy]
@@ -400,105 +200,43 @@ namespace fdgs
 		float (*h_q)[HSTR1B] = reinterpret_cast<float (*)[HSTR1B]>(s_raw + FB * HSTR * 8);
 		__shared__ float red[2][STHREADS / WAVE];
 
-		const TileId tile = ssim_tile_of((W + FT - 1) / FT, (H + FT - 1) / FT, C);
+		const TileId tile = tile_of((W + FT - 1) / FT, (H + FT - 1) / FT, C);
 		if (!tile.valid) return;
-		const int c = tile.c;
 		const int x0 = tile.tx * FT, y0 = tile.ty * FT;
 		const int tid = threadIdx.x;
-		const size_t plane = (size_t)c * H * W;
+		const size_t plane = (size_t)tile.c * H * W;
 
-		// ---- phase 0: the 52x52 inputs; thread -> one column and rows tid / 52, + 4, + 8, ... (208 of the 256 threads) ----
-		float l1 = 0.f;
-		{
-			constexpr int RPT = STHREADS / FA, TRIPS = (FA + RPT - 1) / RPT;   // 4 rows per trip, 13 trips
-			const int lyb = tid / FA, hx = tid - lyb * FA;
-			const int gxh = x0 + hx - 2 * SR;
-			const bool col_in = tid < RPT * FA && (unsigned)gxh < (unsigned)W;
-			const bool col_own = (unsigned)(hx - 2 * SR) < (unsigned)FT;
-			v2f p[TRIPS];
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT, gy = y0 + ly - 2 * SR;
-				const bool in = col_in && ly < FA && (unsigned)gy < (unsigned)H;
-				const size_t o = in ? plane + (size_t)gy * W + gxh : plane;
-				const float vx = img1[o], vy = img2[o];
-				p[t] = in ? v2f{ vx, vy } : v2f{ 0.0f, 0.0f };
-			}
-#pragma unroll
-			for (int t = 0; t < TRIPS; t++)
-			{
-				const int ly = lyb + t * RPT;
-				if (tid < RPT * FA && ly < FA) s_in[ly][hx] = p[t];
-				const bool own = col_own && (unsigned)(ly - 2 * SR) < (unsigned)FT;
-				l1 += own ? fabsf(p[t].x - p[t].y) : 0.0f;
-			}
-			// the two pad columns the last group of four of phase 1 reads (its results, columns 42 and 43, are never used)
-			if (tid < FA) { s_in[tid][FA] = v2f{ 0.0f, 0.0f }; s_in[tid][FA + 1] = v2f{ 0.0f, 0.0f }; }
-		}
-		// the own pixels this thread finishes in phase 4: their values travel meanwhile
+		// ---- phase 0: the 52x52 inputs; thread -> one column and rows tid / 52, + 4, + 8, ... (208 of the 256 threads, 13 trips) ----
+		float sums[2] = { 0.f, 0.f };   // |x - y| and ssim over the tile's own pixels
+		load_halo<FT, FT, 2 * SR>(tid, x0, y0, H, W, plane,
+			[&](size_t o, bool in) { const float vx = img1[o], vy = img2[o]; return in ? v2f{ vx, vy } : v2f{ 0.0f, 0.0f }; },
+			[&](int ly, int hx, v2f p) { s_in[ly][hx] = p; },
+			[&](v2f p, bool own) { sums[0] += own ? fabsf(p.x - p.y) : 0.0f; });
+		// the two pad columns the last group of four of phase 1 reads (its results, columns 42 and 43, are never used)
+		if (tid < FA) { s_in[tid][FA] = v2f{ 0.0f, 0.0f }; s_in[tid][FA + 1] = v2f{ 0.0f, 0.0f }; }
+		// the own pixels this thread finishes in phase 4
 		const int lx = tid & (FT - 1), ly0 = (tid >> 5) * SROWS;
 		const int gx = x0 + lx;
 		float px[SROWS], py[SROWS];
-#pragma unroll
-		for (int j = 0; j < SROWS; j++)
-		{
-			const int gy = y0 + ly0 + j;
-			const size_t o = (gx < W && gy < H) ? plane + (size_t)gy * W + gx : plane;
-			px[j] = img1[o]; py[j] = img2[o];
-		}
+		load_own(img1, img2, gx, y0 + ly0, H, W, plane, px, py);
 		__syncthreads();
 
 		// ---- phase 1: horizontal windows; task -> (row, 4 adjacent columns): 52 x 11 tasks in 3 rounds ----
 		{
-			constexpr int GPR = FBC / 4, NT = FA * GPR, HR = (NT + STHREADS - 1) / STHREADS;
+			constexpr int HR = hpass_rounds(FA, FBC / 4);
 			v2f as[HR][4];
 			float ax[HR][4];
-#pragma unroll
-			for (int r = 0; r < HR; r++)
-			{
-				const int task = tid + r * STHREADS;
-				if (task < NT)
-				{
-					const int ly = task / GPR, cx = (task - ly * GPR) * 4;
-					v2f p[16], sq[14];
-					float xy[14];
-					const v4f* src = reinterpret_cast<const v4f*>(&s_in[ly][cx]);
-#pragma unroll
-					for (int i = 0; i < 7; i++) { const v4f q = src[i]; p[2 * i] = v2f{ q.x, q.y }; p[2 * i + 1] = v2f{ q.z, q.w }; }
-#pragma unroll
-					for (int i = 0; i < 14; i++) { sq[i] = p[i] * p[i]; xy[i] = p[i].x * p[i].y; }
-					v2f am[4];
-#pragma unroll
-					for (int j = 0; j < 4; j++)
-					{
-						am[j] = GW[0] * p[j]; as[r][j] = GW[0] * sq[j]; ax[r][j] = GW[0] * xy[j];
-#pragma unroll
-						for (int k = 1; k < 11; k++) { am[j] += GW[k] * p[j + k]; as[r][j] += GW[k] * sq[j + k]; ax[r][j] += GW[k] * xy[j + k]; }
-					}
-					v4f* dm = reinterpret_cast<v4f*>(&h_m[ly][cx]);
-					dm[0] = v4f{ am[0].x, am[0].y, am[1].x, am[1].y }; dm[1] = v4f{ am[2].x, am[2].y, am[3].x, am[3].y };
-				}
-				__builtin_amdgcn_sched_barrier(0);
-			}
+			hpass_tasks<FA, FBC / 4, true>(tid, [&](int r, int ly, int cx) {
+				v2f am[4];
+				hwin4_sq<true>(&s_in[ly][cx], am, as[r], ax[r]);
+				store4(&h_m[ly][cx], am);
+			});
 			__syncthreads();   // the input tile has been read: its bytes become h_s / h_x
-#pragma unroll
-			for (int r = 0; r < HR; r++)
-			{
-				const int task = tid + r * STHREADS;
-				if (task < NT)
-				{
-					const int ly = task / GPR, cx = (task - ly * GPR) * 4;
-					v4f* ds = reinterpret_cast<v4f*>(&h_s[ly][cx]);
-					ds[0] = v4f{ as[r][0].x, as[r][0].y, as[r][1].x, as[r][1].y }; ds[1] = v4f{ as[r][2].x, as[r][2].y, as[r][3].x, as[r][3].y };
-					*reinterpret_cast<v4f*>(&h_x[ly][cx]) = v4f{ ax[r][0], ax[r][1], ax[r][2], ax[r][3] };
-				}
-			}
+			hpass_tasks<FA, FBC / 4, false>(tid, [&](int r, int ly, int cx) { store4(&h_s[ly][cx], as[r]); store4(&h_x[ly][cx], ax[r]); });
 		}
 		__syncthreads();
 
 		// ---- phase 2: vertical windows + SSIM algebra on the 42x42 derivative region; thread -> (column, 7 adjacent rows) ----
-		float sv = 0.f;
 		{
 			const int bc = tid % FB, rg = tid / FB;          // rg 0..5 (threads 252..255: rg = 6, no work)
 			const bool work = rg < FB / FRV;
@@ -523,18 +261,13 @@ namespace fdgs
 					dp[j] = v2f{ 0.0f, 0.0f }; dq[j] = 0.0f;
 					if (work && (unsigned)gxb < (unsigned)W && (unsigned)gyb < (unsigned)H)
 					{
-						const float mu1 = mu.x, mu2 = mu.y, e11 = e2.x, e22 = e2.y;
-						const float C1 = 0.01f * 0.01f, C2 = 0.03f * 0.03f;
-						const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-						const float sg1 = e11 - mu1_sq, sg2 = e22 - mu2_sq, sg12 = e12 - mu12;
-						const float A = 2.f * mu12 + C1, B = 2.f * sg12 + C2, Cc = mu1_sq + mu2_sq + C1, D = sg1 + sg2 + C2;
-						const float rC = __builtin_amdgcn_rcpf(Cc), rD = __builtin_amdgcn_rcpf(D);
-						const float inv = rC * rD;
-						const float m = A * B * inv;
-						const float dm_dA = B * inv, dm_dB = A * inv, dm_dC = -m * rC, dm_dD = -m * rD;
-						dp[j] = v2f{ dm_dA * 2.f * mu2 - dm_dB * 2.f * mu2 + dm_dC * 2.f * mu1 - dm_dD * 2.f * mu1, dm_dD };
-						dq[j] = 2.f * dm_dB;
-						if (col_own && (unsigned)(br - SR) < (unsigned)FT) sv += m;   // the tile's own pixels: each counted by exactly one tile
+						const float mu1 = mu.x, mu2 = mu.y;
+						const float sg1 = e2.x - mu1 * mu1, sg2 = e2.y - mu2 * mu2, sg12 = e12 - mu1 * mu2;
+						const Ssim s = ssim_of(mu1, mu2, sg12, sg1 + sg2);
+						float d_mu1, d_e11;
+						ssim_derivs(s, d_mu1, d_e11, dq[j]);
+						dp[j] = v2f{ d_mu1, d_e11 };
+						if (col_own && (unsigned)(br - SR) < (unsigned)FT) sums[1] += s.m;   // the tile's own pixels: each counted by exactly one tile
 					}
 				}
 			}
@@ -550,84 +283,28 @@ namespace fdgs
 		__syncthreads();
 
 		// ---- phase 3: horizontal windows of the derivative maps: 42 rows x 8 groups of 4 columns, 2 rounds; results go where h_m was ----
-		{
-			constexpr int NT = FB * (FT / 4), HR = (NT + STHREADS - 1) / STHREADS;
-#pragma unroll
-			for (int r = 0; r < HR; r++)
-			{
-				const int task = tid + r * STHREADS;
-				if (task < NT)
-				{
-					const int ly = task >> 3, cx = (task & 7) * 4;
-					v2f p[16];
-					float q[16];
-					const v4f* sp = reinterpret_cast<const v4f*>(&d_p[ly][cx]);
-					const v4f* sq = reinterpret_cast<const v4f*>(&d_q[ly][cx]);
-#pragma unroll
-					for (int i = 0; i < 7; i++) { const v4f t = sp[i]; p[2 * i] = v2f{ t.x, t.y }; p[2 * i + 1] = v2f{ t.z, t.w }; }
-#pragma unroll
-					for (int i = 0; i < 4; i++) { const v4f t = sq[i]; q[4 * i] = t.x; q[4 * i + 1] = t.y; q[4 * i + 2] = t.z; q[4 * i + 3] = t.w; }
-					v2f ap[4];
-					float aq[4];
-#pragma unroll
-					for (int j = 0; j < 4; j++)
-					{
-						ap[j] = GW[0] * p[j]; aq[j] = GW[0] * q[j];
-#pragma unroll
-						for (int k = 1; k < 11; k++) { ap[j] += GW[k] * p[j + k]; aq[j] += GW[k] * q[j + k]; }
-					}
-					v4f* dpo = reinterpret_cast<v4f*>(&h_p[ly][cx]);
-					dpo[0] = v4f{ ap[0].x, ap[0].y, ap[1].x, ap[1].y }; dpo[1] = v4f{ ap[2].x, ap[2].y, ap[3].x, ap[3].y };
-					*reinterpret_cast<v4f*>(&h_q[ly][cx]) = v4f{ aq[0], aq[1], aq[2], aq[3] };
-				}
-				__builtin_amdgcn_sched_barrier(0);
-			}
-		}
+		hpass_tasks<FB, FT / 4, true>(tid, [&](int, int ly, int cx) {
+			v2f ap[4];
+			float aq[4];
+			hwin4_pq(&d_p[ly][cx], &d_q[ly][cx], ap, aq);
+			store4(&h_p[ly][cx], ap); store4(&h_q[ly][cx], aq);
+		});
 		__syncthreads();
 
 		// ---- phase 4: vertical windows -> the gradient of the tile's own pixels ----
-		{
-			v2f vp[10 + SROWS];
-			float vq[10 + SROWS];
-#pragma unroll
-			for (int r = 0; r < 10 + SROWS; r++) { vp[r] = h_p[ly0 + r][lx]; vq[r] = h_q[ly0 + r][lx]; }
-			const float up = upstream[0];
-#pragma unroll
-			for (int j = 0; j < SROWS; j++)
-			{
-				v2f ab = GW[0] * vp[j];
-				float d = GW[0] * vq[j];
-#pragma unroll
-				for (int k = 1; k < 11; k++) { ab += GW[k] * vp[j + k]; d += GW[k] * vq[j + k]; }
-				const int gy = y0 + ly0 + j;
-				if (gx < W && gy < H)
-				{
-					const size_t o = plane + (size_t)gy * W + gx;
-					const float x = px[j], y = py[j];
-					const float diff = x - y;
-					const float sgn = diff > 0.f ? 1.f : (diff < 0.f ? -1.f : 0.f);
-					dL_dimg1[o] = up * (w_l1 * sgn + w_ssim * (ab.x + 2.f * x * ab.y + y * d));
-				}
-			}
-		}
+		vgrad_pass<SROWS>(h_p, h_q, ly0, lx, upstream, w_l1, w_ssim, px, py, gx, y0 + ly0, H, W, plane, dL_dimg1);
 		// per-tile partial sums of |x - y| and ssim (fixed order: deterministic)
-#pragma unroll
-		for (int o = 32; o > 0; o >>= 1) { l1 += __shfl_down(l1, o); sv += __shfl_down(sv, o); }
-		if ((tid & 63) == 0) { red[0][tid >> 6] = l1; red[1][tid >> 6] = sv; }
-		__syncthreads();
-		if (tid == 0)
-		{
-			const int b = tile.index;
-			partial_l1[b] = red[0][0] + red[0][1] + red[0][2] + red[0][3];
-			partial_ssim[b] = red[1][0] + red[1][1] + red[1][2] + red[1][3];
-		}
+		tile_reduce(sums, red, tid);
+		if (tid == 0) { partial_l1[tile.index] = sum4<false>(red[0]); partial_ssim[tile.index] = sum4<false>(red[1]); }
 	}
 }
 
 namespace fdgs
 {
-	// two register allocations of the same body: held to 3 waves per SIMD (168 VGPRs, a few spills: three workgroups per CU, what the
-	// LDS allows) or free (176 VGPRs, no spills, two workgroups per CU); FDGS_SSIM_FUSED_WPE=2 in the environment selects the second (A/B)
+	// two register allocations of the same body: held to 3 waves per SIMD (three workgroups per CU, what the LDS allows) or free;
+	// FDGS_SSIM_FUSED_WPE=2 in the environment selects the second (A/B).  Hand-written the body took 168 VGPRs and 5 spilled ones when
+	// held and 173, two workgroups per CU, when free; with the address arithmetic the compiler makes of the ssim_window.h helpers both
+	// take 166 VGPRs without a spill -- today the two kernels are the same code
 #define FDGS_SSIM_FUSED_PARAMS const float* __restrict__ img1, const float* __restrict__ img2, int C, int H, int W, const float* __restrict__ upstream, \
 		float w_l1, float w_ssim, float* __restrict__ dL_dimg1, float* __restrict__ partial_l1, float* __restrict__ partial_ssim
 	__global__ void __launch_bounds__(STHREADS) __attribute__((amdgpu_waves_per_eu(3, 3))) ssim_fused_kernel(FDGS_SSIM_FUSED_PARAMS)
@@ -646,11 +323,11 @@ extern "C" int fdgs_l1_ssim_value_and_grad(const float* img, const float* gt, in
                                            float* partial_l1, float* partial_ssim, void* stream)
 {
 	using namespace fdgs;
-	static_assert(STY == 32 && SROWS == 4, "the fused kernel shares the 32-row tile's partial-sum layout with the two-kernel path");
+	static_assert(FT == STX && FT == STY, "the fused kernel shares the tile's partial-sum layout with the two-kernel path");
 	if (!img || !gt || !upstream || !dL_dimg || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
 	const float n = (float)C * (float)H * (float)W;
 	const float w_l1 = (1.0f - lambda_dssim) / n, w_ssim = -lambda_dssim / n;
-	const dim3 grid(ssim_grid(div_up(W, FT), div_up(H, FT), C)), block(STHREADS, 1, 1);
+	const dim3 grid(grid_of(div_up(W, FT) * div_up(H, FT) * C)), block(STHREADS, 1, 1);
 	static const bool wpe2 = []() { const char* e = getenv("FDGS_SSIM_FUSED_WPE"); return e && e[0] == '2'; }();
 	if (wpe2) hipLaunchKernelGGL(ssim_fused_kernel_wpe2, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, upstream, w_l1, w_ssim, dL_dimg, partial_l1, partial_ssim);
 	else hipLaunchKernelGGL(ssim_fused_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, upstream, w_l1, w_ssim, dL_dimg, partial_l1, partial_ssim);
@@ -663,7 +340,7 @@ extern "C" int fdgs_l1_ssim_forward(const float* img, const float* gt, int32_t C
 {
 	using namespace fdgs;
 	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
-	const dim3 grid(ssim_grid(div_up(W, STX), div_up(H, STY), C)), block(STHREADS, 1, 1);
+	const dim3 grid(grid_of(div_up(W, STX) * div_up(H, STY) * C)), block(STHREADS, 1, 1);
 	hipLaunchKernelGGL(ssim_fwd_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, dm_dmu1, dm_de11, dm_de12, partial_l1, partial_ssim);
 	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
 }
@@ -676,7 +353,7 @@ extern "C" int fdgs_l1_ssim_backward(const float* img, const float* gt, int32_t 
 	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !upstream || !dL_dimg || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
 	const float n = (float)C * (float)H * (float)W;
 	const float w_l1 = (1.0f - lambda_dssim) / n, w_ssim = -lambda_dssim / n;
-	const dim3 grid(ssim_grid(div_up(W, STX), div_up(H, STY), C)), block(STHREADS, 1, 1);
+	const dim3 grid(grid_of(div_up(W, STX) * div_up(H, STY) * C)), block(STHREADS, 1, 1);
 	hipLaunchKernelGGL(ssim_bwd_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, dm_dmu1, dm_de11, dm_de12, upstream, w_l1, w_ssim, dL_dimg);
 	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
 }

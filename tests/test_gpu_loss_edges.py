@@ -64,18 +64,7 @@ def test_input_classes_against_float64(name, shape, lam, fused, gpu_device):
 
 
 # ---- 2. shapes -----------------------------------------------------------------------------------------------------------------
-# shape -> number of 32 x 32 tiles = fdgs_l1_ssim_num_partials = C * ceil(H / 32) * ceil(W / 32).  A launch has ceil(tiles / 8) * 8
-# workgroups; workgroup w takes tile (w % 8) * chunk + w / 8 with chunk = ceil(tiles / 8), if that is a tile (ssim_tile_of).
-SHAPES = {
-    # the 11-tap window larger than the image: overhanging both borders at once, sides below the radius 5, sides of 1
-    (3, 1, 1): 3, (1, 1, 37): 2, (1, 37, 1): 2, (3, 4, 4): 3, (3, 5, 6): 3, (3, 10, 11): 3, (1, 11, 10): 1,
-    # tile edges: exact tiles, ragged on either axis and on both
-    (3, 32, 32): 3, (3, 33, 31): 6, (2, 65, 64): 12, (3, 31, 97): 12,
-    # tile counts: 8 = one tile per XCD chunk; 9 = chunk 2, XCD 4 half idle and three XCDs idle, 7 invalid workgroups; 12 = chunk 2 with
-    # 4 tiles per channel: chunks inside a channel and across two; 8 as 2 x 4; 20 = chunk 3, 4 invalid workgroups, a chunk across the
-    # channel boundary at tile 10; 36 = chunk 5, 4 invalid workgroups, chunks across both channel boundaries
-    (1, 32, 225): 8, (1, 32, 257): 9, (3, 33, 33): 12, (1, 33, 97): 8, (2, 64, 129): 20, (3, 95, 97): 36,
-}
+SHAPES = lc.EDGE_SHAPES      # shape -> number of 32 x 32 tiles
 
 
 @pytest.mark.parametrize("fused", PATHS, ids=PATH_IDS)

@@ -9,6 +9,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import loss_cases as lc
 import metrics_oracle as mo
 
 pytestmark = pytest.mark.gpu
@@ -101,6 +102,20 @@ def test_skip_msssim_allows_small_images(gpu_device):
     assert p.dim() == 0 and p.is_cuda and s.dim() == 0 and s.is_cuda
     assert abs(float(p) - mo.psnr(img, gt, clamp=False)) <= BARS[1]
     assert abs(float(s) - mo.ssim(img, gt, clamp=False)) <= BARS[2]
+
+
+@pytest.mark.parametrize("shape", list(lc.EDGE_SHAPES), ids=["x".join(map(str, s)) for s in lc.EDGE_SHAPES])
+def test_edge_shapes_match_oracle(shape, gpu_device):
+    """L1 / PSNR / SSIM without MS-SSIM on the edge shapes of the loss kernels (loss_cases.EDGE_SHAPES: sides of 1, sides below the
+    window, ragged tiles, tile counts around the 8 XCD chunks): the scale kernel shares its halo load and window passes with them.
+    Every one of the 17 shapes is run: the float64 oracle is finite on all of them with these inputs (img != gt everywhere: PSNR of
+    identical images is +inf), asserted here before the comparison."""
+    from fdgs.metrics import image_metrics
+    img, gt = pair(shape, 100 + sum(shape))
+    want = mo.metrics(img, gt, with_msssim=False)
+    assert all(math.isfinite(w) for w in want[:3]) and math.isnan(want[3]), want
+    got = image_metrics(img.to(gpu_device), gt.to(gpu_device), msssim=False).cpu()
+    check(got, want, "x".join(map(str, shape)))
 
 
 @pytest.mark.parametrize("H,W,side", [(175, 240, "height"), (240, 175, "width"), (64, 64, "height")])
