@@ -24,6 +24,7 @@
 #pragma clang fp contract(off)
 #include "fdgs_common.h"
 #include "fdgs_math.h"
+#include "sh_eval.h"
 
 namespace fdgs
 {
@@ -41,42 +42,6 @@ namespace fdgs
 		float4* records; float* depths; float* cov3D; uint32_t* tiles_touched; ushort4* rect; uint8_t* clamped;
 		uint32_t* bin_counters; int bin_counter_words;   // tile instance counters of the binning passes, cleared here (tilebin.hip)
 	};
-
-	__device__ __forceinline__ float3 ld3(const float* p, size_t i) { return make_float3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
-	__device__ __forceinline__ float3 add3(float3 a, float3 b) { return make_float3(a.x + b.x, a.y + b.y, a.z + b.z); }
-	__device__ __forceinline__ float3 scl3(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
-	__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
-
-	// 3D SH (forward.cu:20-71); returns the un-clamped colour + 0.5
-	__device__ float3 sh_color_3d(int deg, const float* __restrict__ sh, float3 dir)
-	{
-		float3 result = scl3(SH_C0, ld3(sh, 0));
-		if (deg > 0)
-		{
-			const float x = dir.x, y = dir.y, z = dir.z;
-			result = sub3(add3(sub3(result, scl3(SH_C1 * y, ld3(sh, 1))), scl3(SH_C1 * z, ld3(sh, 2))), scl3(SH_C1 * x, ld3(sh, 3)));
-			if (deg > 1)
-			{
-				const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-				result = add3(result, scl3(SH_C2[0] * xy, ld3(sh, 4)));
-				result = add3(result, scl3(SH_C2[1] * yz, ld3(sh, 5)));
-				result = add3(result, scl3(SH_C2[2] * (2.0f * zz - xx - yy), ld3(sh, 6)));
-				result = add3(result, scl3(SH_C2[3] * xz, ld3(sh, 7)));
-				result = add3(result, scl3(SH_C2[4] * (xx - yy), ld3(sh, 8)));
-				if (deg > 2)
-				{
-					result = add3(result, scl3(SH_C3[0] * y * (3.0f * xx - yy), ld3(sh, 9)));
-					result = add3(result, scl3(SH_C3[1] * xy * z, ld3(sh, 10)));
-					result = add3(result, scl3(SH_C3[2] * y * (4.0f * zz - xx - yy), ld3(sh, 11)));
-					result = add3(result, scl3(SH_C3[3] * z * (2.0f * zz - 3.0f * xx - 3.0f * yy), ld3(sh, 12)));
-					result = add3(result, scl3(SH_C3[4] * x * (4.0f * zz - xx - yy), ld3(sh, 13)));
-					result = add3(result, scl3(SH_C3[5] * z * (xx - yy), ld3(sh, 14)));
-					result = add3(result, scl3(SH_C3[6] * x * (xx - 3.0f * yy), ld3(sh, 15)));
-				}
-			}
-		}
-		return make_float3(result.x + 0.5f, result.y + 0.5f, result.z + 0.5f);
-	}
 
 	// basis values of the 4D path (forward.cu:87-131; note the double promotion in l2m0)
 	__device__ __forceinline__ void sh_basis_4d(int deg, float x, float y, float z, float* l)
@@ -106,31 +71,6 @@ namespace fdgs
 			}
 		}
 	}
-	__device__ __forceinline__ float3 sh_weighted(const float* l, const float* __restrict__ sh, int lo, int hi, int off)
-	{
-		float3 acc = scl3(l[lo - off], ld3(sh, lo));
-#pragma unroll
-		for (int k = lo + 1; k <= hi; k++) acc = add3(acc, scl3(l[k - off], ld3(sh, k)));
-		return acc;
-	}
-	// 4D SH (forward.cu:73-195), split by coefficient block so each block of 16 coefficients can be staged through
-	// LDS on its own: block 0 = the plain SH sum, blocks 1 / 2 = the same basis times cos(2 pi k dt / T), k = 1, 2
-	// (only when deg > 2).  Evaluation order inside and across blocks is the reference's.
-	__device__ __forceinline__ float3 sh4d_block0(int deg, const float* l, const float* __restrict__ sh)
-	{
-		float3 result = scl3(l[0], ld3(sh, 0));
-		if (deg > 0)
-		{
-			result = add3(result, sh_weighted(l, sh, 1, 3, 0));
-			if (deg > 1)
-			{
-				result = add3(result, sh_weighted(l, sh, 4, 8, 0));
-				if (deg > 2) result = add3(result, sh_weighted(l, sh, 9, 15, 0));
-			}
-		}
-		return result;
-	}
-
 	// Coalesced staging of one coefficient block of 64 consecutive Gaussians into a wave-private LDS tile
 	// (row stride SH_STRIDE floats: odd, so the lane-per-Gaussian reads that follow are bank-conflict free).
 	// The reference reads these 12*M bytes per Gaussian with a 12*M-byte stride between threads (forward.cu:85).
@@ -147,14 +87,12 @@ namespace fdgs
 		const int nf = 3 * ncoeff;                 // floats per Gaussian in this block
 		const int total = WAVE * nf;
 		const size_t row_floats = (size_t)3 * M;
-		int g = lane / nf, pos = lane - g * nf;    // element e = lane, lane + 64, ...  ->  (Gaussian, float)
-		const int dg = WAVE / nf, dpos = WAVE - dg * nf;
+		RowWalk w(lane, nf);                       // element e = lane, lane + 64, ...  ->  (Gaussian, float)
 		for (int e = lane; e < total; e += WAVE)
 		{
-			if (g0 + g < P && ((alive_mask >> g) & 1ull))
-				tile[g * SH_STRIDE + pos] = shs[(size_t)(g0 + g) * row_floats + (size_t)first_coeff * 3 + pos];
-			g += dg; pos += dpos;
-			if (pos >= nf) { pos -= nf; g++; }
+			if (g0 + w.g < P && ((alive_mask >> w.g) & 1ull))
+				tile[w.g * SH_STRIDE + w.q] = shs[(size_t)(g0 + w.g) * row_floats + (size_t)first_coeff * 3 + w.q];
+			w.step();
 		}
 	}
 	// full 16-coefficient block, rows 16-byte aligned: each lane issues its 12 dwordx4 loads back to back
@@ -445,26 +383,24 @@ namespace fdgs
 			const float* row = tile + lane * SH_STRIDE;
 			const unsigned long long amask = __ballot(alive);
 			const int g0 = blockIdx.x * blockDim.x + wave * WAVE;
-			const bool sh3d = (a.gaussian_dim == 3 || a.force_sh_3d);
-			const int ncoef0 = min(16, (a.D + 1) * (a.D + 1));
-			const int nblocks = (!sh3d && a.D > 2) ? 1 + min(max(a.D_t, 0), 2) : 1;
+			const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
 			// Q4: the forward view direction uses the UN-shifted input mean (forward.cu:480-482)
 			float3 dir = sub3(p_in, make_float3(a.campos[0], a.campos[1], a.campos[2]));
 			const float len = sqrtf(dot3(dir.x, dir.y, dir.z, dir.x, dir.y, dir.z));
 			dir = make_float3(dir.x / len, dir.y / len, dir.z / len);
 			float l[16];
-			if (!sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
-			const float dir_t = (!sh3d) ? a.ts[idx] - a.timestamp : 0.f;
+			if (!plan.sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
+			const float dir_t = (!plan.sh3d) ? a.ts[idx] - a.timestamp : 0.f;
 			float3 c = make_float3(0.f, 0.f, 0.f);
-			for (int blk = 0; blk < nblocks; blk++)
+			for (int blk = 0; blk < plan.nblocks; blk++)
 			{
-				stage_sh_block(tile, a.shs, g0, a.P, a.M, 16 * blk, blk == 0 ? ncoef0 : 16, amask, lane, a.sh_vec_ok != 0);
+				stage_sh_block(tile, a.shs, g0, a.P, a.M, 16 * blk, blk == 0 ? plan.ncoef0 : 16, amask, lane, a.sh_vec_ok != 0);
 				// the tile is wave-private and the LDS executes one wave's operations in order: no workgroup barrier (which held the four
 				// waves of the workgroup in lockstep: all loading, then all evaluating) -- only the compiler must keep the order
 				FDGS_TILE_SYNC();
 				if (alive)
 				{
-					if (blk == 0) c = sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
+					if (blk == 0) c = plan.sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
 					else
 					{
 						const float tk = (blk == 1) ? (float)cos(2 * REF_PI * dir_t / a.time_duration)
@@ -476,7 +412,7 @@ namespace fdgs
 			}
 			if (alive)
 			{
-				if (!sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
+				if (!plan.sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
 				clampbits = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
 				rgb = make_float3(fmaxf(c.x, 0.0f), fmaxf(c.y, 0.0f), fmaxf(c.z, 0.0f));
 			}
@@ -588,19 +524,17 @@ namespace fdgs
 		float* tile = s_sh[wave];
 		const float* row = tile + lane * SH_STRIDE;
 		const int g0 = blockIdx.x * blockDim.x + wave * WAVE;
-		const bool sh3d = (a.gaussian_dim == 3 || a.force_sh_3d);
-		const int ncoef0 = min(16, (a.D + 1) * (a.D + 1));
-		const int nblocks = (!sh3d && a.D > 2) ? 1 + min(max(a.D_t, 0), 2) : 1;
+		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
 		const float3 p_in = ld3(a.means3D, idx);   // Q4: the forward view direction uses the UN-shifted input mean (forward.cu:480-482)
-		const float t_in = (!sh3d) ? a.ts[idx] : 0.f;
+		const float t_in = (!plan.sh3d) ? a.ts[idx] : 0.f;
 
 		bool any = false;
 #pragma unroll 1
 		for (int v = 0; v < a.nviews; v++) any = any || (valid && a.v[v].radii[idx] > 0);
 		const unsigned long long amask = __ballot(any);   // rows of Gaussians no view kept are never fetched
-		for (int blk = 0; blk < nblocks; blk++)
+		for (int blk = 0; blk < plan.nblocks; blk++)
 		{
-			stage_sh_block(tile, a.shs, g0, a.P, a.M, 16 * blk, blk == 0 ? ncoef0 : 16, amask, lane, a.sh_vec_ok != 0);
+			stage_sh_block(tile, a.shs, g0, a.P, a.M, 16 * blk, blk == 0 ? plan.ncoef0 : 16, amask, lane, a.sh_vec_ok != 0);
 			__syncthreads();
 #pragma unroll 1
 			for (int v = 0; v < a.nviews; v++)
@@ -611,9 +545,9 @@ namespace fdgs
 				const float len = sqrtf(dot3(dir.x, dir.y, dir.z, dir.x, dir.y, dir.z));
 				dir = make_float3(dir.x / len, dir.y / len, dir.z / len);
 				float l[16];
-				if (!sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
+				if (!plan.sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
 				float3 c;
-				if (blk == 0) c = sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
+				if (blk == 0) c = plan.sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
 				else
 				{
 					const float dir_t = t_in - a.v[v].timestamp;
@@ -622,9 +556,9 @@ namespace fdgs
 					c = make_float3(s_c[3 * v][threadIdx.x], s_c[3 * v + 1][threadIdx.x], s_c[3 * v + 2][threadIdx.x]);
 					c = add3(c, scl3(tk, sh_weighted(l, row, 0, 15, 0)));
 				}
-				if (blk == nblocks - 1)
+				if (blk == plan.nblocks - 1)
 				{
-					if (!sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
+					if (!plan.sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
 					float* rec = reinterpret_cast<float*>(a.v[v].records + 3 * (size_t)idx);
 					rec[6] = fmaxf(c.x, 0.0f); rec[7] = fmaxf(c.y, 0.0f); rec[8] = fmaxf(c.z, 0.0f);
 					a.v[v].clamped[idx] = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));

@@ -23,9 +23,9 @@
 // Q3 the last time block overwrites dRGB/dt, Q4 view direction from the SHIFTED mean.  fdgs_scene.analytic_sh_grad
 // (opt-in) switches Q1-Q3 to the analytic gradient of the forward pass.
 #pragma clang fp contract(off)
-#include <algorithm>
 #include "fdgs_common.h"
 #include "fdgs_math.h"
+#include "sh_eval.h"
 
 namespace fdgs
 {
@@ -43,53 +43,6 @@ namespace fdgs
 		float* gacc; float* dL_dsh;
 		float4* stage;   // deferred mode: [P][2] = (dRGB.xyz, cos factor of time block 1) (dir.xyz, cos factor of block 2) per Gaussian instead of dL_dsh (see sh_flush_kernel)
 	};
-
-	__device__ __forceinline__ float3 s_ld3(const float* p, int k) { return make_float3(p[3 * k], p[3 * k + 1], p[3 * k + 2]); }
-	__device__ __forceinline__ float3 s_add(float3 a, float3 b) { return make_float3(a.x + b.x, a.y + b.y, a.z + b.z); }
-	__device__ __forceinline__ float3 s_scl(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
-	__device__ __forceinline__ float s_dot(float3 a, float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
-	// basis values and derivatives (backward.cu:172-263); entries the reference has no term for stay zero
-	__device__ __forceinline__ void sh_tables(int deg, float x, float y, float z, bool promote, float* l, float* dX, float* dY, float* dZ)
-	{
-#pragma unroll
-		for (int k = 0; k < 16; k++) { l[k] = 0.f; dX[k] = 0.f; dY[k] = 0.f; dZ[k] = 0.f; }
-		l[0] = SH_C0;
-		if (deg > 0)
-		{
-			l[1] = -1 * SH_C1 * y; l[2] = SH_C1 * z; l[3] = -1 * SH_C1 * x;
-			dY[1] = -1 * SH_C1; dZ[2] = SH_C1; dX[3] = -1 * SH_C1;
-			if (deg > 1)
-			{
-				const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-				l[4] = SH_C2[0] * xy; l[5] = SH_C2[1] * yz;
-				l[6] = promote ? (float)(SH_C2[2] * (2.0 * zz - xx - yy)) : SH_C2[2] * (2.f * zz - xx - yy);
-				l[7] = SH_C2[3] * xz; l[8] = SH_C2[4] * (xx - yy);
-				dX[4] = SH_C2[0] * y; dY[4] = SH_C2[0] * x;
-				dY[5] = SH_C2[1] * z; dZ[5] = SH_C2[1] * y;
-				dX[6] = -2 * SH_C2[2] * x; dY[6] = -2 * SH_C2[2] * y; dZ[6] = 4 * SH_C2[2] * z;
-				dX[7] = SH_C2[3] * z; dZ[7] = SH_C2[3] * x;
-				dX[8] = 2 * SH_C2[4] * x; dY[8] = -2 * SH_C2[4] * y;
-				if (deg > 2)
-				{
-					l[9] = SH_C3[0] * y * (3 * xx - yy);
-					l[10] = SH_C3[1] * xy * z;
-					l[11] = SH_C3[2] * y * (4 * zz - xx - yy);
-					l[12] = SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy);
-					l[13] = SH_C3[4] * x * (4 * zz - xx - yy);
-					l[14] = SH_C3[5] * z * (xx - yy);
-					l[15] = SH_C3[6] * x * (xx - 3 * yy);
-					dX[9] = SH_C3[0] * y * 6 * x;               dY[9] = SH_C3[0] * (3 * xx - 3 * yy);
-					dX[10] = SH_C3[1] * yz;                     dY[10] = SH_C3[1] * xz;                     dZ[10] = SH_C3[1] * xy;
-					dX[11] = -SH_C3[2] * y * 2 * x;             dY[11] = SH_C3[2] * (4 * zz - xx - 3 * yy);  dZ[11] = SH_C3[2] * y * 8 * z;
-					dX[12] = -SH_C3[3] * z * 6 * x;             dY[12] = -SH_C3[3] * z * 6 * y;             dZ[12] = SH_C3[3] * (6 * zz - 3 * xx - 3 * yy);
-					dX[13] = SH_C3[4] * (4 * zz - 3 * xx - yy);  dY[13] = -SH_C3[4] * x * 2 * y;             dZ[13] = SH_C3[4] * x * 8 * z;
-					dX[14] = SH_C3[5] * z * 2 * x;              dY[14] = -SH_C3[5] * z * 2 * y;             dZ[14] = SH_C3[5] * (xx - yy);
-					dX[15] = SH_C3[6] * (3 * xx - 3 * yy);      dY[15] = -SH_C3[6] * x * 6 * y;
-				}
-			}
-		}
-	}
 
 	// ---- tile <-> global, coalesced; tile row r belongs to Gaussian g0 + list[r], r < nrows ----
 	constexpr int SHB_BATCH = 6;     // float4 per lane in flight while staging (2 batches per block)
@@ -141,40 +94,24 @@ namespace fdgs
 	__device__ __forceinline__ void rows_load_any(float* __restrict__ tile, const float* __restrict__ src, const uint32_t* list, int nrows,
 	                                              int g0, size_t row_floats, int first_float, int nf, int lane)
 	{
-		int r = lane / nf, pos = lane - r * nf;
-		const int dr = WAVE / nf, dpos = WAVE - dr * nf;
+		RowWalk w(lane, nf);
 		for (int e = lane; e < nrows * nf; e += WAVE)
 		{
-			tile[r * SHB_STRIDE + pos] = src[(size_t)(g0 + list[r]) * row_floats + first_float + pos];
-			r += dr; pos += dpos;
-			if (pos >= nf) { pos -= nf; r++; }
+			tile[w.g * SHB_STRIDE + w.q] = src[(size_t)(g0 + list[w.g]) * row_floats + first_float + w.q];
+			w.step();
 		}
 	}
 	__device__ __forceinline__ void rows_store_any(const float* __restrict__ tile, float* __restrict__ dst, const uint32_t* list, int nrows,
 	                                               int g0, size_t row_floats, int first_float, int nf, int lane, bool accum)
 	{
-		int r = lane / nf, pos = lane - r * nf;
-		const int dr = WAVE / nf, dpos = WAVE - dr * nf;
+		RowWalk w(lane, nf);
 		for (int e = lane; e < nrows * nf; e += WAVE)
 		{
-			float* d = dst + (size_t)(g0 + list[r]) * row_floats + first_float + pos;
-			if (accum) *d += tile[r * SHB_STRIDE + pos];
-			else *d = tile[r * SHB_STRIDE + pos];
-			r += dr; pos += dpos;
-			if (pos >= nf) { pos -= nf; r++; }
+			float* d = dst + (size_t)(g0 + list[w.g]) * row_floats + first_float + w.q;
+			if (accum) *d += tile[w.g * SHB_STRIDE + w.q];
+			else *d = tile[w.g * SHB_STRIDE + w.q];
+			w.step();
 		}
-	}
-
-	// dL_dRGB of a Gaussian as the blend backward left it, clamped channels zeroed (backward.cu:158-161)
-	__device__ __forceinline__ float3 colour_gradient(const ShBwdArgs& a, int idx)
-	{
-		const float4 w = *reinterpret_cast<const float4*>(a.gacc + (size_t)idx * GRAD_ACC_WORDS);
-		float3 dRGB = make_float3(w.x, w.y, w.z);
-		const uint8_t cl = a.clamped[idx];
-		if (cl & 1) dRGB.x = 0.f;
-		if (cl & 2) dRGB.y = 0.f;
-		if (cl & 4) dRGB.z = 0.f;
-		return dRGB;
 	}
 
 	// One wave per workgroup: the tile is wave-private, so no workgroup barrier is needed anywhere (LDS
@@ -193,9 +130,7 @@ namespace fdgs
 		__shared__ uint32_t s_list[2 * WAVE];     // the live Gaussians waiting for evaluation
 		const int lane = threadIdx.x;
 		const size_t row_floats = (size_t)3 * a.M;
-		const bool sh3d = (a.gaussian_dim == 3 || a.force_sh_3d);
-		const int ncoef0 = min(16, (a.D + 1) * (a.D + 1));
-		const int nblocks = (!sh3d && a.D > 2) ? 1 + min(max(a.D_t, 0), 2) : 1;
+		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
 		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 		const float3 campos = make_float3(a.campos[0], a.campos[1], a.campos[2]);
 		const int nchunks = (a.P + WAVE - 1) / WAVE;
@@ -219,7 +154,7 @@ namespace fdgs
 				bool live = false;
 				if (valid && a.radii[idx] > 0)
 				{
-					const float3 dRGB = colour_gradient(a, idx);
+					const float3 dRGB = sh_colour_gradient(a.gacc, a.clamped, idx);
 					live = dRGB.x != 0.f || dRGB.y != 0.f || dRGB.z != 0.f;
 				}
 				const unsigned long long live_mask = __ballot(live);
@@ -234,33 +169,28 @@ namespace fdgs
 				{
 					// dL_dsh is fully written by this call: zero rows for the Gaussians without a colour gradient, zeros beyond the
 					// active degrees for the others (nothing to add when accumulating)
-					const int written = (nblocks - 1) * 48 + 3 * (nblocks > 1 ? 16 : ncoef0);
 					const int span = min(WAVE, g_end - base);
-					if (a.vec_ok && (written & 3) == 0)
+					if (a.vec_ok && (plan.act_floats & 3) == 0)
 					{
 						const int RC = (int)row_floats / 4, total = span * RC;
-						const int dg = WAVE / RC, dq = WAVE - dg * RC;
-						int g = lane / RC, q = lane - g * RC;
+						RowWalk w(lane, RC);
 						for (int c = lane; c < total; c += WAVE)
 						{
-							const bool lv = (live_mask >> g) & 1ull;
-							if (!lv || 4 * q >= written)
-								*reinterpret_cast<float4*>(a.dL_dsh + (size_t)(base + g) * row_floats + 4 * q) = make_float4(0.f, 0.f, 0.f, 0.f);
-							g += dg; q += dq;
-							if (q >= RC) { q -= RC; g++; }
+							const bool lv = (live_mask >> w.g) & 1ull;
+							if (!lv || 4 * w.q >= plan.act_floats)
+								*reinterpret_cast<float4*>(a.dL_dsh + (size_t)(base + w.g) * row_floats + 4 * w.q) = make_float4(0.f, 0.f, 0.f, 0.f);
+							w.step();
 						}
 					}
 					else
 					{
 						const int rf = (int)row_floats, total = span * rf;
-						const int dg = WAVE / rf, dpos = WAVE - dg * rf;
-						int g = lane / rf, pos = lane - g * rf;
+						RowWalk w(lane, rf);
 						for (int e = lane; e < total; e += WAVE)
 						{
-							const bool lv = (live_mask >> g) & 1ull;
-							if (!lv || pos >= written) a.dL_dsh[(size_t)(base + g) * row_floats + pos] = 0.f;
-							g += dg; pos += dpos;
-							if (pos >= rf) { pos -= rf; g++; }
+							const bool lv = (live_mask >> w.g) & 1ull;
+							if (!lv || w.q >= plan.act_floats) a.dL_dsh[(size_t)(base + w.g) * row_floats + w.q] = 0.f;
+							w.step();
 						}
 					}
 				}
@@ -281,16 +211,16 @@ namespace fdgs
 			const float3 dir_orig = make_float3(mean.x - campos.x, mean.y - campos.y, mean.z - campos.z); // Q4: shifted mean
 			const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
 			const float3 dir = make_float3(dir_orig.x / len, dir_orig.y / len, dir_orig.z / len);
-			const float3 dRGB = colour_gradient(a, idx);
-			const float dir_t = sh3d ? 0.f : a.ts[idx] - a.timestamp;
+			const float3 dRGB = sh_colour_gradient(a.gacc, a.clamped, idx);
+			const float dir_t = plan.sh3d ? 0.f : a.ts[idx] - a.timestamp;
 			float l[16], dX[16], dY[16], dZ[16];
-			sh_tables(a.D, dir.x, dir.y, dir.z, !sh3d, l, dX, dY, dZ);
+			sh_tables(a.D, dir.x, dir.y, dir.z, !plan.sh3d, l, dX, dY, dZ);
 
 			float3 gx = make_float3(0.f, 0.f, 0.f), gy = gx, gz = gx, gt = gx;
 			float tk_stage[2] = { 0.f, 0.f };   // cos factors of the two time blocks (deferred mode hands them to the flush)
-			for (int blk = 0; blk < nblocks; blk++)
+			for (int blk = 0; blk < plan.nblocks; blk++)
 			{
-				const int nk = (blk == 0) ? ncoef0 : 16;
+				const int nk = (blk == 0) ? plan.ncoef0 : 16;
 				const int first_float = 48 * blk;
 				const bool vec = a.vec_ok && nk == 16;
 				if (vec) rows_load16(tile, a.shs, list, nrows, g0, row_floats, first_float, lane);
@@ -317,24 +247,24 @@ namespace fdgs
 					for (int k = 0; k < 16; k++)   // fully unrolled: the tables stay in registers (no dynamic indexing)
 					{
 						if (k >= nk) break;
-						const float3 s = s_ld3(row, k);
+						const float3 s = ld3(row, k);
 						float basis = l[k];
-						if (blk == 0 && k == 1 && !sh3d && !a.analytic) basis = l[0]; // Q1
+						if (blk == 0 && k == 1 && !plan.sh3d && !a.analytic) basis = l[0]; // Q1
 						if (!STAGE)
 						{
-							const float3 d = s_scl(blk == 0 ? basis : tk * basis, dRGB);
+							const float3 d = scl3(blk == 0 ? basis : tk * basis, dRGB);
 							row[3 * k] = d.x; row[3 * k + 1] = d.y; row[3 * k + 2] = d.z;
 						}
-						st = s_add(st, s_scl(l[k], s));
-						sx = s_add(sx, s_scl(dX[k], s));
-						sy = s_add(sy, s_scl(dY[k], s));
-						sz = s_add(sz, s_scl(dZ[k], s));
+						st = add3(st, scl3(l[k], s));
+						sx = add3(sx, scl3(dX[k], s));
+						sy = add3(sy, scl3(dY[k], s));
+						sz = add3(sz, scl3(dZ[k], s));
 					}
 					if (blk == 0) { gx = sx; gy = sy; gz = sz; }
 					else
 					{
-						gx = s_add(gx, s_scl(tk, sx)); gy = s_add(gy, s_scl(tk, sy)); gz = s_add(gz, s_scl(tk, sz));
-						gt = a.analytic ? s_add(gt, s_scl(dtk_dt, st)) : s_scl(dtk_dt, st); // Q3: overwrite, not accumulate
+						gx = add3(gx, scl3(tk, sx)); gy = add3(gy, scl3(tk, sy)); gz = add3(gz, scl3(tk, sz));
+						gt = a.analytic ? add3(gt, scl3(dtk_dt, st)) : scl3(dtk_dt, st); // Q3: overwrite, not accumulate
 					}
 				}
 				__builtin_amdgcn_wave_barrier();
@@ -354,7 +284,7 @@ namespace fdgs
 					a.stage[2 * (size_t)idx + 1] = make_float4(dir.x, dir.y, dir.z, tk_stage[1]);
 				}
 				float4 o;
-				const float3 ddir = make_float3(s_dot(gx, dRGB), s_dot(gy, dRGB), s_dot(gz, dRGB));
+				const float3 ddir = make_float3(dot3(gx, dRGB), dot3(gy, dRGB), dot3(gz, dRGB));
 				// dnormvdv, auxiliary.h:108-118
 				const float3 v = dir_orig;
 				const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
@@ -362,7 +292,7 @@ namespace fdgs
 				o.x = ((+sum2 - v.x * v.x) * ddir.x - v.y * v.x * ddir.y - v.z * v.x * ddir.z) * invsum32;
 				o.y = (-v.x * v.y * ddir.x + (sum2 - v.y * v.y) * ddir.y - v.z * v.y * ddir.z) * invsum32;
 				o.z = (-v.x * v.z * ddir.x - v.y * v.z * ddir.y + (sum2 - v.z * v.z) * ddir.z) * invsum32;
-				o.w = sh3d ? 0.f : s_dot(gt, dRGB);
+				o.w = plan.sh3d ? 0.f : dot3(gt, dRGB);
 				reinterpret_cast<float4*>(a.gacc + (size_t)idx * GRAD_ACC_WORDS)[3] = o;
 			}
 			// the Gaussians that did not fit into this batch move to the front of the list
@@ -426,7 +356,8 @@ namespace fdgs
 	// wave-private LDS tile with linear float4 loads, and lane = (Gaussian, view parity) evaluates its Gaussian for the views
 	// v = parity, parity + 2, ...: per view the 8 staged numbers for the flush (dL_dRGB, direction, the two cosine factors) and
 	// the mean / time gradient in words 12..15 of the view's accumulator record.  Same arithmetic, operation by operation, as
-	// sh_bwd_kernel<true> run view by view (tests compare them bit for bit).
+	// sh_bwd_kernel<true> run view by view: on the same accumulator records the two are equal bit for bit
+	// (test_sh_backward_paths_bitwise).
 	// ------------------------------------------------------------------------------------------------
 	constexpr int SBB_MAX = 8;        // views per launch
 	constexpr int SBB_ROWS = 32;
@@ -447,17 +378,6 @@ namespace fdgs
 		} v[SBB_MAX];
 	};
 
-	__device__ __forceinline__ float3 colour_gradient_of(const float* gacc, const uint8_t* clamped, int idx)
-	{
-		const float4 w = *reinterpret_cast<const float4*>(gacc + (size_t)idx * GRAD_ACC_WORDS);
-		float3 dRGB = make_float3(w.x, w.y, w.z);
-		const uint8_t cl = clamped[idx];
-		if (cl & 1) dRGB.x = 0.f;
-		if (cl & 2) dRGB.y = 0.f;
-		if (cl & 4) dRGB.z = 0.f;
-		return dRGB;
-	}
-
 	__global__ void __launch_bounds__(WAVE) sh_bwd_batch_kernel(const ShBwdBatchArgs a)
 	{
 		__shared__ float tile[SBB_ROWS * SBB_STRIDE];
@@ -465,10 +385,7 @@ namespace fdgs
 		const int lane = threadIdx.x;
 		const int g0 = blockIdx.x * SBB_SPAN;
 		const int row_floats = 3 * a.M;
-		const bool sh3d = (a.gaussian_dim == 3 || a.force_sh_3d);
-		const int ncoef0 = min(16, (a.D + 1) * (a.D + 1));
-		const int nblocks = (!sh3d && a.D > 2) ? 1 + min(max(a.D_t, 0), 2) : 1;
-		const int act = (nblocks - 1) * 48 + 3 * (nblocks > 1 ? 16 : ncoef0);   // floats of a row the active degrees read
+		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
 		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		// ---- which Gaussians of the span carry a colour gradient in some view; the others get their zero stage records ----
@@ -483,7 +400,7 @@ namespace fdgs
 				bool live = false;
 				if (valid && a.v[v].radii[idx] > 0)
 				{
-					const float3 d = colour_gradient_of(a.v[v].gacc, a.v[v].clamped, idx);
+					const float3 d = sh_colour_gradient(a.v[v].gacc, a.v[v].clamped, idx);
 					live = d.x != 0.f || d.y != 0.f || d.z != 0.f;
 				}
 				if (valid && !live) a.v[v].stage[2 * (size_t)idx] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -500,11 +417,10 @@ namespace fdgs
 		{
 			const int nrows = min(SBB_ROWS, n - r0);
 			// ---- whole rows into the tile ----
-			if (a.vec_ok && (act & 3) == 0)
+			if (a.vec_ok && (plan.act_floats & 3) == 0)
 			{
-				const int RC = act / 4, total = nrows * RC;
-				const int dg = WAVE / RC, dq = WAVE - dg * RC;
-				int cg = lane / RC, cq = lane - cg * RC;
+				const int RC = plan.act_floats / 4, total = nrows * RC;
+				RowWalk w(lane, RC);
 				for (int c0 = 0; c0 < total; c0 += 6 * WAVE)
 				{
 					float4 val[6];
@@ -512,9 +428,8 @@ namespace fdgs
 #pragma unroll
 					for (int i = 0; i < 6; i++)
 					{
-						og[i] = cg; oq[i] = cq;
-						cg += dg; cq += dq;
-						if (cq >= RC) { cq -= RC; cg++; }
+						og[i] = w.g; oq[i] = w.q;
+						w.step();
 						if (c0 + i * WAVE + lane >= total) og[i] = -1;
 						else val[i] = *reinterpret_cast<const float4*>(a.shs + (size_t)(g0 + (int)s_list[r0 + og[i]]) * row_floats + 4 * oq[i]);
 					}
@@ -529,14 +444,12 @@ namespace fdgs
 			}
 			else
 			{
-				const int total = nrows * act;
-				const int dg = WAVE / act, dpos = WAVE - dg * act;
-				int cg = lane / act, pos = lane - cg * act;
+				const int total = nrows * plan.act_floats;
+				RowWalk w(lane, plan.act_floats);
 				for (int e = lane; e < total; e += WAVE)
 				{
-					tile[cg * SBB_STRIDE + pos] = a.shs[(size_t)(g0 + (int)s_list[r0 + cg]) * row_floats + pos];
-					cg += dg; pos += dpos;
-					if (pos >= act) { pos -= act; cg++; }
+					tile[w.g * SBB_STRIDE + w.q] = a.shs[(size_t)(g0 + (int)s_list[r0 + w.g]) * row_floats + w.q];
+					w.step();
 				}
 			}
 			__builtin_amdgcn_wave_barrier();
@@ -546,26 +459,26 @@ namespace fdgs
 			{
 				const int idx = g0 + (int)s_list[r0 + g];
 				const float* row = tile + g * SBB_STRIDE;
-				const float t_in = sh3d ? 0.f : a.ts[idx];
+				const float t_in = plan.sh3d ? 0.f : a.ts[idx];
 #pragma unroll 1
 				for (int v = vpar; v < a.nviews; v += 2)
 				{
 					if (!(a.v[v].radii[idx] > 0)) continue;
-					const float3 dRGB = colour_gradient_of(a.v[v].gacc, a.v[v].clamped, idx);
+					const float3 dRGB = sh_colour_gradient(a.v[v].gacc, a.v[v].clamped, idx);
 					if (dRGB.x == 0.f && dRGB.y == 0.f && dRGB.z == 0.f) continue;
 					const float* cp = a.v[v].campos;
 					const float* mp = a.v[v].means + 3 * (size_t)idx;
 					const float3 dir_orig = make_float3(mp[0] - cp[0], mp[1] - cp[1], mp[2] - cp[2]); // Q4: shifted mean
 					const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
 					const float3 dir = make_float3(dir_orig.x / len, dir_orig.y / len, dir_orig.z / len);
-					const float dir_t = sh3d ? 0.f : t_in - a.v[v].timestamp;
+					const float dir_t = plan.sh3d ? 0.f : t_in - a.v[v].timestamp;
 					float l[16], dX[16], dY[16], dZ[16];
-					sh_tables(a.D, dir.x, dir.y, dir.z, !sh3d, l, dX, dY, dZ);
+					sh_tables(a.D, dir.x, dir.y, dir.z, !plan.sh3d, l, dX, dY, dZ);
 					float3 gx = make_float3(0.f, 0.f, 0.f), gy = gx, gz = gx, gt = gx;
 					float tk_stage[2] = { 0.f, 0.f };
-					for (int blk = 0; blk < nblocks; blk++)
+					for (int blk = 0; blk < plan.nblocks; blk++)
 					{
-						const int nk = (blk == 0) ? ncoef0 : 16;
+						const int nk = (blk == 0) ? plan.ncoef0 : 16;
 						const float* brow = row + 48 * blk;
 						float tk = 1.f, dtk_dt = 0.f;
 						if (blk == 1)
@@ -586,23 +499,23 @@ namespace fdgs
 						for (int k = 0; k < 16; k++)
 						{
 							if (k >= nk) break;
-							const float3 sv = s_ld3(brow, k);
-							st = s_add(st, s_scl(l[k], sv));
-							sx = s_add(sx, s_scl(dX[k], sv));
-							sy = s_add(sy, s_scl(dY[k], sv));
-							sz = s_add(sz, s_scl(dZ[k], sv));
+							const float3 sv = ld3(brow, k);
+							st = add3(st, scl3(l[k], sv));
+							sx = add3(sx, scl3(dX[k], sv));
+							sy = add3(sy, scl3(dY[k], sv));
+							sz = add3(sz, scl3(dZ[k], sv));
 						}
 						if (blk == 0) { gx = sx; gy = sy; gz = sz; }
 						else
 						{
-							gx = s_add(gx, s_scl(tk, sx)); gy = s_add(gy, s_scl(tk, sy)); gz = s_add(gz, s_scl(tk, sz));
-							gt = a.analytic ? s_add(gt, s_scl(dtk_dt, st)) : s_scl(dtk_dt, st); // Q3: overwrite, not accumulate
+							gx = add3(gx, scl3(tk, sx)); gy = add3(gy, scl3(tk, sy)); gz = add3(gz, scl3(tk, sz));
+							gt = a.analytic ? add3(gt, scl3(dtk_dt, st)) : scl3(dtk_dt, st); // Q3: overwrite, not accumulate
 						}
 					}
 					a.v[v].stage[2 * (size_t)idx] = make_float4(dRGB.x, dRGB.y, dRGB.z, tk_stage[0]);
 					a.v[v].stage[2 * (size_t)idx + 1] = make_float4(dir.x, dir.y, dir.z, tk_stage[1]);
 					float4 o;
-					const float3 ddir = make_float3(s_dot(gx, dRGB), s_dot(gy, dRGB), s_dot(gz, dRGB));
+					const float3 ddir = make_float3(dot3(gx, dRGB), dot3(gy, dRGB), dot3(gz, dRGB));
 					// dnormvdv, auxiliary.h:108-118
 					const float3 w = dir_orig;
 					const float sum2 = w.x * w.x + w.y * w.y + w.z * w.z;
@@ -610,7 +523,7 @@ namespace fdgs
 					o.x = ((+sum2 - w.x * w.x) * ddir.x - w.y * w.x * ddir.y - w.z * w.x * ddir.z) * invsum32;
 					o.y = (-w.x * w.y * ddir.x + (sum2 - w.y * w.y) * ddir.y - w.z * w.y * ddir.z) * invsum32;
 					o.z = (-w.x * w.z * ddir.x - w.y * w.z * ddir.y + (sum2 - w.z * w.z) * ddir.z) * invsum32;
-					o.w = sh3d ? 0.f : s_dot(gt, dRGB);
+					o.w = plan.sh3d ? 0.f : dot3(gt, dRGB);
 					reinterpret_cast<float4*>(a.v[v].gacc + (size_t)idx * GRAD_ACC_WORDS)[3] = o;
 				}
 			}
@@ -666,7 +579,7 @@ namespace fdgs
 	// ------------------------------------------------------------------------------------------------
 	constexpr int SHF_GPW = 32;
 	// LDS row stride of the flush tile: the active blocks' floats + 1 (odd: lane-per-row accesses are conflict free)
-	static inline int shf_tile_stride(int D, int D_t, bool sh3d) { return 48 * ((!sh3d && D > 2) ? 1 + std::min(std::max(D_t, 0), 2) : 1) + 1; }
+	__host__ __device__ static inline int shf_tile_stride(const ShPlan& plan) { return 48 * plan.nblocks + 1; }
 #ifndef FDGS_SHF_BATCH
 #define FDGS_SHF_BATCH 6
 #endif
@@ -674,19 +587,12 @@ namespace fdgs
 
 	struct ShFlushArgs
 	{
-		int P, D, D_t, M, nviews, sh3d, analytic, accum, vec_ok;
+		int P, D, D_t, M, nviews, gaussian_dim, force_sh_3d, analytic, accum, vec_ok;
 		const float4* stages;   // [nviews][P][2]
 		float* dL_dsh;
 		float *p, *m, *v;       // MODE 1
 		AdamScalars k;
 	};
-
-	// basis values only (sh_tables without the derivative tables)
-	__device__ __forceinline__ void sh_values(int deg, float x, float y, float z, bool promote, float* l)
-	{
-		float dX[16], dY[16], dZ[16];
-		sh_tables(deg, x, y, z, promote, l, dX, dY, dZ);
-	}
 
 	template <int MODE>
 	__global__ void __launch_bounds__(WAVE) sh_flush_kernel(const ShFlushArgs a)
@@ -700,11 +606,9 @@ namespace fdgs
 		const bool valid = g0 + g < a.P;
 		const int idx = valid ? g0 + g : a.P - 1;
 		const int row_floats = 3 * a.M;
-		const bool sh3d = a.sh3d != 0;
-		const int ncoef0 = min(16, (a.D + 1) * (a.D + 1));
-		const int nblocks = (!sh3d && a.D > 2) ? 1 + min(max(a.D_t, 0), 2) : 1;
-		const int act_floats = min(48 * nblocks, row_floats);   // row prefix that can carry a gradient
-		const int stride = 48 * nblocks + 1;                    // = shf_tile_stride() of the launcher
+		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
+		const int stride = shf_tile_stride(plan);
+		const int tile_floats = min(stride - 1, row_floats);   // row prefix the tile holds: whole blocks (zeros beyond plan.act_floats)
 
 		float3 acc[3][8];
 #pragma unroll
@@ -720,18 +624,18 @@ namespace fdgs
 			const float4 s1 = a.stages[2 * ((size_t)v * a.P + idx) + 1];
 			any = true;
 			float l[16];
-			sh_values(a.D, s1.x, s1.y, s1.z, !sh3d, l);
+			sh_values(a.D, s1.x, s1.y, s1.z, !plan.sh3d, l);
 #pragma unroll
 			for (int j = 0; j < 8; j++)
 			{
 				const int k = 8 * half + j;
 				const float lk = half ? l[8 + j] : l[j];
 				float basis = lk;
-				if (j == 1 && half == 0 && !sh3d && !a.analytic) basis = l[0]; // Q1
-				if (k >= ncoef0) basis = 0.f;
-				acc[0][j] = s_add(acc[0][j], s_scl(basis, dRGB));
-				if (nblocks > 1) acc[1][j] = s_add(acc[1][j], s_scl(s0.w * lk, dRGB));
-				if (nblocks > 2) acc[2][j] = s_add(acc[2][j], s_scl(s1.w * lk, dRGB));
+				if (j == 1 && half == 0 && !plan.sh3d && !a.analytic) basis = l[0]; // Q1
+				if (k >= plan.ncoef0) basis = 0.f;
+				acc[0][j] = add3(acc[0][j], scl3(basis, dRGB));
+				if (plan.nblocks > 1) acc[1][j] = add3(acc[1][j], scl3(s0.w * lk, dRGB));
+				if (plan.nblocks > 2) acc[2][j] = add3(acc[2][j], scl3(s1.w * lk, dRGB));
 			}
 		}
 		const unsigned long long vmask = __ballot(any);   // bit g (and g + 32)
@@ -741,7 +645,7 @@ namespace fdgs
 #pragma unroll
 			for (int b = 0; b < 3; b++)
 			{
-				if (b >= nblocks) break;
+				if (b >= plan.nblocks) break;
 #pragma unroll
 				for (int j = 0; j < 8; j++)
 				{
@@ -755,8 +659,7 @@ namespace fdgs
 		{
 			// whole rows, float4 by float4, linearly through memory: chunk c of the wave = (Gaussian c / RC, float4 c % RC of its row)
 			const int RC = row_floats / 4, total = SHF_GPW * RC;
-			const int dg = WAVE / RC, dq = WAVE - dg * RC;
-			int cg = lane / RC, cq = lane - cg * RC;
+			RowWalk w(lane, RC);
 			for (int c0 = 0; c0 < total; c0 += SHF_BATCH * WAVE)
 			{
 				float4 pp[SHF_BATCH], mm[SHF_BATCH], vv[SHF_BATCH];
@@ -764,9 +667,8 @@ namespace fdgs
 #pragma unroll
 				for (int i = 0; i < SHF_BATCH; i++)
 				{
-					og[i] = cg; oq[i] = cq;
-					cg += dg; cq += dq;
-					if (cq >= RC) { cq -= RC; cg++; }
+					og[i] = w.g; oq[i] = w.q;
+					w.step();
 					const bool in = c0 + i * WAVE + lane < total && g0 + og[i] < a.P;
 					if (!in) og[i] = -1;
 					if (MODE == 1 && in)
@@ -782,7 +684,7 @@ namespace fdgs
 				{
 					if (og[i] < 0) continue;
 					const int e0 = 4 * oq[i];
-					const bool live = ((vmask >> og[i]) & 1ull) && e0 < act_floats;
+					const bool live = ((vmask >> og[i]) & 1ull) && e0 < tile_floats;
 					const float* t = tile + og[i] * stride + e0;
 					float ge[4] = { 0.f, 0.f, 0.f, 0.f };
 					if (live) { ge[0] = t[0]; ge[1] = t[1]; ge[2] = t[2]; ge[3] = t[3]; }
@@ -820,19 +722,17 @@ namespace fdgs
 		{
 			// any row length / alignment, float by float
 			const int total = SHF_GPW * row_floats;
-			const int dg = WAVE / row_floats, dpos = WAVE - dg * row_floats;
-			int cg = lane / row_floats, pos = lane - cg * row_floats;
+			RowWalk w(lane, row_floats);
 			for (int e = lane; e < total; e += WAVE)
 			{
-				if (g0 + cg < a.P)
+				if (g0 + w.g < a.P)
 				{
-					const bool live = ((vmask >> cg) & 1ull) && pos < act_floats;
-					float* d = a.dL_dsh + (size_t)(g0 + cg) * row_floats + pos;
-					if (!a.accum) *d = live ? tile[cg * stride + pos] : 0.f;
-					else if (live) *d += tile[cg * stride + pos];
+					const bool live = ((vmask >> w.g) & 1ull) && w.q < tile_floats;
+					float* d = a.dL_dsh + (size_t)(g0 + w.g) * row_floats + w.q;
+					if (!a.accum) *d = live ? tile[w.g * stride + w.q] : 0.f;
+					else if (live) *d += tile[w.g * stride + w.q];
 				}
-				cg += dg; pos += dpos;
-				if (pos >= row_floats) { pos -= row_floats; cg++; }
+				w.step();
 			}
 		}
 	}
@@ -841,7 +741,7 @@ namespace fdgs
 	                            const float* stages, float* dL_dsh)
 	{
 		a.P = P; a.D = D; a.D_t = D_t; a.M = M; a.nviews = nviews;
-		a.sh3d = (gaussian_dim == 3 || force_sh_3d) ? 1 : 0;
+		a.gaussian_dim = gaussian_dim; a.force_sh_3d = force_sh_3d;
 		a.analytic = analytic; a.accum = 0;
 		a.vec_ok = ((reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0 && (3 * M) % 4 == 0) ? 1 : 0;
 		a.stages = reinterpret_cast<const float4*>(stages);
@@ -857,7 +757,7 @@ namespace fdgs
 		ShFlushArgs a;
 		fill_flush_args(a, P, D, D_t, M, gaussian_dim, force_sh_3d, analytic, nviews, stages, dL_dsh);
 		a.accum = accumulate;
-		hipLaunchKernelGGL(sh_flush_kernel<0>, dim3(div_up(P, SHF_GPW)), dim3(WAVE), (size_t)SHF_GPW * shf_tile_stride(D, D_t, a.sh3d != 0) * sizeof(float), stream, a);
+		hipLaunchKernelGGL(sh_flush_kernel<0>, dim3(div_up(P, SHF_GPW)), dim3(WAVE), (size_t)SHF_GPW * shf_tile_stride(sh_plan(D, D_t, gaussian_dim, force_sh_3d, M)) * sizeof(float), stream, a);
 		return hipGetLastError();
 	}
 
@@ -873,7 +773,7 @@ namespace fdgs
 		ShFlushArgs a;
 		fill_flush_args(a, P, D, D_t, M, gaussian_dim, force_sh_3d, analytic, nviews, stages, dL_dsh);
 		a.p = params; a.m = exp_avg; a.v = exp_avg_sq; a.k = k;
-		hipLaunchKernelGGL(sh_flush_kernel<1>, dim3(div_up(P, SHF_GPW)), dim3(WAVE), (size_t)SHF_GPW * shf_tile_stride(D, D_t, a.sh3d != 0) * sizeof(float), stream, a);
+		hipLaunchKernelGGL(sh_flush_kernel<1>, dim3(div_up(P, SHF_GPW)), dim3(WAVE), (size_t)SHF_GPW * shf_tile_stride(sh_plan(D, D_t, gaussian_dim, force_sh_3d, M)) * sizeof(float), stream, a);
 		return hipGetLastError();
 	}
 }

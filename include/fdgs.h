@@ -295,7 +295,8 @@ void fdgs_debug_sparse_lists_stats(int64_t* counts3);
 /* View-batched preprocess (the views of ONE optimizer step: same Gaussian tensors, same P / M / degrees / flags; cameras and
  * timestamps differ).  The 12 M bytes of SH coefficients per Gaussian are most of what the preprocess reads, and they are
  * the same for every view: the geometry part runs per view, the SH colours of all views in ONE pass over the coefficients
- * (bit-identical to the per-view forward).  For each view v the call obtains the geometry and the image buffer through
+ * (colours and clamp bits bit-identical to the per-view forward: test_preprocess_batch_forward_is_bit_identical,
+ * test_colour_batch_edge_shapes_bitwise).  For each view v the call obtains the geometry and the image buffer through
  * alloc(alloc_users[v], ...) and fills outs[v]->radii / out_means3D / covs_com; the views' forwards are then completed one by
  * one with fdgs_rasterize_forward(scenes[v], outs[v] with preprocessed = 1, alloc, alloc_users[v], the same stream, ...).
  * The reference has no counterpart (train.py:104-166 renders the views of a batch strictly one after the other). */
@@ -305,8 +306,8 @@ int fdgs_preprocess_batch(int32_t num_views, const fdgs_scene* const* scenes, co
 /* View-batched SH backward (deferred mode), the counterpart of fdgs_preprocess_batch: after the blend backward of every
  * view (fdgs_rasterize_backward with stage_mask = 5, a grad_accum and an sh_stage of the view's own), ONE pass over the SH
  * coefficients produces every view's stage record and its mean / time gradient (words 12..15 of the view's accumulator
- * records); the views' geometry backward (stage_mask = 2) and fdgs_sh_flush / fdgs_adam_step_sh follow.  Bit-identical to the
- * per-view SH backward.  ins[v] / outs[v]: the structs of the views' backward calls. */
+ * records); the views' geometry backward (stage_mask = 2) and fdgs_sh_flush / fdgs_adam_step_sh follow.  Given the same accumulator records,
+ * bit-identical to the per-view SH backward (test_sh_backward_paths_bitwise).  ins[v] / outs[v]: the structs of the views' backward calls. */
 int fdgs_sh_backward_batch(int32_t num_views, const fdgs_scene* const* scenes, const fdgs_backward_in* const* ins,
                            const fdgs_backward_out* const* outs, void* stream);
 

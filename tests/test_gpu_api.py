@@ -792,3 +792,183 @@ def test_geometry_adam_inside_the_last_views_backward_is_the_separate_step(cfg, 
     moved = (got[0][:feat] != before[0][:feat]).float().mean().item()
     assert moved > 0.95, moved
 
+
+
+# ---- the SH kernels' edge shapes: (D, D_t, M, 3D SH, shs one float off its 16-byte alignment) x P ----
+_SH_EDGE_TABLE = [(3, 2, 48, False, False), (3, 1, 32, False, False), (3, 0, 16, False, False), (2, 0, 16, True, False),
+                  (1, 0, 4, True, False), (0, 0, 1, True, False), (3, 2, 48, False, True)]
+_SH_EDGE_IDS = ["d3t2m48", "d3t1m32", "d3t0m16", "d2m16-3d", "d1m4-3d", "d0m1-3d", "d3t2m48-misaligned"]
+_SH_EDGE_P = [1, 63, 65, 97, 229]
+
+
+def _sh_edge_setup(P, D, D_t, M, sh3d, misaligned, dev, nv=9):
+    """A 64x48 scene of P Gaussians seen by nv cameras (different centres and timestamps), its coefficients replaced by a random
+    [P, M, 3] tensor (optionally a view one float into its storage) and the degrees of the table row."""
+    from fdgs import train_host
+    from fdgs.fused import raw_settings
+    cfg = synth.SceneConfig("shedge", P, 64, 48, 3, 2, 0.06, 4.0, True, 4, False)
+    scene = synth.make_scene(cfg, seed=41 + P)
+    model = train_host.GaussianParams(scene, dev)
+    pipe = train_host.PipelineFlags()
+    bg = torch.tensor([0.1, 0.2, 0.3], device=dev)
+    cams = [train_host.SyntheticCamera(scene, dev, timestamp=(b + 0.5) / nv * scene["time_duration"]) for b in range(nv)]
+    for b, c in enumerate(cams):
+        wv = c.world_view_transform.clone()
+        wv[3, 0] += 0.03 * b
+        wv[3, 1] -= 0.02 * b
+        c.world_view_transform = wv
+        c.full_proj_transform = wv @ (torch.linalg.inv(scene["world_view_transform"].to(dev)) @ scene["full_proj_transform"].to(dev))
+        c.camera_center = torch.linalg.inv(wv)[3, :3].contiguous()
+    sets = [raw_settings(c, model, pipe, bg) for c in cams]
+    tens = list(sets[0][1])
+    gen = torch.Generator(device="cpu").manual_seed(1000 * D + 100 * D_t + M + P)
+    store = torch.zeros(P * M * 3 + 4, device=dev)
+    off = 1 if misaligned else 0
+    sh = store[off:off + P * M * 3].view(P, M, 3)
+    sh.copy_((0.4 * torch.randn(P, M, 3, generator=gen)).to(dev))
+    assert sh.is_contiguous() and (sh.data_ptr() % 16 != 0) == misaligned
+    tens[1] = sh
+    rss = [rs._replace(sh_degree=D, sh_degree_t=D_t, force_sh_3d=bool(sh3d)) for rs, _ in sets]
+    return scene, rss, tuple(tens)
+
+
+@pytest.mark.parametrize("P", _SH_EDGE_P)
+@pytest.mark.parametrize("D,D_t,M,sh3d,misaligned", _SH_EDGE_TABLE, ids=_SH_EDGE_IDS)
+def test_colour_batch_edge_shapes_bitwise(gpu_device, D, D_t, M, sh3d, misaligned, P):
+    """colour_batch_kernel against the colour half of preprocess_fwd_kernel at the shapes where the staging takes another path: one
+    Gaussian, one short of / one past a wave, two waves, four waves with a ragged end; 48-, 27-, 12- and 3-float rows; rows that
+    cannot be moved as float4; 1, 2 and 9 views (9: two launches).  Colours, clamp bits, image and radii equal bit for bit."""
+    from fdgs.fused import raw_forward, raw_preprocess_batch
+    from util import collect_forward
+    scene, rss, tens = _sh_edge_setup(P, D, D_t, M, sh3d, misaligned, gpu_device)
+    W, H = scene["W"], scene["H"]
+    single = [collect_forward(raw_forward(rs, *tens), P, W, H) for rs in rss]
+    for nv in (1, 2, 9):
+        handles = raw_preprocess_batch(rss[:nv], *tens)
+        for b in range(nv):
+            got = collect_forward(raw_forward(rss[b], *tens, preprocessed=handles[b]), P, W, H)
+            for key in ("rgb", "clamped_bits", "out_color", "radii"):
+                np.testing.assert_array_equal(single[b][key], got[key], err_msg="%d views, view %d, %s" % (nv, b, key))
+    if P >= 63:
+        assert any((s["radii"] > 0).any() for s in single) and any((s["rgb"] != 0).any() for s in single)
+
+
+def _crafted_colour_gradients(P, nv, seed):
+    """[nv, P, 3] colour gradients with a liveness pattern per view: all, none, exactly one, alternating, 33 consecutive Gaussians
+    inside one 64-span."""
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    g = torch.randn(nv, P, 3, generator=gen) * 0.3
+    g[g == 0] = 0.125
+    want = torch.zeros(nv, P, dtype=torch.bool)
+    for v in range(nv):
+        k = v % 5
+        if k == 0:
+            want[v] = True
+        elif k == 2:
+            want[v, (7 * v + P // 2) % P] = True
+        elif k == 3:
+            want[v, ::2] = True
+        elif k == 4:
+            lo = 64 * ((P - 1) // 64 // 2) + 5
+            want[v, lo:min(P, lo + 33)] = True
+    return torch.where(want[..., None], g, torch.zeros_like(g))
+
+
+@pytest.mark.parametrize("P", _SH_EDGE_P)
+@pytest.mark.parametrize("D,D_t,M,sh3d,misaligned", _SH_EDGE_TABLE, ids=_SH_EDGE_IDS)
+def test_sh_backward_paths_bitwise(gpu_device, D, D_t, M, sh3d, misaligned, P):
+    """The SH backward is a deterministic function of (dL_dRGB, clamp bits, radii, shifted means, coefficients): with crafted
+    colour gradients in the views' accumulators and num_rendered = 0 (no blend backward, no atomics) its three paths are compared
+    bit for bit -- sh_bwd_kernel<true> per view against sh_bwd_batch_kernel (stage records: 8 floats where live, the first 4
+    where dead; words 12..15 of every view's accumulator) and sh_bwd_kernel<false> (first view overwrites, later views
+    accumulate) against fdgs_sh_flush of those stages -- for 1, 2, 5 and 9 views, reference-compatible and analytic gradients."""
+    import ctypes as C
+    from fdgs import _capi
+    from fdgs.fused import raw_backward, raw_forward
+    from fdgs.gaussian_renderer.diff_gaussian_rasterization import _C
+    from util import collect_forward
+    dev = gpu_device
+    NV = 9
+    scene, rss, tens = _sh_edge_setup(P, D, D_t, M, sh3d, misaligned, dev, NV)
+    W, H = scene["W"], scene["H"]
+    (xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, pv) = tens
+    fwd = [raw_forward(rs, *tens) for rs in rss]
+    info = [collect_forward(f, P, W, H) for f in fwd]
+    crafted = _crafted_colour_gradients(P, NV, 7 + P + M)
+    # liveness on the host: visible, and a colour gradient left after the clamped channels are zeroed
+    unclamped = torch.from_numpy(np.stack([1 - i["clamped"].astype(np.int64) for i in info])).bool()      # [NV, P, 3]
+    visible = torch.from_numpy(np.stack([i["radii"] > 0 for i in info]))                                      # [NV, P]
+    live = visible & ((crafted != 0) & unclamped).any(2)
+    gacc = torch.zeros((NV, P, 16), device=dev)
+    stage_a = torch.zeros((NV, P, 8), device=dev)
+    stage_b = torch.zeros((NV, P, 8), device=dev)
+    dsh = torch.zeros((P, M, 3), device=dev)
+    ups = torch.zeros(3, H, W, device=dev)
+    pend = []
+    for b in range(NV):
+        (R, color, flow, depth, T, radii, geom, binb, img, _covs, om) = fwd[b]
+        pend.append(raw_backward(rss[b], xyz, om, radii, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, pv, geom, R, binb, img, ups,
+                                 None, None, None, None, False, grad_accum=gacc[b], sh_stage=stage_a[b], begin_only=True))
+    torch.cuda.synchronize()
+    for p in pend:
+        p["bin"].num_rendered = 0        # fdgs_rasterize_backward: no blend backward
+        assert p["bout"].grad_accum_clean == 1   # ... and no memset of the accumulator
+
+    def sh_backward(p):
+        p["bout"].stage_mask = 1
+        with torch.cuda.device(dev):
+            rc = _capi.lib.fdgs_rasterize_backward(C.byref(p["scene"]), C.byref(p["bin"]), C.byref(p["bout"]), _capi.current_stream_handle(dev))
+        _capi._check(rc, "fdgs_rasterize_backward")
+
+    for nv in (1, 2, 5, 9):
+        lv = live[:nv]
+        if P >= 97:   # the batch kernel's second round of 32 rows
+            n_union = lv.any(0).float()
+            assert max(float(n_union[s:s + 64].sum()) for s in range(0, P, 64)) >= 33
+        if nv >= 2:
+            assert bool((lv.any(0) & ~lv.all(0)).any())   # some Gaussian is live in one view and dead in another
+        snap = torch.zeros((nv, P, 16), device=dev)
+        snap[:, :, 0:3] = crafted[:nv].to(dev)
+        for analytic in (False, True):
+            for p in pend[:nv]:
+                p["scene"].analytic_sh_grad = int(analytic)
+            # sh_bwd_kernel<true>, view by view
+            gacc[:nv].copy_(snap)
+            stage_a.fill_(float("nan"))
+            for b, p in enumerate(pend[:nv]):
+                p["bout"].sh_stage = stage_a[b].data_ptr()
+                sh_backward(p)
+            torch.cuda.synchronize()
+            words_a = gacc[:nv, :, 12:16].clone()
+            # sh_bwd_batch_kernel
+            gacc[:nv].copy_(snap)
+            stage_b.fill_(float("nan"))
+            for b, p in enumerate(pend[:nv]):
+                p["bout"].sh_stage = stage_b[b].data_ptr()
+            _C.sh_backward_batch(pend[:nv])
+            torch.cuda.synchronize()
+            words_b = gacc[:nv, :, 12:16].clone()
+            sa, sb = stage_a[:nv].cpu(), stage_b[:nv].cpu()
+            what = "%d views, analytic %d" % (nv, analytic)
+            assert torch.equal((sa[:, :, :3] != 0).any(2), lv) and torch.equal((sb[:, :, :3] != 0).any(2), lv), what
+            assert torch.equal(sa[lv], sb[lv]) and not torch.isnan(sa[lv]).any(), what
+            assert torch.equal(sa[:, :, :4][~lv], sb[:, :, :4][~lv]) and float(sa[:, :, :4][~lv].abs().sum()) == 0.0, what
+            assert torch.equal(words_a, words_b), what
+            assert float(words_a.cpu()[~lv].abs().sum()) == 0.0, what
+            if lv.any() and D > 0:
+                assert float(words_a.abs().max()) > 0.0, what
+            # sh_bwd_kernel<false>: dL_dsh directly, the first view overwrites, the others accumulate -- against the flush of stage_a
+            gacc[:nv].copy_(snap)
+            dsh.fill_(float("nan"))
+            for b, p in enumerate(pend[:nv]):
+                p["bout"].sh_stage = None
+                p["bout"].dL_dsh = dsh.data_ptr()
+                p["bout"].accumulate = int(b > 0)
+                sh_backward(p)
+            torch.cuda.synchronize()
+            flushed = torch.full((P, M, 3), float("nan"), device=dev)
+            _capi.sh_flush(stage_a[:nv].contiguous(), flushed, D, D_t, rss[0].gaussian_dim, rss[0].force_sh_3d, analytic)
+            torch.cuda.synchronize()
+            assert not torch.isnan(dsh).any() and torch.equal(dsh, flushed), what
+            assert torch.equal((dsh != 0).any(2).any(1).cpu(), lv.any(0)), what
+    gacc.zero_()
