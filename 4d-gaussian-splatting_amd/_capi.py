@@ -81,6 +81,18 @@ class FdgsDebugView(_Sized):
                 ("final_T", _fp), ("tile_order", _fp)]
 
 
+class FdgsSliceIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("D", C.c_int32), ("D_t", C.c_int32), ("M", C.c_int32),
+                ("means3D", _fp), ("shs", _fp), ("opacities", _fp), ("ts", _fp), ("scales", _fp), ("scales_t", _fp), ("rotations", _fp),
+                ("rotations_r", _fp), ("scale_modifier", C.c_float), ("prefilter_var", C.c_float), ("timestamp", C.c_float),
+                ("time_duration", C.c_float), ("rot_4d", C.c_int32), ("force_sh_3d", C.c_int32)]
+
+
+class FdgsSliceOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_int32), ("index", _fp), ("xyz", _fp), ("cov3D", _fp), ("opacity", _fp),
+                ("shs", _fp), ("scales", _fp), ("rotations", _fp), ("n_live", _fp)]
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -96,7 +108,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
-            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_last_error", "fdgs_version")
+            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice", "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 11
 
 
@@ -228,6 +240,10 @@ def _load():
     lib.fdgs_frames_encode_gray_scratch_bytes.restype = C.c_int64
     lib.fdgs_frames_encode_gray.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fdgs_frames_encode_gray.restype = C.c_int
+    lib.fdgs_time_slice_scratch_bytes.argtypes = [C.c_int32]
+    lib.fdgs_time_slice_scratch_bytes.restype = C.c_size_t
+    lib.fdgs_time_slice.argtypes = [C.POINTER(FdgsSliceIn), C.POINTER(FdgsSliceOut), C.c_void_p, C.c_void_p]
+    lib.fdgs_time_slice.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

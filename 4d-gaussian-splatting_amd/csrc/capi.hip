@@ -9,11 +9,13 @@
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <mutex>
+#include <math.h>
 #include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 #include "fdgs_common.h"
+#include "sh_eval.h"   // sh_plan (host side)
 
 using namespace fdgs;
 
@@ -208,6 +210,32 @@ extern "C" size_t fdgs_binning_bytes(int32_t R, int32_t W, int32_t H)
 {
 	return bin_layout(R, false, div_up(W > 0 ? W : 1, TILE_X) * div_up(H > 0 ? H : 1, TILE_Y)).total;
 }
+extern "C" size_t fdgs_time_slice_scratch_bytes(int32_t P) { return time_slice_scratch_bytes(P); }
+extern "C" int fdgs_time_slice(const fdgs_slice_in* in, const fdgs_slice_out* out, void* scratch, void* stream)
+{
+	if (!in || !out) return fail(FDGS_ERR_INVALID_ARG, "in / out must not be NULL");
+	CHECK_STRUCT(in, fdgs_slice_in);
+	CHECK_STRUCT(out, fdgs_slice_out);
+	if (in->P < 0 || in->P >= (1 << 26) || out->capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d capacity=%d", in->P, out->capacity);
+	if (!out->n_live) return fail(FDGS_ERR_INVALID_ARG, "n_live must not be NULL");
+	if (in->P > 0)
+	{
+		if (!in->means3D || !in->shs || !in->opacities || !in->ts || !in->scales || !in->scales_t || !in->rotations || !scratch)
+			return fail(FDGS_ERR_INVALID_ARG, "means3D / shs / opacities / ts / scales / scales_t / rotations / scratch must not be NULL");
+		if (in->rot_4d && !in->rotations_r) return fail(FDGS_ERR_INVALID_ARG, "rot_4d needs rotations_r");
+		if (in->D < 0 || in->D > 3) return fail(FDGS_ERR_INVALID_ARG, "SH degree D=%d outside 0..3", in->D);
+		const ShPlan plan = sh_plan(in->D, in->D_t, 4, in->force_sh_3d, in->M);   // the blocks the kernels read: one statement of the rule
+		if (in->M < plan.act_floats / 3) return fail(FDGS_ERR_INVALID_ARG, "M=%d too small for D=%d D_t=%d", in->M, in->D, in->D_t);
+		if (plan.nblocks > 1 && !(fabsf(in->time_duration) > 0.0f))
+			return fail(FDGS_ERR_INVALID_ARG, "time_duration=%g: the time blocks of the SH rows divide by it", (double)in->time_duration);
+		if (out->capacity > 0 && (!out->index || !out->xyz || !out->cov3D || !out->opacity || !out->shs))
+			return fail(FDGS_ERR_INVALID_ARG, "slice outputs must not be NULL");
+		if ((out->scales == nullptr) != (out->rotations == nullptr)) return fail(FDGS_ERR_INVALID_ARG, "scales and rotations come together");
+	}
+	HIP_TRY(launch_time_slice(*in, *out, scratch, (hipStream_t)stream), "time_slice");
+	return FDGS_OK;
+}
+
 extern "C" void fdgs_debug_tile_sort_limits(int32_t lds_cap, int32_t rank_max) { tile_sort_debug_limits(lds_cap, rank_max); }
 extern "C" const char* fdgs_last_error(void) { return g_err; }
 extern "C" int fdgs_version(void) { return FDGS_VERSION; }

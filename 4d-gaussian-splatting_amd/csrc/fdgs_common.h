@@ -223,6 +223,10 @@ namespace fdgs
 		p = fmaf(-lr_bc1, m / denom, p);
 	}
 
+	// a 4D model at one timestamp as compact 3D Gaussians (time_slice.hip): flags + counts, scan, write + SH fold
+	size_t time_slice_scratch_bytes(int P);
+	hipError_t launch_time_slice(const fdgs_slice_in& in, const fdgs_slice_out& out, void* scratch, hipStream_t stream);
+
 	hipError_t launch_activations(int P, const float* opacity_raw, const float* scales_raw, const float* scales_t_raw, const float* rot_raw,
 	                              const float* rot_r_raw, float* opacity, float* scales, float* scales_t, float* rot, float* rot_r, hipStream_t stream);
 }

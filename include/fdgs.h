@@ -646,6 +646,55 @@ int64_t fdgs_frames_encode_gray_scratch_bytes(int32_t B, int32_t H, int32_t W);
 int fdgs_frames_encode_gray(const float* planes, int64_t plane_stride, int32_t B, int32_t H, int32_t W, uint8_t* frames, int32_t N,
                             const int32_t* index, void* scratch, void* stream);
 
+/* ---- a 4D model at one timestamp as 3D Gaussians ---------------------------------------------------------------------------------
+ * At time t a 4D Gaussian is a 3D Gaussian: the conditional mean and covariance (rot_4d: forward.cu:279-352; otherwise the plain mean
+ * and R S^2 R^T), the opacity times the temporal marginal, an SH row with the time blocks folded in.  The call computes that for the
+ * Gaussians that pass the forward's own temporal cull -- marginal = expf(-0.5 dt^2 / (prefilter_var > 0 ? prefilter_var + cov_t :
+ * cov_t)) > 0.05, cov_t = Sigma[3][3] with rot_4d, else scales_t * scale_modifier (not squared: the reference's quirk,
+ * forward.cu:431-436) -- and writes them COMPACTED, in ascending original index.  Same expressions, promotions and expf as the forward's
+ * preprocess: where the forward keeps a Gaussian, xyz / cov3D / opacity are its out_means3D / cov3D / opacity bit for bit.
+ * The inputs are the model's RAW parameters (as fdgs_scene.raw_params = 1): opacities pre-sigmoid, scales / scales_t pre-exp,
+ * quaternions of any norm; gaussian_dim == 4 is implied.  shs [n,16,3]: coefficient k < (D + 1)^2 is sh[k] + t1 sh[16 + k] + t2 sh[32 + k],
+ * tk = (float)cos(2 pi k (ts - timestamp) / time_duration) as the forward evaluates it, the time terms only where the forward has them
+ * (4D SH, D == 3, D_t >= 1 / 2; force_sh_3d: block 0 only); coefficients at or beyond (D + 1)^2 are written as 0.  SH rows of culled
+ * Gaussians are not read.  One deliberate difference a slice cannot remove: the forward's 4D path takes the SH view direction from the
+ * UNSHIFTED mean (forward.cu:79-81); whoever renders the slice takes it from xyz, the shifted one.
+ * Three launches on `stream`, no atomics.  Rows at or beyond `capacity` are never written; *n_live always is (it may exceed capacity:
+ * the caller then holds the first `capacity` rows).  scratch: fdgs_time_slice_scratch_bytes(P) bytes of device memory. */
+typedef struct fdgs_slice_in
+{
+	uint32_t struct_size;   /* sizeof(fdgs_slice_in)                                 */
+	int32_t P;              /* number of Gaussians                                   */
+	int32_t D, D_t, M;      /* active SH degree, active time degree, SH coeffs/pt    */
+	const float* means3D;     /* [P,3]                                               */
+	const float* shs;         /* [P,M,3]                                             */
+	const float* opacities;   /* [P]   raw                                           */
+	const float* ts;          /* [P]                                                 */
+	const float* scales;      /* [P,3] raw                                           */
+	const float* scales_t;    /* [P]   raw                                           */
+	const float* rotations;   /* [P,4] raw                                           */
+	const float* rotations_r; /* [P,4] raw; NULL without rot_4d                      */
+	float scale_modifier;
+	float prefilter_var;
+	float timestamp, time_duration;
+	int32_t rot_4d, force_sh_3d;
+} fdgs_slice_in;
+typedef struct fdgs_slice_out
+{
+	uint32_t struct_size;   /* sizeof(fdgs_slice_out)                                */
+	int32_t capacity;       /* rows the arrays below hold                            */
+	int32_t* index;         /* [capacity]       original index of the row            */
+	float* xyz;             /* [capacity,3]                                          */
+	float* cov3D;           /* [capacity,6]     xx, xy, xz, yy, yz, zz               */
+	float* opacity;         /* [capacity]       sigmoid(raw) * marginal              */
+	float* shs;             /* [capacity,16,3]                                       */
+	float* scales;          /* [capacity,3] or NULL; with rotations: cov3D = R diag(scales^2) R^T by an in-kernel cyclic Jacobi; */
+	float* rotations;       /* [capacity,4] or NULL  scales floored at 1e-15, unit quaternions (w,x,y,z) of a proper rotation    */
+	int32_t* n_live;        /* device int: how many Gaussians are live               */
+} fdgs_slice_out;
+size_t fdgs_time_slice_scratch_bytes(int32_t P);
+int fdgs_time_slice(const fdgs_slice_in* in, const fdgs_slice_out* out, void* scratch, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
