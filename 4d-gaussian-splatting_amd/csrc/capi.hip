@@ -880,6 +880,53 @@ extern "C" int fdgs_debug_clock_sample(uint64_t* out5, double span_ms, void* str
 	return FDGS_OK;
 }
 
+// Test hook (include/fdgs.h): radix_sort_pairs itself on the caller's pairs.  scratch = two key buffers, two value buffers, the histogram area.
+namespace
+{
+	struct SortDebugLayout { size_t keys[2], vals[2], hist, total; };
+	inline SortDebugLayout sort_debug_layout(int n)
+	{
+		SortDebugLayout L;
+		size_t o = 0;
+		const size_t p = (size_t)(n > 0 ? n : 1);
+		for (int i = 0; i < 2; i++) { L.keys[i] = o; o = align_up(o + p * 4); }
+		for (int i = 0; i < 2; i++) { L.vals[i] = o; o = align_up(o + p * 4); }
+		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)p) + 1) * 4);
+		L.total = o;
+		return L;
+	}
+}
+
+extern "C" size_t fdgs_debug_radix_sort_scratch_bytes(int32_t n) { return sort_debug_layout(n).total; }
+
+extern "C" int fdgs_debug_radix_sort_pairs(int32_t n, int32_t bit_lo, int32_t bit_hi, uint32_t* keys, uint32_t* vals, void* scratch,
+                                           void* stream_v)
+{
+	g_err[0] = 0;
+	if (n < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_radix_sort_pairs: n < 0");
+	if (bit_lo < 0 || bit_hi > 32 || bit_lo > bit_hi)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_radix_sort_pairs: bits [%d, %d) are not within 0 <= bit_lo <= bit_hi <= 32", bit_lo, bit_hi);
+	if ((bit_hi - bit_lo) % RADIX_BITS != 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_radix_sort_pairs: bits [%d, %d): the width must be a multiple of %d (whole passes)", bit_lo,
+		            bit_hi, RADIX_BITS);
+	if (n == 0 || bit_lo == bit_hi) return FDGS_OK;
+	if (!keys || !vals || !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_radix_sort_pairs: NULL argument");
+	hipStream_t stream = (hipStream_t)stream_v;
+	const SortDebugLayout L = sort_debug_layout(n);
+	char* s = (char*)scratch;
+	uint32_t* kb[2] = { (uint32_t*)(s + L.keys[0]), (uint32_t*)(s + L.keys[1]) };
+	uint32_t* vb[2] = { (uint32_t*)(s + L.vals[0]), (uint32_t*)(s + L.vals[1]) };
+	const size_t bytes = (size_t)n * 4;
+	HIP_TRY(hipMemcpyAsync(kb[0], keys, bytes, hipMemcpyDeviceToDevice, stream), "radix sort debug: copy in");
+	HIP_TRY(hipMemcpyAsync(vb[0], vals, bytes, hipMemcpyDeviceToDevice, stream), "radix sort debug: copy in");
+	int res = 0;
+	HIP_TRY(radix_sort_pairs(kb, vb, n, bit_lo, bit_hi, (uint32_t*)(s + L.hist), stream, &res), "radix_sort_pairs");
+	if (res != radix_sort_result_buffer(n, bit_lo, bit_hi)) return fail(FDGS_ERR_HIP, "fdgs_debug_radix_sort_pairs: result buffer %d", res);
+	HIP_TRY(hipMemcpyAsync(keys, kb[res], bytes, hipMemcpyDeviceToDevice, stream), "radix sort debug: copy out");
+	HIP_TRY(hipMemcpyAsync(vals, vb[res], bytes, hipMemcpyDeviceToDevice, stream), "radix sort debug: copy out");
+	return FDGS_OK;
+}
+
 extern "C" int fdgs_debug_views(int32_t P, int32_t W, int32_t H, int32_t R,
                                 const void* geom_v, const void* bin_v, const void* img_v, fdgs_debug_view* v)
 {

@@ -148,6 +148,11 @@ namespace fdgs
 	// keys[0]/vals[0] hold the input; *result receives the index (0/1) of the buffers holding the output.
 	hipError_t radix_sort_pairs(uint32_t* keys[2], uint32_t* vals[2], int n, int bit_lo, int bit_hi,
 	                            uint32_t* hist, hipStream_t stream, int* result);
+	// the *result of that call, known without running it: every pass of RADIX_BITS bits swaps the buffers
+	static inline int radix_sort_result_buffer(int n, int bit_lo, int bit_hi)
+	{
+		return n > 0 && bit_hi > bit_lo ? ((bit_hi - bit_lo + RADIX_BITS - 1) / RADIX_BITS) & 1 : 0;
+	}
 
 	// Tile binning (tilebin.hip).  counters: bin_counter_words(T) words, zero on entry of the count pass (cleared by
 	// preprocess_fwd, the forward's first kernel); after the scan they hold every tile list's start, after the

@@ -5,7 +5,7 @@
 // Same plan as the reference -- Morton order, boxes of 1024 consecutive points, exact search with box pruning --
 // re-cut for wave64 / LDS:
 //   * bounds and Morton codes stay on the device (the reference copies min / max to the host: two syncs);
-//   * the (code, index) pairs go through this library's own radix sort (binning.hip);
+//   * the (code, index) pairs go through this library's own radix sort (radix_sort.hip);
 //   * the search runs one workgroup per 256 consecutive (Morton-sorted, hence spatially close) queries; a candidate
 //     box that ANY of them still needs is staged once into LDS and scanned from there by the lanes that need it,
 //     instead of every thread gathering every candidate point from global memory (simple_knn.cu:176-188).
@@ -411,4 +411,38 @@ extern "C" int fdgs_knn_query(int32_t b, int32_t n, int32_t m, int32_t k, const 
 		else knn_query_launch<64>(n, m, k, xb, sb, L, s, qres, sres, ib, db, stream);
 	}
 	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+}
+
+// Test hook (include/fdgs.h): where the stages above lie in the scratch buffer of a finished call.  Host arithmetic only.
+extern "C" int fdgs_debug_knn_stage_offsets(int32_t query, int32_t n, int32_t m, int64_t* offsets)
+{
+	using namespace fdgs;
+	if (!offsets || n < 0 || m < 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_debug_knn_stage_offsets: bad arguments");
+	if (query)
+	{
+		const KnnQueryLayout L = knn_query_layout(n, m);
+		const int sres = radix_sort_result_buffer(m, 0, 32), qres = radix_sort_result_buffer(n, 0, 32);
+		offsets[FDGS_KNN_STAGE_BOUNDS] = (int64_t)L.bounds;
+		offsets[FDGS_KNN_STAGE_BOXES] = (int64_t)L.boxes;
+		offsets[FDGS_KNN_STAGE_SRC_CODES] = (int64_t)L.scode[sres];
+		offsets[FDGS_KNN_STAGE_SRC_ORDER] = (int64_t)L.sidx[sres];
+		offsets[FDGS_KNN_STAGE_QUERY_CODES] = (int64_t)L.qcode[qres];
+		offsets[FDGS_KNN_STAGE_QUERY_ORDER] = (int64_t)L.qidx[qres];
+		offsets[FDGS_KNN_STAGE_NBOXES] = m > 0 ? div_up(m, KNNQ_BOX) : 0;
+		offsets[FDGS_KNN_STAGE_BOX] = KNNQ_BOX;
+	}
+	else
+	{
+		const KnnLayout L = knn_layout(m);
+		const int res = radix_sort_result_buffer(m, 0, 32);
+		offsets[FDGS_KNN_STAGE_BOUNDS] = (int64_t)L.bounds;
+		offsets[FDGS_KNN_STAGE_BOXES] = (int64_t)L.boxes;
+		offsets[FDGS_KNN_STAGE_SRC_CODES] = (int64_t)L.code[res];
+		offsets[FDGS_KNN_STAGE_SRC_ORDER] = (int64_t)L.idx[res];
+		offsets[FDGS_KNN_STAGE_QUERY_CODES] = -1;
+		offsets[FDGS_KNN_STAGE_QUERY_ORDER] = -1;
+		offsets[FDGS_KNN_STAGE_NBOXES] = m > 0 ? div_up(m, KNN_BOX) : 0;
+		offsets[FDGS_KNN_STAGE_BOX] = KNN_BOX;
+	}
+	return FDGS_OK;
 }

@@ -393,6 +393,41 @@ int fdgs_debug_clock_sample(uint64_t* out5, double span_ms, void* stream);
  * exceeds `rank_max` the LDS bitonic sort (tilebin.hip); values <= 0 restore the defaults (16384, 96).  Process-wide. */
 void fdgs_debug_tile_sort_limits(int32_t lds_cap, int32_t rank_max);
 
+/* Test hook: the library's radix sort (csrc/radix_sort.hip, radix_sort_pairs -- the sort behind fdgs_dist2_knn3, fdgs_knn_query and
+ * fdgs_rigid_motion_backward; there is no second implementation) run on the caller's n (key, value) pairs of uint32, DEVICE memory.
+ * A stable LSD sort by the key bits [bit_lo, bit_hi), RADIX_BITS = 8 bits per pass: pairs with equal selected bits keep their input
+ * order.  The pairs are copied into the first of two ping-pong buffer pairs in `scratch` (fdgs_debug_radix_sort_scratch_bytes(n) bytes
+ * of device memory, which also holds the histogram area), sorted there, and copied back from whichever pair the result landed in (an odd
+ * number of passes leaves it in the second); all on `stream`.  n == 0 and bit_lo == bit_hi are no-ops that return FDGS_OK.
+ * FDGS_ERR_INVALID_ARG, with nothing launched: n < 0, a NULL pointer with n > 0, bit ranges outside 0 <= bit_lo <= bit_hi <= 32, and
+ * a width bit_hi - bit_lo that is not a multiple of 8.  radix_sort_pairs itself does not check the width: its last pass always takes
+ * a whole digit, so a ragged width silently sorts on bits up to the next multiple of 8 above bit_lo (bits beyond 31 read as 0).  The
+ * library's own callers pass (0, 32) (knn.hip) and (0, bits of the largest key) (regularize.hip, whose keys have no bits above that). */
+size_t fdgs_debug_radix_sort_scratch_bytes(int32_t n);
+int fdgs_debug_radix_sort_pairs(int32_t n, int32_t bit_lo, int32_t bit_hi, uint32_t* keys, uint32_t* vals, void* scratch, void* stream);
+
+/* Test hook: where the stages of the two k-NN searches lie in their scratch buffer once fdgs_dist2_knn3(m, ...) (query == 0; n is
+ * ignored) or fdgs_knn_query(1, n, m, ...) (query != 0) has run on it: BYTE offsets from the start of `scratch`, computed from the same
+ * layout functions the two entries use and from the sort's own rule for which of its two buffers holds the result.  Reads nothing from
+ * the device.  offsets[FDGS_KNN_STAGE_*]:
+ *   BOUNDS        float[6]          min x, y, z, max x, y, z over the sources, the queries (query search) and the origin
+ *   BOXES         float[nboxes][6]  min / max of the sources at positions [b * box, (b + 1) * box) of the sorted order
+ *   SRC_CODES     uint32[m]         the sources' 30-bit Morton codes, sorted (stable)
+ *   SRC_ORDER     uint32[m]         SRC_ORDER[j] = index of the source at sorted position j
+ *   QUERY_CODES, QUERY_ORDER        uint32[n] each, the same for the queries; -1 with query == 0
+ *   NBOXES, BOX   not offsets: the number of boxes and the sources per box (1024 / 256)
+ * FDGS_ERR_INVALID_ARG: offsets == NULL, n or m < 0. */
+#define FDGS_KNN_STAGE_BOUNDS 0
+#define FDGS_KNN_STAGE_BOXES 1
+#define FDGS_KNN_STAGE_SRC_CODES 2
+#define FDGS_KNN_STAGE_SRC_ORDER 3
+#define FDGS_KNN_STAGE_QUERY_CODES 4
+#define FDGS_KNN_STAGE_QUERY_ORDER 5
+#define FDGS_KNN_STAGE_NBOXES 6
+#define FDGS_KNN_STAGE_BOX 7
+#define FDGS_KNN_NUM_STAGES 8
+int fdgs_debug_knn_stage_offsets(int32_t query, int32_t n, int32_t m, int64_t* offsets);
+
 /* Optional per-stage timing with HIP events recorded on the caller's stream (so the
  * numbers are the kernels' own durations on that stream, not host wall time).
  * Disabled by default; when enabled each stage of forward / backward is bracketed
