@@ -1,4 +1,5 @@
-// fdgs_math.h -- small fixed-size vector / matrix helpers for the per-Gaussian kernels.
+// fdgs_math.h -- small fixed-size vector / matrix helpers for the per-Gaussian kernels, and the temporal model built from them:
+// the 4D / 3D covariance and their backwards, the temporal marginal, the activations of raw parameters and gaussian_at_time.
 //
 // The forward preprocess has to reproduce the reference's float results BIT-EXACTLY
 // wherever they feed integers (radius, tile rectangle, tile count, depth-key bits),
@@ -71,6 +72,12 @@ namespace fdgs
 	{
 		return (a[0] * b[0] + a[1] * b[1]) + (a[2] * b[2] + a[3] * b[3]);
 	}
+	__device__ __forceinline__ float3 ld3(const float* p, size_t i) { return make_float3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
+	__device__ __forceinline__ void st3(float* p, size_t i, float3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
+	__device__ __forceinline__ float3 add3(float3 a, float3 b) { return make_float3(a.x + b.x, a.y + b.y, a.z + b.z); }
+	__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
+	__device__ __forceinline__ float3 scl3(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
+	__device__ __forceinline__ float dot3(float3 a, float3 b) { return dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
 
 	// Left / right isoclinic factors of the 4D rotation, column-major
 	// (reference forward.cu:315-327): R4 = M_r * M_l.
@@ -155,6 +162,144 @@ namespace fdgs
 	{
 		const float d = (q.x * g.x + q.y * g.y) + (q.z * g.z + q.w * g.w);
 		return make_float4((g.x - q.x * d) * inv_norm, (g.y - q.y * d) * inv_norm, (g.z - q.z * d) * inv_norm, (g.w - q.w * d) * inv_norm);
+	}
+
+	// Raw parameters -> what the covariances are built from: exp on the scales, F.normalize on the quaternions (the inverse norm
+	// goes back to the caller: act_normalize_bwd needs it)
+	__device__ __forceinline__ float3 act_exp3(const float3 s) { return make_float3(expf(s.x), expf(s.y), expf(s.z)); }
+	__device__ __forceinline__ void activate(float3& sc, float4& q, float* inv_norm) { sc = act_exp3(sc); q = act_normalize(q, inv_norm); }
+	__device__ __forceinline__ void activate(float& sct, float4& qr, float* inv_norm) { sct = expf(sct); qr = act_normalize(qr, inv_norm); }
+
+	// The 3D covariance Sigma = M^T M, M = S R (reference forward.cu:242-276) and its backward (backward.cu:621-684): dSig as for
+	// cov4_backward -> d scale and d rot of the NORMALISED quaternion q that R was built from.
+	struct Cov3 { M3 R, M, Sigma; float scl[3]; };
+	__device__ __forceinline__ Cov3 cov3_build(const float3 sc, float mod, const float4 q)
+	{
+		Cov3 c;
+		c.scl[0] = mod * sc.x; c.scl[1] = mod * sc.y; c.scl[2] = mod * sc.z;
+		M3 S;
+#pragma unroll
+		for (int j = 0; j < 3; j++)
+#pragma unroll
+			for (int i = 0; i < 3; i++) S.c[j][i] = 0.0f;
+		S.c[0][0] = c.scl[0]; S.c[1][1] = c.scl[1]; S.c[2][2] = c.scl[2];
+		c.R = quat_to_R(q);
+		c.M = mul(S, c.R);
+		c.Sigma = mul(transpose(c.M), c.M);
+		return c;
+	}
+	__device__ __forceinline__ void cov3_backward(const Cov3& c, const float4 q, const M3& dSig, float3& dscale, float4& drot)
+	{
+		const float r = q.x, x = q.y, y = q.z, z = q.w;
+		M3 M2;
+#pragma unroll
+		for (int j = 0; j < 3; j++)
+#pragma unroll
+			for (int i = 0; i < 3; i++) M2.c[j][i] = 2.0f * c.M.c[j][i];
+		const M3 dM = mul(M2, dSig);
+		const M3 Rt = transpose(c.R);
+		M3 dMt = transpose(dM);
+		dscale.x = dot3(Rt.c[0][0], Rt.c[0][1], Rt.c[0][2], dMt.c[0][0], dMt.c[0][1], dMt.c[0][2]);
+		dscale.y = dot3(Rt.c[1][0], Rt.c[1][1], Rt.c[1][2], dMt.c[1][0], dMt.c[1][1], dMt.c[1][2]);
+		dscale.z = dot3(Rt.c[2][0], Rt.c[2][1], Rt.c[2][2], dMt.c[2][0], dMt.c[2][1], dMt.c[2][2]);
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+#pragma unroll
+			for (int i = 0; i < 3; i++) dMt.c[k][i] *= c.scl[k];
+#define DD(i, j) dMt.c[i][j]
+		drot.x = 2 * z * (DD(0, 1) - DD(1, 0)) + 2 * y * (DD(2, 0) - DD(0, 2)) + 2 * x * (DD(1, 2) - DD(2, 1));
+		drot.y = 2 * y * (DD(1, 0) + DD(0, 1)) + 2 * z * (DD(2, 0) + DD(0, 2)) + 2 * r * (DD(1, 2) - DD(2, 1)) - 4 * x * (DD(2, 2) + DD(1, 1));
+		drot.z = 2 * x * (DD(1, 0) + DD(0, 1)) + 2 * r * (DD(2, 0) - DD(0, 2)) + 2 * z * (DD(1, 2) + DD(2, 1)) - 4 * y * (DD(2, 2) + DD(0, 0));
+		drot.w = 2 * r * (DD(0, 1) - DD(1, 0)) + 2 * x * (DD(2, 0) + DD(0, 2)) + 2 * y * (DD(1, 2) + DD(2, 1)) - 4 * z * (DD(1, 1) + DD(0, 0));
+#undef DD
+	}
+	// the symmetric gradient matrix the two covariance backwards take, from the six gradients of the upper triangle: the
+	// off-diagonal halves split
+	__device__ __forceinline__ M3 sym_split(const float* d)
+	{
+		M3 S;
+		S.c[0][0] = d[0]; S.c[0][1] = 0.5f * d[1]; S.c[0][2] = 0.5f * d[2];
+		S.c[1][0] = 0.5f * d[1]; S.c[1][1] = d[3]; S.c[1][2] = 0.5f * d[4];
+		S.c[2][0] = 0.5f * d[2]; S.c[2][1] = 0.5f * d[4]; S.c[2][2] = d[5];
+		return S;
+	}
+
+	// The 1-D temporal marginal exp(-dt^2 / 2 var) with the reference's double promotion of the exponent (forward.cu:334-336,
+	// 431-437) over the prefiltered variance (prefilter_var <= 0: none).  The cull is marginal > 0.05.
+	__device__ __forceinline__ float prefiltered_var(float var, float prefilter_var) { return (prefilter_var > 0.0) ? (prefilter_var + var) : var; }
+	__device__ __forceinline__ float temporal_marginal(float dt, float var, float prefilter_var)
+	{
+		return expf((float)(-0.5 * dt * dt / prefiltered_var(var, prefilter_var)));
+	}
+
+	// ---- The temporal model: what a Gaussian of the model is at time `timestamp` ----
+	// rot_4d: the mean and covariance of the 4D Gaussian conditioned on t (forward.cu:279-352); otherwise the plain 3D covariance
+	// (forward.cu:242-276) and, for gaussian_dim == 4, the marginal of an independent temporal axis whose VARIANCE is scales_t
+	// (forward.cu:431-437); either way the opacity times the marginal, and no Gaussian whose marginal is <= 0.05.  This is the one
+	// statement of it: the forward preprocess continues from here with the view transform, the time slice stores it.  The geometry
+	// backward differentiates the same cov4_build / cov3_build / temporal_marginal; its conditioning step reads Sigma[3][k] where
+	// this one reads Sigma[k][3] (Q7) and stays its own.
+	// `in`: the parameters AS STORED (raw: the activations run here).  Mean shift, conditional covariance and the opacity product
+	// exist only for a Gaussian that is alive; `alive` starts as `valid` and, on the rot_4d path, is the marginal's test alone.
+	struct GaussIn { float3 p; float opacity; float3 sc; float sct; float4 q, qr; float t; };
+	struct GaussAtTime { bool alive; float3 mean; float cov[6]; float opacity; };
+	__device__ __forceinline__ void gaussian_at_time(const GaussIn& in, const bool valid, const int raw, const int rot_4d, const int gaussian_dim,
+	                                                 const float mod, const float prefilter_var, const float timestamp,
+	                                                 const float* __restrict__ cov_precomp, GaussAtTime& o)
+	{
+		o.alive = valid; o.mean = in.p;
+		o.opacity = raw ? act_sigmoid(in.opacity) : in.opacity;
+#pragma unroll
+		for (int k = 0; k < 6; k++) o.cov[k] = 0.f;
+		float unused;
+		if (cov_precomp != nullptr)
+		{
+#pragma unroll
+			for (int k = 0; k < 6; k++) o.cov[k] = cov_precomp[k];
+		}
+		else if (rot_4d)
+		{
+			float3 sc = in.sc;
+			float sct = in.sct;
+			float4 q = in.q, qr = in.qr;
+			if (raw) { activate(sc, q, &unused); activate(sct, qr, &unused); }
+			const float dt = timestamp - in.t;
+			const M4 Sigma = cov4_build(sc, sct, mod, q, qr).Sigma;
+			const float cov_t = Sigma.c[3][3];
+			const float marginal_t = temporal_marginal(dt, cov_t, prefilter_var);
+			o.alive = marginal_t > 0.05;
+			if (o.alive)
+			{
+				o.opacity *= marginal_t;
+				const float c12[3] = { Sigma.c[0][3], Sigma.c[1][3], Sigma.c[2][3] };
+				o.cov[0] = Sigma.c[0][0] - (c12[0] * c12[0]) / cov_t;
+				o.cov[1] = Sigma.c[0][1] - (c12[1] * c12[0]) / cov_t;
+				o.cov[2] = Sigma.c[0][2] - (c12[2] * c12[0]) / cov_t;
+				o.cov[3] = Sigma.c[1][1] - (c12[1] * c12[1]) / cov_t;
+				o.cov[4] = Sigma.c[1][2] - (c12[2] * c12[1]) / cov_t;
+				o.cov[5] = Sigma.c[2][2] - (c12[2] * c12[2]) / cov_t;
+				o.mean.x += c12[0] / cov_t * dt;
+				o.mean.y += c12[1] / cov_t * dt;
+				o.mean.z += c12[2] / cov_t * dt;
+			}
+		}
+		else
+		{
+			float3 sc = in.sc;
+			float4 q = in.q;
+			if (raw) activate(sc, q, &unused);
+			const M3 Sigma = cov3_build(sc, mod, q).Sigma;
+			o.cov[0] = Sigma.c[0][0]; o.cov[1] = Sigma.c[0][1]; o.cov[2] = Sigma.c[0][2];
+			o.cov[3] = Sigma.c[1][1]; o.cov[4] = Sigma.c[1][2]; o.cov[5] = Sigma.c[2][2];
+			if (gaussian_dim == 4)
+			{
+				const float dt = in.t - timestamp;   // (the other sign than above: as the reference has it)
+				const float sigma = (raw ? expf(in.sct) : in.sct) * mod;
+				const float marginal_t = temporal_marginal(dt, sigma, prefilter_var);
+				if (marginal_t <= 0.05) o.alive = false;
+				else o.opacity *= marginal_t;
+			}
+		}
 	}
 
 	// SH constants (reference auxiliary.h:23-40)

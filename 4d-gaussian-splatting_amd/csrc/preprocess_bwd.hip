@@ -49,12 +49,6 @@ namespace fdgs
 		float ad_b1, ad_b2, ad_eps, ad_inv_sqrt_bc2;
 	};
 
-	__device__ __forceinline__ float3 b_ld3(const float* p, size_t i) { return make_float3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
-	__device__ __forceinline__ void b_st3(float* p, size_t i, float3 v) { p[3 * i] = v.x; p[3 * i + 1] = v.y; p[3 * i + 2] = v.z; }
-	__device__ __forceinline__ float3 b_add(float3 a, float3 b) { return make_float3(a.x + b.x, a.y + b.y, a.z + b.z); }
-	__device__ __forceinline__ float3 b_scl(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
-	__device__ __forceinline__ float b_dot(float3 a, float3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-
 	// auxiliary.h:108-118
 	__device__ __forceinline__ float3 dnormvdv(float3 v, float3 dv)
 	{
@@ -112,7 +106,7 @@ namespace fdgs
 
 		if (visible)
 		{
-			const float3 mean = b_ld3(a.means, idx);
+			const float3 mean = ld3(a.means, idx);
 			const float* cov3D = (a.cov3D_precomp ? a.cov3D_precomp : a.cov3D) + 6 * (size_t)idx;
 			float c3[6];
 #pragma unroll
@@ -194,14 +188,10 @@ namespace fdgs
 			if (a.scales)
 			{
 				const float mod = a.scale_modifier;
-				float3 sc = b_ld3(a.scales, idx);
+				float3 sc = ld3(a.scales, idx);
 				float4 q = reinterpret_cast<const float4*>(a.rotations)[idx];
 				float inv_nq = 1.f, inv_nqr = 1.f;
-				if (a.raw)
-				{
-					sc = make_float3(expf(sc.x), expf(sc.y), expf(sc.z));
-					q = act_normalize(q, &inv_nq);
-				}
+				if (a.raw) activate(sc, q, &inv_nq);
 				if (a.rot_4d)
 				{
 					// backward.cu:689-834
@@ -210,23 +200,17 @@ namespace fdgs
 					float opac = a.opacities[idx];
 					if (a.raw)
 					{
-						scale_t = expf(scale_t);
-						qr = act_normalize(qr, &inv_nqr);
+						activate(scale_t, qr, &inv_nqr);
 						opac = act_sigmoid(opac);
 					}
 					const float dt = a.timestamp - a.ts[idx];
-					const M4 S = diag4(mod * sc.x, mod * sc.y, mod * sc.z, mod * scale_t);
-					M4 Ml, Mr;
-					build_Ml_Mr(q, qr, Ml, Mr);
-					const M4 R = mul(Mr, Ml);
-					const M4 M = mul(S, R);
-					const M4 Sigma = mul(transpose(M), M);
-					const float cov_t = Sigma.c[3][3];
-					const float cov_t_pre = (a.prefilter_var > 0.0) ? (a.prefilter_var + cov_t) : cov_t;
-					const float marginal_t = expf((float)(-0.5 * dt * dt / cov_t_pre));
+					const Cov4 c = cov4_build(sc, scale_t, mod, q, qr);
+					const float cov_t = c.Sigma.c[3][3];
+					const float cov_t_pre = prefiltered_var(cov_t, a.prefilter_var);
+					const float marginal_t = temporal_marginal(dt, cov_t, a.prefilter_var);
 					if (marginal_t > 0.05)
 					{
-						const float c12[3] = { Sigma.c[3][0], Sigma.c[3][1], Sigma.c[3][2] }; // Q7
+						const float c12[3] = { c.Sigma.c[3][0], c.Sigma.c[3][1], c.Sigma.c[3][2] }; // Q7
 						float d12[3];
 						d12[0] = -(float)(dcov[0] * c12[0] + dcov[1] * c12[1] * 0.5 + dcov[2] * c12[2] * 0.5) * 2.0f / cov_t;
 						d12[1] = -(float)(dcov[1] * c12[0] * 0.5 + dcov[3] * c12[1] + dcov[4] * c12[2] * 0.5) * 2.0f / cov_t;
@@ -242,42 +226,21 @@ namespace fdgs
 						float dL_dt = dL_dmarginal_t * dmarg_dt;
 						// Q5: the whole mean gradient is treated as the gradient of delta_mean
 						d12[0] += dmean.x / cov_t * dt; d12[1] += dmean.y / cov_t * dt; d12[2] += dmean.z / cov_t * dt;
-						const float ddot = dmean.x * c12[0] + dmean.y * c12[1] + dmean.z * c12[2];
+						const float ddot = dot3(dmean, make_float3(c12[0], c12[1], c12[2]));
 						dL_dcovt += -ddot / (cov_t * cov_t) * dt;
 						dL_dt += -ddot / cov_t;
 						dts += dL_dt;
+						const M3 d11 = sym_split(dcov);
 						M4 dSig;
-						dSig.c[0][0] = dcov[0]; dSig.c[0][1] = 0.5f * dcov[1]; dSig.c[0][2] = 0.5f * dcov[2]; dSig.c[0][3] = 0.5f * d12[0];
-						dSig.c[1][0] = 0.5f * dcov[1]; dSig.c[1][1] = dcov[3]; dSig.c[1][2] = 0.5f * dcov[4]; dSig.c[1][3] = 0.5f * d12[1];
-						dSig.c[2][0] = 0.5f * dcov[2]; dSig.c[2][1] = 0.5f * dcov[4]; dSig.c[2][2] = dcov[5]; dSig.c[2][3] = 0.5f * d12[2];
-						dSig.c[3][0] = 0.5f * d12[0]; dSig.c[3][1] = 0.5f * d12[1]; dSig.c[3][2] = 0.5f * d12[2]; dSig.c[3][3] = dL_dcovt;
-						M4 M2;
 #pragma unroll
-						for (int j = 0; j < 4; j++)
+						for (int j = 0; j < 3; j++)
+						{
 #pragma unroll
-							for (int i = 0; i < 4; i++) M2.c[j][i] = 2.0f * M.c[j][i];
-						const M4 dM = mul(M2, dSig);
-						const M4 Rt = transpose(R);
-						M4 dMt = transpose(dM);
-						dscale.x = dot4(Rt.c[0], dMt.c[0]);
-						dscale.y = dot4(Rt.c[1], dMt.c[1]);
-						dscale.z = dot4(Rt.c[2], dMt.c[2]);
-						dscale_t = dot4(Rt.c[3], dMt.c[3]);
-						const float scl[4] = { mod * sc.x, mod * sc.y, mod * sc.z, mod * scale_t };
-#pragma unroll
-						for (int k = 0; k < 4; k++)
-#pragma unroll
-							for (int i = 0; i < 4; i++) dMt.c[k][i] *= scl[k];
-						const M4 A = mul(dMt, Mr);
-						drot.x = A.c[0][0] + A.c[1][1] + A.c[2][2] + A.c[3][3];
-						drot.y = -A.c[0][1] + A.c[1][0] - A.c[2][3] + A.c[3][2];
-						drot.z = A.c[0][2] - A.c[1][3] - A.c[2][0] + A.c[3][1];
-						drot.w = -A.c[0][3] - A.c[1][2] + A.c[2][1] + A.c[3][0];
-						const M4 B = mul(Ml, dMt);
-						drot_r.x = B.c[0][0] + B.c[1][1] + B.c[2][2] + B.c[3][3];
-						drot_r.y = -B.c[0][1] + B.c[1][0] + B.c[2][3] - B.c[3][2];
-						drot_r.z = B.c[0][2] + B.c[1][3] - B.c[2][0] - B.c[3][1];
-						drot_r.w = B.c[0][3] - B.c[1][2] + B.c[2][1] - B.c[3][0];
+							for (int i = 0; i < 3; i++) dSig.c[j][i] = d11.c[j][i];
+							dSig.c[j][3] = 0.5f * d12[j]; dSig.c[3][j] = 0.5f * d12[j];
+						}
+						dSig.c[3][3] = dL_dcovt;
+						cov4_backward(c, dSig, dscale, dscale_t, drot, drot_r);
 						if (a.raw)
 						{
 							dscale_t *= scale_t;                       // d exp
@@ -287,43 +250,8 @@ namespace fdgs
 				}
 				else
 				{
-					// backward.cu:621-684
-					const float r = q.x, x = q.y, y = q.z, z = q.w;
-					const M3 R = quat_to_R(q);
-					const float s3[3] = { mod * sc.x, mod * sc.y, mod * sc.z };
-					M3 S;
-#pragma unroll
-					for (int j = 0; j < 3; j++)
-#pragma unroll
-						for (int i = 0; i < 3; i++) S.c[j][i] = 0.f;
-					S.c[0][0] = s3[0]; S.c[1][1] = s3[1]; S.c[2][2] = s3[2];
-					const M3 M = mul(S, R);
-					M3 dSig;
-					dSig.c[0][0] = dcov[0]; dSig.c[0][1] = 0.5f * dcov[1]; dSig.c[0][2] = 0.5f * dcov[2];
-					dSig.c[1][0] = 0.5f * dcov[1]; dSig.c[1][1] = dcov[3]; dSig.c[1][2] = 0.5f * dcov[4];
-					dSig.c[2][0] = 0.5f * dcov[2]; dSig.c[2][1] = 0.5f * dcov[4]; dSig.c[2][2] = dcov[5];
-					M3 M2;
-#pragma unroll
-					for (int j = 0; j < 3; j++)
-#pragma unroll
-						for (int i = 0; i < 3; i++) M2.c[j][i] = 2.0f * M.c[j][i];
-					const M3 dM = mul(M2, dSig);
-					const M3 Rt = transpose(R);
-					M3 dMt = transpose(dM);
-					dscale.x = dot3(Rt.c[0][0], Rt.c[0][1], Rt.c[0][2], dMt.c[0][0], dMt.c[0][1], dMt.c[0][2]);
-					dscale.y = dot3(Rt.c[1][0], Rt.c[1][1], Rt.c[1][2], dMt.c[1][0], dMt.c[1][1], dMt.c[1][2]);
-					dscale.z = dot3(Rt.c[2][0], Rt.c[2][1], Rt.c[2][2], dMt.c[2][0], dMt.c[2][1], dMt.c[2][2]);
-#pragma unroll
-					for (int k = 0; k < 3; k++)
-#pragma unroll
-						for (int i = 0; i < 3; i++) dMt.c[k][i] *= s3[k];
-#define DD(i, j) dMt.c[i][j]
-					drot.x = 2 * z * (DD(0, 1) - DD(1, 0)) + 2 * y * (DD(2, 0) - DD(0, 2)) + 2 * x * (DD(1, 2) - DD(2, 1));
-					drot.y = 2 * y * (DD(1, 0) + DD(0, 1)) + 2 * z * (DD(2, 0) + DD(0, 2)) + 2 * r * (DD(1, 2) - DD(2, 1)) - 4 * x * (DD(2, 2) + DD(1, 1));
-					drot.z = 2 * x * (DD(1, 0) + DD(0, 1)) + 2 * r * (DD(2, 0) - DD(0, 2)) + 2 * z * (DD(1, 2) + DD(2, 1)) - 4 * y * (DD(2, 2) + DD(0, 0));
-					drot.w = 2 * r * (DD(0, 1) - DD(1, 0)) + 2 * x * (DD(2, 0) + DD(0, 2)) + 2 * y * (DD(1, 2) + DD(2, 1)) - 4 * z * (DD(1, 1) + DD(0, 0));
-#undef DD
-					// Q6: gaussian_dim == 4 without rot_4d has no marginal-opacity backward
+					// backward.cu:621-684.  Q6: gaussian_dim == 4 without rot_4d has no marginal-opacity backward
+					cov3_backward(cov3_build(sc, mod, q), q, sym_split(dcov), dscale, drot);
 				}
 				if (a.raw)
 				{
@@ -340,9 +268,9 @@ namespace fdgs
 			g_opacity *= o * (1.0f - o);
 		}
 		// ---- stores (every output written for every Gaussian) ----
-		b_st3(a.dL_dmean2D, idx, g_mean2D);
+		st3(a.dL_dmean2D, idx, g_mean2D);
 		// (the three per-view outputs nobody downstream of a training step reads may be NULL: fdgs_backward_out)
-		if (a.dL_dcolor) b_st3(a.dL_dcolor, idx, g_color);
+		if (a.dL_dcolor) st3(a.dL_dcolor, idx, g_color);
 		if (a.dL_dflows) { a.dL_dflows[2 * (size_t)idx] = g_flow.x; a.dL_dflows[2 * (size_t)idx + 1] = g_flow.y; }
 		if (a.dL_dcov3D)
 		{
@@ -389,9 +317,9 @@ namespace fdgs
 			return;
 		}
 		a.dL_dopacity[idx] = g_opacity;
-		b_st3(a.dL_dmeans, idx, dmean);
+		st3(a.dL_dmeans, idx, dmean);
 		if (a.dL_dts) a.dL_dts[idx] = dts;
-		if (a.dL_dscale) b_st3(a.dL_dscale, idx, dscale);
+		if (a.dL_dscale) st3(a.dL_dscale, idx, dscale);
 		if (a.dL_dscale_t) a.dL_dscale_t[idx] = dscale_t;
 		if (a.dL_drot) reinterpret_cast<float4*>(a.dL_drot)[idx] = drot;
 		if (a.dL_drot_r) reinterpret_cast<float4*>(a.dL_drot_r)[idx] = drot_r;

@@ -163,104 +163,30 @@ namespace fdgs
 		return make_ushort4((unsigned short)tx0, (unsigned short)ty0, (unsigned short)tx1, (unsigned short)ty1);
 	}
 
-	// The geometry of one Gaussian (everything of preprocessCUDA but the colour): forward.cu:279-352 / 242-276 / 431-437, the near cull,
-	// the EWA projection, conic, radius and tile rectangle.  ``in``: the inputs AS STORED (raw parameters when a.raw: the activations run
-	// here); shared by the one-launch kernel, the geometry half of the split forward and the streaming kernel below.
-	struct GeoIn { float3 p; float opacity; float3 sc; float sct; float4 q, qr; float t; };
+	// The geometry of one Gaussian (everything of preprocessCUDA but the colour): what the Gaussian is at the view's timestamp
+	// (fdgs_math.h: gaussian_at_time), then the near cull, the EWA projection, conic, radius and tile rectangle.  ``in``: the inputs AS
+	// STORED; shared by the one-launch kernel and the geometry half of the split forward.
 	struct GeoOut
 	{
 		bool alive; int radius; uint32_t tiles; ushort4 rect; float depth; float2 pix; float3 conic; float opacity; float3 p_orig; float cov[6];
 	};
-	__device__ __forceinline__ void pre_geometry(const PreArgs& a, const GeoIn& in, const float* __restrict__ cov_precomp, const bool valid, GeoOut& o,
+	__device__ __forceinline__ void pre_geometry(const PreArgs& a, const GaussIn& in, const float* __restrict__ cov_precomp, const bool valid, GeoOut& o,
 	                                             const float* __restrict__ viewmatrix, const float* __restrict__ projmatrix)
 	{
-		float3 p_orig = in.p;
-		float opacity = in.opacity;
-		if (a.raw) opacity = act_sigmoid(opacity);
-		float cov[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-		bool alive = valid;
+		GaussAtTime g;
+		gaussian_at_time(in, valid, a.raw, a.rot_4d, a.gaussian_dim, a.scale_modifier, a.prefilter_var, a.timestamp, cov_precomp, g);
+		bool alive = g.alive;
+		const float3 p_orig = g.mean;
+		const float opacity = g.opacity;
+		float cov[6];
+#pragma unroll
+		for (int k = 0; k < 6; k++) cov[k] = g.cov[k];
 		int radius = 0;
 		uint32_t tiles = 0;
 		ushort4 rect = make_ushort4(0, 0, 0, 0);
 		float depth = 0.0f;
 		float2 pix = make_float2(0.f, 0.f);
 		float3 conic = make_float3(0.f, 0.f, 0.f);
-		if (cov_precomp != nullptr)
-		{
-#pragma unroll
-			for (int k = 0; k < 6; k++) cov[k] = cov_precomp[k];
-		}
-		else if (a.rot_4d)
-		{
-			// forward.cu:279-352
-			float3 sc = in.sc;
-			float sct = in.sct;
-			float4 q = in.q, qr = in.qr;
-			if (a.raw)
-			{
-				float unused;
-				sc = make_float3(expf(sc.x), expf(sc.y), expf(sc.z));
-				sct = expf(sct);
-				q = act_normalize(q, &unused);
-				qr = act_normalize(qr, &unused);
-			}
-			const float mod = a.scale_modifier;
-			const float dt = a.timestamp - in.t;
-			const M4 S = diag4(mod * sc.x, mod * sc.y, mod * sc.z, mod * sct);
-			M4 Ml, Mr;
-			build_Ml_Mr(q, qr, Ml, Mr);
-			const M4 M = mul(S, mul(Mr, Ml));
-			const M4 Sigma = mul(transpose(M), M);
-			const float cov_t = Sigma.c[3][3];
-			const float marginal_t = expf((float)(-0.5 * dt * dt / ((a.prefilter_var > 0.0) ? (a.prefilter_var + cov_t) : cov_t)));
-			alive = marginal_t > 0.05;
-			if (alive)
-			{
-				opacity *= marginal_t;
-				const float c12[3] = { Sigma.c[0][3], Sigma.c[1][3], Sigma.c[2][3] };
-				cov[0] = Sigma.c[0][0] - (c12[0] * c12[0]) / cov_t;
-				cov[1] = Sigma.c[0][1] - (c12[1] * c12[0]) / cov_t;
-				cov[2] = Sigma.c[0][2] - (c12[2] * c12[0]) / cov_t;
-				cov[3] = Sigma.c[1][1] - (c12[1] * c12[1]) / cov_t;
-				cov[4] = Sigma.c[1][2] - (c12[2] * c12[1]) / cov_t;
-				cov[5] = Sigma.c[2][2] - (c12[2] * c12[2]) / cov_t;
-				p_orig.x += c12[0] / cov_t * dt;
-				p_orig.y += c12[1] / cov_t * dt;
-				p_orig.z += c12[2] / cov_t * dt;
-			}
-		}
-		else
-		{
-			// forward.cu:242-276
-			float3 sc = in.sc;
-			float4 q = in.q;
-			if (a.raw)
-			{
-				float unused;
-				sc = make_float3(expf(sc.x), expf(sc.y), expf(sc.z));
-				q = act_normalize(q, &unused);
-			}
-			const float mod = a.scale_modifier;
-			M3 S;
-#pragma unroll
-			for (int j = 0; j < 3; j++)
-#pragma unroll
-				for (int i = 0; i < 3; i++) S.c[j][i] = 0.0f;
-			S.c[0][0] = mod * sc.x; S.c[1][1] = mod * sc.y; S.c[2][2] = mod * sc.z;
-			const M3 M = mul(S, quat_to_R(q));
-			const M3 Sigma = mul(transpose(M), M);
-			cov[0] = Sigma.c[0][0]; cov[1] = Sigma.c[0][1]; cov[2] = Sigma.c[0][2];
-			cov[3] = Sigma.c[1][1]; cov[4] = Sigma.c[1][2]; cov[5] = Sigma.c[2][2];
-			if (a.gaussian_dim == 4)
-			{
-				// forward.cu:431-437 (scales_t used as a variance)
-				const float dt = in.t - a.timestamp;
-				const float sigma = (a.raw ? expf(in.sct) : in.sct) * mod;
-				const float marginal_t = expf((float)(-0.5 * dt * dt / ((a.prefilter_var > 0.0) ? (a.prefilter_var + sigma) : sigma)));
-				if (marginal_t <= 0.05) alive = false;
-				else opacity *= marginal_t;
-			}
-		}
 
 		if (alive)
 		{
@@ -347,7 +273,7 @@ namespace fdgs
 		if constexpr (PART == 2) alive = valid && a.radii[idx] > 0;   // what the geometry launch kept
 		else
 		{
-			GeoIn in;
+			GaussIn in;
 			in.p = p_orig; in.opacity = opacity;
 			in.sc = make_float3(0.f, 0.f, 0.f); in.sct = 0.f; in.t = 0.f;
 			in.q = make_float4(1.f, 0.f, 0.f, 0.f); in.qr = in.q;
@@ -622,11 +548,7 @@ namespace fdgs
 		if (idx >= P) return;
 		float unused;
 		if (opacity_raw && opacity) opacity[idx] = act_sigmoid(opacity_raw[idx]);
-		if (scales_raw && scales)
-		{
-			const float3 sc = ld3(scales_raw, idx);
-			scales[3 * (size_t)idx + 0] = expf(sc.x); scales[3 * (size_t)idx + 1] = expf(sc.y); scales[3 * (size_t)idx + 2] = expf(sc.z);
-		}
+		if (scales_raw && scales) st3(scales, idx, act_exp3(ld3(scales_raw, idx)));
 		if (scales_t_raw && scales_t) scales_t[idx] = expf(scales_t_raw[idx]);
 		if (rot_raw && rot) reinterpret_cast<float4*>(rot)[idx] = act_normalize(reinterpret_cast<const float4*>(rot_raw)[idx], &unused);
 		if (rot_r_raw && rot_r) reinterpret_cast<float4*>(rot_r)[idx] = act_normalize(reinterpret_cast<const float4*>(rot_r_raw)[idx], &unused);

@@ -4,7 +4,7 @@
 //   motion  L_motion = mean_i |v_i|
 //   mask    L_opa    = mean(-(1 - gt_alpha_mask) log(1 - clamp(alpha, 1e-6, 1 - 1e-6)))
 // with the velocity v = Sigma[0:3,3] / Sigma[3,3] * dt, dt = (t + 0.1f) - t: the conditional mean shift of the 4D Gaussian
-// (scene/gaussian_model.py:34-47, 247-251), Sigma built by fdgs_math.h's cov4_build exactly as the preprocess builds it.
+// (scene/gaussian_model.py:34-47, 247-251), Sigma from fdgs_math.h's cov4_build: the call the preprocess and the time slice make.
 // Every sum is a fixed-order reduction of per-workgroup partials (no float atomics), and the rigid term's neighbour-side gradient
 // is GATHERED through a reverse-neighbour list -- the (neighbour, pair) table sorted stably by neighbour with the library's radix
 // sort -- so the gradients are bitwise reproducible (its cost at C3: profiles/HISTORY.md).
@@ -43,27 +43,26 @@ namespace fdgs
 		return (red[0] + red[1]) + (red[2] + red[3]);
 	}
 
-	struct RegGauss { Cov4 c; float4 q, qr; float inv_q, inv_qr, sc[3], sct, dt; };
+	struct RegGauss { Cov4 c; float4 q, qr; float inv_q, inv_qr; float3 sc; float sct, dt; };
 
 	__device__ __forceinline__ RegGauss reg_gauss(int i, const float* __restrict__ scaling, const float* __restrict__ scaling_t,
 	                                              const float* __restrict__ rotation, const float* __restrict__ rotation_r,
 	                                              const float* __restrict__ t)
 	{
 		RegGauss g;
-		g.sc[0] = expf(scaling[3 * (size_t)i]); g.sc[1] = expf(scaling[3 * (size_t)i + 1]); g.sc[2] = expf(scaling[3 * (size_t)i + 2]);
-		g.sct = expf(scaling_t[i]);
+		g.sc = ld3(scaling, i);
+		g.sct = scaling_t[i];
 		// scalar loads: a slice of a flat parameter bucket need not be 16-byte aligned
-		g.q = act_normalize(make_float4(rotation[4 * (size_t)i], rotation[4 * (size_t)i + 1], rotation[4 * (size_t)i + 2], rotation[4 * (size_t)i + 3]),
-		                    &g.inv_q);
-		g.qr = act_normalize(make_float4(rotation_r[4 * (size_t)i], rotation_r[4 * (size_t)i + 1], rotation_r[4 * (size_t)i + 2],
-		                                 rotation_r[4 * (size_t)i + 3]), &g.inv_qr);
-		g.c = cov4_build(make_float3(g.sc[0], g.sc[1], g.sc[2]), g.sct, 1.0f, g.q, g.qr);
+		g.q = make_float4(rotation[4 * (size_t)i], rotation[4 * (size_t)i + 1], rotation[4 * (size_t)i + 2], rotation[4 * (size_t)i + 3]);
+		g.qr = make_float4(rotation_r[4 * (size_t)i], rotation_r[4 * (size_t)i + 1], rotation_r[4 * (size_t)i + 2], rotation_r[4 * (size_t)i + 3]);
+		activate(g.sc, g.q, &g.inv_q);
+		activate(g.sct, g.qr, &g.inv_qr);
+		g.c = cov4_build(g.sc, g.sct, 1.0f, g.q, g.qr);
 		const float ti = t[i];
 		g.dt = (ti + 0.1f) - ti;
 		return g;
 	}
 
-	__device__ __forceinline__ float3 ld3(const float* __restrict__ v, size_t i) { return make_float3(v[3 * i], v[3 * i + 1], v[3 * i + 2]); }
 	__device__ __forceinline__ float norm3(float x, float y, float z) { return sqrtf((x * x + y * y) + z * z); }
 
 	__global__ void __launch_bounds__(REG_THREADS) reg_velocity_kernel(int P, const float* __restrict__ scaling, const float* __restrict__ scaling_t,
@@ -185,7 +184,7 @@ namespace fdgs
 		const float cr = g_rigid / (float)k / (float)P;
 		gv.x += cr * acc.x; gv.y += cr * acc.y; gv.z += cr * acc.z;
 
-		// v = c12 / ct * dt  ->  Sigma  ->  scale / rotations (the preprocess backward's chain, preprocess_bwd.hip)
+		// v = c12 / ct * dt  ->  Sigma  ->  scale / rotations (cov4_backward, as the preprocess backward)
 		const RegGauss g = reg_gauss(i, scaling, scaling_t, rotation, rotation_r, t);
 		const float ct = g.c.Sigma.c[3][3];
 		const float c12[3] = { g.c.Sigma.c[0][3], g.c.Sigma.c[1][3], g.c.Sigma.c[2][3] };
@@ -203,9 +202,9 @@ namespace fdgs
 		float dscale_t;
 		float4 drot, drot_r;
 		cov4_backward(g.c, dSig, dscale, dscale_t, drot, drot_r);
-		d_scaling[3 * (size_t)i] += dscale.x * g.sc[0];            // d exp
-		d_scaling[3 * (size_t)i + 1] += dscale.y * g.sc[1];
-		d_scaling[3 * (size_t)i + 2] += dscale.z * g.sc[2];
+		d_scaling[3 * (size_t)i] += dscale.x * g.sc.x;             // d exp
+		d_scaling[3 * (size_t)i + 1] += dscale.y * g.sc.y;
+		d_scaling[3 * (size_t)i + 2] += dscale.z * g.sc.z;
 		d_scaling_t[i] += dscale_t * g.sct;
 		const float4 dq = act_normalize_bwd(g.q, g.inv_q, drot), dqr = act_normalize_bwd(g.qr, g.inv_qr, drot_r);
 		float* oq = d_rotation + 4 * (size_t)i;

@@ -1,5 +1,5 @@
 // sh_eval.h -- the spherical-harmonics pieces that the forward colour (preprocess_fwd.hip) and the SH backward and its flush
-// (sh_bwd.hip) share, each ONCE: the float3 helpers, the block plan, the basis tables, the forward's block sums, the colour
+// (sh_bwd.hip) share, each ONCE: the block plan, the basis tables, the forward's block sums, the colour
 // gradient and the row walker.
 //
 // Every piece carries a quirk of the reference: Q1 dL_dsh[1] = l[0] * dRGB in the 4D path, Q2 the sign
@@ -16,12 +16,6 @@
 
 namespace fdgs
 {
-	__device__ __forceinline__ float3 ld3(const float* p, size_t i) { return make_float3(p[3 * i], p[3 * i + 1], p[3 * i + 2]); }
-	__device__ __forceinline__ float3 add3(float3 a, float3 b) { return make_float3(a.x + b.x, a.y + b.y, a.z + b.z); }
-	__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
-	__device__ __forceinline__ float3 scl3(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
-	__device__ __forceinline__ float dot3(float3 a, float3 b) { return dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
-
 	// ---- which coefficient blocks of a row are active ----
 	// Block 0 = the plain SH sum over ncoef0 coefficients; blocks 1 / 2 = all 16 basis values times cos(2 pi k dt / T), k = 1, 2:
 	// only the 4D path at degree 3 has them (forward.cu:133-192).

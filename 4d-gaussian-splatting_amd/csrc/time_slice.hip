@@ -14,9 +14,10 @@
 //              16 bytes per lane where the rows allow it.  SH rows of culled Gaussians are never read.
 // Rows at or beyond `capacity` are never written; n_live always is.
 //
-// Bit-exactness: slice_geometry restates pre_geometry (preprocess_fwd.hip) operation for operation, on the shared helpers of
-// fdgs_math.h, with the same flags (no FP contraction, no SLP vectorizer): where the forward keeps a Gaussian, mean, covariance and
-// opacity here are the forward's, bit for bit (tests/test_gpu_slice.py).
+// Bit-exactness: slice_geometry is the forward's gaussian_at_time (fdgs_math.h) for raw parameters, put together from the same shared
+// pieces -- activate, cov4_build / cov3_build, temporal_marginal -- in the same order and built with the same flags (no FP contraction,
+// no SLP vectorizer): where the forward keeps a Gaussian, mean, covariance and opacity here are the forward's, bit for bit
+// (tests/test_gpu_slice.py).  Nothing of a culled Gaussian is stored.
 #pragma clang fp contract(off)
 #include "fdgs_common.h"
 #include "fdgs_math.h"
@@ -35,69 +36,48 @@ namespace fdgs
 		uint32_t* counts;            // [workgroups] live Gaussians per workgroup -> (scan) the workgroup's first rank
 	};
 
-	struct SliceGeo { bool live; float3 p; float cov[6]; float opacity; };
-
-	// pre_geometry's covariance / marginal / mean shift on RAW parameters (a.raw), gaussian_dim == 4
-	__device__ __forceinline__ void slice_geometry(const SliceArgs& a, const int idx, SliceGeo& o)
+	// gaussian_at_time (fdgs_math.h) for raw parameters and gaussian_dim == 4, from the same shared pieces in the same order.  Kept as
+	// its own function: calling gaussian_at_time here compiles to the same operations per Gaussian, but its per-branch activations and
+	// `if (alive)` form cost slice_write_kernel 14 registers (62 -> 76).  A culled Gaussian's fields are computed and never stored.
+	__device__ __forceinline__ void slice_geometry(const SliceArgs& a, const int idx, GaussAtTime& o)
 	{
-		float3 p_orig = ld3(a.means3D, idx);
-		float opacity = act_sigmoid(a.opacities[idx]);
-		float cov[6] = { 0.f, 0.f, 0.f, 0.f, 0.f, 0.f };
-		bool alive;
+		o.mean = ld3(a.means3D, idx);
+		o.opacity = act_sigmoid(a.opacities[idx]);
 		float unused;
 		float3 sc = ld3(a.scales, idx);
-		sc = make_float3(expf(sc.x), expf(sc.y), expf(sc.z));
-		const float4 q = act_normalize(reinterpret_cast<const float4*>(a.rotations)[idx], &unused);
+		float4 q = reinterpret_cast<const float4*>(a.rotations)[idx];
+		activate(sc, q, &unused);
 		const float mod = a.scale_modifier;
+		float marginal_t;
 		if (a.rot_4d)
 		{
-			// forward.cu:279-352
-			const float sct = expf(a.scales_t[idx]);
-			const float4 qr = act_normalize(reinterpret_cast<const float4*>(a.rotations_r)[idx], &unused);
+			float sct = a.scales_t[idx];
+			float4 qr = reinterpret_cast<const float4*>(a.rotations_r)[idx];
+			activate(sct, qr, &unused);
 			const float dt = a.timestamp - a.ts[idx];
-			const M4 S = diag4(mod * sc.x, mod * sc.y, mod * sc.z, mod * sct);
-			M4 Ml, Mr;
-			build_Ml_Mr(q, qr, Ml, Mr);
-			const M4 M = mul(S, mul(Mr, Ml));
-			const M4 Sigma = mul(transpose(M), M);
+			const M4 Sigma = cov4_build(sc, sct, mod, q, qr).Sigma;
 			const float cov_t = Sigma.c[3][3];
-			const float marginal_t = expf((float)(-0.5 * dt * dt / ((a.prefilter_var > 0.0) ? (a.prefilter_var + cov_t) : cov_t)));
-			alive = marginal_t > 0.05;
-			opacity *= marginal_t;
+			marginal_t = temporal_marginal(dt, cov_t, a.prefilter_var);
 			const float c12[3] = { Sigma.c[0][3], Sigma.c[1][3], Sigma.c[2][3] };
-			cov[0] = Sigma.c[0][0] - (c12[0] * c12[0]) / cov_t;
-			cov[1] = Sigma.c[0][1] - (c12[1] * c12[0]) / cov_t;
-			cov[2] = Sigma.c[0][2] - (c12[2] * c12[0]) / cov_t;
-			cov[3] = Sigma.c[1][1] - (c12[1] * c12[1]) / cov_t;
-			cov[4] = Sigma.c[1][2] - (c12[2] * c12[1]) / cov_t;
-			cov[5] = Sigma.c[2][2] - (c12[2] * c12[2]) / cov_t;
-			p_orig.x += c12[0] / cov_t * dt;
-			p_orig.y += c12[1] / cov_t * dt;
-			p_orig.z += c12[2] / cov_t * dt;
+			o.cov[0] = Sigma.c[0][0] - (c12[0] * c12[0]) / cov_t;
+			o.cov[1] = Sigma.c[0][1] - (c12[1] * c12[0]) / cov_t;
+			o.cov[2] = Sigma.c[0][2] - (c12[2] * c12[0]) / cov_t;
+			o.cov[3] = Sigma.c[1][1] - (c12[1] * c12[1]) / cov_t;
+			o.cov[4] = Sigma.c[1][2] - (c12[2] * c12[1]) / cov_t;
+			o.cov[5] = Sigma.c[2][2] - (c12[2] * c12[2]) / cov_t;
+			o.mean.x += c12[0] / cov_t * dt;
+			o.mean.y += c12[1] / cov_t * dt;
+			o.mean.z += c12[2] / cov_t * dt;
 		}
 		else
 		{
-			// forward.cu:242-276
-			M3 S;
-#pragma unroll
-			for (int j = 0; j < 3; j++)
-#pragma unroll
-				for (int i = 0; i < 3; i++) S.c[j][i] = 0.0f;
-			S.c[0][0] = mod * sc.x; S.c[1][1] = mod * sc.y; S.c[2][2] = mod * sc.z;
-			const M3 M = mul(S, quat_to_R(q));
-			const M3 Sigma = mul(transpose(M), M);
-			cov[0] = Sigma.c[0][0]; cov[1] = Sigma.c[0][1]; cov[2] = Sigma.c[0][2];
-			cov[3] = Sigma.c[1][1]; cov[4] = Sigma.c[1][2]; cov[5] = Sigma.c[2][2];
-			// forward.cu:431-437 (scales_t used as a variance)
-			const float dt = a.ts[idx] - a.timestamp;
-			const float sigma = expf(a.scales_t[idx]) * mod;
-			const float marginal_t = expf((float)(-0.5 * dt * dt / ((a.prefilter_var > 0.0) ? (a.prefilter_var + sigma) : sigma)));
-			alive = marginal_t > 0.05;
-			opacity *= marginal_t;
+			const M3 Sigma = cov3_build(sc, mod, q).Sigma;
+			o.cov[0] = Sigma.c[0][0]; o.cov[1] = Sigma.c[0][1]; o.cov[2] = Sigma.c[0][2];
+			o.cov[3] = Sigma.c[1][1]; o.cov[4] = Sigma.c[1][2]; o.cov[5] = Sigma.c[2][2];
+			marginal_t = temporal_marginal(a.ts[idx] - a.timestamp, expf(a.scales_t[idx]) * mod, a.prefilter_var);
 		}
-		o.live = alive; o.p = p_orig; o.opacity = opacity;
-#pragma unroll
-		for (int k = 0; k < 6; k++) o.cov[k] = cov[k];
+		o.alive = marginal_t > 0.05;
+		o.opacity *= marginal_t;
 	}
 
 	constexpr int SLICE_THREADS = 256;
@@ -111,9 +91,9 @@ namespace fdgs
 		const bool valid = tid_g < a.P;
 		const int idx = valid ? tid_g : a.P - 1;   // out-of-range lanes shadow the last Gaussian and count for nothing
 		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		SliceGeo g;
+		GaussAtTime g;
 		slice_geometry(a, idx, g);
-		const unsigned long long mask = __ballot(valid && g.live);
+		const unsigned long long mask = __ballot(valid && g.alive);
 		if (lane == 0)
 		{
 			a.masks[(size_t)blockIdx.x * SLICE_WAVES + wave] = mask;
@@ -256,13 +236,13 @@ namespace fdgs
 		const ShPlan plan = sh_plan(a.D, a.D_t, 4, a.force_sh_3d, a.M);
 		if (live)
 		{
-			SliceGeo g;
+			GaussAtTime g;
 			slice_geometry(a, idx, g);
 			const size_t r = (size_t)rank0 + (size_t)r_in;
 			if (r < (size_t)a.capacity)
 			{
 				a.index[r] = idx;
-				a.xyz[3 * r + 0] = g.p.x; a.xyz[3 * r + 1] = g.p.y; a.xyz[3 * r + 2] = g.p.z;
+				st3(a.xyz, r, g.mean);
 #pragma unroll
 				for (int k = 0; k < 6; k++) a.cov3D[6 * r + k] = g.cov[k];
 				a.opacity[r] = g.opacity;

@@ -972,3 +972,51 @@ def test_sh_backward_paths_bitwise(gpu_device, D, D_t, M, sh3d, misaligned, P):
             assert not torch.isnan(dsh).any() and torch.equal(dsh, flushed), what
             assert torch.equal((dsh != 0).any(2).any(1).cpu(), lv.any(0)), what
     gacc.zero_()
+
+
+# ---- the geometry kernels' bits, pinned (tests/golden/make_golden_geometry.py) ----
+def _golden_geometry():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_geometry.py")
+    spec = importlib.util.spec_from_file_location("make_golden_geometry", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_GG = _golden_geometry()
+_GG_CACHE = {}
+
+
+def _geometry_fixture(name):
+    """models.npz or one case file, loaded once"""
+    import os
+    if name not in _GG_CACHE:
+        _GG_CACHE[name] = _GG.load_models() if name == "models" else np.load(os.path.join(_GG.OUT_DIR, name + ".npz"))
+    return _GG_CACHE[name]
+
+
+@pytest.mark.parametrize("P", _GG.SIZES)
+@pytest.mark.parametrize("mod", list(_GG.MODIFIER))
+@pytest.mark.parametrize("pf", list(_GG.PREFILTER))
+@pytest.mark.parametrize("variant", list(_GG.VARIANTS))
+def test_geometry_kernels_pinned_bits(gpu_device, variant, pf, mod, P):
+    """One forward and the geometry backward alone (stage_mask 2: a thread per Gaussian, no atomics) on a crafted accumulator
+    pattern, against the bits the library produced before the covariance-at-time code was gathered in fdgs_math.h: radii, shifted
+    means, covariances, the image and every dL_d* output equal as 32-bit patterns.  rot_4d raw and activated, gaussian_dim 4
+    without rot_4d raw and activated, gaussian_dim 3, cov3D_precomp; prefilter off and on; scale modifier 1 and 0.7; 1, 63, 65 and
+    229 Gaussians on a 48x40 image.  The fixtures are this toolchain's bits: the generator's docstring says how to re-record."""
+    model = _geometry_fixture("models")[P]
+    want = _geometry_fixture("%s_%s_%s" % (variant, pf, mod))
+    got = _GG.run_case(model, variant, pf, mod, gpu_device)
+    assert set(got) == set(_GG.FORWARD_KEYS + _GG.BACKWARD_KEYS)
+    for k in _GG.FORWARD_KEYS + _GG.BACKWARD_KEYS:
+        w = want["P%d_%s" % (P, k)]
+        assert got[k].shape == w.shape and got[k].dtype == w.dtype, k
+        a, b = got[k].view(np.uint32), w.view(np.uint32)
+        bad = np.argwhere(a != b)
+        assert bad.size == 0, "%s: %d of %d words differ, first at %s: %08x != %08x" % (
+            k, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
+    if P >= 63:
+        _GG.check_contents(model, variant, pf, mod, got)
