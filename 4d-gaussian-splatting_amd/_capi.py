@@ -93,6 +93,18 @@ class FdgsSliceOut(_Sized):
                 ("shs", _fp), ("scales", _fp), ("rotations", _fp), ("n_live", _fp)]
 
 
+class FdgsFlowIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("means3D", _fp), ("ts", _fp),
+                ("scales", _fp), ("scales_t", _fp), ("rotations", _fp), ("rotations_r", _fp), ("viewmatrix", _fp), ("projmatrix", _fp),
+                ("viewmatrix_to", _fp), ("projmatrix_to", _fp), ("timestamp", C.c_float), ("timestamp_to", C.c_float),
+                ("scale_modifier", C.c_float), ("rot_4d", C.c_int32), ("gaussian_dim", C.c_int32), ("raw_params", C.c_int32)]
+
+
+class FdgsFlowGrads(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("d_means3D", _fp), ("d_ts", _fp), ("d_scales", _fp), ("d_scales_t", _fp),
+                ("d_rotations", _fp), ("d_rotations_r", _fp)]
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -108,7 +120,8 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
-            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice", "fdgs_last_error", "fdgs_version")
+            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
+            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 11
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
 KNN_STAGE_BOUNDS, KNN_STAGE_BOXES, KNN_STAGE_SRC_CODES, KNN_STAGE_SRC_ORDER, KNN_STAGE_QUERY_CODES, KNN_STAGE_QUERY_ORDER, \
@@ -253,6 +266,10 @@ def _load():
     lib.fdgs_time_slice_scratch_bytes.restype = C.c_size_t
     lib.fdgs_time_slice.argtypes = [C.POINTER(FdgsSliceIn), C.POINTER(FdgsSliceOut), C.c_void_p, C.c_void_p]
     lib.fdgs_time_slice.restype = C.c_int
+    lib.fdgs_gaussian_flow_forward.argtypes = [C.POINTER(FdgsFlowIn), C.c_void_p, C.c_void_p]
+    lib.fdgs_gaussian_flow_forward.restype = C.c_int
+    lib.fdgs_gaussian_flow_backward.argtypes = [C.POINTER(FdgsFlowIn), C.c_void_p, C.c_float, C.POINTER(FdgsFlowGrads), C.c_void_p]
+    lib.fdgs_gaussian_flow_backward.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

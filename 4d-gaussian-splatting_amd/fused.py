@@ -23,20 +23,21 @@ import torch
 from .gaussian_renderer.diff_gaussian_rasterization import GaussianRasterizationSettings, _C, _is_given
 
 
-def _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var):
+def _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, flows=None):
     e = torch.Tensor([])
-    return (rs.bg, means3D, e, e, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
+    return (rs.bg, means3D, e, e if flows is None else flows, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
             rs.scale_modifier, e, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
             rs.image_height, rs.image_width, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp,
             rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, rs.prefiltered, rs.debug)
 
 
 def raw_forward(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var,
-                split_colour=False, preprocessed=None, tile_cull=False, lazy=False, sparse_lists=False, colour_stream=None):
-    """Native forward on RAW parameters (fdgs_scene.raw_params = 1); the reference binding's 11-tuple.
+                split_colour=False, preprocessed=None, tile_cull=False, lazy=False, sparse_lists=False, colour_stream=None, flows=None):
+    """Native forward on RAW parameters (fdgs_scene.raw_params = 1); the reference binding's 11-tuple.  ``flows``: the rasterizer's
+    per-Gaussian ``flow_2d`` input [P, 2] (default: none, the flow image is zero).
     ``preprocessed``: the view's handle from ``raw_preprocess_batch``; ``tile_cull``: fdgs_forward_out.tile_cull; ``lazy``:
     fdgs_forward_out.lazy (num_rendered comes back as -1, the host does not wait); ``sparse_lists``: fdgs_forward_out.sparse_lists; ``colour_stream``: fdgs_forward_out.colour_stream (a torch.cuda.Stream)."""
-    args = _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var)
+    args = _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, flows)
     return _C.rasterize_gaussians(*args, raw_params=True, split_colour=split_colour, preprocessed=preprocessed, tile_cull=tile_cull, lazy=lazy,
                                   sparse_lists=sparse_lists, colour_stream=colour_stream)
 
@@ -52,13 +53,13 @@ def raw_preprocess_batch(settings, means3D, sh, opacity_raw, ts, scaling_raw, sc
 
 def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
                  prefilter_var, geom, R, binb, img, g_color, g_depth, g_alpha, g_flow, sink, accumulate, grad_accum=None, after_sh=None,
-                 sh_stage=None, begin_only=False, per_view_outputs=True, geometry_adam=None):
-    """Native backward on RAW parameters; gradients go into ``sink`` where given; the binding's 12-tuple.
+                 sh_stage=None, begin_only=False, per_view_outputs=True, geometry_adam=None, flows=None):
+    """Native backward on RAW parameters; gradients go into ``sink`` where given; the binding's 12-tuple.  ``flows``: the forward's.
     ``begin_only``: only the blend backward (``_C.backward_begin``): returns the pending call for ``_C.sh_backward_batch`` /
     ``_C.backward_finish``.  ``per_view_outputs=False``: dL_dcolors / dL_dcov3D / dL_dflows are not written (None in the tuple).
     ``geometry_adam``: see ``_C.rasterize_gaussians_backward`` (the geometry parameters' Adam step inside the geometry backward)."""
     e = torch.Tensor([])
-    args = (rs.bg, means3D, out_means3D, radii, e, e, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
+    args = (rs.bg, means3D, out_means3D, radii, e, e if flows is None else flows, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
             rotation_r_raw, rs.scale_modifier, e, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
             rs.tanfovy, g_color, g_depth, g_alpha, g_flow, sh, rs.sh_degree, rs.sh_degree_t, rs.campos,
             rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, geom, R, binb, img, rs.debug)
@@ -108,13 +109,15 @@ def raw_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
 class _RasterizeRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
-                prefilter_var, raster_settings, grad_sink, accumulate, tile_cull=False):
+                prefilter_var, raster_settings, grad_sink, accumulate, tile_cull=False, flows=None):
         rs = raster_settings
         (R, color, flow, depth, T, radii, geom, binb, img, covs_com, out_means3D) = raw_forward(
-            rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, tile_cull=tile_cull)
+            rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, tile_cull=tile_cull,
+            flows=flows)
         ctx.rs, ctx.R, ctx.prefilter_var, ctx.sink, ctx.accumulate = rs, R, prefilter_var, grad_sink, bool(accumulate)
+        ctx.has_flows = flows is not None
         ctx.save_for_backward(means3D, out_means3D, scaling_raw, rotation_raw, radii, sh, opacity_raw, ts, scaling_t_raw,
-                              rotation_r_raw, geom, binb, img)
+                              rotation_r_raw, geom, binb, img, *((flows,) if flows is not None else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)  # unused outputs -> None gradients -> colour-only backward
         return color, radii, depth, 1 - T, flow
@@ -123,12 +126,13 @@ class _RasterizeRaw(torch.autograd.Function):
     def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_flow):
         rs = ctx.rs
         (means3D, out_means3D, scaling_raw, rotation_raw, radii, sh, opacity_raw, ts, scaling_t_raw, rotation_r_raw,
-         geom, binb, img) = ctx.saved_tensors
+         geom, binb, img) = ctx.saved_tensors[:13]
+        flows = ctx.saved_tensors[13] if ctx.has_flows else None
         sink = ctx.sink
-        (d_means2D, _d_colors, d_opacity, d_means3D, _d_cov3D, d_sh, _d_flows, d_ts, d_scales, d_scales_t, d_rot,
+        (d_means2D, _d_colors, d_opacity, d_means3D, _d_cov3D, d_sh, d_flows, d_ts, d_scales, d_scales_t, d_rot,
          d_rot_r) = raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
                                  rotation_r_raw, ctx.prefilter_var, geom, ctx.R, binb, img, g_color, g_depth, g_alpha, g_flow,
-                                 sink, ctx.accumulate)
+                                 sink, ctx.accumulate, flows=flows)
 
         def ret(name, given, g):
             if not _is_given(given):
@@ -141,18 +145,33 @@ class _RasterizeRaw(torch.autograd.Function):
                 ret("dL_dopacity", opacity_raw, d_opacity), ret("dL_dts", ts, d_ts),
                 ret("dL_dscales", scaling_raw, d_scales), ret("dL_dscales_t", scaling_t_raw, d_scales_t),
                 ret("dL_drotations", rotation_raw, d_rot), ret("dL_drotations_r", rotation_r_raw, d_rot_r),
-                None, None, None, None, None)
+                None, None, None, None, None) + ((d_flows.reshape(flows.shape),) if ctx.has_flows else ())
 
 
-def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, grad_sink=None, accumulate=False, tile_cull=False):
+def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, grad_sink=None, accumulate=False, tile_cull=False,
+               *, flow_to=None):
     """``render()`` with the activations fused into the kernels; see the module docstring.  ``tile_cull``:
-    fdgs_forward_out.tile_cull (shorter tile lists, same pixels and gradients)."""
+    fdgs_forward_out.tile_cull (shorter tile lists, same pixels and gradients).  ``flow_to``: a camera of the same image size
+    (``fdgs.playback.with_timestamp(viewpoint_camera, t1)``: the same camera at another time); the rasterizer's per-Gaussian flow input
+    is then every Gaussian's screen motion from this view to that one (``fdgs.flow.gaussian_flow`` of the raw parameters) instead of
+    zeros and ``"flow"`` is the blended image ``sum_i flow_i alpha_i T_i`` in pixels, NOT divided by alpha (divide by ``"alpha"`` for
+    the mean motion of what a pixel shows).  A loss on ``"flow"`` reaches the parameters through the rasterizer and through the flow
+    itself, both by autograd: not together with ``grad_sink``."""
     rs, (xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var) = raw_settings(
         viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
-    color, radii, depth, alpha, flow = _RasterizeRaw.apply(
-        xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
-        prefilter_var, rs, grad_sink, accumulate, tile_cull)
+    if flow_to is None:
+        color, radii, depth, alpha, flow = _RasterizeRaw.apply(
+            xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
+            prefilter_var, rs, grad_sink, accumulate, tile_cull)
+    else:
+        if grad_sink:
+            raise ValueError("render_raw: flow_to with grad_sink is not supported: the gradients of the flow arrive through autograd")
+        from .flow import model_flow
+        flows = model_flow(viewpoint_camera, flow_to, pc, raw=True, scaling_modifier=scaling_modifier)
+        color, radii, depth, alpha, flow = _RasterizeRaw.apply(
+            xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
+            prefilter_var, rs, grad_sink, accumulate, tile_cull, flows)
     if getattr(pipe, "env_map_res", 0):
         from .envmap import env_composite
         if getattr(pc, "env_map", None) is None:

@@ -111,8 +111,13 @@ def _fast_path(viewpoint_camera, pc, pipe, raster_settings, means2D):
                                  raster_settings, opt, bool(render_options["tile_cull"]), lazy)
 
 
-def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None):
-    """Render the scene seen by ``viewpoint_camera``.  ``bg_color`` must live on the model's device."""
+def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, flow_to=None):
+    """Render the scene seen by ``viewpoint_camera``.  ``bg_color`` must live on the model's device.
+    ``flow_to``: a camera of the same image size (``fdgs.playback.with_timestamp(viewpoint_camera, t1)``: the same camera at another
+    time).  The rasterizer's ``flow_2d`` is then every Gaussian's screen motion from this view to that one (``fdgs.flow.gaussian_flow``
+    of the activated getters) instead of zeros, and ``"flow"`` is the blended image ``sum_i flow_i alpha_i T_i`` in pixels -- NOT
+    divided by alpha: divide by ``"alpha"`` for the mean motion of what a pixel shows.  A loss on ``"flow"`` reaches the parameters
+    through the rasterizer (alpha, T) and through the flow itself."""
     xyz = pc.get_xyz
     device = xyz.device
 
@@ -145,7 +150,8 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     )
     rasterizer = GaussianRasterizer(raster_settings=raster_settings)
 
-    fast = _fast_path(viewpoint_camera, pc, pipe, raster_settings, screenspace_points) if override_color is None else None
+    # (the fast path has no flow input: with flow_to the model goes through the reference's own sequence below)
+    fast = _fast_path(viewpoint_camera, pc, pipe, raster_settings, screenspace_points) if (override_color is None and flow_to is None) else None
     if fast is not None:
         rendered_image, radii, depth, alpha, flow = fast
         return _finish(viewpoint_camera, pc, pipe, screenspace_points, rendered_image, radii, depth, alpha, flow, None)
@@ -201,7 +207,11 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         if is_4d and ts is None:
             ts = pc.get_t
 
-    flow_2d = torch.zeros_like(xyz[:, :2])
+    if flow_to is None:
+        flow_2d = torch.zeros_like(xyz[:, :2])
+    else:
+        from ..flow import model_flow
+        flow_2d = model_flow(viewpoint_camera, flow_to, pc, raw=False, scaling_modifier=scaling_modifier)
 
     # temporal pre-filter when the marginal was folded into opacity in Python
     mask = None

@@ -730,6 +730,57 @@ typedef struct fdgs_slice_out
 size_t fdgs_time_slice_scratch_bytes(int32_t P);
 int fdgs_time_slice(const fdgs_slice_in* in, const fdgs_slice_out* out, void* scratch, void* stream);
 
+/* ---- optical flow: how far every Gaussian moves on the screen between two views ----------------------------------------------------
+ *   flows[i] = pix(mu_i(timestamp_to); target camera) - pix(mu_i(timestamp); source camera)        [pixels]
+ * mu_i(t): the mean as the forward's preprocess has it at time t -- with rot_4d the conditional mean p + Sigma[0:3,3] / Sigma[3,3] *
+ * (t - ts), Sigma built exactly as the forward builds it (same scale_modifier): where the forward keeps the Gaussian, its
+ * out_means3D bit for bit -- otherwise the plain mean (the flow is then the camera's alone).  pix: the forward's own mean -> pixel
+ * expressions (full projection, 1 / (w + 1e-7f), ndc2Pix in double): the flow of a Gaussian that the forward keeps in both views is
+ * the difference of the positions in its two blend records, bit for bit; equal timestamps and one camera give exactly (0, 0).
+ * viewmatrix_to / projmatrix_to: the target camera (same image size), both NULL: the source camera.  A Gaussian whose view-space
+ * z <= 0.2 (the forward's near cull) at either end gets (0, 0) and no gradient; the temporal cull is NOT applied, every row is
+ * written.  This is what fdgs_scene.flows takes: the blend then renders sum_i flows[i] alpha_i T_i into out_flow.
+ * The parameter tensors are as in fdgs_scene (raw_params = 1: scales / scales_t before exp, quaternions of any norm); without rot_4d
+ * only means3D is read.  gaussian_dim 3 or 4; rot_4d needs 4 and ts / scales / scales_t / rotations / rotations_r.  The quaternions
+ * need not be 16-byte aligned.  One launch on `stream`, no atomics; P == 0: nothing is launched.  FDGS_ERR_INVALID_ARG before any
+ * launch: a NULL in / viewmatrix / projmatrix / flows / required tensor, only one of the _to matrices, P < 0, W or H <= 0. */
+typedef struct fdgs_flow_in
+{
+	uint32_t struct_size;      /* sizeof(fdgs_flow_in)                                  */
+	int32_t P;                 /* number of Gaussians                                   */
+	int32_t W, H;              /* image size of both views                              */
+	const float* means3D;      /* [P,3]                                                 */
+	const float* ts;           /* [P]                      rot_4d only                  */
+	const float* scales;       /* [P,3]                    rot_4d only                  */
+	const float* scales_t;     /* [P]                      rot_4d only                  */
+	const float* rotations;    /* [P,4]                    rot_4d only                  */
+	const float* rotations_r;  /* [P,4]                    rot_4d only                  */
+	const float* viewmatrix;   /* [16] source camera, as fdgs_scene.viewmatrix          */
+	const float* projmatrix;   /* [16] source camera, as fdgs_scene.projmatrix          */
+	const float* viewmatrix_to;/* [16] target camera or NULL                            */
+	const float* projmatrix_to;/* [16] target camera or NULL                            */
+	float timestamp;           /* source time                                           */
+	float timestamp_to;        /* target time                                           */
+	float scale_modifier;
+	int32_t rot_4d, gaussian_dim, raw_params;
+} fdgs_flow_in;
+int fdgs_gaussian_flow_forward(const fdgs_flow_in* in, float* flows, void* stream);
+/* ADDS scale * dL/d(parameter) of L(flows) to every array that is not NULL, given dL_dflows [P,2]: the analytic gradient of the
+ * forward above (the cameras and the timestamps are constants), with respect to the tensors AS PASSED: through exp and the
+ * quaternion normalisation with raw_params = 1, with respect to the activated values otherwise.  Without rot_4d only d_means3D
+ * receives anything.  One launch, one lane per Gaussian, no atomics: bitwise reproducible. */
+typedef struct fdgs_flow_grads
+{
+	uint32_t struct_size;      /* sizeof(fdgs_flow_grads)                               */
+	float* d_means3D;          /* [P,3] or NULL                                         */
+	float* d_ts;               /* [P]   or NULL                                         */
+	float* d_scales;           /* [P,3] or NULL                                         */
+	float* d_scales_t;         /* [P]   or NULL                                         */
+	float* d_rotations;        /* [P,4] or NULL                                         */
+	float* d_rotations_r;      /* [P,4] or NULL                                         */
+} fdgs_flow_grads;
+int fdgs_gaussian_flow_backward(const fdgs_flow_in* in, const float* dL_dflows, float scale, const fdgs_flow_grads* out, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
