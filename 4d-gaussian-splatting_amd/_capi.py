@@ -105,6 +105,16 @@ class FdgsFlowGrads(_Sized):
                 ("d_rotations", _fp), ("d_rotations_r", _fp)]
 
 
+class FdgsContributionIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("geom_buffer", _fp),
+                ("binning_buffer", _fp), ("image_buffer", _fp), ("num_rendered", C.c_int32), ("pix_weight", _fp)]
+
+
+class FdgsContributionOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("weight_sum", _fp), ("weight_max", _fp), ("hits", _fp), ("dominant", _fp),
+                ("dominant_id", _fp)]
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -121,7 +131,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
             "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
-            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_last_error", "fdgs_version")
+            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 11
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
 KNN_STAGE_BOUNDS, KNN_STAGE_BOXES, KNN_STAGE_SRC_CODES, KNN_STAGE_SRC_ORDER, KNN_STAGE_QUERY_CODES, KNN_STAGE_QUERY_ORDER, \
@@ -270,6 +280,8 @@ def _load():
     lib.fdgs_gaussian_flow_forward.restype = C.c_int
     lib.fdgs_gaussian_flow_backward.argtypes = [C.POINTER(FdgsFlowIn), C.c_void_p, C.c_float, C.POINTER(FdgsFlowGrads), C.c_void_p]
     lib.fdgs_gaussian_flow_backward.restype = C.c_int
+    lib.fdgs_contribution.argtypes = [C.POINTER(FdgsContributionIn), C.POINTER(FdgsContributionOut), C.c_void_p]
+    lib.fdgs_contribution.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

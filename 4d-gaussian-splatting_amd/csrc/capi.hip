@@ -722,6 +722,39 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	return FDGS_OK;
 }
 
+extern "C" int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_contribution_out* out, void* stream_v)
+{
+	g_err[0] = 0;
+	if (!in || !out) return fail(FDGS_ERR_INVALID_ARG, "in / out must not be NULL");
+	CHECK_STRUCT(in, fdgs_contribution_in);
+	CHECK_STRUCT(out, fdgs_contribution_out);
+	const int P = in->P, W = in->W, H = in->H;
+	if (P < 0 || P >= (1 << 26) || W <= 0 || H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, W, H);
+	if (div_up(W, TILE_X) > 65535 || div_up(H, TILE_Y) > 65535 || (long long)div_up(W, TILE_X) * div_up(H, TILE_Y) >= (1ll << 24))
+		return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d", W, H);
+	if (!out->weight_sum && !out->weight_max && !out->hits && !out->dominant && !out->dominant_id)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_contribution: every output is NULL");
+	hipStream_t stream = (hipStream_t)stream_v;
+	if (P > 0 && (!in->geom_buffer || !in->binning_buffer || !in->image_buffer))
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_contribution: geom_buffer / binning_buffer / image_buffer must not be NULL");
+	if (P == 0 || in->num_rendered == 0)
+	{
+		// no list to walk: the per-Gaussian outputs stay as they are, no pixel has a contributor
+		if (out->dominant_id) HIP_TRY(hipMemsetAsync(out->dominant_id, 0xFF, (size_t)W * H * 4, stream), "dominant_id memset");
+		return FDGS_OK;
+	}
+	const GeomLayout GL = geom_layout(P);
+	const ImageLayout IL = image_layout(W, H);
+	const BinLayout BL = bin_layout(in->num_rendered, false, 0);   // point_list sits at the front whatever layout the forward chose
+	const char* geom = (const char*)in->geom_buffer;
+	const char* img = (const char*)in->image_buffer;
+	const char* bin = (const char*)in->binning_buffer;
+	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;   // as the backward finds it
+	HIP_TRY(launch_contribution(*in, *out, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
+	                            (const uint32_t*)(img + IL.ranges), tile_order, stream), "contribution");
+	return FDGS_OK;
+}
+
 // the views of a batch must describe the same Gaussians: sizes, degrees, flags and the shared tensors
 static int check_same_gaussians(const fdgs_scene& a, const fdgs_scene& b, int v)
 {

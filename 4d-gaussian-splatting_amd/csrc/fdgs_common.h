@@ -191,6 +191,10 @@ namespace fdgs
 	                            const float* final_T, const uint32_t* n_contrib, const uint32_t* ctl /* cull planes: see launch_blend_fwd */,
 	                            hipStream_t stream);
 
+	// per-Gaussian contribution statistics and the per-pixel ID map of a finished forward (contribution.hip); tile_order: NULL = index order
+	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const float* records,
+	                               const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
+
 	// SH / 4D-SH backward (coalesced); must run after the blend backward and before launch_preprocess_bwd
 	hipError_t launch_sh_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,
 	                         const char* geom, hipStream_t stream);

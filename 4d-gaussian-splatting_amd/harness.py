@@ -165,7 +165,8 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
           densify_until_iter: int = 15000, densify_from_iter: int = 500, densification_interval: int = 100,
           opacity_reset_interval: int = 3000, densify_grad_threshold: float = 2e-4, densify_grad_t_threshold: float = 2e-4 / 40,
           thresh_opa_prune: float = 0.005, percent_dense: float = 0.01, cameras_extent: Optional[float] = None,
-          densify_until_num_points: int = -1, on_densify: Optional[Callable] = None, log_every: int = 0,
+          densify_until_num_points: int = -1, on_densify: Optional[Callable] = None,
+          contribution_prune: Optional[Dict[int, float]] = None, log_every: int = 0,
           log: Callable[[str], None] = print, spatial_order: bool = True,
           on_resort: Optional[Callable] = None, lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0,
           alpha_masks: Optional[Sequence[torch.Tensor]] = None, env_lr: float = 2.5e-3,
@@ -210,7 +211,12 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
     stats)``; ``on_evaluate`` with the same function is the reference's best-PSNR checkpoint.  ``start_iteration`` = n resumes a run
     that was saved after n iterations: the loop runs from n + 1 to ``iterations``, the shard starts at its batch number n, and
     ``stats`` (the loaded ``DensificationStats``) replaces the fresh ones.  ``spatial_order`` re-derives its permutation from the
-    loaded parameters (the identity for a model that was saved in Morton order and has not moved since); ``stats`` follows it."""
+    loaded parameters (the identity for a model that was saved in Morton order and has not moved since); ``stats`` follows it.
+    ``contribution_prune`` = {iteration: keep_fraction}: after the step of such an iteration the blending weights of all training
+    cameras are accumulated (``fdgs.importance.accumulate``) and the model is cut down to the top ``keep_fraction`` by summed weight
+    (``prune_by_contribution``: Adam moments and densification statistics follow).  The summed weight is a float atomic sum whose
+    last bits differ from run to run, so with ``world_size`` > 1 every rank accumulates and then takes RANK 0's sums (one broadcast
+    of P floats, ``ContributionStats.broadcast_``): the ranks keep the same rows.  None (the default): nothing changes."""
     from .train_host import spatial_sort
 
     def resort(stats=None):
@@ -297,6 +303,16 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
                     if iteration % opacity_reset_interval == 0 or (white_background and iteration == densify_from_iter):   # train.py:243
                         from .densify import reset_opacity
                         reset_opacity(model, optimizer)
+        if contribution_prune and iteration in contribution_prune:
+            from .importance import accumulate, prune_by_contribution
+            cstats = accumulate(model, cameras, pipe, bg)
+            if world_size > 1:
+                cstats.broadcast_(0)   # the float sums differ in their last bits between ranks: one rank's decide for all
+            rep = prune_by_contribution(model, optimizer, cstats, keep_fraction=float(contribution_prune[iteration]), dens_stats=stats)
+            if spatial_order and rep["P_new"] != rep["P_old"]:
+                resort(stats)
+            if rank == 0 and log_every:
+                log("[it %5d] contribution prune: %d -> %d Gaussians" % (iteration, rep["P_old"], rep["P_new"]))
         if log_every and (iteration % log_every == 0 or iteration == 1 or iteration == iterations):
             with torch.no_grad():
                 loss = float(torch.stack(losses).mean())

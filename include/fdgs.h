@@ -781,6 +781,44 @@ typedef struct fdgs_flow_grads
 } fdgs_flow_grads;
 int fdgs_gaussian_flow_backward(const fdgs_flow_in* in, const float* dL_dflows, float scale, const fdgs_flow_grads* out, void* stream);
 
+/* ---- contribution statistics: which Gaussians a finished forward actually used ----------------------------------------------------
+ * One pass over the three scratch buffers of a forward on the same stream (any list layout: compact or sparse, tile_cull on or off,
+ * num_rendered = -1 from a lazy forward; the forward's cull planes are not read).  Per pixel the tile list is walked front to back
+ * with the forward blend's own decisions and arithmetic (skip power > 0 and alpha < 1/255; the entry that would take T below 1e-4
+ * ends the pixel and does not contribute), so the contributions counted are exactly the rendered image's.  w = alpha * T.
+ * pix_weight [H,W] or NULL (all ones): a pixel with weight <= 0 is skipped entirely -- it adds to no output and its ID is -1.
+ * Outputs (any may be NULL, not all): ACCUMULATED in place -- the caller zero-fills them once, every further view adds / maxes into
+ * them -- except dominant_id, which is overwritten:
+ *   weight_sum [P]  += sum over pixels of pix_weight * w          (float atomic adds: the last bits depend on the arrival order)
+ *   weight_max [P]   = max(weight_max, max over pixels of w)      (integer max on the float's bits, w >= 0: reproducible)
+ *   hits [P]        += pixels the Gaussian contributed to         (reproducible)
+ *   dominant [P]    += pixels whose largest-w contributor it is; on equal w the earliest list entry wins   (reproducible)
+ *   dominant_id [H,W] = that Gaussian's index, -1 for a pixel without a contributor
+ * One launch; at most one atomic request per (8x8 pixel block, Gaussian, output), none for a Gaussian that contributed to no pixel
+ * of the block.  P == 0 (and num_rendered == 0): nothing is walked, dominant_id is filled with -1.
+ * FDGS_ERR_INVALID_ARG before any launch: NULL in / out, a wrong struct_size, P < 0 or >= 2^26, W or H <= 0, every output NULL,
+ * P > 0 with a NULL scratch buffer. */
+typedef struct fdgs_contribution_in
+{
+	uint32_t struct_size;      /* sizeof(fdgs_contribution_in)                          */
+	int32_t P, W, H;           /* as the forward's fdgs_scene                           */
+	const void* geom_buffer;   /* the forward's three scratch buffers                   */
+	const void* binning_buffer;
+	const void* image_buffer;
+	int32_t num_rendered;      /* as returned by the forward (-1: a lazy forward)       */
+	const float* pix_weight;   /* [H,W] or NULL                                         */
+} fdgs_contribution_in;
+typedef struct fdgs_contribution_out
+{
+	uint32_t struct_size;      /* sizeof(fdgs_contribution_out)                         */
+	float* weight_sum;         /* [P] or NULL                                           */
+	float* weight_max;         /* [P] or NULL                                           */
+	uint32_t* hits;            /* [P] or NULL                                           */
+	uint32_t* dominant;        /* [P] or NULL                                           */
+	int32_t* dominant_id;      /* [H,W] or NULL                                         */
+} fdgs_contribution_out;
+int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_contribution_out* out, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
