@@ -115,6 +115,11 @@ class FdgsContributionOut(_Sized):
                 ("dominant_id", _fp)]
 
 
+class FdgsCameraGrads(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("dL_dviewmatrix", _fp), ("dL_dprojmatrix", _fp), ("dL_dcampos", _fp),
+                ("dL_dtimestamp", _fp), ("scale", C.c_float), ("accumulate", C.c_int32)]
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -131,8 +136,9 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
             "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
-            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_last_error", "fdgs_version")
-NUM_STAGES = 11
+            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
+            "fdgs_last_error", "fdgs_version")
+NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
 KNN_STAGE_BOUNDS, KNN_STAGE_BOXES, KNN_STAGE_SRC_CODES, KNN_STAGE_SRC_ORDER, KNN_STAGE_QUERY_CODES, KNN_STAGE_QUERY_ORDER, \
     KNN_STAGE_NBOXES, KNN_STAGE_BOX, KNN_NUM_STAGES = range(9)
@@ -282,6 +288,11 @@ def _load():
     lib.fdgs_gaussian_flow_backward.restype = C.c_int
     lib.fdgs_contribution.argtypes = [C.POINTER(FdgsContributionIn), C.POINTER(FdgsContributionOut), C.c_void_p]
     lib.fdgs_contribution.restype = C.c_int
+    lib.fdgs_camera_backward_scratch.argtypes = [C.c_int32]
+    lib.fdgs_camera_backward_scratch.restype = C.c_size_t
+    lib.fdgs_camera_backward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsBackwardIn), C.c_void_p, C.POINTER(FdgsCameraGrads), C.c_void_p,
+                                         C.c_size_t, C.c_void_p]
+    lib.fdgs_camera_backward.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -108,7 +108,7 @@ namespace
 		}
 	};
 	const char* const STAGE_NAMES[FDGS_NUM_STAGES] = { "preprocess_fwd", "tile_count", "tile_scan", "tile_scatter",
-		"tile_sort", "colour_fwd", "blend_fwd", "blend_bwd", "preprocess_bwd", "grad_zero", "sh_bwd" };
+		"tile_sort", "colour_fwd", "blend_fwd", "blend_bwd", "preprocess_bwd", "grad_zero", "sh_bwd", "camera_bwd" };
 }
 
 extern "C" int fdgs_profile_enable(int stage_mask) { g_prof_mask.store((uint32_t)stage_mask); return FDGS_OK; }
@@ -719,6 +719,29 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 	}
 	if (stages & 2)
 		STAGE(q, FDGS_STAGE_PREPROCESS_BWD, launch_preprocess_bwd(s, *in, *out, geom, stream), "preprocess_bwd");
+	return FDGS_OK;
+}
+
+extern "C" size_t fdgs_camera_backward_scratch(int32_t P) { return camera_bwd_scratch_bytes(P); }
+extern "C" int fdgs_camera_backward(const fdgs_scene* scene, const fdgs_backward_in* in, const float* grad_accum, const fdgs_camera_grads* grads,
+                                    void* scratch, size_t scratch_bytes, void* stream_v)
+{
+	g_err[0] = 0;
+	if (!scene || !in || !grads) return fail(FDGS_ERR_INVALID_ARG, "scene / in / grads must not be NULL");
+	CHECK_STRUCT(scene, fdgs_scene);
+	CHECK_STRUCT(in, fdgs_backward_in);
+	CHECK_STRUCT(grads, fdgs_camera_grads);
+	if (!grads->dL_dviewmatrix && !grads->dL_dprojmatrix && !grads->dL_dcampos && !grads->dL_dtimestamp)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_camera_backward: every output is NULL");
+	const int rc = check_scene(scene);
+	if (rc != FDGS_OK) return rc;
+	if (!scratch || scratch_bytes < camera_bwd_scratch_bytes(scene->P))
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_camera_backward: scratch of %zu bytes, fdgs_camera_backward_scratch(%d) = %zu are needed",
+		            scratch ? scratch_bytes : (size_t)0, scene->P, camera_bwd_scratch_bytes(scene->P));
+	if (scene->P > 0 && (!in->radii || !in->out_means3D || !in->geom_buffer || !grad_accum))
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_camera_backward: radii / out_means3D / geom_buffer / grad_accum must not be NULL");
+	const StageCtx q{ (hipStream_t)stream_v, scene->debug != 0 };
+	STAGE(q, FDGS_STAGE_CAMERA_BWD, launch_camera_bwd(*scene, *in, grad_accum, *grads, scratch, q.stream), "camera_bwd");
 	return FDGS_OK;
 }
 

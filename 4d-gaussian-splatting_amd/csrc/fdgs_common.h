@@ -217,6 +217,11 @@ namespace fdgs
 	hipError_t launch_preprocess_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,
 	                                 const char* geom, hipStream_t stream);
 
+	// camera gradients (camera_bwd.hip): after the blend + SH backward, before launch_preprocess_bwd; grad_accum is only read
+	size_t camera_bwd_scratch_bytes(int P);
+	hipError_t launch_camera_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const float* grad_accum, const fdgs_camera_grads& out,
+	                             void* scratch, hipStream_t stream);
+
 	hipError_t launch_mark_visible(int P, const float* means3D, const float* viewmatrix, uint8_t* present, hipStream_t stream);
 
 	hipError_t launch_block_reaches_debug(int n, const float* tuples, uint8_t* out, hipStream_t stream);

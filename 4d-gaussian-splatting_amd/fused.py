@@ -20,7 +20,7 @@ import math
 
 import torch
 
-from .gaussian_renderer.diff_gaussian_rasterization import GaussianRasterizationSettings, _C, _is_given
+from .gaussian_renderer.diff_gaussian_rasterization import GaussianRasterizationSettings, _C, _is_given, camera_tensors, detached_settings
 
 
 def _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, flows=None):
@@ -53,11 +53,12 @@ def raw_preprocess_batch(settings, means3D, sh, opacity_raw, ts, scaling_raw, sc
 
 def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
                  prefilter_var, geom, R, binb, img, g_color, g_depth, g_alpha, g_flow, sink, accumulate, grad_accum=None, after_sh=None,
-                 sh_stage=None, begin_only=False, per_view_outputs=True, geometry_adam=None, flows=None):
+                 sh_stage=None, begin_only=False, per_view_outputs=True, geometry_adam=None, flows=None, camera=None):
     """Native backward on RAW parameters; gradients go into ``sink`` where given; the binding's 12-tuple.  ``flows``: the forward's.
     ``begin_only``: only the blend backward (``_C.backward_begin``): returns the pending call for ``_C.sh_backward_batch`` /
     ``_C.backward_finish``.  ``per_view_outputs=False``: dL_dcolors / dL_dcov3D / dL_dflows are not written (None in the tuple).
-    ``geometry_adam``: see ``_C.rasterize_gaussians_backward`` (the geometry parameters' Adam step inside the geometry backward)."""
+    ``geometry_adam``: see ``_C.rasterize_gaussians_backward`` (the geometry parameters' Adam step inside the geometry backward);
+    ``camera``: as there (the camera gradients, computed between the two halves of the backward)."""
     e = torch.Tensor([])
     args = (rs.bg, means3D, out_means3D, radii, e, e if flows is None else flows, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
             rotation_r_raw, rs.scale_modifier, e, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
@@ -67,7 +68,8 @@ def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_r
         return _C.backward_begin(*args, raw_params=True, grad_out=sink, accumulate=accumulate, grad_accum=grad_accum, sh_stage=sh_stage,
                                  per_view_outputs=per_view_outputs)
     return _C.rasterize_gaussians_backward(*args, raw_params=True, grad_out=sink, accumulate=accumulate, grad_accum=grad_accum,
-                                           after_sh=after_sh, sh_stage=sh_stage, per_view_outputs=per_view_outputs, geometry_adam=geometry_adam)
+                                           after_sh=after_sh, sh_stage=sh_stage, per_view_outputs=per_view_outputs, geometry_adam=geometry_adam,
+                                           camera=camera)
 
 
 _BLACK = {}
@@ -109,8 +111,13 @@ def raw_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
 class _RasterizeRaw(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
-                prefilter_var, raster_settings, grad_sink, accumulate, tile_cull=False, flows=None):
+                prefilter_var, raster_settings, grad_sink, accumulate, tile_cull=False, flows=None, *cam):
+        # cam: () or (viewmatrix, projmatrix, campos, timestamp tensor or None) as explicit inputs: a camera under optimisation
         rs = raster_settings
+        ctx.cam_meta = None
+        if cam:
+            rs = detached_settings(rs._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2]), cam[3])
+            ctx.cam_meta = [None if t is None else (t.shape, t.dtype) for t in cam]
         (R, color, flow, depth, T, radii, geom, binb, img, covs_com, out_means3D) = raw_forward(
             rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, tile_cull=tile_cull,
             flows=flows)
@@ -129,10 +136,17 @@ class _RasterizeRaw(torch.autograd.Function):
          geom, binb, img) = ctx.saved_tensors[:13]
         flows = ctx.saved_tensors[13] if ctx.has_flows else None
         sink = ctx.sink
+        camera = {"want": tuple(bool(n) for n in ctx.needs_input_grad[15:19])} if ctx.cam_meta is not None else None
         (d_means2D, _d_colors, d_opacity, d_means3D, _d_cov3D, d_sh, d_flows, d_ts, d_scales, d_scales_t, d_rot,
          d_rot_r) = raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
                                  rotation_r_raw, ctx.prefilter_var, geom, ctx.R, binb, img, g_color, g_depth, g_alpha, g_flow,
-                                 sink, ctx.accumulate, flows=flows)
+                                 sink, ctx.accumulate, flows=flows, camera=camera)
+
+        cam_grads = ()
+        if camera is not None:
+            for need, name, meta in zip(camera["want"], ("viewmatrix", "projmatrix", "campos", "timestamp"), ctx.cam_meta):
+                g = camera["grads"].get(name) if (need and meta is not None) else None
+                cam_grads += (None if g is None else g.reshape(meta[0]).to(meta[1]),)
 
         def ret(name, given, g):
             if not _is_given(given):
@@ -145,7 +159,7 @@ class _RasterizeRaw(torch.autograd.Function):
                 ret("dL_dopacity", opacity_raw, d_opacity), ret("dL_dts", ts, d_ts),
                 ret("dL_dscales", scaling_raw, d_scales), ret("dL_dscales_t", scaling_t_raw, d_scales_t),
                 ret("dL_drotations", rotation_raw, d_rot), ret("dL_drotations_r", rotation_r_raw, d_rot_r),
-                None, None, None, None, None) + ((d_flows.reshape(flows.shape),) if ctx.has_flows else ())
+                None, None, None, None, None) + ((d_flows.reshape(flows.shape),) if ctx.has_flows else ((None,) if camera else ())) + cam_grads
 
 
 def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, grad_sink=None, accumulate=False, tile_cull=False,
@@ -160,10 +174,16 @@ def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modif
     rs, (xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var) = raw_settings(
         viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
+    # a camera under optimisation (fdgs.camera.LearnableCamera): its tensors become inputs of the autograd function
+    cam_time = viewpoint_camera.timestamp
+    cam, camera_grad = camera_tensors(rs, cam_time if isinstance(cam_time, torch.Tensor) else None)
+    cam = cam if camera_grad else ()
+    if isinstance(cam_time, torch.Tensor) and not camera_grad:
+        rs = rs._replace(timestamp=float(cam_time.detach()))
     if flow_to is None:
         color, radii, depth, alpha, flow = _RasterizeRaw.apply(
             xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
-            prefilter_var, rs, grad_sink, accumulate, tile_cull)
+            prefilter_var, rs, grad_sink, accumulate, tile_cull, *((None,) + cam if cam else ()))
     else:
         if grad_sink:
             raise ValueError("render_raw: flow_to with grad_sink is not supported: the gradients of the flow arrive through autograd")
@@ -171,7 +191,7 @@ def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modif
         flows = model_flow(viewpoint_camera, flow_to, pc, raw=True, scaling_modifier=scaling_modifier)
         color, radii, depth, alpha, flow = _RasterizeRaw.apply(
             xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
-            prefilter_var, rs, grad_sink, accumulate, tile_cull, flows)
+            prefilter_var, rs, grad_sink, accumulate, tile_cull, flows, *cam)
     if getattr(pipe, "env_map_res", 0):
         from .envmap import env_composite
         if getattr(pc, "env_map", None) is None:

@@ -12,7 +12,7 @@ import math
 import torch
 from torch.nn import functional as F
 
-from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer
+from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, camera_tensors
 from ..sh_utils import eval_sh, eval_shfs_4d
 
 
@@ -128,6 +128,10 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
     except Exception:
         pass
 
+    # a camera under optimisation (fdgs.camera.LearnableCamera): its matrices are differentiable torch expressions and its timestamp a
+    # 0-d tensor; the rasterizer returns their gradients when they require one
+    cam_time = viewpoint_camera.timestamp
+    timestamp_tensor = cam_time if isinstance(cam_time, torch.Tensor) else None
     raster_settings = GaussianRasterizationSettings(
         image_height=int(viewpoint_camera.image_height),
         image_width=int(viewpoint_camera.image_width),
@@ -140,7 +144,7 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         sh_degree=pc.active_sh_degree,
         sh_degree_t=pc.active_sh_degree_t,
         campos=viewpoint_camera.camera_center,
-        timestamp=viewpoint_camera.timestamp,
+        timestamp=cam_time if timestamp_tensor is None else float(cam_time.detach()),
         time_duration=pc.time_duration[1] - pc.time_duration[0],
         rot_4d=pc.rot_4d,
         gaussian_dim=pc.gaussian_dim,
@@ -148,10 +152,12 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
         prefiltered=False,
         debug=pipe.debug,
     )
-    rasterizer = GaussianRasterizer(raster_settings=raster_settings)
+    rasterizer = GaussianRasterizer(raster_settings=raster_settings, timestamp_tensor=timestamp_tensor)
+    _, camera_grad = camera_tensors(raster_settings, timestamp_tensor)
 
-    # (the fast path has no flow input: with flow_to the model goes through the reference's own sequence below)
-    fast = _fast_path(viewpoint_camera, pc, pipe, raster_settings, screenspace_points) if (override_color is None and flow_to is None) else None
+    # (the fast path has no flow input and no camera gradients: with flow_to, or a camera tensor that requires a gradient, the model goes
+    # through the reference's own sequence below)
+    fast = _fast_path(viewpoint_camera, pc, pipe, raster_settings, screenspace_points) if (override_color is None and flow_to is None and not camera_grad) else None
     if fast is not None:
         rendered_image, radii, depth, alpha, flow = fast
         return _finish(viewpoint_camera, pc, pipe, screenspace_points, rendered_image, radii, depth, alpha, flow, None)

@@ -232,13 +232,41 @@ class _NativeRasterizer:
         return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
                 g["dL_dflows"], g["dL_dts"], g["dL_dscales"], g["dL_dscales_t"], g["dL_drotations"], g["dL_drotations_r"])
 
+    def camera_backward(self, pending, want=(True, True, True, True), scale=1.0, out=None, accumulate=False):
+        """The camera gradients of a view (fdgs_camera_backward) between the two halves of its backward: ``pending`` is what
+        ``backward_begin`` returned (or the split backward's own state), the blend backward is enqueued, the geometry backward
+        (``backward_finish``) is not.  ``want``: which of (viewmatrix, projmatrix, campos, timestamp) to compute; ``out``: optional dict
+        of preallocated float32 tensors under those names ([4,4], [4,4], [3], [1]); ``accumulate``: add to their contents; ``scale``
+        multiplies the result.  Returns {name: tensor or None}.  Only reads the accumulator records."""
+        dev, scene = pending["dev"], pending["scene"]
+        names, shapes = ("viewmatrix", "projmatrix", "campos", "timestamp"), ((4, 4), (4, 4), (3,), (1,))
+        g = {}
+        for name, shape, w in zip(names, shapes, want):
+            t = out.get(name) if out else None
+            if t is not None:
+                if t.numel() != (16, 16, 3, 1)[names.index(name)] or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                    raise RuntimeError("fdgs: camera_backward out[%r] must be a contiguous float32 GPU tensor of shape %s" % (name, shape))
+            elif w:
+                if accumulate:
+                    raise RuntimeError("fdgs: camera_backward accumulate=True needs out[%r]" % name)
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            g[name] = t
+        nbytes = int(_capi.lib.fdgs_camera_backward_scratch(scene.P))
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        cg = _capi.FdgsCameraGrads(*[_capi._ptr(g[n]) for n in names], float(scale), int(bool(accumulate)))
+        with torch.cuda.device(dev):
+            rc = _capi.lib.fdgs_camera_backward(C.byref(scene), C.byref(pending["bin"]), _capi._ptr(pending["grad_accum"]), C.byref(cg),
+                                                scratch.data_ptr(), nbytes, _capi.current_stream_handle(dev))
+        _capi._check(rc, "fdgs_camera_backward")
+        return g
+
     def rasterize_gaussians_backward(self, bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales,
                                      scales_t, rotations, rotations_r, scale_modifier, cov3D_precomp, prefilter_var,
                                      viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
                                      dL_dout_mask, dL_dout_flow, sh, degree, degree_t, campos, timestamp,
                                      time_duration, rot_4d, gaussian_dim, force_sh_3d, geomBuffer, R, binningBuffer,
                                      imageBuffer, debug, *, raw_params=False, grad_out=None, accumulate=False, grad_accum=None,
-                                     after_sh=None, sh_stage=None, per_view_outputs=True, geometry_adam=None, _phase=None):
+                                     after_sh=None, sh_stage=None, per_view_outputs=True, geometry_adam=None, camera=None, _phase=None):
         """37 positional arguments and the 12-tuple result of the reference binding (rasterize_points.h:51-89).
         Keyword-only extensions: ``raw_params`` as in the forward; ``grad_out`` maps gradient names
         (dL_dmeans3D, dL_dsh, dL_dopacity, dL_dts, dL_dscales, dL_dscales_t, dL_drotations, dL_drotations_r) to
@@ -253,7 +281,10 @@ class _NativeRasterizer:
         ``per_view_outputs=False``: dL_dcolors, dL_dcov3D and dL_dflows are not written (NULL at the C ABI) and come back as None;
         ``geometry_adam``: a callable evaluated right before the geometry backward is enqueued (after ``after_sh``) that returns None or
         dict(flat, exp_avg, exp_avg_sq, lr={means3D, opacities, ts, scales, scales_t, rotations, rotations_r}, betas, eps, step): the
-        geometry backward then also takes the Adam step of the geometry parameters (fdgs_backward_out.adam; raw_params only)."""
+        geometry backward then also takes the Adam step of the geometry parameters (fdgs_backward_out.adam; raw_params only);
+        ``camera``: a dict (optional keys want, scale, out, accumulate: ``camera_backward``'s arguments) -> the backward runs as blend + SH
+        backward, ``camera_backward``, geometry backward, and
+        leaves the four camera gradients in ``camera["grads"]`` (the per-Gaussian gradients are bit for bit those of the unsplit call)."""
         dev = means3D.device
         # The reference always receives four dense tensors (autograd materialises zeros).  Here an image gradient may
         # be None = "no upstream gradient": the kernels then skip that term (colour-only backward when only
@@ -332,7 +363,7 @@ class _NativeRasterizer:
             bout.adam = C.pointer(st)
             return (st, ga)
         with torch.cuda.device(dev):
-            if after_sh is None:
+            if after_sh is None and camera is None:
                 adam_keep = attach_adam()
                 rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
                                                        _capi.current_stream_handle(dev))
@@ -341,7 +372,12 @@ class _NativeRasterizer:
                 rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
                                                        _capi.current_stream_handle(dev))
                 if rc == 0:
-                    after_sh()
+                    if after_sh is not None:
+                        after_sh()
+                    if camera is not None:
+                        camera["grads"] = self.camera_backward({"dev": dev, "scene": scene, "bin": bin_, "grad_accum": g["grad_accum"]},
+                                                               want=camera.get("want", (True, True, True, True)), scale=camera.get("scale", 1.0),
+                                                               out=camera.get("out"), accumulate=camera.get("accumulate", False))
                     bout.stage_mask = 2
                     adam_keep = attach_adam()
                     rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
@@ -416,72 +452,130 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+def _rg_forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
+                rotations_r, cov3Ds_precomp, prefilter_var, rs):
+    native_args = (
+        rs.bg, means3D, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
+        rs.scale_modifier, cov3Ds_precomp, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
+        rs.image_height, rs.image_width, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp,
+        rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, rs.prefiltered, rs.debug,
+    )
+    (num_rendered, color, flow, depth, T, radii, geomBuffer, binningBuffer, imgBuffer, covs_com,
+     out_means3D) = _call_native(_C.rasterize_gaussians, native_args, rs.debug, "snapshot_fw.dump", "forward")
+
+    ctx.raster_settings = rs
+    ctx.num_rendered = num_rendered
+    ctx.prefilter_var = prefilter_var
+    ctx.save_for_backward(colors_precomp, means3D, out_means3D, scales, rotations, cov3Ds_precomp, radii, sh,
+                          flow_2d, opacities, ts, scales_t, rotations_r, geomBuffer, binningBuffer, imgBuffer)
+    # outputs nobody differentiates arrive as None in backward instead of dense zeros (see the native binding)
+    ctx.set_materialize_grads(False)
+    ctx.mark_non_differentiable(radii)
+    return color, radii, depth, 1 - T, flow, covs_com
+
+
+def _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow, camera=None):
+    rs = ctx.raster_settings
+    (colors_precomp, means3D, out_means3D, scales, rotations, cov3Ds_precomp, radii, sh, flow_2d, opacities, ts,
+     scales_t, rotations_r, geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
+    if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_flow is None:
+        # only covs_com was differentiated: the reference ignores that gradient, the images contribute zeros
+        grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
+    native_args = (
+        rs.bg, means3D, out_means3D, radii, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
+        rotations_r, rs.scale_modifier, cov3Ds_precomp, ctx.prefilter_var, rs.viewmatrix, rs.projmatrix,
+        rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, grad_alpha, grad_flow, sh, rs.sh_degree,
+        rs.sh_degree_t, rs.campos, rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d,
+        geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug,
+    )
+    fn = _C.rasterize_gaussians_backward if camera is None else (lambda *a: _C.rasterize_gaussians_backward(*a, camera=camera))
+    (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_flows,
+     grad_ts, grad_scales, grad_scales_t, grad_rotations, grad_rotations_r) = _call_native(
+        fn, native_args, rs.debug, "snapshot_bw.dump", "backward")
+
+    def shaped(given, g):
+        """gradient reshaped like its input, or None when that optional input was absent"""
+        return g.reshape(given.shape) if _is_given(given) else None
+
+    # order = forward's inputs (gaussian_renderer/diff_gaussian_rasterization.py:208-225)
+    return (
+        grad_means3D, grad_means2D, shaped(sh, grad_sh), shaped(colors_precomp, grad_colors_precomp),
+        shaped(flow_2d, grad_flows), shaped(opacities, grad_opacities), shaped(ts, grad_ts),
+        shaped(scales, grad_scales), shaped(scales_t, grad_scales_t), shaped(rotations, grad_rotations),
+        shaped(rotations_r, grad_rotations_r), shaped(cov3Ds_precomp, grad_cov3Ds_precomp), None, None,
+    )
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
                 rotations_r, cov3Ds_precomp, prefilter_var, raster_settings):
-        rs = raster_settings
-        native_args = (
-            rs.bg, means3D, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
-            rs.scale_modifier, cov3Ds_precomp, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-            rs.image_height, rs.image_width, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp,
-            rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, rs.prefiltered, rs.debug,
-        )
-        (num_rendered, color, flow, depth, T, radii, geomBuffer, binningBuffer, imgBuffer, covs_com,
-         out_means3D) = _call_native(_C.rasterize_gaussians, native_args, rs.debug, "snapshot_fw.dump", "forward")
-
-        ctx.raster_settings = rs
-        ctx.num_rendered = num_rendered
-        ctx.prefilter_var = prefilter_var
-        ctx.save_for_backward(colors_precomp, means3D, out_means3D, scales, rotations, cov3Ds_precomp, radii, sh,
-                              flow_2d, opacities, ts, scales_t, rotations_r, geomBuffer, binningBuffer, imgBuffer)
-        # outputs nobody differentiates arrive as None in backward instead of dense zeros (see the native binding)
-        ctx.set_materialize_grads(False)
-        ctx.mark_non_differentiable(radii)
-        return color, radii, depth, 1 - T, flow, covs_com
+        return _rg_forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
+                           rotations_r, cov3Ds_precomp, prefilter_var, raster_settings)
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_flow, grad_covs_com):
-        rs = ctx.raster_settings
-        (colors_precomp, means3D, out_means3D, scales, rotations, cov3Ds_precomp, radii, sh, flow_2d, opacities, ts,
-         scales_t, rotations_r, geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
-        if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_flow is None:
-            # only covs_com was differentiated: the reference ignores that gradient, the images contribute zeros
-            grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
-        native_args = (
-            rs.bg, means3D, out_means3D, radii, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
-            rotations_r, rs.scale_modifier, cov3Ds_precomp, ctx.prefilter_var, rs.viewmatrix, rs.projmatrix,
-            rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, grad_alpha, grad_flow, sh, rs.sh_degree,
-            rs.sh_degree_t, rs.campos, rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d,
-            geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug,
-        )
-        (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_flows,
-         grad_ts, grad_scales, grad_scales_t, grad_rotations, grad_rotations_r) = _call_native(
-            _C.rasterize_gaussians_backward, native_args, rs.debug, "snapshot_bw.dump", "backward")
+        return _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow)
 
-        def shaped(given, g):
-            """gradient reshaped like its input, or None when that optional input was absent"""
-            return g.reshape(given.shape) if _is_given(given) else None
 
-        # order = forward's inputs (gaussian_renderer/diff_gaussian_rasterization.py:208-225)
-        return (
-            grad_means3D, grad_means2D, shaped(sh, grad_sh), shaped(colors_precomp, grad_colors_precomp),
-            shaped(flow_2d, grad_flows), shaped(opacities, grad_opacities), shaped(ts, grad_ts),
-            shaped(scales, grad_scales), shaped(scales_t, grad_scales_t), shaped(rotations, grad_rotations),
-            shaped(rotations_r, grad_rotations_r), shaped(cov3Ds_precomp, grad_cov3Ds_precomp), None, None,
-        )
+def camera_tensors(rs, timestamp_tensor=None):
+    """(viewmatrix, projmatrix, campos, timestamp tensor or None) of a view, and whether any of them asks for a gradient."""
+    cam = (rs.viewmatrix, rs.projmatrix, rs.campos, timestamp_tensor)
+    return cam, torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in cam)
+
+
+def detached_settings(rs, timestamp_tensor=None):
+    """The settings as the kernels take them: the camera tensors detached, the timestamp a float (a 0-d tensor is read back)."""
+    ts = timestamp_tensor if timestamp_tensor is not None else rs.timestamp
+    return rs._replace(viewmatrix=rs.viewmatrix.detach(), projmatrix=rs.projmatrix.detach(), campos=rs.campos.detach(),
+                       timestamp=float(ts.detach() if isinstance(ts, torch.Tensor) else ts))
+
+
+class _RasterizeGaussiansCamera(torch.autograd.Function):
+    """_RasterizeGaussians with the camera as explicit inputs: viewmatrix, projmatrix, campos and the timestamp (a tensor, or None:
+    raster_settings.timestamp) receive their gradients from fdgs_camera_backward, which the backward runs between the blend + SH
+    backward and the geometry backward.  Taken only when one of them requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
+                rotations_r, cov3Ds_precomp, prefilter_var, raster_settings, viewmatrix, projmatrix, campos, timestamp_tensor):
+        rs = detached_settings(raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos), timestamp_tensor)
+        ctx.cam_meta = [None if t is None else (t.shape, t.dtype) for t in (viewmatrix, projmatrix, campos, timestamp_tensor)]
+        return _rg_forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
+                           rotations_r, cov3Ds_precomp, prefilter_var, rs)
+
+    @staticmethod
+    def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_flow, grad_covs_com):
+        needs = ctx.needs_input_grad[14:18]
+        camera = {"want": tuple(bool(n) for n in needs)}
+        per_gaussian = _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow, camera=camera)
+        out = []
+        for need, name, meta in zip(needs, ("viewmatrix", "projmatrix", "campos", "timestamp"), ctx.cam_meta):
+            g = camera["grads"].get(name) if (need and meta is not None) else None
+            out.append(None if g is None else g.reshape(meta[0]).to(meta[1]))
+        return per_gaussian + tuple(out)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
-                        rotations_r, cov3Ds_precomp, prefilter_var, raster_settings):
+                        rotations_r, cov3Ds_precomp, prefilter_var, raster_settings, timestamp_tensor=None):
+    cam, cam_grad = camera_tensors(raster_settings, timestamp_tensor)
+    if cam_grad:
+        return _RasterizeGaussiansCamera.apply(means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t,
+                                               rotations, rotations_r, cov3Ds_precomp, prefilter_var, raster_settings, *cam)
+    if timestamp_tensor is not None or isinstance(raster_settings.timestamp, torch.Tensor):
+        raster_settings = raster_settings._replace(timestamp=float((timestamp_tensor if timestamp_tensor is not None else raster_settings.timestamp).detach()))
     return _RasterizeGaussians.apply(means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t,
                                      rotations, rotations_r, cov3Ds_precomp, prefilter_var, raster_settings)
 
 
 class GaussianRasterizer(nn.Module):
-    def __init__(self, raster_settings):
+    def __init__(self, raster_settings, timestamp_tensor=None):
+        """``timestamp_tensor``: the view's timestamp as a (0-d or one-element) tensor, for a camera whose time offset is being
+        optimised: it takes the place of ``raster_settings.timestamp`` (which stays a float) and, when it requires a gradient, receives
+        dL/dtimestamp.  ``viewmatrix`` / ``projmatrix`` / ``campos`` of the settings receive theirs when they require one."""
         super().__init__()
         self.raster_settings = raster_settings
+        self.timestamp_tensor = timestamp_tensor
 
     def markVisible(self, positions):
         """Boolean mask of the points in front of the near plane (frustum culling for the camera)."""
@@ -508,4 +602,4 @@ class GaussianRasterizer(nn.Module):
 
         return rasterize_gaussians(means3D, means2D, absent(shs), absent(colors_precomp), absent(flow_2d), opacities,
                                    absent(ts), absent(scales), absent(scales_t), absent(rotations),
-                                   absent(rotations_r), absent(cov3D_precomp), prefilter_var, rs)
+                                   absent(rotations_r), absent(cov3D_precomp), prefilter_var, rs, self.timestamp_tensor)

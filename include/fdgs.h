@@ -444,7 +444,8 @@ int fdgs_debug_knn_stage_offsets(int32_t query, int32_t n, int32_t m, int64_t* o
 #define FDGS_STAGE_PREPROCESS_BWD 8
 #define FDGS_STAGE_GRAD_ZERO 9
 #define FDGS_STAGE_SH_BWD 10
-#define FDGS_NUM_STAGES 11
+#define FDGS_STAGE_CAMERA_BWD 11 /* fdgs_camera_backward: both of its launches */
+#define FDGS_NUM_STAGES 12
 int fdgs_profile_enable(int stage_mask); /* bit i set: bracket stage i with HIP events; 0 = off, -1 = all stages */
 int fdgs_profile_sample_every(int32_t n); /* n >= 1: only every n-th launch of a bracketed stage gets its event pair (default 1: every
                                              launch).  An event pair costs its stream ~13 us of idle time around the launch (measured: a
@@ -818,6 +819,40 @@ typedef struct fdgs_contribution_out
 	int32_t* dominant_id;      /* [H,W] or NULL                                         */
 } fdgs_contribution_out;
 int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_contribution_out* out, void* stream);
+
+/* ---- camera gradients: dL/d(viewmatrix, projmatrix, campos, timestamp) of one view --------------------------------------------------
+ * The analytic derivatives of the forward with respect to the four camera inputs of fdgs_scene, every discrete decision held constant
+ * (culls, radii, tile lists, n_contrib, the alpha and T cut-offs); not the reference backward's quirks: the camera is no parameter of
+ * the reference.  36 sums over the P Gaussians:
+ *   dL_dviewmatrix [16], laid out as fdgs_scene.viewmatrix: through the view-space mean t (EWA Jacobian, depth, 1 / tz) and through the
+ *                        rotation block W of T = J W.  Entries 3, 7, 11, 15 (the column t does not read) are exactly zero.
+ *   dL_dprojmatrix [16]: through p_hom.x, .y, .w into the pixel position.  Entries 2, 6, 10, 14 (the depth column) are exactly zero.
+ *   dL_dcampos [3]:      through the SH view direction (from the input mean, as the forward takes it); zero with colors_precomp.
+ *   dL_dtimestamp [1]:   through the temporal marginal, the conditional mean shift of rot_4d and the 4D-SH time factors; zero for
+ *                        gaussian_dim == 3 (and for cov3D_precomp, where the forward applies neither marginal nor shift, without 4D SH).
+ * CALL ORDER: fdgs_rasterize_backward(scene, in, out with stage_mask = 1) first, THIS call on the same stream with the same scene, in
+ * and out->grad_accum, then fdgs_rasterize_backward(... stage_mask = 2): the per-Gaussian quantities it needs live in words 0-11 of the
+ * accumulator records between those two calls only.  grad_accum is only READ here (also with grad_accum_clean: the geometry backward
+ * still finds, and re-zeroes, what the blend backward left), so the per-Gaussian gradients are bit for bit what they are without this call.
+ * Each result is scale * the sum, written, or with accumulate != 0 added to what the array holds.  Any output may be NULL, not all four.
+ * scratch: fdgs_camera_backward_scratch(P) bytes of device memory the call may overwrite.  Two launches, no atomics: one lane per
+ * Gaussian, fixed-order wave / block reduction to one row of partial sums per 256 Gaussians, summed in fixed order in double:
+ * bitwise reproducible.  P == 0 or every Gaussian culled: zeros (accumulate: the arrays keep their contents).
+ * FDGS_ERR_INVALID_ARG before any launch: a NULL scene / in / grads, a wrong struct_size, every output NULL, scratch NULL or
+ * scratch_bytes too small, an invalid scene, P > 0 with a NULL radii / out_means3D / geom_buffer / grad_accum. */
+typedef struct fdgs_camera_grads
+{
+	uint32_t struct_size;      /* sizeof(fdgs_camera_grads)                             */
+	float* dL_dviewmatrix;     /* [16] or NULL                                          */
+	float* dL_dprojmatrix;     /* [16] or NULL                                          */
+	float* dL_dcampos;         /* [3]  or NULL                                          */
+	float* dL_dtimestamp;      /* [1]  or NULL                                          */
+	float scale;               /* multiplies every result                               */
+	int32_t accumulate;        /* 0: overwrite, otherwise add to the arrays' contents   */
+} fdgs_camera_grads;
+size_t fdgs_camera_backward_scratch(int32_t P);
+int fdgs_camera_backward(const fdgs_scene* scene, const fdgs_backward_in* in, const float* grad_accum, const fdgs_camera_grads* grads,
+                         void* scratch, size_t scratch_bytes, void* stream);
 
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
