@@ -137,6 +137,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
             "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
             "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
+            "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
@@ -293,6 +294,16 @@ def _load():
     lib.fdgs_camera_backward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsBackwardIn), C.c_void_p, C.POINTER(FdgsCameraGrads), C.c_void_p,
                                          C.c_size_t, C.c_void_p]
     lib.fdgs_camera_backward.restype = C.c_int
+    lib.fdgs_kmeans_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    lib.fdgs_kmeans_scratch_bytes.restype = C.c_size_t
+    lib.fdgs_kmeans_assign.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6
+    lib.fdgs_kmeans_assign.restype = C.c_int
+    lib.fdgs_kmeans_update.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 7
+    lib.fdgs_kmeans_update.restype = C.c_int
+    lib.fdgs_quantize_columns.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.fdgs_quantize_columns.restype = C.c_int
+    lib.fdgs_compact_decode.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.fdgs_compact_decode.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -854,6 +854,37 @@ size_t fdgs_camera_backward_scratch(int32_t P);
 int fdgs_camera_backward(const fdgs_scene* scene, const fdgs_backward_in* in, const float* grad_accum, const fdgs_camera_grads* grads,
                          void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- storing a trained model small: k-means codebooks, quantised columns and their decode (compress.hip) ---------------------------
+ * k-means over rows x [N,D] with a codebook c [K,D], both row-major float in device memory; 1 <= D <= 192, 1 <= K <= 65536, N >= 1,
+ * no multiple of any tile size is assumed.  scratch: fdgs_kmeans_scratch_bytes(N, K) bytes of device memory, shared by both calls.
+ *
+ * fdgs_kmeans_assign: index[n] = argmin_k |x_n - c_k|^2, ties to the lowest k.  The score compared is |c_k|^2 - 2 x_n . c_k in fp32: the
+ * norm a d-ordered sum, the dot product the d-ordered fma chain of the f32-input MFMA (v_mfma_f32_32x32x2_f32); both depend on the values
+ * of row k alone, so equal codebook rows score bit-identically and the tie rule is exact.  For every row the chosen centroid is within
+ * 4 (D + 4) 2^-24 (|x_n|^2 + max_k |c_k|^2) of the nearest one in squared distance.  dist2 [N] or NULL: the winner's squared distance as
+ * the direct sum of (x_d - c_d)^2.  No N x K intermediate touches memory: codebook tiles pass through LDS, the running best stays in
+ * registers.
+ *
+ * fdgs_kmeans_update: c_k = sum_{index[n] = k} w_n x_n / sum w_n (w [N] or NULL: all ones), IN PLACE in c; a cluster without rows or
+ * with a total weight of zero keeps its row bit for bit.  counts [K] or NULL: rows per cluster.  The (index, row) pairs go through the
+ * stable radix sort and every cluster's rows are summed in ascending row id by one workgroup: no float atomics, bitwise reproducible.
+ * An index outside [0, K) belongs to no cluster. */
+size_t fdgs_kmeans_scratch_bytes(int32_t N, int32_t K);
+int fdgs_kmeans_assign(int32_t N, int32_t K, int32_t D, const float* x, const float* c, int32_t* index, float* dist2, void* scratch,
+                       void* stream);
+int fdgs_kmeans_update(int32_t N, int32_t K, int32_t D, const float* x, const int32_t* index, const float* w, float* c, int32_t* counts,
+                       void* scratch, void* stream);
+/* q[p][col] = min(max(rintf((x[p][col] - lo[col]) * inv[col]), 0), qmax) for x [P,C]; lo / inv [C] in device memory; q is uint8 with
+ * qmax = 255, uint16 with qmax = 65535 (no other value).  fp32, these IEEE operations in this order, no fused multiply-add. */
+int fdgs_quantize_columns(int32_t P, int32_t C, const float* x, const float* lo, const float* inv, int32_t qmax, void* q, void* stream);
+/* Row p of out [P, C + D]: first the C stored columns -- bits 8 / 16: lo[col] + (float)q[p][col] * step[col] (one product, one sum, no
+ * fused multiply-add), bits 32: q holds floats, copied bit for bit -- then, with D > 0, row index[p] of rows [K,D] (index NULL: row p of
+ * rows [P,D]; an index outside [0, K) is clamped into it).  That is a whole segment of a flat parameter bucket (D = 0), or a row of SH
+ * coefficients in two parts: the DC triple, then its codebook row.  One launch; a lane produces four consecutive floats and stores them
+ * as 16 bytes where out is 16-byte aligned and C + D a multiple of 4. */
+int fdgs_compact_decode(int32_t P, int32_t C, int32_t bits, const void* q, const float* lo, const float* step, int32_t D, const float* rows,
+                        const int32_t* index, int32_t K, float* out, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
