@@ -115,6 +115,14 @@ class FdgsContributionOut(_Sized):
                 ("dominant_id", _fp)]
 
 
+class FdgsFeatureIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("C", C.c_int32), ("geom_buffer", _fp),
+                ("binning_buffer", _fp), ("image_buffer", _fp), ("num_rendered", C.c_int32), ("features", _fp)]
+
+
+FDGS_FEATURE_MAX_CHANNELS = 256  # include/fdgs.h
+
+
 class FdgsCameraGrads(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("dL_dviewmatrix", _fp), ("dL_dprojmatrix", _fp), ("dL_dcampos", _fp),
                 ("dL_dtimestamp", _fp), ("scale", C.c_float), ("accumulate", C.c_int32)]
@@ -136,7 +144,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
             "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
-            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
+            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
@@ -289,6 +297,10 @@ def _load():
     lib.fdgs_gaussian_flow_backward.restype = C.c_int
     lib.fdgs_contribution.argtypes = [C.POINTER(FdgsContributionIn), C.POINTER(FdgsContributionOut), C.c_void_p]
     lib.fdgs_contribution.restype = C.c_int
+    lib.fdgs_feature_blend.argtypes = [C.POINTER(FdgsFeatureIn), C.c_void_p, C.c_void_p]
+    lib.fdgs_feature_blend.restype = C.c_int
+    lib.fdgs_feature_blend_backward.argtypes = [C.POINTER(FdgsFeatureIn), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fdgs_feature_blend_backward.restype = C.c_int
     lib.fdgs_camera_backward_scratch.argtypes = [C.c_int32]
     lib.fdgs_camera_backward_scratch.restype = C.c_size_t
     lib.fdgs_camera_backward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsBackwardIn), C.c_void_p, C.POINTER(FdgsCameraGrads), C.c_void_p,

@@ -98,4 +98,59 @@ namespace fdgs
 		const float qmin = fminf(xin ? 3.0e38f : qv, yin ? 3.0e38f : qh);
 		return qmin <= tau;
 	}
+
+	// ---- the walk of a finished forward's lists: blend_fwd.hip's decisions once more ----
+	// The two steps of contribution_kernel's walk as inline functions, for the kernels of features.hip.  contribution.hip keeps its
+	// own statement of them: built on these functions it computes the same but compiles to other code (queue_chunk: another register
+	// allocation and block layout; blend_weight: one instruction moves), and that kernel's code object is not to change for a refactor.
+
+	// One chunk of a tile's list (entries [base, base + 64) of the n the range holds): lane `lane` fetches one entry, tests it against
+	// the wave's pixel block and the survivors go, in list order, into the wave-private queue as (x, y, conic.x, conic.y) and
+	// (conic.z, opacity, Gaussian id, -).  Returns the number queued; `id` / `slot`: this lane's Gaussian and its queue slot
+	// (meaningful where `keep`).  The caller puts a __syncthreads() between this and its reads of the queue.
+	__device__ __forceinline__ int queue_chunk(const uint32_t* __restrict__ point_list, const float4* __restrict__ records, const uint2 range,
+	                                           const int n, const int base, const int lane, const unsigned long long lt_mask, const float rx0,
+	                                           const float rx1, const float ry0, const float ry1, float4* s_qa, float4* s_qb, bool& keep,
+	                                           uint32_t& id, int& slot)
+	{
+		const int pos = base + lane;
+		keep = false;
+		id = 0;
+		float4 a, b;
+		if (pos < n)
+		{
+			id = point_list[range.x + pos];
+			a = record_word(records, id, 0);
+			b = record_word(records, id, 1);
+			keep = block_reaches(a, b, rx0, rx1, ry0, ry1);
+		}
+		const unsigned long long mask = __ballot(keep);
+		slot = 0;
+		if (keep)
+		{
+			slot = __popcll(mask & lt_mask);   // list order is preserved
+			s_qa[slot] = a;
+			s_qb[slot] = make_float4(b.x, b.y, __uint_as_float(id), 0.0f);
+		}
+		return __popcll(mask);
+	}
+
+	// One queued entry at this lane's pixel: blend_fwd.hip's expressions, element for element (forward.cu:585-597).  Returns the
+	// blending weight w = alpha * T (0 where the entry does not contribute), steps T and `done`; `contrib`: the lanes it contributes to.
+	__device__ __forceinline__ float blend_weight(const float4 qa, const float4 qb, const float pixfx, const float pixfy, float& T,
+	                                              lanemask& done, lanemask& contrib)
+	{
+		const float dx = qa.x - pixfx, dy = qa.y - pixfy;
+		const float s2 = fmaf(qb.x * dy, dy, (qa.z * dx) * dx);
+		const float power = fmaf(-0.5f, s2, -((qa.w * dx) * dy));
+		const float alpha = fminf(0.99f, qb.y * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
+		const float test_T = T * (1.0f - alpha);
+		const lanemask valid = ~done & mask_of(!(power > 0.0f)) & mask_of(!(alpha < 1.0f / 255.0f));
+		const lanemask low = mask_of(test_T < 0.0001f);
+		contrib = valid & ~low;
+		const float w = mask_select(contrib, alpha * T, 0.0f);
+		T = mask_select(contrib, test_T, T);
+		done |= valid & low;
+		return w;
+	}
 }

@@ -21,7 +21,7 @@ COMMON="--offload-arch=$ARCH -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno
 declare -A EXTRA=( [preprocess_fwd]="-ffp-contract=off -fno-slp-vectorize" [preprocess_bwd]="-ffp-contract=off -fno-slp-vectorize" [sh_bwd]="-ffp-contract=off -fno-slp-vectorize" [time_slice]="-ffp-contract=off -fno-slp-vectorize" [flow]="-ffp-contract=off -fno-slp-vectorize" [camera_bwd]="-ffp-contract=off -fno-slp-vectorize" [knn]="-ffp-contract=off" [regularize]="-ffp-contract=off" [ssim]="-fno-slp-vectorize" [frames]="-ffp-contract=off" [frame_encode]="-ffp-contract=off" [compress]="-ffp-contract=off" )
 OBJS=()
 PIDS=()
-for src in preprocess_fwd tilebin radix_sort blend_fwd blend_bwd preprocess_bwd sh_bwd ssim adam densify knn regularize envmap metrics frames frame_encode time_slice flow contribution camera_bwd compress capi; do
+for src in preprocess_fwd tilebin radix_sort blend_fwd blend_bwd preprocess_bwd sh_bwd ssim adam densify knn regularize envmap metrics frames frame_encode time_slice flow contribution features camera_bwd compress capi; do
   obj=build/$src.o
   OBJS+=("$obj")
   if [[ ! -f $obj || $src.hip -nt $obj || fdgs_common.h -nt $obj || ssim_window.h -nt $obj || blend_common.h -nt $obj || fdgs_math.h -nt $obj || sh_eval.h -nt $obj || ../../include/fdgs.h -nt $obj ]]; then

@@ -778,6 +778,68 @@ extern "C" int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_cont
 	return FDGS_OK;
 }
 
+// what fdgs_feature_blend and fdgs_feature_blend_backward check alike; FDGS_OK: sizes and buffers are usable
+static int check_feature_in(const char* fn, const fdgs_feature_in* in)
+{
+	const int P = in->P, W = in->W, H = in->H, Cn = in->C;
+	if (P < 0 || P >= (1 << 26) || W <= 0 || H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, W, H);
+	if (div_up(W, TILE_X) > 65535 || div_up(H, TILE_Y) > 65535 || (long long)div_up(W, TILE_X) * div_up(H, TILE_Y) >= (1ll << 24))
+		return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d", W, H);
+	if (Cn < 1 || Cn > FDGS_FEATURE_MAX_CHANNELS)
+		return fail(FDGS_ERR_INVALID_ARG, "%s: C=%d channels, 1 .. %d are supported", fn, Cn, FDGS_FEATURE_MAX_CHANNELS);
+	if (P > 0 && (!in->geom_buffer || !in->binning_buffer || !in->image_buffer))
+		return fail(FDGS_ERR_INVALID_ARG, "%s: geom_buffer / binning_buffer / image_buffer must not be NULL", fn);
+	return FDGS_OK;
+}
+
+extern "C" int fdgs_feature_blend(const fdgs_feature_in* in, float* out, void* stream_v)
+{
+	g_err[0] = 0;
+	if (!in || !out) return fail(FDGS_ERR_INVALID_ARG, "in / out must not be NULL");
+	CHECK_STRUCT(in, fdgs_feature_in);
+	const int rc = check_feature_in("fdgs_feature_blend", in);
+	if (rc != FDGS_OK) return rc;
+	if (!in->features) return fail(FDGS_ERR_INVALID_ARG, "fdgs_feature_blend: features must not be NULL");
+	hipStream_t stream = (hipStream_t)stream_v;
+	if (in->P == 0 || in->num_rendered == 0)
+	{
+		// no list to walk: no pixel has a contributor
+		HIP_TRY(hipMemsetAsync(out, 0, (size_t)in->C * in->W * in->H * 4, stream), "feature memset");
+		return FDGS_OK;
+	}
+	const GeomLayout GL = geom_layout(in->P);
+	const ImageLayout IL = image_layout(in->W, in->H);
+	const BinLayout BL = bin_layout(in->num_rendered, false, 0);   // point_list sits at the front whatever layout the forward chose
+	const char* geom = (const char*)in->geom_buffer;
+	const char* img = (const char*)in->image_buffer;
+	const char* bin = (const char*)in->binning_buffer;
+	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;   // as the backward finds it
+	HIP_TRY(launch_feature_blend(*in, out, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
+	                             (const uint32_t*)(img + IL.ranges), tile_order, stream), "feature_blend");
+	return FDGS_OK;
+}
+
+extern "C" int fdgs_feature_blend_backward(const fdgs_feature_in* in, const float* dL_dout, float* dL_dfeatures, void* stream_v)
+{
+	g_err[0] = 0;
+	if (!in || !dL_dout || !dL_dfeatures) return fail(FDGS_ERR_INVALID_ARG, "in / dL_dout / dL_dfeatures must not be NULL");
+	CHECK_STRUCT(in, fdgs_feature_in);
+	const int rc = check_feature_in("fdgs_feature_blend_backward", in);
+	if (rc != FDGS_OK) return rc;
+	if (in->P == 0 || in->num_rendered == 0) return FDGS_OK;   // no list to walk: nothing is added
+	hipStream_t stream = (hipStream_t)stream_v;
+	const GeomLayout GL = geom_layout(in->P);
+	const ImageLayout IL = image_layout(in->W, in->H);
+	const BinLayout BL = bin_layout(in->num_rendered, false, 0);
+	const char* geom = (const char*)in->geom_buffer;
+	const char* img = (const char*)in->image_buffer;
+	const char* bin = (const char*)in->binning_buffer;
+	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;
+	HIP_TRY(launch_feature_blend_bwd(*in, dL_dout, dL_dfeatures, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
+	                                 (const uint32_t*)(img + IL.ranges), tile_order, stream), "feature_blend_backward");
+	return FDGS_OK;
+}
+
 // the views of a batch must describe the same Gaussians: sizes, degrees, flags and the shared tensors
 static int check_same_gaussians(const fdgs_scene& a, const fdgs_scene& b, int v)
 {

@@ -195,6 +195,12 @@ namespace fdgs
 	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const float* records,
 	                               const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
 
+	// per-Gaussian feature channels blended with a finished forward's weights, and the adjoint (features.hip); tile_order: NULL = index order
+	hipError_t launch_feature_blend(const fdgs_feature_in& in, float* out, const float* records, const uint32_t* point_list,
+	                                const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
+	hipError_t launch_feature_blend_bwd(const fdgs_feature_in& in, const float* dL_dout, float* dL_dfeatures, const float* records,
+	                                    const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
+
 	// SH / 4D-SH backward (coalesced); must run after the blend backward and before launch_preprocess_bwd
 	hipError_t launch_sh_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,
 	                         const char* geom, hipStream_t stream);

@@ -820,6 +820,40 @@ typedef struct fdgs_contribution_out
 } fdgs_contribution_out;
 int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_contribution_out* out, void* stream);
 
+/* ---- feature channels: per-Gaussian data blended with the weights of a finished forward, and the adjoint ------------------------------
+ * CALL ORDER: after the forward, on the same stream, with its three scratch buffers (any list layout: compact or sparse, tile_cull on
+ * or off, num_rendered = -1 from a lazy forward; the forward's cull planes are not read) -- exactly as fdgs_contribution.  Per pixel
+ * the tile list is walked front to back with the forward blend's own decisions and arithmetic (skip power > 0 and alpha < 1/255; the
+ * entry that would take T below 1e-4 ends the pixel and does not contribute), so the weights w = alpha * T are the rendered image's.
+ *   fdgs_feature_blend:           out[c, y, x] = sum over the pixel's contributions of w * features[id, c]
+ *       features [P,C] float32, row-major, rows contiguous, finite; out [C,H,W] is OVERWRITTEN; a pixel without a contributor is
+ *       exactly 0 and nothing is composited behind the features (the caller does that with the forward's alpha if it wants a
+ *       background).  No atomics: bit-identical run to run, and the value of a channel does not depend on C or on the channels
+ *       rendered with it.
+ *   fdgs_feature_blend_backward:  dL_dfeatures[id, c] += sum over the pixels id contributes to of w * dL_dout[c, y, x]
+ *       the adjoint of the above; dL_dfeatures [P,C] is ACCUMULATED in place -- the caller zero-fills it once, further views add to
+ *       it -- with float atomic adds (the last bits depend on the arrival order): at most one request per (8x8 pixel block,
+ *       Gaussian, channel), none for a Gaussian that contributed to no pixel of the block.  in->features is not read (NULL).
+ * GEOMETRY IS HELD CONSTANT: w is a number here; no gradient reaches alpha, the positions or the covariances.
+ * 1 <= C <= FDGS_FEATURE_MAX_CHANNELS, any C in that range.  P == 0 (and num_rendered == 0): the forward zero-fills out, the
+ * backward does nothing.
+ * FDGS_ERR_INVALID_ARG before any launch: NULL in / out / dL_dout / dL_dfeatures, a wrong struct_size, P < 0 or >= 2^26, W or H <= 0,
+ * C outside [1, FDGS_FEATURE_MAX_CHANNELS], P > 0 with a NULL scratch buffer, NULL features in the forward. */
+#define FDGS_FEATURE_MAX_CHANNELS 256
+typedef struct fdgs_feature_in
+{
+	uint32_t struct_size;      /* sizeof(fdgs_feature_in)                               */
+	int32_t P, W, H, C;        /* as the forward's fdgs_scene; C: feature channels      */
+	const void* geom_buffer;   /* the forward's three scratch buffers                   */
+	const void* binning_buffer;
+	const void* image_buffer;
+	int32_t num_rendered;      /* as returned by the forward (-1: a lazy forward)       */
+	const float* features;     /* [P,C]; NULL for the backward                          */
+} fdgs_feature_in;
+int fdgs_feature_blend(const fdgs_feature_in* in, float* out /* [C,H,W] */, void* stream);
+int fdgs_feature_blend_backward(const fdgs_feature_in* in, const float* dL_dout /* [C,H,W] */, float* dL_dfeatures /* [P,C], accumulated */,
+                                void* stream);
+
 /* ---- camera gradients: dL/d(viewmatrix, projmatrix, campos, timestamp) of one view --------------------------------------------------
  * The analytic derivatives of the forward with respect to the four camera inputs of fdgs_scene, every discrete decision held constant
  * (culls, radii, tile lists, n_contrib, the alpha and T cut-offs); not the reference backward's quirks: the camera is no parameter of
