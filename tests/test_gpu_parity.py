@@ -171,7 +171,8 @@ def test_depth_only_backward_vs_oracle(gpu_device):
 # ----------------------------------------------------------------------------------------------------------------
 
 def _timed_path_vs_oracle(cfg, dev, n_views, label, max_border, tile_cull=True, scale_modifier=1.0, prefilter_var=-1.0, poses=None, alloc=None,
-                          make_kw=None, raw_quat_scale=None, chain=("_scaling", "_scaling_t", "_rotation", "_rotation_r"), repeats=1, scene_hook=None, dump=None):
+                          make_kw=None, raw_quat_scale=None, chain=("_scaling", "_scaling_t", "_rotation", "_rotation_r"), repeats=1, scene_hook=None, dump=None,
+                          ready=None):
     """The calls fdgs/pipeline.py::StepPipeline makes for one optimizer step -- raw parameters (activations fused into
     the kernels, fdgs_scene.raw_params = 1), fused L1 + SSIM gradient as the only upstream gradient (colour-only blend
     backward), parameter gradients accumulated over the views into the flat bucket, persistent always-zero blend
@@ -183,17 +184,25 @@ def _timed_path_vs_oracle(cfg, dev, n_views, label, max_border, tile_cull=True, 
     tensors in ``chain`` (default: the four covariance-chain tensors) beyond that bar is held to the conditioning-aware bar of
     util.check_backward_noise_aware: 1e-4 * scale + NOISE_K x what the reference's own accumulation orders do to THAT Gaussian.
     ``repeats``: the HIP backward is drawn that many times against the same oracle results (FDGS_PARITY_REPEATS).  ``tile_cull`` (what StepPipeline runs with): the lists are the reference's with the instances taken out that
-    cannot reach alpha >= 1/255 in their tile -- checked as such (util.check_culled_lists) instead of bit for bit."""
+    cannot reach alpha >= 1/255 in their tile -- checked as such (util.check_culled_lists) instead of bit for bit.
+    ``ready`` = (model, scene, cameras): a ready GaussianParams (e.g. GaussianParams.from_raw of a recorded trained state) instead of one
+    built from fdgs.synth -- ``cfg`` is then None; ``scene``: the scene dict the oracle is fed from (its per-Gaussian ACTIVATED tensors are
+    replaced by the kernels' own, its means3D / ts / shs must be the model's), ``cameras``: ``n_views`` pairs (camera tensors as
+    synth.camera_for returns them, timestamp)."""
     from fdgs import _capi, train_host
     from fdgs.fused import raw_backward, raw_forward, raw_settings
     from fdgs.loss import l1_ssim_grad
     from util import collect_forward
 
-    scene = synth.make_scene(cfg, seed=0, **(make_kw or {}))
-    if scene_hook is not None:
-        scene_hook(scene)
+    if ready is None:
+        scene = synth.make_scene(cfg, seed=0, **(make_kw or {}))
+        if scene_hook is not None:
+            scene_hook(scene)
+        model = train_host.GaussianParams(scene, dev)
+    else:
+        model, scene, ready_cams = ready
+        assert len(ready_cams) == n_views and model.P == int(scene["means3D"].shape[0])
     P, W, H = int(scene["means3D"].shape[0]), scene["W"], scene["H"]
-    model = train_host.GaussianParams(scene, dev)
     if raw_quat_scale is not None:
         # the RAW quaternions of a trained model are not unit (scene/gaussian_model.py:191-197 normalises in the getter, nothing keeps
         # the parameter itself on the sphere): lengths from raw_quat_scale[0] to [1], so that the normalisation's chain rule
@@ -207,8 +216,12 @@ def _timed_path_vs_oracle(cfg, dev, n_views, label, max_border, tile_cull=True, 
     pipe = train_host.PipelineFlags()
     bg = scene["bg"].to(dev)
     dur = scene["time_duration"]
-    cam_tensors = [synth.camera_for(poses[b] if poses else "axis", W, H) for b in range(n_views)]
-    cams = [train_host.SyntheticCamera(dict(scene, **cam_tensors[b]), dev, timestamp=(b + 0.5) / n_views * dur) for b in range(n_views)]
+    if ready is None:
+        cam_tensors = [synth.camera_for(poses[b] if poses else "axis", W, H) for b in range(n_views)]
+        stamps = [(b + 0.5) / n_views * dur for b in range(n_views)]
+    else:
+        cam_tensors, stamps = [c for c, _ in ready_cams], [t for _, t in ready_cams]
+    cams = [train_host.SyntheticCamera(dict(scene, **cam_tensors[b]), dev, timestamp=stamps[b]) for b in range(n_views)]
     gen = torch.Generator(device="cpu").manual_seed(99)
     gts = [torch.rand(3, H, W, generator=gen).to(dev) for _ in range(n_views)]
     # The loss is a mean over 3 N pixels: its image gradient is O(1 / (3 N)).  The kernels are linear in the upstream
@@ -321,7 +334,10 @@ def _timed_path_vs_oracle(cfg, dev, n_views, label, max_border, tile_cull=True, 
         total_rev = rr if total_rev is None else {k: total_rev[k] + rr[k] for k in rr}
         total_f64 = r64 if total_f64 is None else {k: total_f64[k] + r64[k] for k in r64}
 
-    n_active = synth.active_sh_coeffs(cfg.sh_degree, cfg.sh_degree_t, cfg.force_sh_3d, cfg.gaussian_dim)
+    if ready is None:
+        n_active = synth.active_sh_coeffs(cfg.sh_degree, cfg.sh_degree_t, cfg.force_sh_3d, cfg.gaussian_dim)
+    else:
+        n_active = synth.active_sh_coeffs(model.active_sh_degree, model.active_sh_degree_t, model.force_sh_3d, model.gaussian_dim)
     assert float(np.abs(total["_features"].reshape(P, -1, 3)[:, n_active:]).max(initial=0.0)) == 0.0   # the reference's zeros
     # Gradients of the covariance parameters are cancelling sums of products of dL/dcov3D (O(1e3) here) with the
     # scale / rotation matrices: the chain amplifies a 1e-6 relative rounding difference in the blend backward's per-Gaussian

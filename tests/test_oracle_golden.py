@@ -12,9 +12,8 @@ FLOAT_KEYS = ("out_color", "out_flow", "out_depth", "out_T", "out_means3D", "mea
               "conic_opacity")
 
 
-@pytest.mark.parametrize("name", golden_util.NAMES)
-def test_port_oracle_matches_golden(name):
-    scene, up, fw, bw = golden_util.load(name)
+def assert_port_matches_reference(name, scene, up, fw, bw):
+    """The port oracle on ``scene`` / ``up`` against the stored outputs of the reference's own kernels (``fw`` / ``bw``)."""
     out, grads = run_oracle(scene, up, kind="port")
     assert out["R"] == fw["R"]
     for k in INT_KEYS:
@@ -30,6 +29,12 @@ def test_port_oracle_matches_golden(name):
         scale = max(1.0, float(np.abs(b).max()) if b.size else 1.0)
         err = float(np.abs(a - b).max()) if b.size else 0.0
         assert err <= 2e-5 * scale, "%s %s: %g (scale %g)" % (name, k, err, scale)
+    return out, grads
+
+
+@pytest.mark.parametrize("name", golden_util.NAMES)
+def test_port_oracle_matches_golden(name):
+    assert_port_matches_reference(name, *golden_util.load(name))
 
 
 def test_golden_fixtures_present():

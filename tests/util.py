@@ -336,6 +336,19 @@ def oracle_four_modes(o, grads):
     return out
 
 
+def ill_conditioned_count(o, grads, vis):
+    """How many of the Gaussians in ``vis`` (bool [P]) the oracle ``o`` (port: the only one with accumulation modes; pinned to the reference's
+    own kernels by tests/test_oracle_golden.py) differs from ITSELF on by more than GRAD_TOL * scale on a tensor of CHAIN_ACTIVATED: its
+    atomics in the opposite order (mode 1) and its per-Gaussian sums accumulated in double (mode 2), each against mode 0."""
+    g0, g1, g2, _ = oracle_four_modes(o, grads)
+    bad = np.zeros(vis.shape[0], bool)
+    for n in CHAIN_ACTIVATED:
+        scale = max(1.0, float(np.abs(g0[n]).max()))
+        for other in (g1, g2):
+            bad |= np.abs(other[n] - g0[n]).reshape(vis.shape[0], -1).max(1) > GRAD_TOL * scale
+    return int((bad & vis).sum())
+
+
 # ----------------------------------------------------------------------------------------------------------------------------
 # Uniformly distributed orientations with a moderate footprint (tests/test_gpu_orientations.py, tests/golden/make_golden.py)
 # ----------------------------------------------------------------------------------------------------------------------------
