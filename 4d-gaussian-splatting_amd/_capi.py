@@ -143,7 +143,8 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
             "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
             "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
-            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
+            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_frames_resize", "fdgs_frames_resize_scratch_bytes",
+            "fdgs_debug_frames_resize_path", "fdgs_frames_composite", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
             "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
             "fdgs_last_error", "fdgs_version")
@@ -287,6 +288,15 @@ def _load():
     lib.fdgs_frames_encode_gray_scratch_bytes.restype = C.c_int64
     lib.fdgs_frames_encode_gray.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     lib.fdgs_frames_encode_gray.restype = C.c_int
+    lib.fdgs_frames_resize.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [
+        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+    lib.fdgs_frames_resize.restype = C.c_int
+    lib.fdgs_frames_resize_scratch_bytes.argtypes = [C.c_int32] * 6
+    lib.fdgs_frames_resize_scratch_bytes.restype = C.c_int64
+    lib.fdgs_debug_frames_resize_path.argtypes = [C.c_int32]
+    lib.fdgs_debug_frames_resize_path.restype = None
+    lib.fdgs_frames_composite.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]
+    lib.fdgs_frames_composite.restype = C.c_int
     lib.fdgs_time_slice_scratch_bytes.argtypes = [C.c_int32]
     lib.fdgs_time_slice_scratch_bytes.restype = C.c_size_t
     lib.fdgs_time_slice.argtypes = [C.POINTER(FdgsSliceIn), C.POINTER(FdgsSliceOut), C.c_void_p, C.c_void_p]

@@ -682,6 +682,42 @@ int64_t fdgs_frames_encode_gray_scratch_bytes(int32_t B, int32_t H, int32_t W);
 int fdgs_frames_encode_gray(const float* planes, int64_t plane_stride, int32_t B, int32_t H, int32_t W, uint8_t* frames, int32_t N,
                             const int32_t* index, void* scratch, void* stream);
 
+/* ---- 8-bit frames resized on the device: Pillow's Image.resize (BICUBIC), byte for byte -----------------------------------------------
+ * What the reference's loader does on the host for every image (utils/camera_utils.py:19-49 loadCam -> PILtoTorch(image, resolution)
+ * = pil_image.resize(resolution)), done here from full-size 8-bit frames: dst[b] = resize(src[index[b]]) for the B entries of a
+ * DEVICE-side index.  src: N frames uint8 [Hs, Ws, C], dst: M >= B frames [Hd, Wd, C], interleaved, C = 3 or 4, as for
+ * fdgs_frames_decode; an index outside [0, N) leaves its destination frame unwritten.  Integer arithmetic only:
+ *   one pass:  out = clip(0, 255, (2^21 + sum_x k[x] * in[xmin + x]) >> 22), int32 accumulator, arithmetic shift;
+ *   the horizontal pass first, into an intermediate rounded to uint8, the vertical pass over that; a pass whose axis keeps its
+ *   length is skipped, and with both skipped the result is a plain copy;
+ *   RGBA, whenever a pass runs: premultiplied first, c' = ((t >> 8) + t) >> 8 with t = c a + 128; afterwards, where the new alpha
+ *   is neither 0 nor 255, c = min(255, (255 c') / a).
+ * kx [Wd, ksize_x] / ky [Hd, ksize_y]: the taps in fixed point (22 fractional bits), bx [Wd, 2] / by [Hd, 2]: (xmin, count) per
+ * output index, int32 in device memory, built on the host in float64 (fdgs.resize.coefficients); ksize = ceil(2 max(n_in / n_out,
+ * 1)) * 2 + 1 per axis.  The tables of an unchanged axis must be passed and are not read.  Bounds outside the axis are clamped,
+ * never followed.  One launch (a fused kernel with the intermediate of an output tile in LDS) whenever the source window of some
+ * tile fits LDS; otherwise two launches with the intermediate [B, Hs, Wd, C] in `scratch`:
+ * fdgs_frames_resize_scratch_bytes(...) bytes (0 where none is needed: scratch may then be NULL; -1 for invalid sizes).  Enqueued on
+ * `stream`, no host synchronisation.  FDGS_ERR_INVALID_ARG with nothing launched: C outside {3, 4}, non-positive sizes, B > 65535,
+ * B > M, a frame / result / intermediate of 2^31 - 4096 bytes or more, a NULL src / index / dst / table (or scratch where needed),
+ * a ksize that disagrees with the sizes.
+ * fdgs_debug_frames_resize_path(1) makes every later call take the two-launch path (tests, A/B timing); 0 restores the choice. */
+int fdgs_frames_resize(const uint8_t* src, int32_t N, int32_t Hs, int32_t Ws, int32_t C, const int32_t* index, int32_t B,
+                       uint8_t* dst, int32_t M, int32_t Hd, int32_t Wd,
+                       const int32_t* kx, const int32_t* bx, int32_t ksize_x,
+                       const int32_t* ky, const int32_t* by, int32_t ksize_y,
+                       void* scratch, void* stream);
+int64_t fdgs_frames_resize_scratch_bytes(int32_t B, int32_t Hs, int32_t Ws, int32_t Hd, int32_t Wd, int32_t C);
+void fdgs_debug_frames_resize_path(int32_t path);
+
+/* RGBA frames over a white (white != 0) or black background, the step of the reference's readers before the resize
+ * (scene/dataset_readers.py:249-259, utils/data_utils.py:20-23), in float64 with every operation rounded on its own:
+ *   out = floor(((c / 255.0) * (a / 255.0) + bg * (1.0 - a / 255.0)) * 255.0)
+ * src_rgba: N frames uint8 [H, W, 4]; dst: [N, H, W, 4] with the alpha byte kept (keep_alpha != 0) or [N, H, W, 3].  One launch.
+ * FDGS_ERR_INVALID_ARG: non-positive sizes, a frame of 2^31 - 4096 bytes or more, a NULL pointer. */
+int fdgs_frames_composite(const uint8_t* src_rgba, int32_t N, int32_t H, int32_t W, int32_t white, int32_t keep_alpha,
+                          uint8_t* dst, void* stream);
+
 /* ---- a 4D model at one timestamp as 3D Gaussians ---------------------------------------------------------------------------------
  * At time t a 4D Gaussian is a 3D Gaussian: the conditional mean and covariance (rot_4d: forward.cu:279-352; otherwise the plain mean
  * and R S^2 R^T), the opacity times the temporal marginal, an SH row with the time blocks folded in.  The call computes that for the
