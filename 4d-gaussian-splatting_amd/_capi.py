@@ -368,6 +368,21 @@ def _dev_f32(t, name):
     return t.contiguous()
 
 
+def _common_device(named):
+    """The common device of the tensors ``named`` ((name, tensor) pairs; None and empty tensors are skipped: an empty model leaves
+    buffers out), or None; a CPU tensor raises."""
+    dev = None
+    for name, t in named:
+        if t is None or t.numel() == 0:
+            continue
+        if not t.is_cuda:
+            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        if dev is not None and t.device != dev:
+            raise RuntimeError("fdgs: '%s' lives on %s, the forward's buffers on %s" % (name, t.device, dev))
+        dev = t.device
+    return dev
+
+
 def debug_activations(opacity_raw=None, scales_raw=None, scales_t_raw=None, rotations_raw=None, rotations_r_raw=None):
     """The activated tensors the kernels derive from raw parameters (fdgs_debug_activations): bit-identical to what
     preprocess computes in flight with fdgs_scene.raw_params = 1.  Returns a 5-tuple (None where the input was None)."""

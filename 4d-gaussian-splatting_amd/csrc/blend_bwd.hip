@@ -278,6 +278,7 @@ namespace fdgs
 		// loop addresses the whole queue with ONE base register and immediate offsets
 		__shared__ float4 s_q[7][QP];
 
+		// (pixel_block of blend_common.h, stated here: built on that function the kernel compiles to other code)
 		const BlockId blk = block_of(blockIdx.x, ntiles, tile_order);
 		if (blk.tile >= ntiles) return;
 		const int lane = threadIdx.x;
@@ -574,17 +575,12 @@ namespace fdgs
 #undef FDGS_BWD_PARAMS
 #undef FDGS_BWD_ARGS
 
-	hipError_t launch_blend_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,
-	                            const float* records, const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order,
-	                            const float* final_T, const uint32_t* n_contrib, const uint32_t* ctl, hipStream_t stream)
+	hipError_t launch_blend_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out, const FinishedForward& ff,
+	                            hipStream_t stream)
 	{
-		const int gx = div_up(s.W, TILE_X), gy = div_up(s.H, TILE_Y);
-		const int ntiles = gx * gy;
-#define LAUNCH_BWD(AUX) hipLaunchKernelGGL((blend_bwd_kernel<AUX>), dim3(blend_grid(ntiles)), dim3(WAVE), 0, stream, \
-		                   reinterpret_cast<const uint2*>(ranges), point_list, reinterpret_cast<const float4*>(records), \
-		                   tile_order, s.W, s.H, gx, ntiles, s.bg, final_T, n_contrib, \
-		                   in.dL_dout_color, in.dL_dout_depth, in.dL_dout_alpha, in.dL_dout_flow, out.grad_accum, ctl)
-		if (s.P >= (1 << 26)) return hipErrorInvalidValue;   // 32-bit byte offsets into the 64-byte accumulator records
+#define LAUNCH_BWD(AUX) hipLaunchKernelGGL((blend_bwd_kernel<AUX>), dim3(blend_grid(ff.ntiles)), dim3(WAVE), 0, stream, \
+		                   ff.ranges, ff.point_list, ff.records, ff.tile_order, ff.W, ff.H, ff.gx, ff.ntiles, s.bg, ff.final_T, ff.n_contrib, \
+		                   in.dL_dout_color, in.dL_dout_depth, in.dL_dout_alpha, in.dL_dout_flow, out.grad_accum, ff.ctl)
 		if (in.dL_dout_depth || in.dL_dout_alpha || in.dL_dout_flow) LAUNCH_BWD(true);
 		else LAUNCH_BWD(false);
 #undef LAUNCH_BWD

@@ -99,51 +99,104 @@ namespace fdgs
 		return qmin <= tau;
 	}
 
-	// ---- the walk of a finished forward's lists: blend_fwd.hip's decisions once more ----
-	// The two steps of contribution_kernel's walk as inline functions, for the kernels of features.hip.  contribution.hip keeps its
-	// own statement of them: built on these functions it computes the same but compiles to other code (queue_chunk: another register
-	// allocation and block layout; blend_weight: one instruction moves), and that kernel's code object is not to change for a refactor.
+	// ---- the wave's pixel block and the walk of a tile's list: stated once, for every kernel that takes a forward's lists ----
+	// blend_fwd.hip, blend_bwd.hip, contribution.hip and features.hip all start from pixel_block; the walk itself is fetch_and_cull
+	// (one list entry per lane, culled against the block) -> queue_chunk (the survivors, in list order, into the wave-private queue)
+	// -> blend_weight per queued entry (entry_alpha, then blend_step: the decisions of forward.cu:585-597).  A change to the cull or
+	// to the transmittance logic is made here, once -- and in the copies the two timed kernels keep, each marked with the name of the
+	// function it mirrors, because built on the function they compile to other code: fetch_and_cull and blend_step in blend_fwd.hip
+	// (which shares pixel_block and, in its debug kernel, entry_alpha), pixel_block in blend_bwd.hip (which reads the forward's cull
+	// planes instead of testing again).
 
-	// One chunk of a tile's list (entries [base, base + 64) of the n the range holds): lane `lane` fetches one entry, tests it against
-	// the wave's pixel block and the survivors go, in list order, into the wave-private queue as (x, y, conic.x, conic.y) and
-	// (conic.z, opacity, Gaussian id, -).  Returns the number queued; `id` / `slot`: this lane's Gaussian and its queue slot
-	// (meaningful where `keep`).  The caller puts a __syncthreads() between this and its reads of the queue.
-	__device__ __forceinline__ int queue_chunk(const uint32_t* __restrict__ point_list, const float4* __restrict__ records, const uint2 range,
-	                                           const int n, const int base, const int lane, const unsigned long long lt_mask, const float rx0,
-	                                           const float rx1, const float ry0, const float ry1, float4* s_qa, float4* s_qb, bool& keep,
-	                                           uint32_t& id, int& slot)
+	// The 8x8 pixel block of a workgroup and this lane's pixel in it.
+	struct PixelBlock
 	{
-		const int pos = base + lane;
+		int tile, sub;                // tile index, 8x8 sub-block of the tile (0..3)
+		int bx0, by0;                 // the block's first pixel
+		int px, py;                   // this lane's pixel
+		bool inside;                  // ... is inside the image
+		float pixfx, pixfy;           // ... as floats
+		float rx0, rx1, ry0, ry1;     // pixel-centre bounds of the block, clamped to the image (block_reaches)
+		unsigned long long lt_mask;   // the lanes below this one
+	};
+	// false: nothing to do (beyond the grid's padding, or entirely outside the image)
+	__device__ __forceinline__ bool pixel_block(int wg, int ntiles, const uint32_t* __restrict__ tile_order, int grid_x, int W, int H, int lane,
+	                                            PixelBlock& pb)
+	{
+		const BlockId blk = block_of(wg, ntiles, tile_order);
+		if (blk.tile >= ntiles) return false;
+		pb.tile = blk.tile;
+		pb.sub = blk.sub;
+		pb.bx0 = (blk.tile % grid_x) * TILE_X + (blk.sub & 1) * BLK;
+		pb.by0 = (blk.tile / grid_x) * TILE_Y + (blk.sub >> 1) * BLK;
+		if (pb.bx0 >= W || pb.by0 >= H) return false;
+		pb.px = pb.bx0 + (lane & (BLK - 1));
+		pb.py = pb.by0 + (lane >> 3);
+		pb.inside = pb.px < W && pb.py < H;
+		pb.pixfx = (float)pb.px;
+		pb.pixfy = (float)pb.py;
+		pb.rx0 = (float)pb.bx0;
+		pb.rx1 = (float)min(pb.bx0 + BLK - 1, W - 1);
+		pb.ry0 = (float)pb.by0;
+		pb.ry1 = (float)min(pb.by0 + BLK - 1, H - 1);
+		pb.lt_mask = (1ull << lane) - 1ull;
+		return true;
+	}
+
+	// List position `pos` of the n entries the range holds: this lane fetches the entry's Gaussian id and record words a, b (meaningful
+	// where `keep`) and tests it against the block.  Returns the wave's mask of survivors.
+	__device__ __forceinline__ unsigned long long fetch_and_cull(const uint32_t* __restrict__ point_list, const float4* __restrict__ records,
+	                                                             const uint2 range, const int n, const int pos, const PixelBlock& pb, bool& keep,
+	                                                             uint32_t& id, float4& a, float4& b)
+	{
 		keep = false;
 		id = 0;
-		float4 a, b;
 		if (pos < n)
 		{
 			id = point_list[range.x + pos];
 			a = record_word(records, id, 0);
 			b = record_word(records, id, 1);
-			keep = block_reaches(a, b, rx0, rx1, ry0, ry1);
+			keep = block_reaches(a, b, pb.rx0, pb.rx1, pb.ry0, pb.ry1);
 		}
-		const unsigned long long mask = __ballot(keep);
+		return __ballot(keep);
+	}
+
+	// One chunk of a tile's list (entries [base, base + 64) of n): the survivors of fetch_and_cull go, in list order, into the
+	// wave-private queue as (x, y, conic.x, conic.y) and (conic.z, opacity, Gaussian id, -).  Returns the number queued; `id` / `slot`:
+	// this lane's Gaussian and its queue slot (meaningful where `keep`).  The caller puts a __syncthreads() between this and its reads
+	// of the queue.
+	__device__ __forceinline__ int queue_chunk(const uint32_t* __restrict__ point_list, const float4* __restrict__ records, const uint2 range,
+	                                           const int n, const int base, const int lane, const PixelBlock& pb, float4* s_qa, float4* s_qb,
+	                                           bool& keep, uint32_t& id, int& slot)
+	{
+		float4 a, b;
+		const unsigned long long mask = fetch_and_cull(point_list, records, range, n, base + lane, pb, keep, id, a, b);
 		slot = 0;
 		if (keep)
 		{
-			slot = __popcll(mask & lt_mask);   // list order is preserved
+			slot = __popcll(mask & pb.lt_mask);   // list order is preserved
 			s_qa[slot] = a;
 			s_qb[slot] = make_float4(b.x, b.y, __uint_as_float(id), 0.0f);
 		}
 		return __popcll(mask);
 	}
 
-	// One queued entry at this lane's pixel: blend_fwd.hip's expressions, element for element (forward.cu:585-597).  Returns the
-	// blending weight w = alpha * T (0 where the entry does not contribute), steps T and `done`; `contrib`: the lanes it contributes to.
-	__device__ __forceinline__ float blend_weight(const float4 qa, const float4 qb, const float pixfx, const float pixfy, float& T,
-	                                              lanemask& done, lanemask& contrib)
+	// alpha of the entry with record words a = (x, y, conic.x, conic.y), b = (conic.z, opacity, ..) at pixel (pixfx, pixfy), and the
+	// exponent `power`: the reference's association per element (forward.cu:585-590), FMA, hardware exp2.  blend_fwd.hip and
+	// blend_bwd.hip evaluate the same expressions on two entries at once (packed fp32).
+	__device__ __forceinline__ float entry_alpha(const float4 a, const float4 b, const float pixfx, const float pixfy, float& power)
 	{
-		const float dx = qa.x - pixfx, dy = qa.y - pixfy;
-		const float s2 = fmaf(qb.x * dy, dy, (qa.z * dx) * dx);
-		const float power = fmaf(-0.5f, s2, -((qa.w * dx) * dy));
-		const float alpha = fminf(0.99f, qb.y * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
+		const float dx = a.x - pixfx, dy = a.y - pixfy;
+		const float s2 = fmaf(b.x * dy, dy, (a.z * dx) * dx);
+		power = fmaf(-0.5f, s2, -((a.w * dx) * dy));
+		return fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
+	}
+
+	// forward.cu:588-597 on lane masks: valid = not finished, power <= 0, alpha >= 1/255; a valid entry that would take T below 1e-4
+	// finishes the pixel (and is not counted), any other valid entry contributes.  Returns the blending weight w = alpha * T (0 where
+	// the entry does not contribute), steps T and `done`; `contrib`: the lanes it contributes to.
+	__device__ __forceinline__ float blend_step(const float alpha, const float power, float& T, lanemask& done, lanemask& contrib)
+	{
 		const float test_T = T * (1.0f - alpha);
 		const lanemask valid = ~done & mask_of(!(power > 0.0f)) & mask_of(!(alpha < 1.0f / 255.0f));
 		const lanemask low = mask_of(test_T < 0.0001f);
@@ -152,5 +205,14 @@ namespace fdgs
 		T = mask_select(contrib, test_T, T);
 		done |= valid & low;
 		return w;
+	}
+
+	// One queued entry at this lane's pixel: its blending weight (see blend_step)
+	__device__ __forceinline__ float blend_weight(const float4 qa, const float4 qb, const float pixfx, const float pixfy, float& T,
+	                                              lanemask& done, lanemask& contrib)
+	{
+		float power;
+		const float alpha = entry_alpha(qa, qb, pixfx, pixfy, power);
+		return blend_step(alpha, power, T, done, contrib);
 	}
 }

@@ -41,20 +41,14 @@ namespace fdgs
 		const int lane = threadIdx.x;
 		// where the backward finds the cull planes: stride and offset (64-bit words from the start of the binning buffer)
 		if (blockIdx.x == 0 && lane == 0 && ctl != nullptr) { ctl[2] = cull_bits ? cull_stride : 0u; ctl[3] = cull_word_off; }
-		const BlockId blk = block_of(blockIdx.x, ntiles, tile_order);
-		if (blk.tile >= ntiles) return;
-		const int bx0 = (blk.tile % grid_x) * TILE_X + (blk.sub & 1) * BLK;
-		const int by0 = (blk.tile / grid_x) * TILE_Y + (blk.sub >> 1) * BLK;
-		if (bx0 >= W || by0 >= H) return; // block entirely outside the image
-		const int px = bx0 + (lane & (BLK - 1)), py = by0 + (lane >> 3);
-		const bool inside = px < W && py < H;
-		const float pixfx = (float)px, pixfy = (float)py;
-		const float rx0 = (float)bx0, rx1 = (float)min(bx0 + BLK - 1, W - 1);
-		const float ry0 = (float)by0, ry1 = (float)min(by0 + BLK - 1, H - 1);
+		PixelBlock pb;
+		if (!pixel_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, lane, pb)) return;
+		const int px = pb.px, py = pb.py;
+		const bool inside = pb.inside;
+		const float pixfx = pb.pixfx, pixfy = pb.pixfy;
 
-		const uint2 range = ranges[blk.tile];
+		const uint2 range = ranges[pb.tile];
 		const int n = (int)(range.y - range.x);
-		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		lanemask done = mask_of(!inside);   // pixels that take no further contribution
 		float T = 1.0f;
@@ -64,6 +58,7 @@ namespace fdgs
 		for (int base = 0; base < n; base += WAVE)
 		{
 			if (done == ~0ull) break; // all 64 pixels saturated
+			// (fetch_and_cull of blend_common.h, stated here: built on that function the kernel compiles to other code)
 			const int pos = base + lane;
 			bool keep = false;
 			uint32_t id = 0;
@@ -73,16 +68,16 @@ namespace fdgs
 				id = point_list[range.x + pos];
 				a = record_word(records, id, 0);
 				b = record_word(records, id, 1);
-				keep = block_reaches(a, b, rx0, rx1, ry0, ry1);
+				keep = block_reaches(a, b, pb.rx0, pb.rx1, pb.ry0, pb.ry1);
 			}
 			const unsigned long long mask = __ballot(keep);
 			const int cnt = __popcll(mask);
 			// kept for the backward (bit i = list position base + i): it takes the same 64-entry chunks and skips the test
 			if (cull_bits != nullptr && lane == 0)
-				cull_bits[(size_t)blk.sub * cull_stride + (range.x >> 6) + (uint32_t)blk.tile + (uint32_t)(base >> 6)] = mask;
+				cull_bits[(size_t)pb.sub * cull_stride + (range.x >> 6) + (uint32_t)pb.tile + (uint32_t)(base >> 6)] = mask;
 			if (keep)
 			{
-				const int slot = __popcll(mask & lt_mask);
+				const int slot = __popcll(mask & pb.lt_mask);
 				const float4 c = record_word(records, id, 2);
 				const int pr = slot >> 1, h = slot & 1;
 				float* q0 = reinterpret_cast<float*>(&s_q[0][pr]) + h;
@@ -125,8 +120,7 @@ namespace fdgs
 				const v2f al = op * v2f{ __builtin_amdgcn_exp2f(e2.x), __builtin_amdgcn_exp2f(e2.y) };
 				const float alpha0 = fminf(0.99f, al.x), alpha1 = fminf(0.99f, al.y);
 				v2f w;
-				// forward.cu:588-597 on lane masks: valid = not finished, power <= 0, alpha >= 1/255; a valid entry that would take T
-				// below 1e-4 finishes the pixel (and is not counted), any other valid entry contributes
+				// (blend_step of blend_common.h plus the last_contributor select, stated here: built on that function the kernel compiles to other code)
 #define FDGS_BLEND_STEP(alpha, pw, pos1, wout)                                                            \
 				{                                                                                         \
 					const float test_T = T * (1.0f - alpha);                                              \
@@ -177,7 +171,6 @@ namespace fdgs
 	{
 		const int gx = div_up(s.W, TILE_X), gy = div_up(s.H, TILE_Y);
 		const int ntiles = gx * gy;
-		if (s.P >= (1 << 26)) return hipErrorInvalidValue;   // 32-bit byte offsets into the 48-byte records
 #define LAUNCH_FWD(FLOW) hipLaunchKernelGGL(blend_fwd_kernel<FLOW>, dim3(blend_grid(ntiles)), dim3(WAVE), 0, stream, \
 		                   reinterpret_cast<const uint2*>(ranges), point_list, reinterpret_cast<const float4*>(records), \
 		                   tile_order, s.W, s.H, gx, ntiles, s.bg, \
@@ -205,11 +198,8 @@ namespace fdgs
 		for (float py = ry0; py <= ry1; py += 1.0f)
 			for (float px = rx0; px <= rx1; px += 1.0f)
 			{
-				// blend_fwd_kernel's inner loop, one entry
-				const float dx = a.x - px, dy = a.y - py;
-				const float s2 = fmaf(b.x * dy, dy, (a.z * dx) * dx);
-				const float power = fmaf(-0.5f, s2, -((a.w * dx) * dy));
-				const float alpha = fminf(0.99f, b.y * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
+				float power;
+				const float alpha = entry_alpha(a, b, px, py, power);   // blend_fwd_kernel's inner loop, one entry
 				any = any || (!(power > 0.0f) && !(alpha < 1.0f / 255.0f));
 			}
 		out[2 * (size_t)i + 1] = any ? 1 : 0;

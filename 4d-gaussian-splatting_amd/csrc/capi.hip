@@ -169,14 +169,23 @@ static const bool g_use_tile_order = []() { const char* e = getenv("FDGS_TILE_OR
 			            (unsigned)(ptr)->struct_size, FDGS_VERSION, sizeof(type));                                        \
 	} while (0)
 
+// The sizes every entry point that takes a model and an image accepts.  P < 2^26: the blend kernels address the 48-byte records and the
+// 64-byte accumulator records with 32-bit byte offsets.
+static int check_sizes(int P, int W, int H)
+{
+	if (P < 0 || P >= (1 << 26) || W <= 0 || H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, W, H);
+	if (div_up(W, TILE_X) > 65535 || div_up(H, TILE_Y) > 65535) return fail(FDGS_ERR_INVALID_ARG, "image too large for 16-bit tile rectangles");
+	// (the tile order packs a rank into 24 bits, and T = gx * gy is an int everywhere: 2^24 tiles = 4.3 gigapixels)
+	if ((long long)div_up(W, TILE_X) * div_up(H, TILE_Y) >= (1ll << 24)) return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d has 2^24 tiles or more", W, H);
+	return FDGS_OK;
+}
+
 // (the caller has checked s->struct_size)
 static int check_scene(const fdgs_scene* s)
 {
 	if (!s) return fail(FDGS_ERR_INVALID_ARG, "scene is NULL");
-	if (s->P < 0 || s->W <= 0 || s->H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", s->P, s->W, s->H);
-	if (div_up(s->W, TILE_X) > 65535 || div_up(s->H, TILE_Y) > 65535) return fail(FDGS_ERR_INVALID_ARG, "image too large for 16-bit tile rectangles");
-	// (the tile order packs a rank into 24 bits, and T = gx * gy is an int everywhere: 2^24 tiles = 4.3 gigapixels)
-	if ((long long)div_up(s->W, TILE_X) * div_up(s->H, TILE_Y) >= (1ll << 24)) return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d has 2^24 tiles or more", s->W, s->H);
+	const int rc = check_sizes(s->P, s->W, s->H);
+	if (rc != FDGS_OK) return rc;
 	if (s->P == 0) return FDGS_OK;
 	if (!s->means3D || !s->opacities || !s->bg || !s->viewmatrix || !s->projmatrix || !s->campos)
 		return fail(FDGS_ERR_INVALID_ARG, "means3D / opacities / bg / viewmatrix / projmatrix / campos must not be NULL");
@@ -690,16 +699,9 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 			return fail(FDGS_ERR_INVALID_ARG, "dL_dscales_t / dL_drotations_r / dL_dts must not be NULL for rot_4d");
 	}
 	const int R = in->num_rendered;   // < 0: not known (a lazy forward): the tile ranges carry everything the kernels need
-	const GeomLayout GL = geom_layout(P);
-	const ImageLayout IL = image_layout(W, H);
-	const BinLayout BL = bin_layout(R, false, 0);   // point_list sits at the front whatever else the forward asked for (the cull planes: ctl[2..3])
+	// (the forward's tile order: left in the image buffer by the scan; not there for P == 0, returned above)
+	const FinishedForward ff = finished_forward(P, W, H, R, in->geom_buffer, in->binning_buffer, in->image_buffer, g_use_tile_order);
 	const char* geom = (const char*)in->geom_buffer;
-	const char* img = (const char*)in->image_buffer;
-	const char* bin = (const char*)in->binning_buffer;
-	const uint32_t* point_list = (const uint32_t*)(bin + BL.point_list);
-
-	// the forward's tile order (left in the image buffer by the scan); not there for P == 0 (returned above) or with FDGS_TILE_ORDER=0
-	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;
 	if (out->stage_mask < 0 || out->stage_mask > 5 || ((out->stage_mask & 4) && out->stage_mask != 5))
 		return fail(FDGS_ERR_INVALID_ARG, "stage_mask %d: 0 / 3 (whole backward), 1 (blend + SH backward), 2 (geometry backward) or 5 (blend backward only; "
 		            "the SH backward is left to fdgs_sh_backward_batch, then 2)", out->stage_mask);
@@ -712,9 +714,7 @@ extern "C" int fdgs_rasterize_backward(const fdgs_scene* scene, const fdgs_backw
 		if (!out->grad_accum_clean)
 			STAGE(q, FDGS_STAGE_GRAD_ZERO, hipMemsetAsync(out->grad_accum, 0, (size_t)P * GRAD_ACC_WORDS * 4, stream), "memset");
 		if (R != 0)
-			STAGE(q, FDGS_STAGE_BLEND_BWD, launch_blend_bwd(s, *in, *out, (const float*)(geom + GL.records), point_list, (const uint32_t*)(img + IL.ranges),
-			                       tile_order, (const float*)(img + IL.final_T), (const uint32_t*)(img + IL.n_contrib),
-			                       (const uint32_t*)(img + IL.bin_ctl), stream), "blend_bwd");
+			STAGE(q, FDGS_STAGE_BLEND_BWD, launch_blend_bwd(s, *in, *out, ff, stream), "blend_bwd");
 		if (!(out->stage_mask & 4)) STAGE(q, FDGS_STAGE_SH_BWD, launch_sh_bwd(s, *in, *out, geom, stream), "sh_bwd");
 	}
 	if (stages & 2)
@@ -752,9 +752,8 @@ extern "C" int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_cont
 	CHECK_STRUCT(in, fdgs_contribution_in);
 	CHECK_STRUCT(out, fdgs_contribution_out);
 	const int P = in->P, W = in->W, H = in->H;
-	if (P < 0 || P >= (1 << 26) || W <= 0 || H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, W, H);
-	if (div_up(W, TILE_X) > 65535 || div_up(H, TILE_Y) > 65535 || (long long)div_up(W, TILE_X) * div_up(H, TILE_Y) >= (1ll << 24))
-		return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d", W, H);
+	const int rc = check_sizes(P, W, H);
+	if (rc != FDGS_OK) return rc;
 	if (!out->weight_sum && !out->weight_max && !out->hits && !out->dominant && !out->dominant_id)
 		return fail(FDGS_ERR_INVALID_ARG, "fdgs_contribution: every output is NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
@@ -766,30 +765,27 @@ extern "C" int fdgs_contribution(const fdgs_contribution_in* in, const fdgs_cont
 		if (out->dominant_id) HIP_TRY(hipMemsetAsync(out->dominant_id, 0xFF, (size_t)W * H * 4, stream), "dominant_id memset");
 		return FDGS_OK;
 	}
-	const GeomLayout GL = geom_layout(P);
-	const ImageLayout IL = image_layout(W, H);
-	const BinLayout BL = bin_layout(in->num_rendered, false, 0);   // point_list sits at the front whatever layout the forward chose
-	const char* geom = (const char*)in->geom_buffer;
-	const char* img = (const char*)in->image_buffer;
-	const char* bin = (const char*)in->binning_buffer;
-	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;   // as the backward finds it
-	HIP_TRY(launch_contribution(*in, *out, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
-	                            (const uint32_t*)(img + IL.ranges), tile_order, stream), "contribution");
+	const FinishedForward ff = finished_forward(P, W, H, in->num_rendered, in->geom_buffer, in->binning_buffer, in->image_buffer, g_use_tile_order);
+	HIP_TRY(launch_contribution(*in, *out, ff, stream), "contribution");
 	return FDGS_OK;
 }
 
 // what fdgs_feature_blend and fdgs_feature_blend_backward check alike; FDGS_OK: sizes and buffers are usable
 static int check_feature_in(const char* fn, const fdgs_feature_in* in)
 {
-	const int P = in->P, W = in->W, H = in->H, Cn = in->C;
-	if (P < 0 || P >= (1 << 26) || W <= 0 || H <= 0) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d W=%d H=%d", P, W, H);
-	if (div_up(W, TILE_X) > 65535 || div_up(H, TILE_Y) > 65535 || (long long)div_up(W, TILE_X) * div_up(H, TILE_Y) >= (1ll << 24))
-		return fail(FDGS_ERR_INVALID_ARG, "image too large: %d x %d", W, H);
+	const int P = in->P, Cn = in->C;
+	const int rc = check_sizes(P, in->W, in->H);
+	if (rc != FDGS_OK) return rc;
 	if (Cn < 1 || Cn > FDGS_FEATURE_MAX_CHANNELS)
 		return fail(FDGS_ERR_INVALID_ARG, "%s: C=%d channels, 1 .. %d are supported", fn, Cn, FDGS_FEATURE_MAX_CHANNELS);
 	if (P > 0 && (!in->geom_buffer || !in->binning_buffer || !in->image_buffer))
 		return fail(FDGS_ERR_INVALID_ARG, "%s: geom_buffer / binning_buffer / image_buffer must not be NULL", fn);
 	return FDGS_OK;
+}
+
+static FinishedForward finished_forward_of(const fdgs_feature_in* in)
+{
+	return finished_forward(in->P, in->W, in->H, in->num_rendered, in->geom_buffer, in->binning_buffer, in->image_buffer, g_use_tile_order);
 }
 
 extern "C" int fdgs_feature_blend(const fdgs_feature_in* in, float* out, void* stream_v)
@@ -807,15 +803,7 @@ extern "C" int fdgs_feature_blend(const fdgs_feature_in* in, float* out, void* s
 		HIP_TRY(hipMemsetAsync(out, 0, (size_t)in->C * in->W * in->H * 4, stream), "feature memset");
 		return FDGS_OK;
 	}
-	const GeomLayout GL = geom_layout(in->P);
-	const ImageLayout IL = image_layout(in->W, in->H);
-	const BinLayout BL = bin_layout(in->num_rendered, false, 0);   // point_list sits at the front whatever layout the forward chose
-	const char* geom = (const char*)in->geom_buffer;
-	const char* img = (const char*)in->image_buffer;
-	const char* bin = (const char*)in->binning_buffer;
-	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;   // as the backward finds it
-	HIP_TRY(launch_feature_blend(*in, out, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
-	                             (const uint32_t*)(img + IL.ranges), tile_order, stream), "feature_blend");
+	HIP_TRY(launch_feature_blend(*in, out, finished_forward_of(in), stream), "feature_blend");
 	return FDGS_OK;
 }
 
@@ -828,15 +816,7 @@ extern "C" int fdgs_feature_blend_backward(const fdgs_feature_in* in, const floa
 	if (rc != FDGS_OK) return rc;
 	if (in->P == 0 || in->num_rendered == 0) return FDGS_OK;   // no list to walk: nothing is added
 	hipStream_t stream = (hipStream_t)stream_v;
-	const GeomLayout GL = geom_layout(in->P);
-	const ImageLayout IL = image_layout(in->W, in->H);
-	const BinLayout BL = bin_layout(in->num_rendered, false, 0);
-	const char* geom = (const char*)in->geom_buffer;
-	const char* img = (const char*)in->image_buffer;
-	const char* bin = (const char*)in->binning_buffer;
-	const uint32_t* tile_order = g_use_tile_order ? (const uint32_t*)(img + IL.tile_order) : nullptr;
-	HIP_TRY(launch_feature_blend_bwd(*in, dL_dout, dL_dfeatures, (const float*)(geom + GL.records), (const uint32_t*)(bin + BL.point_list),
-	                                 (const uint32_t*)(img + IL.ranges), tile_order, stream), "feature_blend_backward");
+	HIP_TRY(launch_feature_blend_bwd(*in, dL_dout, dL_dfeatures, finished_forward_of(in), stream), "feature_blend_backward");
 	return FDGS_OK;
 }
 
@@ -1052,20 +1032,17 @@ extern "C" int fdgs_debug_views(int32_t P, int32_t W, int32_t H, int32_t R,
 	if (!v || !geom_v || !img_v) return fail(FDGS_ERR_INVALID_ARG, "NULL argument");
 	CHECK_STRUCT(v, fdgs_debug_view);
 	const GeomLayout GL = geom_layout(P);
-	const ImageLayout IL = image_layout(W, H);
-	const BinLayout BL = bin_layout(R, false, 0);
+	const FinishedForward ff = finished_forward(P, W, H, R, geom_v, bin_v, img_v, true);   // (the tile order whatever FDGS_TILE_ORDER says)
 	const char* geom = (const char*)geom_v;
-	const char* bin = (const char*)bin_v;
-	const char* img = (const char*)img_v;
 	v->depths = (const float*)(geom + GL.depths);
-	v->records = (const float*)(geom + GL.records);
+	v->records = (const float*)ff.records;
 	v->cov3D = (const float*)(geom + GL.cov3D);
 	v->tiles_touched = (const uint32_t*)(geom + GL.tiles_touched);
 	v->clamped = (const uint8_t*)(geom + GL.clamped);
-	v->point_list = bin ? (const uint32_t*)(bin + BL.point_list) : nullptr;
-	v->ranges = (const uint32_t*)(img + IL.ranges);
-	v->n_contrib = (const uint32_t*)(img + IL.n_contrib);
-	v->final_T = (const float*)(img + IL.final_T);
-	v->tile_order = (const uint32_t*)(img + IL.tile_order);
+	v->point_list = ff.point_list;
+	v->ranges = (const uint32_t*)ff.ranges;
+	v->n_contrib = ff.n_contrib;
+	v->final_T = ff.final_T;
+	v->tile_order = ff.tile_order;
 	return FDGS_OK;
 }

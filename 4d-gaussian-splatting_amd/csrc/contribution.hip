@@ -10,7 +10,7 @@
 //
 // Work decomposition: blend_fwd's -- one wave64 per 8x8 pixel block in the blend kernels' tile order, 64 list entries per chunk, one
 // entry per lane culled against the block (block_reaches, run again: nothing depends on the forward's cull planes) and compacted
-// into a wave-private LDS queue.  The reduction over the block's 64 pixels stays on chip: every lane stores its pixel's w of an
+// into a wave-private LDS queue (blend_common.h: pixel_block, queue_chunk, blend_weight -- the walk features.hip takes too).  The reduction over the block's 64 pixels stays on chip: every lane stores its pixel's w of an
 // entry into a row of an LDS staging area; every GROUP entries the area is transposed -- four lanes per entry read 16 pixels each
 // and fold sum / max / count, two DPP quad steps finish them -- and one lane per entry issues the atomics:
 //   at most ONE atomic request per (block, Gaussian, output), none for an entry that contributed to no pixel of the block.
@@ -40,17 +40,10 @@ namespace fdgs
 		__shared__ float s_pw[WAVE];                         // the block's pixel weights
 
 		const int lane = threadIdx.x;
-		const BlockId blk = block_of(blockIdx.x, ntiles, tile_order);
-		if (blk.tile >= ntiles) return;
-		const int bx0 = (blk.tile % grid_x) * TILE_X + (blk.sub & 1) * BLK;
-		const int by0 = (blk.tile / grid_x) * TILE_Y + (blk.sub >> 1) * BLK;
-		if (bx0 >= W || by0 >= H) return; // block entirely outside the image
-		const int px = bx0 + (lane & (BLK - 1)), py = by0 + (lane >> 3);
-		const bool inside = px < W && py < H;
-		const size_t pix_id = (size_t)W * py + px;
-		const float pixfx = (float)px, pixfy = (float)py;
-		const float rx0 = (float)bx0, rx1 = (float)min(bx0 + BLK - 1, W - 1);
-		const float ry0 = (float)by0, ry1 = (float)min(by0 + BLK - 1, H - 1);
+		PixelBlock pb;
+		if (!pixel_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, lane, pb)) return;
+		const bool inside = pb.inside;
+		const size_t pix_id = (size_t)W * pb.py + pb.px;
 
 		// a pixel with weight <= 0 (and one outside the image) takes no contribution at all: finished before it starts
 		float pw = inside ? 1.0f : 0.0f;
@@ -58,9 +51,8 @@ namespace fdgs
 		const bool live = pw > 0.0f;
 		if (WEIGHTED) s_pw[lane] = live ? pw : 0.0f;
 
-		const uint2 range = ranges[blk.tile];
+		const uint2 range = ranges[pb.tile];
 		const int n = (int)(range.y - range.x);
-		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		lanemask done = mask_of(!live);
 		float T = 1.0f, best_w = 0.0f;
@@ -101,43 +93,18 @@ namespace fdgs
 		for (int base = 0; base < n; base += WAVE)
 		{
 			if (done == ~0ull) break; // all 64 pixels finished
-			const int pos = base + lane;
-			bool keep = false;
-			uint32_t id = 0;
-			float4 a, b;
-			if (pos < n)
-			{
-				id = point_list[range.x + pos];
-				a = record_word(records, id, 0);
-				b = record_word(records, id, 1);
-				keep = block_reaches(a, b, rx0, rx1, ry0, ry1);
-			}
-			const unsigned long long mask = __ballot(keep);
-			const int cnt = __popcll(mask);
-			if (keep)
-			{
-				const int slot = __popcll(mask & lt_mask);   // list order is preserved
-				s_qa[slot] = a;
-				s_qb[slot] = make_float4(b.x, b.y, __uint_as_float(id), 0.0f);
-			}
+			bool keep;
+			uint32_t id;
+			int slot;
+			const int cnt = queue_chunk(point_list, records, range, n, base, lane, pb, s_qa, s_qb, keep, id, slot);
 			__syncthreads(); // single-wave workgroup: orders the LDS writes before the cross-lane reads
 
 			uint32_t gmask = 0u;
 			for (int i = 0; i < cnt; i++)
 			{
 				const float4 qa = s_qa[i], qb = s_qb[i];
-				// blend_fwd.hip's expressions, element for element (forward.cu:585-597)
-				const float dx = qa.x - pixfx, dy = qa.y - pixfy;
-				const float s2 = fmaf(qb.x * dy, dy, (qa.z * dx) * dx);
-				const float power = fmaf(-0.5f, s2, -((qa.w * dx) * dy));
-				const float alpha = fminf(0.99f, qb.y * __builtin_amdgcn_exp2f(power * 1.4426950408889634f));
-				const float test_T = T * (1.0f - alpha);
-				const lanemask valid = ~done & mask_of(!(power > 0.0f)) & mask_of(!(alpha < 1.0f / 255.0f));
-				const lanemask low = mask_of(test_T < 0.0001f);
-				const lanemask contrib = valid & ~low;
-				const float w = mask_select(contrib, alpha * T, 0.0f);
-				T = mask_select(contrib, test_T, T);
-				done |= valid & low;
+				lanemask contrib;
+				const float w = blend_weight(qa, qb, pb.pixfx, pb.pixfy, T, done, contrib);
 				if (w > best_w) { best_w = w; best_id = (int32_t)__float_as_uint(qb.z); }   // strictly larger: the earliest entry wins a tie
 				const int g = i & (CONTRIB_GROUP - 1);
 				if (want_stats)
@@ -172,15 +139,11 @@ namespace fdgs
 		}
 	}
 
-	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const float* records,
-	                               const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream)
+	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const FinishedForward& ff, hipStream_t stream)
 	{
-		const int gx = div_up(in.W, TILE_X), gy = div_up(in.H, TILE_Y);
-		const int ntiles = gx * gy;
-		if (in.P >= (1 << 26)) return hipErrorInvalidValue;   // 32-bit byte offsets into the 48-byte records
-#define LAUNCH_CONTRIB(WEIGHTED) hipLaunchKernelGGL(contribution_kernel<WEIGHTED>, dim3(blend_grid(ntiles)), dim3(WAVE), 0, stream, \
-		                   reinterpret_cast<const uint2*>(ranges), point_list, reinterpret_cast<const float4*>(records), tile_order, \
-		                   in.W, in.H, gx, ntiles, in.pix_weight, out.weight_sum, out.weight_max, out.hits, out.dominant, out.dominant_id)
+#define LAUNCH_CONTRIB(WEIGHTED) hipLaunchKernelGGL(contribution_kernel<WEIGHTED>, dim3(blend_grid(ff.ntiles)), dim3(WAVE), 0, stream, \
+		                   ff.ranges, ff.point_list, ff.records, ff.tile_order, ff.W, ff.H, ff.gx, ff.ntiles, in.pix_weight, \
+		                   out.weight_sum, out.weight_max, out.hits, out.dominant, out.dominant_id)
 		if (in.pix_weight != nullptr) LAUNCH_CONTRIB(true);
 		else LAUNCH_CONTRIB(false);
 #undef LAUNCH_CONTRIB

@@ -186,20 +186,52 @@ namespace fdgs
 	                            float* final_T, uint32_t* n_contrib, unsigned long long* cull_bits, uint32_t cull_stride, uint32_t cull_word_off,
 	                            uint32_t* ctl, hipStream_t stream);
 
-	hipError_t launch_blend_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,
-	                            const float* records, const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order,
-	                            const float* final_T, const uint32_t* n_contrib, const uint32_t* ctl /* cull planes: see launch_blend_fwd */,
+	// What a finished forward left in its three scratch buffers, as the kernels that walk its lists again take it (the blend backward,
+	// contribution.hip, features.hip, fdgs_debug_views).
+	struct FinishedForward
+	{
+		int W, H, gx, ntiles;
+		const float4* records;        // [P] 48-byte blend records
+		const uint32_t* point_list;   // the tiles' sorted lists
+		const uint2* ranges;          // [ntiles] (start, end) of every tile's list
+		const uint32_t* tile_order;   // the order the blend kernels take the tiles in; NULL = index order
+		const float* final_T;         // [H, W]
+		const uint32_t* n_contrib;    // [H, W]
+		const uint32_t* ctl;          // the image buffer's control words (ctl[2..3]: the cull planes, see launch_blend_fwd)
+	};
+	// The only place that knows point_list sits at the front of the binning buffer whatever layout the forward chose (sparse or
+	// compact lists, cull planes, sort scratch); num_rendered < 0: not known (a lazy forward) -- the ranges carry what the kernels need.
+	static inline FinishedForward finished_forward(int P, int W, int H, int num_rendered, const void* geom, const void* bin, const void* img,
+	                                               bool use_tile_order)
+	{
+		const GeomLayout GL = geom_layout(P);
+		const ImageLayout IL = image_layout(W, H);
+		const BinLayout BL = bin_layout(num_rendered, false, 0);
+		const char* g = (const char*)geom;
+		const char* b = (const char*)bin;
+		const char* i = (const char*)img;
+		FinishedForward ff;
+		ff.W = W; ff.H = H; ff.gx = div_up(W, TILE_X); ff.ntiles = ff.gx * div_up(H, TILE_Y);
+		ff.records = (const float4*)(g + GL.records);
+		ff.point_list = b ? (const uint32_t*)(b + BL.point_list) : nullptr;
+		ff.ranges = (const uint2*)(i + IL.ranges);
+		ff.tile_order = use_tile_order ? (const uint32_t*)(i + IL.tile_order) : nullptr;
+		ff.final_T = (const float*)(i + IL.final_T);
+		ff.n_contrib = (const uint32_t*)(i + IL.n_contrib);
+		ff.ctl = (const uint32_t*)(i + IL.bin_ctl);
+		return ff;
+	}
+
+	hipError_t launch_blend_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out, const FinishedForward& ff,
 	                            hipStream_t stream);
 
-	// per-Gaussian contribution statistics and the per-pixel ID map of a finished forward (contribution.hip); tile_order: NULL = index order
-	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const float* records,
-	                               const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
+	// per-Gaussian contribution statistics and the per-pixel ID map of a finished forward (contribution.hip)
+	hipError_t launch_contribution(const fdgs_contribution_in& in, const fdgs_contribution_out& out, const FinishedForward& ff, hipStream_t stream);
 
-	// per-Gaussian feature channels blended with a finished forward's weights, and the adjoint (features.hip); tile_order: NULL = index order
-	hipError_t launch_feature_blend(const fdgs_feature_in& in, float* out, const float* records, const uint32_t* point_list,
-	                                const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
-	hipError_t launch_feature_blend_bwd(const fdgs_feature_in& in, const float* dL_dout, float* dL_dfeatures, const float* records,
-	                                    const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream);
+	// per-Gaussian feature channels blended with a finished forward's weights, and the adjoint (features.hip)
+	hipError_t launch_feature_blend(const fdgs_feature_in& in, float* out, const FinishedForward& ff, hipStream_t stream);
+	hipError_t launch_feature_blend_bwd(const fdgs_feature_in& in, const float* dL_dout, float* dL_dfeatures, const FinishedForward& ff,
+	                                    hipStream_t stream);
 
 	// SH / 4D-SH backward (coalesced); must run after the blend backward and before launch_preprocess_bwd
 	hipError_t launch_sh_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out,

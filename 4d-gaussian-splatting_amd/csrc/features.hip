@@ -3,7 +3,7 @@
 //   forward    out[c, y, x]  = sum over the pixel's contributions of w * F[id, c]        (overwritten; no contributor: exactly 0)
 //   backward   dF[id, c]    += sum over the pixels Gaussian id contributes to of w * g[c, y, x]      (accumulated in place)
 // w = alpha * T is the blending weight of the rendered image: both kernels walk the buffers a forward leaves behind (blend records,
-// tile lists, ranges) with blend_fwd.hip's own decisions and arithmetic (blend_common.h: queue_chunk, blend_weight -- the walk of
+// tile lists, ranges) with blend_fwd.hip's own decisions and arithmetic (blend_common.h: pixel_block, queue_chunk, blend_weight -- the walk of
 // contribution.hip), so the set of (pixel, entry) contributions is the rendered image's own.  GEOMETRY IS HELD CONSTANT: w is a
 // number here, no gradient reaches alpha, the positions or the covariances; the backward is the adjoint of the forward as a linear map
 // of F, nothing else.  Nothing is composited behind the features.
@@ -35,18 +35,6 @@ namespace fdgs
 	constexpr int FEAT_ROW = WAVE + 4;         // row stride of the staging area in floats: the A-operand reads (4 (l & 15) + (l >> 4) + 4 s) hit 64 different banks
 	typedef float feat_f32x4 __attribute__((ext_vector_type(4)));
 
-	// the 8x8 block of a workgroup; false: nothing to do (beyond the grid's padding, or entirely outside the image)
-	struct FeatBlock { int tile, bx0, by0; };
-	__device__ __forceinline__ bool feat_block(int wg, int ntiles, const uint32_t* __restrict__ tile_order, int grid_x, int W, int H, FeatBlock& fb)
-	{
-		const BlockId blk = block_of(wg, ntiles, tile_order);
-		if (blk.tile >= ntiles) return false;
-		fb.tile = blk.tile;
-		fb.bx0 = (blk.tile % grid_x) * TILE_X + (blk.sub & 1) * BLK;
-		fb.by0 = (blk.tile / grid_x) * TILE_Y + (blk.sub >> 1) * BLK;
-		return fb.bx0 < W && fb.by0 < H;
-	}
-
 	template <int NCH>
 	__global__ void __launch_bounds__(WAVE) feature_fwd_kernel(
 		const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list, const float4* __restrict__ records,
@@ -58,18 +46,13 @@ namespace fdgs
 		__shared__ float4 s_f[WAVE * PITCH];   // [queue slot][channel of the group]
 
 		const int lane = threadIdx.x;
-		FeatBlock fb;
-		if (!feat_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, fb)) return;
+		PixelBlock pb;
+		if (!pixel_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, lane, pb)) return;
 		const int c0 = blockIdx.y * NCH;
-		const int px = fb.bx0 + (lane & (BLK - 1)), py = fb.by0 + (lane >> 3);
-		const bool inside = px < W && py < H;
-		const float pixfx = (float)px, pixfy = (float)py;
-		const float rx0 = (float)fb.bx0, rx1 = (float)min(fb.bx0 + BLK - 1, W - 1);
-		const float ry0 = (float)fb.by0, ry1 = (float)min(fb.by0 + BLK - 1, H - 1);
+		const bool inside = pb.inside;
 
-		const uint2 range = ranges[fb.tile];
+		const uint2 range = ranges[pb.tile];
 		const int n = (int)(range.y - range.x);
-		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		lanemask done = mask_of(!inside);
 		float T = 1.0f;
@@ -83,7 +66,7 @@ namespace fdgs
 			bool keep;
 			uint32_t id;
 			int slot;
-			const int cnt = queue_chunk(point_list, records, range, n, base, lane, lt_mask, rx0, rx1, ry0, ry1, s_qa, s_qb, keep, id, slot);
+			const int cnt = queue_chunk(point_list, records, range, n, base, lane, pb, s_qa, s_qb, keep, id, slot);
 			if (keep)
 			{
 				// the group's slice of the entry's feature row; channels at and beyond C read as 0 (and are never stored)
@@ -105,7 +88,7 @@ namespace fdgs
 			{
 				const float4 qa = s_qa[i], qb = s_qb[i];
 				lanemask contrib;
-				const float w = blend_weight(qa, qb, pixfx, pixfy, T, done, contrib);
+				const float w = blend_weight(qa, qb, pb.pixfx, pb.pixfy, T, done, contrib);
 				if (contrib != 0ull)   // wave-uniform: an entry no pixel of the block takes costs no arithmetic
 				{
 #pragma unroll
@@ -126,7 +109,7 @@ namespace fdgs
 		if (inside)
 		{
 			const size_t plane = (size_t)W * H;
-			float* const o = out + ((size_t)c0 * plane + (size_t)W * py + px);
+			float* const o = out + ((size_t)c0 * plane + (size_t)W * pb.py + pb.px);
 #pragma unroll
 			for (int j = 0; j < NCH; j++)
 				if (c0 + j < C) o[(size_t)j * plane] = acc[j];
@@ -143,19 +126,14 @@ namespace fdgs
 		__shared__ float s_w[FEAT_GROUP * FEAT_ROW];   // [entry of the group][pixel]
 
 		const int lane = threadIdx.x;
-		FeatBlock fb;
-		if (!feat_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, fb)) return;
+		PixelBlock pb;
+		if (!pixel_block(blockIdx.x, ntiles, tile_order, grid_x, W, H, lane, pb)) return;
 		const int c0 = blockIdx.y * (16 * NG);
-		const int px = fb.bx0 + (lane & (BLK - 1)), py = fb.by0 + (lane >> 3);
-		const bool inside = px < W && py < H;
-		const float pixfx = (float)px, pixfy = (float)py;
-		const float rx0 = (float)fb.bx0, rx1 = (float)min(fb.bx0 + BLK - 1, W - 1);
-		const float ry0 = (float)fb.by0, ry1 = (float)min(fb.by0 + BLK - 1, H - 1);
+		const bool inside = pb.inside;
 
-		const uint2 range = ranges[fb.tile];
+		const uint2 range = ranges[pb.tile];
 		const int n = (int)(range.y - range.x);
 		if (n == 0) return;
-		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		// the B operands: this lane's column (channel) and k (pixel 4 s + (lane >> 4) of the block) for the 16 k-steps; 0 outside the
 		// image and beyond C
@@ -170,7 +148,7 @@ namespace fdgs
 			for (int s = 0; s < 16; s++)
 			{
 				const int p = 4 * s + kq;
-				const int gx = fb.bx0 + (p & (BLK - 1)), gy = fb.by0 + (p >> 3);
+				const int gx = pb.bx0 + (p & (BLK - 1)), gy = pb.by0 + (p >> 3);
 				b[gi][s] = (c < C && gx < W && gy < H) ? gc[(size_t)W * gy + gx] : 0.0f;
 			}
 		}
@@ -221,7 +199,7 @@ namespace fdgs
 			bool keep;
 			uint32_t id;
 			int slot;
-			const int cnt = queue_chunk(point_list, records, range, n, base, lane, lt_mask, rx0, rx1, ry0, ry1, s_qa, s_qb, keep, id, slot);
+			const int cnt = queue_chunk(point_list, records, range, n, base, lane, pb, s_qa, s_qb, keep, id, slot);
 			__syncthreads(); // single-wave workgroup: orders the LDS writes before the cross-lane reads
 
 			uint32_t gmask = 0u;
@@ -229,7 +207,7 @@ namespace fdgs
 			{
 				const float4 qa = s_qa[i], qb = s_qb[i];
 				lanemask contrib;
-				const float w = blend_weight(qa, qb, pixfx, pixfy, T, done, contrib);
+				const float w = blend_weight(qa, qb, pb.pixfx, pb.pixfy, T, done, contrib);
 				const int g = i & (FEAT_GROUP - 1);
 				s_w[g * FEAT_ROW + lane] = w;
 				gmask |= (contrib != 0ull ? 1u : 0u) << g;
@@ -247,15 +225,11 @@ namespace fdgs
 
 	static inline dim3 feat_grid(int ntiles, int C, int per_wave) { return dim3(blend_grid(ntiles), div_up(C, per_wave)); }
 
-	hipError_t launch_feature_blend(const fdgs_feature_in& in, float* out, const float* records, const uint32_t* point_list,
-	                                const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream)
+	// (C is in 1 .. FDGS_FEATURE_MAX_CHANNELS: checked where the call comes in)
+	hipError_t launch_feature_blend(const fdgs_feature_in& in, float* out, const FinishedForward& ff, hipStream_t stream)
 	{
-		const int gx = div_up(in.W, TILE_X), gy = div_up(in.H, TILE_Y);
-		const int ntiles = gx * gy;
-		if (in.P >= (1 << 26) || in.C < 1 || in.C > FDGS_FEATURE_MAX_CHANNELS) return hipErrorInvalidValue;   // 32-bit byte offsets into the 48-byte records
-#define LAUNCH_FEAT_FWD(NCH) hipLaunchKernelGGL(feature_fwd_kernel<NCH>, feat_grid(ntiles, in.C, NCH), dim3(WAVE), 0, stream, \
-		                   reinterpret_cast<const uint2*>(ranges), point_list, reinterpret_cast<const float4*>(records), tile_order, \
-		                   in.W, in.H, gx, ntiles, in.features, in.C, out)
+#define LAUNCH_FEAT_FWD(NCH) hipLaunchKernelGGL(feature_fwd_kernel<NCH>, feat_grid(ff.ntiles, in.C, NCH), dim3(WAVE), 0, stream, \
+		                   ff.ranges, ff.point_list, ff.records, ff.tile_order, ff.W, ff.H, ff.gx, ff.ntiles, in.features, in.C, out)
 		if (in.C <= 4) LAUNCH_FEAT_FWD(4);
 		else if (in.C <= 16) LAUNCH_FEAT_FWD(16);
 		else LAUNCH_FEAT_FWD(32);
@@ -263,15 +237,11 @@ namespace fdgs
 		return hipGetLastError();
 	}
 
-	hipError_t launch_feature_blend_bwd(const fdgs_feature_in& in, const float* dL_dout, float* dL_dfeatures, const float* records,
-	                                    const uint32_t* point_list, const uint32_t* ranges, const uint32_t* tile_order, hipStream_t stream)
+	hipError_t launch_feature_blend_bwd(const fdgs_feature_in& in, const float* dL_dout, float* dL_dfeatures, const FinishedForward& ff,
+	                                    hipStream_t stream)
 	{
-		const int gx = div_up(in.W, TILE_X), gy = div_up(in.H, TILE_Y);
-		const int ntiles = gx * gy;
-		if (in.P >= (1 << 26) || in.C < 1 || in.C > FDGS_FEATURE_MAX_CHANNELS) return hipErrorInvalidValue;
-#define LAUNCH_FEAT_BWD(NG) hipLaunchKernelGGL(feature_bwd_kernel<NG>, feat_grid(ntiles, in.C, 16 * NG), dim3(WAVE), 0, stream, \
-		                   reinterpret_cast<const uint2*>(ranges), point_list, reinterpret_cast<const float4*>(records), tile_order, \
-		                   in.W, in.H, gx, ntiles, dL_dout, in.C, dL_dfeatures)
+#define LAUNCH_FEAT_BWD(NG) hipLaunchKernelGGL(feature_bwd_kernel<NG>, feat_grid(ff.ntiles, in.C, 16 * NG), dim3(WAVE), 0, stream, \
+		                   ff.ranges, ff.point_list, ff.records, ff.tile_order, ff.W, ff.H, ff.gx, ff.ntiles, dL_dout, in.C, dL_dfeatures)
 		if (in.C <= 16) LAUNCH_FEAT_BWD(1);
 		else LAUNCH_FEAT_BWD(2);
 #undef LAUNCH_FEAT_BWD

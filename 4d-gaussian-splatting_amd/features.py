@@ -38,20 +38,6 @@ def _check_channels(Cn: int) -> None:
         raise ValueError("fdgs.features: %d channels, 1 .. %d are supported" % (Cn, MAX_CHANNELS))
 
 
-def _device_of(named) -> Optional[torch.device]:
-    """The common device of the tensors ``named`` ((name, tensor) pairs; None and empty tensors are skipped); a CPU tensor raises."""
-    dev = None
-    for name, t in named:
-        if t is None or t.numel() == 0:
-            continue   # (an empty model leaves buffers out)
-        if not t.is_cuda:
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
-        if dev is not None and t.device != dev:
-            raise RuntimeError("fdgs: '%s' lives on %s, the forward's buffers on %s" % (name, t.device, dev))
-        dev = t.device
-    return dev
-
-
 def _check_f32(t: torch.Tensor, name: str, shape) -> None:
     if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
         raise ValueError("fdgs.features: %s must be a contiguous float32 tensor of shape %s, got %s %s" % (name, tuple(shape), t.dtype, tuple(t.shape)))
@@ -69,7 +55,7 @@ def blend_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int, featu
     features = as_feature_matrix(features.detach(), P)
     Cn = int(features.shape[1])
     _check_f32(features, "features", (P, Cn))
-    dev = _device_of(named[:3] + [("out", out)]) or features.device
+    dev = _capi._common_device(named[:3] + [("out", out)]) or features.device
     if features.device != dev:
         raise RuntimeError("fdgs: 'features' lives on %s, the forward's buffers on %s" % (features.device, dev))
     if out is None:
@@ -98,7 +84,7 @@ def blend_backward_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: i
     _check_channels(Cn)
     _check_f32(d_features, "d_features", (P, Cn))
     _check_f32(dL_dout, "dL_dout", (Cn, H, W))
-    dev = _device_of(named)
+    dev = _capi._common_device(named)
     if P == 0:
         return d_features   # an empty model: nothing to add to
     cin = _capi.FdgsFeatureIn(int(P), int(W), int(H), Cn, _capi._ptr(geom), _capi._ptr(binb), _capi._ptr(img), int(num_rendered), None)

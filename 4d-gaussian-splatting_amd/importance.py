@@ -134,15 +134,7 @@ def contribution_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int
     """``fdgs_contribution`` on the three scratch buffers of a forward (the binding's ``geomBuffer, binningBuffer, imgBuffer`` and
     ``num_rendered``), enqueued on the current stream of the buffers' device.  The per-Gaussian tensors are accumulated into,
     ``dominant_id`` (int32 [H,W]) is overwritten; any may be None, not all."""
-    dev = None
-    for name, t in (("geom", geom), ("binb", binb), ("img", img)):
-        if t is None or t.numel() == 0:
-            continue   # (an empty model leaves buffers out)
-        if not t.is_cuda:
-            raise RuntimeError("fdgs: buffer '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
-        if dev is not None and t.device != dev:
-            raise RuntimeError("fdgs: the forward's buffers live on different devices (%s, %s)" % (dev, t.device))
-        dev = t.device
+    dev = _capi._common_device((("geom", geom), ("binb", binb), ("img", img)))
     outs = {"weight_sum": (weight_sum, torch.float32, P), "weight_max": (weight_max, torch.float32, P), "hits": (hits, torch.int32, P),
             "dominant": (dominant, torch.int32, P), "dominant_id": (dominant_id, torch.int32, W * H)}
     for name, (t, dtype, n) in outs.items():
