@@ -93,6 +93,19 @@ class FdgsSliceOut(_Sized):
                 ("shs", _fp), ("scales", _fp), ("rotations", _fp), ("n_live", _fp)]
 
 
+class FdgsTransformIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("M", C.c_int32), ("gaussian_dim", C.c_int32), ("rot_4d", C.c_int32),
+                ("means3D", _fp), ("ts", _fp), ("scales", _fp), ("scales_t", _fp), ("rotations", _fp), ("rotations_r", _fp), ("shs", _fp),
+                ("rotation", C.c_double * 9), ("translation", C.c_double * 3), ("scale", C.c_double), ("time_scale", C.c_double),
+                ("time_shift", C.c_double), ("quat", C.c_double * 4), ("iso_u", C.c_double * 4), ("iso_v", C.c_double * 4),
+                ("log_scale", C.c_double), ("log_time_scale", C.c_double), ("sh_rot", C.c_float * 83)]
+
+
+class FdgsTransformOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("means3D", _fp), ("ts", _fp), ("scales", _fp), ("scales_t", _fp), ("rotations", _fp),
+                ("rotations_r", _fp), ("shs", _fp)]
+
+
 class FdgsFlowIn(_Sized):
     _fields_ = [("struct_size", C.c_uint32), ("P", C.c_int32), ("W", C.c_int32), ("H", C.c_int32), ("means3D", _fp), ("ts", _fp),
                 ("scales", _fp), ("scales_t", _fp), ("rotations", _fp), ("rotations_r", _fp), ("viewmatrix", _fp), ("projmatrix", _fp),
@@ -147,6 +160,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_debug_frames_resize_path", "fdgs_frames_composite", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
             "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
+            "fdgs_model_transform",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
@@ -326,6 +340,8 @@ def _load():
     lib.fdgs_quantize_columns.restype = C.c_int
     lib.fdgs_compact_decode.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
     lib.fdgs_compact_decode.restype = C.c_int
+    lib.fdgs_model_transform.argtypes = [C.POINTER(FdgsTransformIn), C.POINTER(FdgsTransformOut), C.c_void_p]
+    lib.fdgs_model_transform.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

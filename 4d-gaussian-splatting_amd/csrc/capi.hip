@@ -245,6 +245,31 @@ extern "C" int fdgs_time_slice(const fdgs_slice_in* in, const fdgs_slice_out* ou
 	return FDGS_OK;
 }
 
+extern "C" int fdgs_model_transform(const fdgs_transform_in* in, const fdgs_transform_out* out, void* stream)
+{
+	if (!in || !out) return fail(FDGS_ERR_INVALID_ARG, "in / out must not be NULL");
+	CHECK_STRUCT(in, fdgs_transform_in);
+	CHECK_STRUCT(out, fdgs_transform_out);
+	if (in->P < 0 || in->P >= (1 << 26)) return fail(FDGS_ERR_INVALID_ARG, "bad sizes P=%d", in->P);
+	if (in->gaussian_dim != 3 && in->gaussian_dim != 4) return fail(FDGS_ERR_INVALID_ARG, "gaussian_dim=%d outside {3, 4}", in->gaussian_dim);
+	if (in->rot_4d && in->gaussian_dim != 4) return fail(FDGS_ERR_INVALID_ARG, "rot_4d needs gaussian_dim == 4");
+	if (!(in->scale > 0.0) || !(in->time_scale > 0.0) || !isfinite(in->scale) || !isfinite(in->time_scale))
+		return fail(FDGS_ERR_INVALID_ARG, "scale=%g and time_scale=%g must be positive and finite", in->scale, in->time_scale);
+	if ((in->shs == nullptr) != (out->shs == nullptr)) return fail(FDGS_ERR_INVALID_ARG, "shs must be given on both sides or on neither");
+	if (in->M != 1 && in->M != 4 && in->M != 9 && in->M != 16 && in->M != 32 && in->M != 48)
+		return fail(FDGS_ERR_INVALID_ARG, "M=%d: the SH pass walks rows of 1, 4, 9, 16, 32 or 48 coefficients", in->M);
+	if (in->P > 0)
+	{
+		if (!in->means3D || !in->scales || !in->rotations || !out->means3D || !out->scales || !out->rotations)
+			return fail(FDGS_ERR_INVALID_ARG, "means3D / scales / rotations must not be NULL");
+		if (in->gaussian_dim == 4 && (!in->ts || !in->scales_t || !out->ts || !out->scales_t))
+			return fail(FDGS_ERR_INVALID_ARG, "gaussian_dim == 4 needs ts and scales_t: they must not be NULL");
+		if (in->rot_4d && (!in->rotations_r || !out->rotations_r)) return fail(FDGS_ERR_INVALID_ARG, "rot_4d needs rotations_r: it must not be NULL");
+	}
+	HIP_TRY(launch_model_transform(*in, *out, (hipStream_t)stream), "model_transform");
+	return FDGS_OK;
+}
+
 extern "C" void fdgs_debug_tile_sort_limits(int32_t lds_cap, int32_t rank_max) { tile_sort_debug_limits(lds_cap, rank_max); }
 extern "C" const char* fdgs_last_error(void) { return g_err; }
 extern "C" int fdgs_version(void) { return FDGS_VERSION; }

@@ -278,6 +278,7 @@ namespace fdgs
 	// a 4D model at one timestamp as compact 3D Gaussians (time_slice.hip): flags + counts, scan, write + SH fold
 	size_t time_slice_scratch_bytes(int P);
 	hipError_t launch_time_slice(const fdgs_slice_in& in, const fdgs_slice_out& out, void* scratch, hipStream_t stream);
+	hipError_t launch_model_transform(const fdgs_transform_in& in, const fdgs_transform_out& out, hipStream_t stream);
 
 	hipError_t launch_activations(int P, const float* opacity_raw, const float* scales_raw, const float* scales_t_raw, const float* rot_raw,
 	                              const float* rot_r_raw, float* opacity, float* scales, float* scales_t, float* rot, float* rot_r, hipStream_t stream);

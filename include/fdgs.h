@@ -955,6 +955,66 @@ int fdgs_quantize_columns(int32_t P, int32_t C, const float* x, const float* lo,
 int fdgs_compact_decode(int32_t P, int32_t C, int32_t bits, const void* q, const float* lo, const float* step, int32_t D, const float* rows,
                         const int32_t* index, int32_t K, float* out, void* stream);
 
+/* ---- a model under a similarity transform: x' = s R x + T, t' = a t + b (model_transform.hip) -----------------------------------------
+ * RAW parameters in (as fdgs_scene.raw_params = 1: scales / scales_t before exp, quaternions of any norm), raw parameters out; opacity is
+ * not an argument: it does not change.  Two launches on `stream`, one lane per Gaussian for the geometry, one lane per 16-coefficient
+ * block for the SH rows; no atomics, no scratch memory, P == 0: nothing is launched.
+ *   means3D' = s * (R x) + T, the row of R times x summed left to right, ts' = a * t + b (fp32).
+ *   gaussian_dim == 3, or 4 without rot_4d: rotations' = quat * rotations (Hamilton product, no renormalisation), scales' = scales +
+ *     log_scale, and for gaussian_dim == 4 scales_t' = scales_t + 2 log_time_scale (exp(scales_t) is a VARIANCE there).
+ *   rot_4d, scale == time_scale: rotations' = rotations * iso_v and rotations_r' = rotations_r * iso_u, the products of the left / right
+ *     isoclinic families of build_Ml_Mr (M_r(iso_u) M_l(iso_v) = diag(R, 1)^T), scales' = scales + log_scale, scales_t' = scales_t +
+ *     log_time_scale.  The products and sums are formed in double and rounded once.
+ *   rot_4d, scale != time_scale: Sigma = R4^T S^2 R4 of the activated parameters, A Sigma A^T with A = diag(s R, a), a cyclic Jacobi on the
+ *     symmetric 4x4, all in double; the eigenvector with the largest |time component| becomes axis 3 (scales_t), one eigenvector is
+ *     negated where the determinant needs it, R4' is factored into unit (rotations', rotations_r') through its rank-1 coefficient
+ *     matrix, and the logarithms of the square roots of the eigenvalues (floored at 1e-15) are stored.
+ *   shs [P,M,3], M in {1, 4, 9, 16, 32, 48}: in every block of 16 coefficients the row holds, bands 1-3 are multiplied by the 3x3, 5x5,
+ *     7x7 matrices of sh_rot (row-major, 83 entries; c' = D c, each sum pairwise in fp32 starting from +0) for all three channels;
+ *     coefficient 0 of a block is copied bit for bit, a block of zeros stays zeros.  Skipped when `rotation` is the identity to 0 ulp
+ *     (then the rows are copied unless out aliases in).  shs NULL (both): no SH pass.
+ * A transform whose spatial part (or rotation, or time part) is the identity to 0 ulp copies what it would otherwise recompute: the
+ * identity returns the input bit for bit on the first three paths.  quat, iso_u, iso_v, log_scale, log_time_scale and sh_rot are
+ * functions of rotation / scale / time_scale that the caller computes in double (fdgs.edit); the library does not re-derive them.
+ * Every pointer of `out` may alias its counterpart of `in` (in place); other overlaps are not allowed.  Segments the mode does not read
+ * (ts / scales_t for gaussian_dim 3, rotations_r without rot_4d) may be NULL and are not written.
+ * FDGS_ERR_INVALID_ARG before any launch: NULL in / out, a wrong struct_size, P < 0 or >= 2^26, P > 0 with a NULL required pointer, shs
+ * given on one side only, M outside {1, 4, 9, 16, 32, 48} (also without shs), scale or time_scale not positive and finite, gaussian_dim
+ * outside {3, 4}, rot_4d with gaussian_dim 3. */
+typedef struct fdgs_transform_in
+{
+	uint32_t struct_size;     /* sizeof(fdgs_transform_in)                             */
+	int32_t P;                /* number of Gaussians                                   */
+	int32_t M;                /* SH coefficients per Gaussian                          */
+	int32_t gaussian_dim, rot_4d;
+	const float* means3D;     /* [P,3]                                                 */
+	const float* ts;          /* [P]   gaussian_dim 4                                  */
+	const float* scales;      /* [P,3] raw                                             */
+	const float* scales_t;    /* [P]   raw, gaussian_dim 4                             */
+	const float* rotations;   /* [P,4] raw                                             */
+	const float* rotations_r; /* [P,4] raw, rot_4d                                     */
+	const float* shs;         /* [P,M,3] or NULL                                       */
+	double rotation[9];       /* R, row-major                                          */
+	double translation[3];    /* T                                                     */
+	double scale, time_scale, time_shift;   /* s > 0, a > 0, b                         */
+	double quat[4];           /* unit (w,x,y,z) of R                                   */
+	double iso_u[4], iso_v[4];/* M_r(iso_u) M_l(iso_v) = diag(R, 1)^T                  */
+	double log_scale, log_time_scale;
+	float sh_rot[83];         /* bands 1, 2, 3 of the SH rotation, row-major           */
+} fdgs_transform_in;
+typedef struct fdgs_transform_out
+{
+	uint32_t struct_size;     /* sizeof(fdgs_transform_out)                            */
+	float* means3D;           /* the counterparts of fdgs_transform_in's tensors       */
+	float* ts;
+	float* scales;
+	float* scales_t;
+	float* rotations;
+	float* rotations_r;
+	float* shs;
+} fdgs_transform_out;
+int fdgs_model_transform(const fdgs_transform_in* in, const fdgs_transform_out* out, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
