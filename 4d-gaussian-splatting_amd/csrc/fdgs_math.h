@@ -78,6 +78,17 @@ namespace fdgs
 	__device__ __forceinline__ float3 sub3(float3 a, float3 b) { return make_float3(a.x - b.x, a.y - b.y, a.z - b.z); }
 	__device__ __forceinline__ float3 scl3(float s, float3 a) { return make_float3(s * a.x, s * a.y, s * a.z); }
 	__device__ __forceinline__ float dot3(float3 a, float3 b) { return dot3(a.x, a.y, a.z, b.x, b.y, b.z); }
+	// backward of v / |v| (auxiliary.h:108-118): the geometry backward's and the SH backward's view direction
+	__device__ __forceinline__ float3 dnormvdv(float3 v, float3 dv)
+	{
+		const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
+		const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
+		float3 r;
+		r.x = ((+sum2 - v.x * v.x) * dv.x - v.y * v.x * dv.y - v.z * v.x * dv.z) * invsum32;
+		r.y = (-v.x * v.y * dv.x + (sum2 - v.y * v.y) * dv.y - v.z * v.y * dv.z) * invsum32;
+		r.z = (-v.x * v.z * dv.x - v.y * v.z * dv.y + (sum2 - v.z * v.z) * dv.z) * invsum32;
+		return r;
+	}
 
 	// Left / right isoclinic factors of the 4D rotation, column-major
 	// (reference forward.cu:315-327): R4 = M_r * M_l.

@@ -49,18 +49,6 @@ namespace fdgs
 		float ad_b1, ad_b2, ad_eps, ad_inv_sqrt_bc2;
 	};
 
-	// auxiliary.h:108-118
-	__device__ __forceinline__ float3 dnormvdv(float3 v, float3 dv)
-	{
-		const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
-		const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-		float3 r;
-		r.x = ((+sum2 - v.x * v.x) * dv.x - v.y * v.x * dv.y - v.z * v.x * dv.z) * invsum32;
-		r.y = (-v.x * v.y * dv.x + (sum2 - v.y * v.y) * dv.y - v.z * v.y * dv.z) * invsum32;
-		r.z = (-v.x * v.z * dv.x - v.y * v.z * dv.y + (sum2 - v.z * v.z) * dv.z) * invsum32;
-		return r;
-	}
-
 	__device__ __forceinline__ void preprocess_bwd_body(const BwdArgs& a)
 	{
 		const int idx = blockIdx.x * blockDim.x + threadIdx.x;

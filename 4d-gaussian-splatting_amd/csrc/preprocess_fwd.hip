@@ -43,34 +43,6 @@ namespace fdgs
 		uint32_t* bin_counters; int bin_counter_words;   // tile instance counters of the binning passes, cleared here (tilebin.hip)
 	};
 
-	// basis values of the 4D path (forward.cu:87-131; note the double promotion in l2m0)
-	__device__ __forceinline__ void sh_basis_4d(int deg, float x, float y, float z, float* l)
-	{
-		l[0] = SH_C0;
-		if (deg > 0)
-		{
-			l[1] = -1 * SH_C1 * y; l[2] = SH_C1 * z; l[3] = -1 * SH_C1 * x;
-			if (deg > 1)
-			{
-				const float xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-				l[4] = SH_C2[0] * xy;
-				l[5] = SH_C2[1] * yz;
-				l[6] = (float)(SH_C2[2] * (2.0 * zz - xx - yy));
-				l[7] = SH_C2[3] * xz;
-				l[8] = SH_C2[4] * (xx - yy);
-				if (deg > 2)
-				{
-					l[9] = SH_C3[0] * y * (3 * xx - yy);
-					l[10] = SH_C3[1] * xy * z;
-					l[11] = SH_C3[2] * y * (4 * zz - xx - yy);
-					l[12] = SH_C3[3] * z * (2 * zz - 3 * xx - 3 * yy);
-					l[13] = SH_C3[4] * x * (4 * zz - xx - yy);
-					l[14] = SH_C3[5] * z * (xx - yy);
-					l[15] = SH_C3[6] * x * (xx - 3 * yy);
-				}
-			}
-		}
-	}
 	// Coalesced staging of one coefficient block of 64 consecutive Gaussians into a wave-private LDS tile
 	// (row stride SH_STRIDE floats: odd, so the lane-per-Gaussian reads that follow are bank-conflict free).
 	// The reference reads these 12*M bytes per Gaussian with a 12*M-byte stride between threads (forward.cu:85).
@@ -310,10 +282,9 @@ namespace fdgs
 			const unsigned long long amask = __ballot(alive);
 			const int g0 = blockIdx.x * blockDim.x + wave * WAVE;
 			const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
-			// Q4: the forward view direction uses the UN-shifted input mean (forward.cu:480-482)
-			float3 dir = sub3(p_in, make_float3(a.campos[0], a.campos[1], a.campos[2]));
-			const float len = sqrtf(dot3(dir.x, dir.y, dir.z, dir.x, dir.y, dir.z));
-			dir = make_float3(dir.x / len, dir.y / len, dir.z / len);
+			// the view's colour of this thread's Gaussian (sh_eval.h), c kept in registers across the blocks
+			float3 unused;
+			const float3 dir = sh_view_dir(p_in, a.campos, unused);   // Q4: the UN-shifted input mean
 			float l[16];
 			if (!plan.sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
 			const float dir_t = (!plan.sh3d) ? a.ts[idx] - a.timestamp : 0.f;
@@ -324,6 +295,9 @@ namespace fdgs
 				// the tile is wave-private and the LDS executes one wave's operations in order: no workgroup barrier (which held the four
 				// waves of the workgroup in lockstep: all loading, then all evaluating) -- only the compiler must keep the order
 				FDGS_TILE_SYNC();
+				// sh_colour_block (sh_eval.h) WRITTEN OUT, time factor included: called as a function -- it or sh_time_factor alone -- this
+				// kernel is compiled to 188 / 168 VGPRs (PART 0 / 2) instead of 173 / 153, past the budget tests/test_capi_host.py holds
+				// it to.  Same operations, same order; test_sh_kernels_pinned_bits and test_colour_batch_edge_shapes_bitwise hold the two together.
 				if (alive)
 				{
 					if (blk == 0) c = plan.sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
@@ -336,12 +310,7 @@ namespace fdgs
 				}
 				FDGS_TILE_SYNC();
 			}
-			if (alive)
-			{
-				if (!plan.sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
-				clampbits = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
-				rgb = make_float3(fmaxf(c.x, 0.0f), fmaxf(c.y, 0.0f), fmaxf(c.z, 0.0f));
-			}
+			if (alive) rgb = sh_colour_finish(plan, c, clampbits);
 		}
 
 		if (!valid) return;
@@ -397,7 +366,7 @@ namespace fdgs
 		a.focal_x = s.W / (2.0f * s.tan_fovx);
 		a.timestamp = s.timestamp; a.time_duration = s.time_duration;
 		a.rot_4d = s.rot_4d; a.gaussian_dim = s.gaussian_dim; a.force_sh_3d = s.force_sh_3d; a.raw = s.raw_params;
-		a.sh_vec_ok = (s.shs != nullptr && (reinterpret_cast<uintptr_t>(s.shs) & 15) == 0 && (3 * s.M) % 4 == 0) ? 1 : 0;
+		a.sh_vec_ok = (s.shs != nullptr && sh_rows_vec_ok(s.M, s.shs)) ? 1 : 0;
 		a.grid_x = div_up(s.W, TILE_X); a.grid_y = div_up(s.H, TILE_Y);
 		a.tile_cull = out.tile_cull != 0 ? 1 : 0;
 		a.radii = out.radii; a.out_means3D = out.out_means3D; a.covs_com = out.covs_com;
@@ -420,7 +389,8 @@ namespace fdgs
 	// Within one optimizer step the parameters are constant, and the 12 M bytes of SH coefficients per Gaussian are the bulk of
 	// what the preprocess reads (173 of ~200 MB per view at C3): the views' geometry runs per view (PART 1 above), their
 	// colours here -- every coefficient block is staged through LDS ONCE and evaluated for each view's direction and timestamp.
-	// Same device functions, same order of operations as PART 2: colours and clamp bits are bit-identical to the per-view path.
+	// The views' colours come from the same functions as PART 2's (sh_eval.h: sh_view_dir, sh_basis_4d, sh_colour_block, sh_colour_finish):
+	// colours and clamp bits are bit-identical to the per-view path.
 	// ------------------------------------------------------------------------------------------------
 	constexpr int COLOUR_BATCH_MAX = 8;
 	struct ColourBatchArgs
@@ -466,28 +436,21 @@ namespace fdgs
 			for (int v = 0; v < a.nviews; v++)
 			{
 				if (!(valid && a.v[v].radii[idx] > 0)) continue;
-				const float* cp = a.v[v].campos;
-				float3 dir = sub3(p_in, make_float3(cp[0], cp[1], cp[2]));
-				const float len = sqrtf(dot3(dir.x, dir.y, dir.z, dir.x, dir.y, dir.z));
-				dir = make_float3(dir.x / len, dir.y / len, dir.z / len);
+				// direction and basis are rebuilt per block and view (registers: see s_c); the running colour comes from s_c
+				float3 unused;
+				const float3 dir = sh_view_dir(p_in, a.v[v].campos, unused);
 				float l[16];
 				if (!plan.sh3d) sh_basis_4d(a.D, dir.x, dir.y, dir.z, l);
-				float3 c;
-				if (blk == 0) c = plan.sh3d ? sh_color_3d(a.D, row, dir) : sh4d_block0(a.D, l, row);
-				else
-				{
-					const float dir_t = t_in - a.v[v].timestamp;
-					const float tk = (blk == 1) ? (float)cos(2 * REF_PI * dir_t / a.time_duration)
-					                            : (float)cos(2 * REF_PI * dir_t * 2 / a.time_duration);
-					c = make_float3(s_c[3 * v][threadIdx.x], s_c[3 * v + 1][threadIdx.x], s_c[3 * v + 2][threadIdx.x]);
-					c = add3(c, scl3(tk, sh_weighted(l, row, 0, 15, 0)));
-				}
+				float3 c = make_float3(0.f, 0.f, 0.f);
+				if (blk > 0) c = make_float3(s_c[3 * v][threadIdx.x], s_c[3 * v + 1][threadIdx.x], s_c[3 * v + 2][threadIdx.x]);
+				c = sh_colour_block(blk, plan, a.D, l, row, dir, t_in - a.v[v].timestamp, a.time_duration, c);
 				if (blk == plan.nblocks - 1)
 				{
-					if (!plan.sh3d) c = make_float3(c.x + 0.5f, c.y + 0.5f, c.z + 0.5f); // sh_color_3d already added it
+					uint8_t clampbits;
+					const float3 rgb = sh_colour_finish(plan, c, clampbits);
 					float* rec = reinterpret_cast<float*>(a.v[v].records + 3 * (size_t)idx);
-					rec[6] = fmaxf(c.x, 0.0f); rec[7] = fmaxf(c.y, 0.0f); rec[8] = fmaxf(c.z, 0.0f);
-					a.v[v].clamped[idx] = (uint8_t)((c.x < 0 ? 1 : 0) | (c.y < 0 ? 2 : 0) | (c.z < 0 ? 4 : 0));
+					rec[6] = rgb.x; rec[7] = rgb.y; rec[8] = rgb.z;
+					a.v[v].clamped[idx] = clampbits;
 				}
 				else { s_c[3 * v][threadIdx.x] = c.x; s_c[3 * v + 1][threadIdx.x] = c.y; s_c[3 * v + 2][threadIdx.x] = c.z; }
 			}
@@ -508,7 +471,7 @@ namespace fdgs
 			a.P = s.P; a.D = s.D; a.D_t = s.D_t; a.M = s.M; a.nviews = min(COLOUR_BATCH_MAX, nviews - v0);
 			a.means3D = s.means3D; a.shs = s.shs; a.ts = s.ts; a.time_duration = s.time_duration;
 			a.gaussian_dim = s.gaussian_dim; a.force_sh_3d = s.force_sh_3d;
-			a.sh_vec_ok = ((reinterpret_cast<uintptr_t>(s.shs) & 15) == 0 && (3 * s.M) % 4 == 0) ? 1 : 0;
+			a.sh_vec_ok = sh_rows_vec_ok(s.M, s.shs) ? 1 : 0;
 			for (int v = 0; v < COLOUR_BATCH_MAX; v++)
 			{
 				const int w = min(v0 + v, nviews - 1);

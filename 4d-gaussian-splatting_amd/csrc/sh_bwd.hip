@@ -22,6 +22,12 @@
 // reference: Q1 dL_dsh[1] = l[0] * dRGB in the 4D path, Q2 sign of d cos/dt,
 // Q3 the last time block overwrites dRGB/dt, Q4 view direction from the SHIFTED mean.  fdgs_scene.analytic_sh_grad
 // (opt-in) switches Q1-Q3 to the analytic gradient of the forward pass.
+//
+// Where things live: the per-(Gaussian, view) evaluation -- liveness (sh_live), ShBwdEval::begin / block / finish with the tables,
+// the time factors and Q1-Q4 -- and the launchers' float4 flag (sh_rows_vec_ok) are in sh_eval.h; dnormvdv is in fdgs_math.h.  This
+// file holds what differs between the kernels: how rows travel between memory and LDS (sh_bwd_kernel: block by block, gathered
+// rows; sh_bwd_batch_kernel: whole rows once for all views; sh_flush_kernel: whole rows out), the argument structs (ShModelArgs +
+// ShViewArgs, one fill function each) and the launchers.
 #pragma clang fp contract(off)
 #include "fdgs_common.h"
 #include "fdgs_math.h"
@@ -33,16 +39,48 @@ namespace fdgs
 	constexpr int SHB_CH = 12;       // float4 chunks per Gaussian and block (16 coefficients x 3 / 4)
 	constexpr int SHB_ROWS = WAVE;   // live Gaussians evaluated per round, one per lane (tile: 12.5 KB)
 
-	struct ShBwdArgs
+	// what the views of an optimizer step share, and what is a view's own: sh_bwd_kernel takes one view, sh_bwd_batch_kernel SBB_MAX
+	struct ShModelArgs
 	{
 		int P, D, D_t, M;
-		const float *shs, *ts, *campos;
-		float timestamp, time_duration;
-		int gaussian_dim, force_sh_3d, vec_ok, accum, analytic;
+		const float *shs, *ts;
+		float time_duration;
+		int gaussian_dim, force_sh_3d, analytic, vec_ok;
+	};
+	struct ShViewArgs
+	{
+		const float* campos; float timestamp;
 		const int32_t* radii; const float* means; const uint8_t* clamped;
-		float* gacc; float* dL_dsh;
+		float* gacc;
 		float4* stage;   // deferred mode: [P][2] = (dRGB.xyz, cos factor of time block 1) (dir.xyz, cos factor of block 2) per Gaussian instead of dL_dsh (see sh_flush_kernel)
 	};
+	struct ShBwdArgs
+	{
+		ShModelArgs m; ShViewArgs v;
+		int accum; float* dL_dsh;   // the dense gradient (not in deferred mode)
+	};
+	static void fill_sh_model(ShModelArgs& m, const fdgs_scene& s, bool vec_ok)
+	{
+		m.P = s.P; m.D = s.D; m.D_t = s.D_t; m.M = s.M;
+		m.shs = s.shs; m.ts = s.ts; m.time_duration = s.time_duration;
+		m.gaussian_dim = s.gaussian_dim; m.force_sh_3d = s.force_sh_3d; m.analytic = s.analytic_sh_grad;
+		m.vec_ok = vec_ok ? 1 : 0;
+	}
+	static void fill_sh_view(ShViewArgs& v, const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out, const char* geom)
+	{
+		v.campos = s.campos; v.timestamp = s.timestamp;
+		v.radii = in.radii; v.means = in.out_means3D;
+		v.clamped = reinterpret_cast<const uint8_t*>(geom + geom_layout(s.P).clamped);
+		v.gacc = out.grad_accum; v.stage = reinterpret_cast<float4*>(out.sh_stage);
+	}
+	// the end of one (Gaussian, view) evaluation (sh_eval.h): the stage records (deferred mode) and words 12..15 of the accumulator record
+	__device__ __forceinline__ void sh_bwd_finish(const ShBwdEval& e, const ShViewArgs& v, const ShPlan& plan, int idx, bool stage)
+	{
+		float4 s0, s1;
+		const float4 words = e.finish(plan, s0, s1);
+		if (stage) { v.stage[2 * (size_t)idx] = s0; v.stage[2 * (size_t)idx + 1] = s1; }
+		reinterpret_cast<float4*>(v.gacc + (size_t)idx * GRAD_ACC_WORDS)[3] = words;
+	}
 
 	// ---- tile <-> global, coalesced; tile row r belongs to Gaussian g0 + list[r], r < nrows ----
 	constexpr int SHB_BATCH = 6;     // float4 per lane in flight while staging (2 batches per block)
@@ -129,11 +167,12 @@ namespace fdgs
 		__shared__ float tile[SHB_ROWS * SHB_STRIDE];
 		__shared__ uint32_t s_list[2 * WAVE];     // the live Gaussians waiting for evaluation
 		const int lane = threadIdx.x;
-		const size_t row_floats = (size_t)3 * a.M;
-		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
+		const ShModelArgs& m = a.m;
+		const ShViewArgs& v = a.v;
+		const size_t row_floats = (size_t)3 * m.M;
+		const ShPlan plan = sh_plan(m.D, m.D_t, m.gaussian_dim, m.force_sh_3d, m.M);
 		const unsigned long long lt_mask = (1ull << lane) - 1ull;
-		const float3 campos = make_float3(a.campos[0], a.campos[1], a.campos[2]);
-		const int nchunks = (a.P + WAVE - 1) / WAVE;
+		const int nchunks = (m.P + WAVE - 1) / WAVE;
 
 		int n = 0;      // live Gaussians waiting in s_list
 		int next = blockIdx.x;
@@ -147,22 +186,18 @@ namespace fdgs
 				else
 				{
 				next += gridDim.x;
-				const int g_end = a.P;
+				const int g_end = m.P;
 				// ---- which of the next 64 Gaussians carry a colour gradient (visible: backward.cu:873) ----
 				const int idx = base + lane;
 				const bool valid = idx < g_end;
-				bool live = false;
-				if (valid && a.radii[idx] > 0)
-				{
-					const float3 dRGB = sh_colour_gradient(a.gacc, a.clamped, idx);
-					live = dRGB.x != 0.f || dRGB.y != 0.f || dRGB.z != 0.f;
-				}
+				float3 dRGB;
+				const bool live = valid && sh_live(v.radii, v.gacc, v.clamped, idx, dRGB);
 				const unsigned long long live_mask = __ballot(live);
 				if (live) s_list[n + __popcll(live_mask & lt_mask)] = (uint32_t)idx;
 				n += __popcll(live_mask);
 				// a Gaussian without a colour gradient: all of its outputs are zero.  Record words 12..15 already are (the record is
 				// all zero when the blend backward starts and nobody else writes them); dL_dsh: below; the flush looks at dRGB only
-				if (STAGE && valid && !live) a.stage[2 * (size_t)idx] = make_float4(0.f, 0.f, 0.f, 0.f);
+				if (STAGE && valid && !live) v.stage[2 * (size_t)idx] = make_float4(0.f, 0.f, 0.f, 0.f);
 				__builtin_amdgcn_wave_barrier();
 
 				if (!STAGE && !a.accum)
@@ -170,7 +205,7 @@ namespace fdgs
 					// dL_dsh is fully written by this call: zero rows for the Gaussians without a colour gradient, zeros beyond the
 					// active degrees for the others (nothing to add when accumulating)
 					const int span = min(WAVE, g_end - base);
-					if (a.vec_ok && (plan.act_floats & 3) == 0)
+					if (m.vec_ok && (plan.act_floats & 3) == 0)
 					{
 						const int RC = (int)row_floats / 4, total = span * RC;
 						RowWalk w(lane, RC);
@@ -206,67 +241,18 @@ namespace fdgs
 			const bool live = lane < nrows;
 			const int idx = g0 + (int)list[live ? lane : 0];
 			float* row = tile + lane * SHB_STRIDE;
-			// per-Gaussian prologue
-			const float3 mean = make_float3(a.means[3 * (size_t)idx], a.means[3 * (size_t)idx + 1], a.means[3 * (size_t)idx + 2]);
-			const float3 dir_orig = make_float3(mean.x - campos.x, mean.y - campos.y, mean.z - campos.z); // Q4: shifted mean
-			const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
-			const float3 dir = make_float3(dir_orig.x / len, dir_orig.y / len, dir_orig.z / len);
-			const float3 dRGB = sh_colour_gradient(a.gacc, a.clamped, idx);
-			const float dir_t = plan.sh3d ? 0.f : a.ts[idx] - a.timestamp;
-			float l[16], dX[16], dY[16], dZ[16];
-			sh_tables(a.D, dir.x, dir.y, dir.z, !plan.sh3d, l, dX, dY, dZ);
-
-			float3 gx = make_float3(0.f, 0.f, 0.f), gy = gx, gz = gx, gt = gx;
-			float tk_stage[2] = { 0.f, 0.f };   // cos factors of the two time blocks (deferred mode hands them to the flush)
+			// the evaluation (sh_eval.h) of the lane's Gaussian: it is on the list, so sh_live said yes -- its dRGB again
+			ShBwdEval e;
+			e.begin(plan, m.D, ld3(v.means, idx), v.campos, plan.sh3d ? 0.f : m.ts[idx], v.timestamp, sh_colour_gradient(v.gacc, v.clamped, idx));
 			for (int blk = 0; blk < plan.nblocks; blk++)
 			{
 				const int nk = (blk == 0) ? plan.ncoef0 : 16;
 				const int first_float = 48 * blk;
-				const bool vec = a.vec_ok && nk == 16;
-				if (vec) rows_load16(tile, a.shs, list, nrows, g0, row_floats, first_float, lane);
-				else rows_load_any(tile, a.shs, list, nrows, g0, row_floats, first_float, 3 * nk, lane);
+				const bool vec = m.vec_ok && nk == 16;
+				if (vec) rows_load16(tile, m.shs, list, nrows, g0, row_floats, first_float, lane);
+				else rows_load_any(tile, m.shs, list, nrows, g0, row_floats, first_float, 3 * nk, lane);
 				__builtin_amdgcn_wave_barrier();
-				if (live)
-				{
-					float tk = 1.f, dtk_dt = 0.f;
-					if (blk == 1)
-					{
-						tk = (float)cos(2 * REF_PI * dir_t / a.time_duration);
-						dtk_dt = (float)(sin(2 * REF_PI * dir_t / a.time_duration) * 2 * REF_PI / a.time_duration); // Q2
-					}
-					else if (blk == 2)
-					{
-						tk = (float)cos(2 * REF_PI * dir_t * 2 / a.time_duration);
-						dtk_dt = (float)(sin(2 * REF_PI * dir_t * 2 / a.time_duration) * 2 * REF_PI * 2 / a.time_duration);
-					}
-					if (a.analytic) dtk_dt = -dtk_dt;   // d cos(u) / dt = -sin(u) du/dt
-					if (blk == 1) tk_stage[0] = tk;
-					if (blk == 2) tk_stage[1] = tk;
-					float3 st = make_float3(0.f, 0.f, 0.f), sx = st, sy = st, sz = st;
-#pragma unroll
-					for (int k = 0; k < 16; k++)   // fully unrolled: the tables stay in registers (no dynamic indexing)
-					{
-						if (k >= nk) break;
-						const float3 s = ld3(row, k);
-						float basis = l[k];
-						if (blk == 0 && k == 1 && !plan.sh3d && !a.analytic) basis = l[0]; // Q1
-						if (!STAGE)
-						{
-							const float3 d = scl3(blk == 0 ? basis : tk * basis, dRGB);
-							row[3 * k] = d.x; row[3 * k + 1] = d.y; row[3 * k + 2] = d.z;
-						}
-						st = add3(st, scl3(l[k], s));
-						sx = add3(sx, scl3(dX[k], s));
-						sy = add3(sy, scl3(dY[k], s));
-						sz = add3(sz, scl3(dZ[k], s));
-					}
-					if (blk == 0) { gx = sx; gy = sy; gz = sz; }
-					else
-					{
-						gx = add3(gx, scl3(tk, sx)); gy = add3(gy, scl3(tk, sy)); gz = add3(gz, scl3(tk, sz));
-						gt = a.analytic ? add3(gt, scl3(dtk_dt, st)) : scl3(dtk_dt, st); // Q3: overwrite, not accumulate
-					}
-				}
+				if (live) e.block<!STAGE>(plan, m.analytic != 0, m.time_duration, row, nk, blk);
 				__builtin_amdgcn_wave_barrier();
 				if (!STAGE)
 				{
@@ -275,26 +261,7 @@ namespace fdgs
 					__builtin_amdgcn_wave_barrier();
 				}
 			}
-			if (live)
-			{
-				if (STAGE)
-				{
-					// what the flush needs to rebuild this view's contribution basis(dir) x time factor x dRGB to dL_dsh
-					a.stage[2 * (size_t)idx] = make_float4(dRGB.x, dRGB.y, dRGB.z, tk_stage[0]);
-					a.stage[2 * (size_t)idx + 1] = make_float4(dir.x, dir.y, dir.z, tk_stage[1]);
-				}
-				float4 o;
-				const float3 ddir = make_float3(dot3(gx, dRGB), dot3(gy, dRGB), dot3(gz, dRGB));
-				// dnormvdv, auxiliary.h:108-118
-				const float3 v = dir_orig;
-				const float sum2 = v.x * v.x + v.y * v.y + v.z * v.z;
-				const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-				o.x = ((+sum2 - v.x * v.x) * ddir.x - v.y * v.x * ddir.y - v.z * v.x * ddir.z) * invsum32;
-				o.y = (-v.x * v.y * ddir.x + (sum2 - v.y * v.y) * ddir.y - v.z * v.y * ddir.z) * invsum32;
-				o.z = (-v.x * v.z * ddir.x - v.y * v.z * ddir.y + (sum2 - v.z * v.z) * ddir.z) * invsum32;
-				o.w = plan.sh3d ? 0.f : dot3(gt, dRGB);
-				reinterpret_cast<float4*>(a.gacc + (size_t)idx * GRAD_ACC_WORDS)[3] = o;
-			}
+			if (live) sh_bwd_finish(e, v, plan, idx, STAGE);
 			// the Gaussians that did not fit into this batch move to the front of the list
 			const int left = n - nrows;
 			const uint32_t moved = lane < left ? s_list[nrows + lane] : 0u;
@@ -321,17 +288,10 @@ namespace fdgs
 	hipError_t launch_sh_bwd(const fdgs_scene& s, const fdgs_backward_in& in, const fdgs_backward_out& out, const char* geom, hipStream_t stream)
 	{
 		if (s.shs == nullptr || s.M <= 0) return hipSuccess;
-		const GeomLayout L = geom_layout(s.P);
 		ShBwdArgs a;
-		a.P = s.P; a.D = s.D; a.D_t = s.D_t; a.M = s.M;
-		a.shs = s.shs; a.ts = s.ts; a.campos = s.campos;
-		a.timestamp = s.timestamp; a.time_duration = s.time_duration;
-		a.gaussian_dim = s.gaussian_dim; a.force_sh_3d = s.force_sh_3d; a.analytic = s.analytic_sh_grad;
-		a.vec_ok = ((reinterpret_cast<uintptr_t>(s.shs) & 15) == 0 && (reinterpret_cast<uintptr_t>(out.dL_dsh) & 15) == 0 && (3 * s.M) % 4 == 0) ? 1 : 0;
-		a.radii = in.radii; a.means = in.out_means3D;
-		a.clamped = reinterpret_cast<const uint8_t*>(geom + L.clamped);
-		a.gacc = out.grad_accum; a.dL_dsh = out.dL_dsh; a.accum = out.accumulate;
-		a.stage = reinterpret_cast<float4*>(out.sh_stage);
+		fill_sh_model(a.m, s, sh_rows_vec_ok(s.M, s.shs, out.dL_dsh));
+		fill_sh_view(a.v, s, in, out, geom);
+		a.dL_dsh = out.dL_dsh; a.accum = out.accumulate;
 		// one wave per wave slot the device has for this kernel (cached per device)
 		constexpr int MAXDEV = 64;
 		static int slots_of[2][MAXDEV] = {};   // same value whoever writes it first
@@ -355,9 +315,9 @@ namespace fdgs
 	// view, and takes them 32 at a time: their WHOLE rows (the prefix the active degrees use) are staged once through a
 	// wave-private LDS tile with linear float4 loads, and lane = (Gaussian, view parity) evaluates its Gaussian for the views
 	// v = parity, parity + 2, ...: per view the 8 staged numbers for the flush (dL_dRGB, direction, the two cosine factors) and
-	// the mean / time gradient in words 12..15 of the view's accumulator record.  Same arithmetic, operation by operation, as
-	// sh_bwd_kernel<true> run view by view: on the same accumulator records the two are equal bit for bit
-	// (test_sh_backward_paths_bitwise).
+	// the mean / time gradient in words 12..15 of the view's accumulator record.  The per-(Gaussian, view) evaluation is made of the same functions as
+	// sh_bwd_kernel<true>'s (sh_eval.h: sh_live, ShBwdEval; sh_bwd_finish above): on the same accumulator records the two are equal
+	// bit for bit (test_sh_backward_paths_bitwise).
 	// ------------------------------------------------------------------------------------------------
 	constexpr int SBB_MAX = 8;        // views per launch
 	constexpr int SBB_ROWS = 32;
@@ -366,16 +326,8 @@ namespace fdgs
 	constexpr int SBB_STRIDE = SBB_ACT + 1;
 	struct ShBwdBatchArgs
 	{
-		int P, D, D_t, M, nviews;
-		const float *shs, *ts;
-		float time_duration;
-		int gaussian_dim, force_sh_3d, vec_ok, analytic;
-		struct View
-		{
-			const float* campos; float timestamp;
-			const int32_t* radii; const float* means; const uint8_t* clamped;
-			float* gacc; float4* stage;
-		} v[SBB_MAX];
+		ShModelArgs m; int nviews;
+		ShViewArgs v[SBB_MAX];
 	};
 
 	__global__ void __launch_bounds__(WAVE) sh_bwd_batch_kernel(const ShBwdBatchArgs a)
@@ -384,31 +336,28 @@ namespace fdgs
 		__shared__ uint32_t s_list[SBB_SPAN];
 		const int lane = threadIdx.x;
 		const int g0 = blockIdx.x * SBB_SPAN;
-		const int row_floats = 3 * a.M;
-		const ShPlan plan = sh_plan(a.D, a.D_t, a.gaussian_dim, a.force_sh_3d, a.M);
+		const ShModelArgs& m = a.m;
+		const int row_floats = 3 * m.M;
+		const ShPlan plan = sh_plan(m.D, m.D_t, m.gaussian_dim, m.force_sh_3d, m.M);
 		const unsigned long long lt_mask = (1ull << lane) - 1ull;
 
 		// ---- which Gaussians of the span carry a colour gradient in some view; the others get their zero stage records ----
 		int n = 0;
 		{
 			const int idx = g0 + lane;
-			const bool valid = idx < a.P;
+			const bool valid = idx < m.P;
 			bool any = false;
 #pragma unroll 1
 			for (int v = 0; v < a.nviews; v++)
 			{
-				bool live = false;
-				if (valid && a.v[v].radii[idx] > 0)
-				{
-					const float3 d = sh_colour_gradient(a.v[v].gacc, a.v[v].clamped, idx);
-					live = d.x != 0.f || d.y != 0.f || d.z != 0.f;
-				}
+				float3 dRGB;
+				const bool live = valid && sh_live(a.v[v].radii, a.v[v].gacc, a.v[v].clamped, idx, dRGB);
 				if (valid && !live) a.v[v].stage[2 * (size_t)idx] = make_float4(0.f, 0.f, 0.f, 0.f);
 				any = any || live;
 			}
-			const unsigned long long m = __ballot(any);
-			if (any) s_list[__popcll(m & lt_mask)] = (uint32_t)lane;
-			n = __popcll(m);
+			const unsigned long long any_mask = __ballot(any);
+			if (any) s_list[__popcll(any_mask & lt_mask)] = (uint32_t)lane;
+			n = __popcll(any_mask);
 		}
 		__builtin_amdgcn_wave_barrier();
 
@@ -417,7 +366,7 @@ namespace fdgs
 		{
 			const int nrows = min(SBB_ROWS, n - r0);
 			// ---- whole rows into the tile ----
-			if (a.vec_ok && (plan.act_floats & 3) == 0)
+			if (m.vec_ok && (plan.act_floats & 3) == 0)
 			{
 				const int RC = plan.act_floats / 4, total = nrows * RC;
 				RowWalk w(lane, RC);
@@ -431,7 +380,7 @@ namespace fdgs
 						og[i] = w.g; oq[i] = w.q;
 						w.step();
 						if (c0 + i * WAVE + lane >= total) og[i] = -1;
-						else val[i] = *reinterpret_cast<const float4*>(a.shs + (size_t)(g0 + (int)s_list[r0 + og[i]]) * row_floats + 4 * oq[i]);
+						else val[i] = *reinterpret_cast<const float4*>(m.shs + (size_t)(g0 + (int)s_list[r0 + og[i]]) * row_floats + 4 * oq[i]);
 					}
 #pragma unroll
 					for (int i = 0; i < 6; i++)
@@ -448,7 +397,7 @@ namespace fdgs
 				RowWalk w(lane, plan.act_floats);
 				for (int e = lane; e < total; e += WAVE)
 				{
-					tile[w.g * SBB_STRIDE + w.q] = a.shs[(size_t)(g0 + (int)s_list[r0 + w.g]) * row_floats + w.q];
+					tile[w.g * SBB_STRIDE + w.q] = m.shs[(size_t)(g0 + (int)s_list[r0 + w.g]) * row_floats + w.q];
 					w.step();
 				}
 			}
@@ -458,73 +407,18 @@ namespace fdgs
 			if (g < nrows)
 			{
 				const int idx = g0 + (int)s_list[r0 + g];
-				const float* row = tile + g * SBB_STRIDE;
-				const float t_in = plan.sh3d ? 0.f : a.ts[idx];
+				float* row = tile + g * SBB_STRIDE;
+				const float t_in = plan.sh3d ? 0.f : m.ts[idx];
 #pragma unroll 1
 				for (int v = vpar; v < a.nviews; v += 2)
 				{
-					if (!(a.v[v].radii[idx] > 0)) continue;
-					const float3 dRGB = sh_colour_gradient(a.v[v].gacc, a.v[v].clamped, idx);
-					if (dRGB.x == 0.f && dRGB.y == 0.f && dRGB.z == 0.f) continue;
-					const float* cp = a.v[v].campos;
-					const float* mp = a.v[v].means + 3 * (size_t)idx;
-					const float3 dir_orig = make_float3(mp[0] - cp[0], mp[1] - cp[1], mp[2] - cp[2]); // Q4: shifted mean
-					const float len = sqrtf(dir_orig.x * dir_orig.x + dir_orig.y * dir_orig.y + dir_orig.z * dir_orig.z);
-					const float3 dir = make_float3(dir_orig.x / len, dir_orig.y / len, dir_orig.z / len);
-					const float dir_t = plan.sh3d ? 0.f : t_in - a.v[v].timestamp;
-					float l[16], dX[16], dY[16], dZ[16];
-					sh_tables(a.D, dir.x, dir.y, dir.z, !plan.sh3d, l, dX, dY, dZ);
-					float3 gx = make_float3(0.f, 0.f, 0.f), gy = gx, gz = gx, gt = gx;
-					float tk_stage[2] = { 0.f, 0.f };
+					float3 dRGB;
+					if (!sh_live(a.v[v].radii, a.v[v].gacc, a.v[v].clamped, idx, dRGB)) continue;
+					ShBwdEval e;
+					e.begin(plan, m.D, ld3(a.v[v].means, idx), a.v[v].campos, t_in, a.v[v].timestamp, dRGB);
 					for (int blk = 0; blk < plan.nblocks; blk++)
-					{
-						const int nk = (blk == 0) ? plan.ncoef0 : 16;
-						const float* brow = row + 48 * blk;
-						float tk = 1.f, dtk_dt = 0.f;
-						if (blk == 1)
-						{
-							tk = (float)cos(2 * REF_PI * dir_t / a.time_duration);
-							dtk_dt = (float)(sin(2 * REF_PI * dir_t / a.time_duration) * 2 * REF_PI / a.time_duration); // Q2
-						}
-						else if (blk == 2)
-						{
-							tk = (float)cos(2 * REF_PI * dir_t * 2 / a.time_duration);
-							dtk_dt = (float)(sin(2 * REF_PI * dir_t * 2 / a.time_duration) * 2 * REF_PI * 2 / a.time_duration);
-						}
-						if (a.analytic) dtk_dt = -dtk_dt;
-						if (blk == 1) tk_stage[0] = tk;
-						if (blk == 2) tk_stage[1] = tk;
-						float3 st = make_float3(0.f, 0.f, 0.f), sx = st, sy = st, sz = st;
-#pragma unroll
-						for (int k = 0; k < 16; k++)
-						{
-							if (k >= nk) break;
-							const float3 sv = ld3(brow, k);
-							st = add3(st, scl3(l[k], sv));
-							sx = add3(sx, scl3(dX[k], sv));
-							sy = add3(sy, scl3(dY[k], sv));
-							sz = add3(sz, scl3(dZ[k], sv));
-						}
-						if (blk == 0) { gx = sx; gy = sy; gz = sz; }
-						else
-						{
-							gx = add3(gx, scl3(tk, sx)); gy = add3(gy, scl3(tk, sy)); gz = add3(gz, scl3(tk, sz));
-							gt = a.analytic ? add3(gt, scl3(dtk_dt, st)) : scl3(dtk_dt, st); // Q3: overwrite, not accumulate
-						}
-					}
-					a.v[v].stage[2 * (size_t)idx] = make_float4(dRGB.x, dRGB.y, dRGB.z, tk_stage[0]);
-					a.v[v].stage[2 * (size_t)idx + 1] = make_float4(dir.x, dir.y, dir.z, tk_stage[1]);
-					float4 o;
-					const float3 ddir = make_float3(dot3(gx, dRGB), dot3(gy, dRGB), dot3(gz, dRGB));
-					// dnormvdv, auxiliary.h:108-118
-					const float3 w = dir_orig;
-					const float sum2 = w.x * w.x + w.y * w.y + w.z * w.z;
-					const float invsum32 = 1.0f / sqrtf(sum2 * sum2 * sum2);
-					o.x = ((+sum2 - w.x * w.x) * ddir.x - w.y * w.x * ddir.y - w.z * w.x * ddir.z) * invsum32;
-					o.y = (-w.x * w.y * ddir.x + (sum2 - w.y * w.y) * ddir.y - w.z * w.y * ddir.z) * invsum32;
-					o.z = (-w.x * w.z * ddir.x - w.y * w.z * ddir.y + (sum2 - w.z * w.z) * ddir.z) * invsum32;
-					o.w = plan.sh3d ? 0.f : dot3(gt, dRGB);
-					reinterpret_cast<float4*>(a.v[v].gacc + (size_t)idx * GRAD_ACC_WORDS)[3] = o;
+						e.block<false>(plan, m.analytic != 0, m.time_duration, row + 48 * blk, (blk == 0) ? plan.ncoef0 : 16, blk);
+					sh_bwd_finish(e, a.v[v], plan, idx, true);
 				}
 			}
 			__builtin_amdgcn_wave_barrier();
@@ -538,21 +432,15 @@ namespace fdgs
 	{
 		const fdgs_scene& s = *views[0];
 		if (s.shs == nullptr || s.M <= 0 || s.P <= 0) return hipSuccess;
-		const GeomLayout L = geom_layout(s.P);
 		for (int v0 = 0; v0 < nviews; v0 += SBB_MAX)
 		{
 			ShBwdBatchArgs a;
-			a.P = s.P; a.D = s.D; a.D_t = s.D_t; a.M = s.M; a.nviews = min(SBB_MAX, nviews - v0);
-			a.shs = s.shs; a.ts = s.ts; a.time_duration = s.time_duration;
-			a.gaussian_dim = s.gaussian_dim; a.force_sh_3d = s.force_sh_3d; a.analytic = s.analytic_sh_grad;
-			a.vec_ok = ((reinterpret_cast<uintptr_t>(s.shs) & 15) == 0 && (3 * s.M) % 4 == 0) ? 1 : 0;
+			fill_sh_model(a.m, s, sh_rows_vec_ok(s.M, s.shs));
+			a.nviews = min(SBB_MAX, nviews - v0);
 			for (int v = 0; v < SBB_MAX; v++)
 			{
 				const int w = min(v0 + v, nviews - 1);
-				a.v[v].campos = views[w]->campos; a.v[v].timestamp = views[w]->timestamp;
-				a.v[v].radii = ins[w]->radii; a.v[v].means = ins[w]->out_means3D;
-				a.v[v].clamped = reinterpret_cast<const uint8_t*>(reinterpret_cast<const char*>(ins[w]->geom_buffer) + L.clamped);
-				a.v[v].gacc = outs[w]->grad_accum; a.v[v].stage = reinterpret_cast<float4*>(outs[w]->sh_stage);
+				fill_sh_view(a.v[v], *views[w], *ins[w], *outs[w], reinterpret_cast<const char*>(ins[w]->geom_buffer));
 			}
 			hipLaunchKernelGGL(sh_bwd_batch_kernel, dim3(div_up(s.P, SBB_SPAN)), dim3(WAVE), 0, stream, a);
 		}
@@ -630,9 +518,7 @@ namespace fdgs
 			{
 				const int k = 8 * half + j;
 				const float lk = half ? l[8 + j] : l[j];
-				float basis = lk;
-				if (j == 1 && half == 0 && !plan.sh3d && !a.analytic) basis = l[0]; // Q1
-				if (k >= plan.ncoef0) basis = 0.f;
+				const float basis = k < plan.ncoef0 ? sh_grad_basis0(k, lk, l[0], plan, a.analytic != 0) : 0.f;   // Q1: as sh_bwd_kernel<false>
 				acc[0][j] = add3(acc[0][j], scl3(basis, dRGB));
 				if (plan.nblocks > 1) acc[1][j] = add3(acc[1][j], scl3(s0.w * lk, dRGB));
 				if (plan.nblocks > 2) acc[2][j] = add3(acc[2][j], scl3(s1.w * lk, dRGB));
@@ -743,7 +629,7 @@ namespace fdgs
 		a.P = P; a.D = D; a.D_t = D_t; a.M = M; a.nviews = nviews;
 		a.gaussian_dim = gaussian_dim; a.force_sh_3d = force_sh_3d;
 		a.analytic = analytic; a.accum = 0;
-		a.vec_ok = ((reinterpret_cast<uintptr_t>(dL_dsh) & 15) == 0 && (3 * M) % 4 == 0) ? 1 : 0;
+		a.vec_ok = sh_rows_vec_ok(M, dL_dsh) ? 1 : 0;
 		a.stages = reinterpret_cast<const float4*>(stages);
 		a.dL_dsh = dL_dsh;
 		a.p = a.m = a.v = nullptr;
@@ -766,10 +652,8 @@ namespace fdgs
 	                          const AdamScalars& k, hipStream_t stream)
 	{
 		if (P <= 0 || M <= 0) return hipSuccess;
-		const uintptr_t align = reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(exp_avg) |
-		                        reinterpret_cast<uintptr_t>(exp_avg_sq) | reinterpret_cast<uintptr_t>(dL_dsh);
 		// the DC learning rate is applied to the first 3 floats of a row: rows must start on a float4 boundary
-		if (nviews <= 0 || (3 * M) % 4 != 0 || (align & 15) != 0) return hipErrorInvalidValue;
+		if (nviews <= 0 || !sh_rows_vec_ok(M, params, exp_avg, exp_avg_sq, dL_dsh)) return hipErrorInvalidValue;
 		ShFlushArgs a;
 		fill_flush_args(a, P, D, D_t, M, gaussian_dim, force_sh_3d, analytic, nviews, stages, dL_dsh);
 		a.p = params; a.m = exp_avg; a.v = exp_avg_sq; a.k = k;

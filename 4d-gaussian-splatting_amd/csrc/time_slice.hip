@@ -256,11 +256,11 @@ namespace fdgs
 					a.out_rotations[4 * r + 2] = q.z; a.out_rotations[4 * r + 3] = q.w;
 				}
 			}
-			// the forward's time factors (preprocess_fwd.hip: dir_t = ts - timestamp in fp32, the cosine in double)
+			// the forward's time factors (sh_eval.h; dir_t = ts - timestamp in fp32 as in preprocess_fwd.hip)
 			const float dir_t = a.ts[idx] - a.timestamp;
 			s_src[wave][r_in] = lane;
-			s_t1[wave][r_in] = plan.nblocks > 1 ? (float)cos(2 * REF_PI * dir_t / a.time_duration) : 0.f;
-			s_t2[wave][r_in] = plan.nblocks > 2 ? (float)cos(2 * REF_PI * dir_t * 2 / a.time_duration) : 0.f;
+			s_t1[wave][r_in] = plan.nblocks > 1 ? sh_time_factor(1, dir_t, a.time_duration) : 0.f;
+			s_t2[wave][r_in] = plan.nblocks > 2 ? sh_time_factor(2, dir_t, a.time_duration) : 0.f;
 		}
 		// wave-private LDS rows, one wave's LDS operations execute in order: only the compiler must keep the order
 		__builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

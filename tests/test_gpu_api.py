@@ -1020,3 +1020,44 @@ def test_geometry_kernels_pinned_bits(gpu_device, variant, pf, mod, P):
             k, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
     if P >= 63:
         _GG.check_contents(model, variant, pf, mod, got)
+
+
+# ---- the SH kernels' bits, pinned (tests/golden/make_golden_sh.py) ----
+def _golden_sh():
+    import importlib.util
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_golden_sh.py")
+    spec = importlib.util.spec_from_file_location("make_golden_sh", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+_GSH = _golden_sh()
+
+
+@pytest.mark.parametrize("P", _GSH.SIZES)
+@pytest.mark.parametrize("D,D_t,M,sh3d,misaligned", _SH_EDGE_TABLE, ids=_SH_EDGE_IDS)
+def test_sh_kernels_pinned_bits(gpu_device, request, D, D_t, M, sh3d, misaligned, P):
+    """The forward's colours (preprocess_fwd_kernel<0> per view; the geometry launches + colour_batch_kernel) and the SH backward of
+    crafted colour gradients (sh_bwd_kernel<true> per view, sh_bwd_batch_kernel, sh_bwd_kernel<false> overwriting then accumulating,
+    fdgs_sh_flush; reference-compatible and analytic) of 5 views, against the bits the library produced before the per-view SH
+    evaluation was gathered in sh_eval.h: colours, clamp bits, radii, stage records, accumulator words 12..15 and (P <= 65) dL_dsh
+    equal as 32-bit patterns, on the recorded inputs.  Every row of the edge table at 1, 65 and 97 Gaussians.  The fixtures are this
+    toolchain's bits: the generator's docstring says how to re-record."""
+    row_id = _SH_EDGE_IDS[_SH_EDGE_TABLE.index((D, D_t, M, sh3d, misaligned))]
+    inp = dict(np.load(_GSH.fixture_path(row_id, P, "inputs")))
+    got = _GSH.run_case(inp, (D, D_t, M, sh3d, misaligned), gpu_device)
+    files = _GSH.files_of(P)
+    assert set(got) == set(files) and ("dsh_ref" in files) == (P <= 65)
+    for name, keys in files.items():
+        want = np.load(_GSH.fixture_path(row_id, P, name))
+        assert set(got[name]) == set(keys) == set(want.files), name
+        for k in keys:
+            g, w = got[name][k], want[k]
+            assert g.shape == w.shape and g.dtype == w.dtype and g.dtype.itemsize in (1, 4), (name, k)
+            a, b = (g, w) if g.dtype.itemsize == 1 else (g.view(np.uint32), w.view(np.uint32))
+            bad = np.argwhere(a != b)
+            assert bad.size == 0, "%s %s: %d of %d words differ, first at %s: %08x != %08x" % (
+                name, k, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
+    _GSH.check_contents(inp, got)
