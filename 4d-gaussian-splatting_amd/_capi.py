@@ -141,6 +141,19 @@ class FdgsCameraGrads(_Sized):
                 ("dL_dtimestamp", _fp), ("scale", C.c_float), ("accumulate", C.c_int32)]
 
 
+class FdgsDepthIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", _fp), ("alpha", _fp), ("mask", _fp),
+                ("alpha_min", C.c_float)]
+
+
+class FdgsDepthGrads(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("d_depth", _fp), ("d_alpha", _fp), ("g_upstream", _fp), ("scale", C.c_float),
+                ("accumulate", C.c_int32)]
+
+
+FDGS_DEPTH_PEARSON, FDGS_DEPTH_SSI = 0, 1  # include/fdgs.h
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -160,7 +173,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_debug_frames_resize_path", "fdgs_frames_composite", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
             "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
-            "fdgs_model_transform",
+            "fdgs_model_transform", "fdgs_depth_loss_num_partials", "fdgs_depth_loss", "fdgs_depth_normals", "fdgs_depth_normals_backward",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
@@ -342,6 +355,15 @@ def _load():
     lib.fdgs_compact_decode.restype = C.c_int
     lib.fdgs_model_transform.argtypes = [C.POINTER(FdgsTransformIn), C.POINTER(FdgsTransformOut), C.c_void_p]
     lib.fdgs_model_transform.restype = C.c_int
+    lib.fdgs_depth_loss_num_partials.argtypes = [C.c_int32, C.c_int32]
+    lib.fdgs_depth_loss_num_partials.restype = C.c_int
+    lib.fdgs_depth_loss.argtypes = [C.POINTER(FdgsDepthIn), C.c_void_p, C.c_int32, C.POINTER(FdgsDepthGrads), C.c_void_p, C.c_void_p, C.c_void_p]
+    lib.fdgs_depth_loss.restype = C.c_int
+    lib.fdgs_depth_normals.argtypes = [C.POINTER(FdgsDepthIn)] + [C.c_float] * 4 + [C.c_void_p] * 4
+    lib.fdgs_depth_normals.restype = C.c_int
+    lib.fdgs_depth_normals_backward.argtypes = [C.POINTER(FdgsDepthIn)] + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.POINTER(FdgsDepthGrads),
+                                                                                             C.c_void_p]
+    lib.fdgs_depth_normals_backward.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -1015,6 +1015,55 @@ typedef struct fdgs_transform_out
 } fdgs_transform_out;
 int fdgs_model_transform(const fdgs_transform_in* in, const fdgs_transform_out* out, void* stream);
 
+/* ---- depth supervision on the rendered depth map (csrc/depth_loss.hip) ---------------------------------------------------
+ * The per-pixel depth and its validity, shared by the three calls below:
+ *   z = depth / alpha where alpha >= alpha_min (alpha == NULL: z = depth and every pixel passes); a pixel is VALID if it passes
+ *   that test, mask == NULL or mask > 0, and -- for fdgs_depth_loss -- the prior is finite and > 0.
+ * Invalid pixels contribute nothing and receive exactly 0 gradient.  Gradients go to depth and alpha: dz/dD = 1 / A,
+ * dz/dA = -D / A^2.  All on `stream`, no host synchronisation, no atomics: every output is bitwise reproducible.
+ * FDGS_ERR_INVALID_ARG before any launch: a NULL struct or required pointer, a wrong struct_size, H or W <= 0, H * W >= 2^30,
+ * H >= 16 * 65535, alpha given with alpha_min not positive and finite, d_alpha given without alpha, an unknown mode. */
+typedef struct fdgs_depth_in
+{
+	uint32_t struct_size;     /* sizeof(fdgs_depth_in)                                 */
+	int32_t H, W;
+	const float* depth;       /* [H,W]  the forward's out_depth = sum z_i alpha_i T_i  */
+	const float* alpha;       /* [H,W]  1 - T, or NULL                                 */
+	const float* mask;        /* [H,W]  or NULL                                        */
+	float alpha_min;          /* the alpha test's threshold (> 0 where alpha is given) */
+} fdgs_depth_in;
+
+typedef struct fdgs_depth_grads
+{
+	uint32_t struct_size;     /* sizeof(fdgs_depth_grads)                              */
+	float* d_depth;           /* [H,W] or NULL: not computed                           */
+	float* d_alpha;           /* [H,W] or NULL (needs fdgs_depth_in.alpha)             */
+	const float* g_upstream;  /* one float of device memory, or NULL: 1                */
+	float scale;              /* the gradient is scale * g_upstream * dL/d.            */
+	int32_t accumulate;       /* 0: written to every one of the H * W elements; else added */
+} fdgs_depth_grads;
+
+#define FDGS_DEPTH_PEARSON 0  /* L = 1 - rho(z, prior) over the valid pixels                                                   */
+#define FDGS_DEPTH_SSI 1      /* L = sum |s z + b - prior| / n with (s, b) the least-squares fit, constants for the gradient   */
+/* The value in out[0], and with `grads` != NULL its gradient.  out: 4 floats of device memory { L, n, rho, 0 } (pearson) or
+ * { L, n, s, b } (ssi).  partials: fdgs_depth_loss_num_partials(H, W) DOUBLES of device memory (the per-workgroup float64 moments
+ * n, sum z, sum p, sum z^2, sum z p, sum p^2, the ssi residual sums and the finished statistics).  Degenerate inputs -- n < 2, or a
+ * variance of z or of the prior at or below 1e-12 max(1, mean^2) -- give exactly L = 1 (pearson) or 0 (ssi) and an all-zero
+ * gradient.  pearson: dL/dz_i = -((p_i - pm) - rho (sigma_p / sigma_z) (z_i - zm)) / (n sigma_z sigma_p); ssi: s sign(r_i) / n. */
+int fdgs_depth_loss_num_partials(int32_t H, int32_t W);
+int fdgs_depth_loss(const fdgs_depth_in* in, const float* prior, int32_t mode, const fdgs_depth_grads* grads, double* partials,
+                    float* out, void* stream);
+/* Normals from the depth: pixel centres at +0.5, P(u,v) = ((u+.5-cx)/fl_x z, (v+.5-cy)/fl_y z, z), a = P(u+1,v) - P(u-1,v),
+ * b = P(u,v+1) - P(u,v-1), n = (b x a) / |b x a| (towards the camera: n_z < 0 on a fronto-parallel plane).  A normal is valid if
+ * the pixel and its four neighbours are inside the image and valid and |b x a|^2 > 1e-20; otherwise n = 0 and valid = 0.
+ * normals [3,H,W], valid [H,W] bytes.  viewmatrix != NULL (16 floats of device memory, world_view_transform as the rasterizer
+ * takes it): the normal is rotated to world space.  The backward maps dL_dnormals [3,H,W] to d_depth / d_alpha of `grads` as a
+ * gather over the four neighbouring normals of every pixel. */
+int fdgs_depth_normals(const fdgs_depth_in* in, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix, float* normals,
+                       uint8_t* valid, void* stream);
+int fdgs_depth_normals_backward(const fdgs_depth_in* in, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix,
+                                const float* dL_dnormals, const fdgs_depth_grads* grads, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
