@@ -154,6 +154,23 @@ class FdgsDepthGrads(_Sized):
 FDGS_DEPTH_PEARSON, FDGS_DEPTH_SSI = 0, 1  # include/fdgs.h
 
 
+class FdgsTsdfVolume(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("nx", C.c_int32), ("ny", C.c_int32), ("nz", C.c_int32), ("ox", C.c_float), ("oy", C.c_float),
+                ("oz", C.c_float), ("voxel_size", C.c_float), ("trunc", C.c_float), ("tsdf", _fp), ("weight", _fp), ("color", _fp),
+                ("cweight", _fp)]   # (ox, oy, oz): float origin[3]
+
+
+class FdgsTsdfView(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("H", C.c_int32), ("W", C.c_int32), ("depth", _fp), ("alpha", _fp), ("mask", _fp),
+                ("image", _fp), ("viewmatrix", _fp), ("alpha_min", C.c_float), ("fl_x", C.c_float), ("fl_y", C.c_float), ("cx", C.c_float),
+                ("cy", C.c_float), ("view_weight", C.c_float)]
+
+
+class FdgsSurfaceOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("vertex_capacity", C.c_int32), ("face_capacity", C.c_int32), ("vertices", _fp),
+                ("normals", _fp), ("colors", _fp), ("faces", _fp), ("n_vertices", _fp), ("n_faces", _fp)]
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -174,6 +191,7 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
             "fdgs_model_transform", "fdgs_depth_loss_num_partials", "fdgs_depth_loss", "fdgs_depth_normals", "fdgs_depth_normals_backward",
+            "fdgs_tsdf_integrate", "fdgs_surface_extract_scratch_bytes", "fdgs_surface_extract",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
@@ -364,6 +382,12 @@ def _load():
     lib.fdgs_depth_normals_backward.argtypes = [C.POINTER(FdgsDepthIn)] + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.POINTER(FdgsDepthGrads),
                                                                                              C.c_void_p]
     lib.fdgs_depth_normals_backward.restype = C.c_int
+    lib.fdgs_tsdf_integrate.argtypes = [C.POINTER(FdgsTsdfVolume), C.c_int32, C.POINTER(FdgsTsdfView), C.c_void_p]
+    lib.fdgs_tsdf_integrate.restype = C.c_int
+    lib.fdgs_surface_extract_scratch_bytes.argtypes = [C.c_int32] * 3
+    lib.fdgs_surface_extract_scratch_bytes.restype = C.c_size_t
+    lib.fdgs_surface_extract.argtypes = [C.POINTER(FdgsTsdfVolume), C.c_float, C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
+    lib.fdgs_surface_extract.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -1,0 +1,266 @@
+"""A coloured surface from a trained model, on the GPU (csrc/tsdf.hip): TSDF fusion of rendered depth maps and surface nets.
+
+* ``TSDFVolume(origin, voxel_size, dims)`` -- ``nx x ny x nz`` voxels of edge ``s``; voxel (i, j, k) has its centre at
+  ``origin + (i + .5, j + .5, k + .5) s``.  float32 tensors, x fastest: ``tsdf`` and ``weight`` [nz, ny, nx], optionally ``color``
+  [3, nz, ny, nx] and ``cweight`` [nz, ny, nx].  All zeros when fresh (``weight = 0``: never seen); ``reset()`` zeroes it.
+* ``integrate(volume, views)`` -- every view (``depth``, ``alpha``, ``image``, ``mask``, ``camera``, ``weight``) is applied to every
+  voxel centre in order: project with ``fdgs.depth.intrinsics_of(camera)``, keep the pixel under ``fdgs.depth``'s validity rule
+  (``alpha >= alpha_min``, ``mask > 0``, ``zp = depth / alpha`` finite and positive), ``sdf = zp - z``, skip below ``-trunc``,
+  ``d = min(1, sdf / trunc)``, a running weighted mean of ``d`` -- and of the pixel's colour where ``d < 1``.  One launch per 16 views
+  with the voxel in registers; bit-identical to one call per view.  ``tsdf`` is in units of ``trunc``.
+* ``fuse(model, cameras, pipe, bg, volume)`` renders the cameras with ``render()`` and integrates them; ``extract(volume)`` is the
+  mesh: one vertex per cell the surface crosses (surface nets: no case tables, quads between the four cells around every
+  sign-changing grid edge, vertices shared by construction), with normals from the distance gradient and colours from the volume.
+* ``prepare_views`` does the host side of ``integrate`` once (tensor checks, view matrices on the device, intrinsics) for callers that
+  integrate the same buffers repeatedly.  ``fuse_sequence`` yields one mesh per timestamp; ``save_mesh_ply`` / ``load_mesh_ply`` write and read it.
+
+Everything runs on the current stream; ``extract`` reads two counters from the device once, to size its outputs.  No atomics: two
+runs are bit-identical.  There is no CPU path.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _capi
+from .depth import intrinsics_of
+
+
+class TSDFVolume:
+    def __init__(self, origin, voxel_size, dims, trunc=None, color=True, device="cuda"):
+        self.origin = tuple(float(v) for v in origin)
+        self.voxel_size = float(voxel_size)
+        self.dims = tuple(int(v) for v in dims)          # (nx, ny, nz)
+        self.trunc = 4.0 * self.voxel_size if trunc is None else float(trunc)
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("fdgs: a TSDFVolume lives on the GPU (got %s); there is no CPU path" % (device,))
+        if len(self.origin) != 3 or len(self.dims) != 3 or min(self.dims) < 0:
+            raise ValueError("fdgs: TSDFVolume needs origin (x, y, z) and dims (nx, ny, nz) >= 0; got %s, %s" % (origin, dims))
+        nx, ny, nz = self.dims
+        self.tsdf = torch.zeros((nz, ny, nx), dtype=torch.float32, device=device)
+        self.device = self.tsdf.device                   # with its index ("cuda" -> the current device), as every tensor reports it
+        self.weight = torch.zeros_like(self.tsdf)
+        self.color = torch.zeros((3, nz, ny, nx), dtype=torch.float32, device=self.device) if color else None
+        self.cweight = torch.zeros_like(self.tsdf) if color else None
+
+    def reset(self):
+        for t in (self.tsdf, self.weight, self.color, self.cweight):
+            if t is not None:
+                t.zero_()
+
+    def arrays(self):
+        return {"tsdf": self.tsdf, "weight": self.weight, "color": self.color, "cweight": self.cweight}
+
+    @property
+    def voxels(self) -> int:
+        return self.dims[0] * self.dims[1] * self.dims[2]
+
+    def _struct(self):
+        return _capi.FdgsTsdfVolume(*self.dims, *self.origin, self.voxel_size, self.trunc, _capi._ptr(self.tsdf), _capi._ptr(self.weight),
+                                    _capi._ptr(self.color), _capi._ptr(self.cweight))
+
+
+def _field(view, key, default=None):
+    v = view.get(key, default) if isinstance(view, dict) else getattr(view, key, default)
+    return default if v is None else v
+
+
+def _image(t, name, dev, shape=None):
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+    if t.device != dev:
+        raise RuntimeError("fdgs: '%s' lives on %s, the volume on %s" % (name, t.device, dev))
+    t = t.detach().contiguous().float()
+    if shape is not None and (t.numel() != shape[0] * shape[1] or tuple(t.shape[-2:]) != shape):
+        raise ValueError("fdgs: '%s' must have the depth's [1, H, W] shape %s; got %s" % (name, shape, tuple(t.shape)))
+    return t
+
+
+class PreparedViews:
+    """Views as ``fdgs_tsdf_integrate`` takes them: the array of structs and the tensors its pointers refer to."""
+
+    def __init__(self, structs, count, device, tensors):
+        self.structs, self.count, self.device, self.tensors = structs, count, device, tensors
+
+    def __len__(self):
+        return self.count
+
+
+def prepare_views(views, device) -> PreparedViews:
+    """The host side of ``integrate``, once: checks the tensors, puts every view matrix on ``device`` and reads the intrinsics --
+    a view's own ``intrinsics`` = (fl_x, fl_y, cx, cy) where it carries them, else ``fdgs.depth.intrinsics_of(camera)`` (a host read
+    of two matrices).  ``integrate(volume, prepared)`` is then the C call alone; the views' tensors may be rewritten in place between
+    calls (a render into the same buffers)."""
+    views = list(views)
+    dev = torch.device(device)
+    keep, structs = [], (_capi.FdgsTsdfView * max(len(views), 1))()
+    for n, view in enumerate(views):
+        d = _field(view, "depth")
+        if d is None:
+            raise ValueError("fdgs: view %d has no depth" % n)
+        d = _image(d, "depth", dev)
+        if d.dim() < 2 or d.numel() != d.shape[-2] * d.shape[-1]:
+            raise ValueError("fdgs: depth must be one [1, H, W] image; got %s" % (tuple(d.shape),))
+        shape = (int(d.shape[-2]), int(d.shape[-1]))
+        a, m = _image(_field(view, "alpha"), "alpha", dev, shape), _image(_field(view, "mask"), "mask", dev, shape)
+        img = _image(_field(view, "image"), "image", dev)
+        if img is not None and tuple(img.shape) != (3,) + shape:
+            raise ValueError("fdgs: image must be [3, H, W] = %s; got %s" % ((3,) + shape, tuple(img.shape)))
+        cam = _field(view, "camera")
+        if cam is None:
+            raise ValueError("fdgs: view %d has no camera" % n)
+        get = (lambda k: cam.get(k)) if isinstance(cam, dict) else (lambda k: getattr(cam, k, None))
+        vm = get("world_view_transform")
+        if vm is None:
+            raise ValueError("fdgs: the camera of view %d has no world_view_transform" % n)
+        vm = vm.detach().to(dev, torch.float32).contiguous()
+        intr = _field(view, "intrinsics")
+        fx, fy, cx, cy = (float(v) for v in intr) if intr is not None else intrinsics_of(cam)
+        keep.append((d, a, m, img, vm))
+        structs[n] = _capi.FdgsTsdfView(shape[0], shape[1], d.data_ptr(), _capi._ptr(a), _capi._ptr(m), _capi._ptr(img), vm.data_ptr(),
+                                        float(_field(view, "alpha_min", 0.5)), fx, fy, cx, cy, float(_field(view, "weight", 1.0)))
+    return PreparedViews(structs, len(views), dev, keep)
+
+
+def integrate(volume: TSDFVolume, views) -> None:
+    """Fuses ``views`` -- dicts or objects with ``depth`` [1, H, W], ``camera`` and optionally ``alpha``, ``mask`` (both [1, H, W]),
+    ``image`` [3, H, W], ``weight`` (1.0), ``alpha_min`` (0.5) and ``intrinsics``, or a ``PreparedViews`` -- into ``volume``, in
+    order, in one call."""
+    dev = volume.device
+    if not isinstance(views, PreparedViews):
+        views = prepare_views(views, dev)
+    elif views.device != dev:
+        raise RuntimeError("fdgs: the views were prepared for %s, the volume lives on %s" % (views.device, dev))
+    if volume.voxels == 0 or len(views) == 0:
+        return
+    vol = volume._struct()
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_tsdf_integrate(C.byref(vol), len(views), views.structs, _capi.current_stream_handle(dev))
+    _capi._check(rc, "fdgs_tsdf_integrate")
+
+
+@torch.no_grad()
+def fuse(model, cameras, pipe, bg, volume: TSDFVolume, *, alpha_min: float = 0.5, masks=None, intrinsics=None) -> TSDFVolume:
+    """Renders every camera with ``render()`` and integrates depth, alpha and colour of all of them into ``volume`` in one call.
+    ``masks``: one [1, H, W] tensor (or None) per camera.  ``intrinsics``: one ``intrinsics_of(camera)`` per camera, for callers that
+    fuse the same rig again and again (``fuse_sequence``); default: read from the cameras here."""
+    from .gaussian_renderer import render
+    cameras = list(cameras)
+    if masks is not None and len(masks) != len(cameras):
+        raise ValueError("fdgs: fuse needs one mask (or None) per camera")
+    if intrinsics is not None and len(intrinsics) != len(cameras):
+        raise ValueError("fdgs: fuse needs one intrinsics tuple per camera")
+    views = []
+    for n, cam in enumerate(cameras):
+        pkg = render(cam, model, pipe, bg)
+        views.append({"depth": pkg["depth"], "alpha": pkg["alpha"], "image": pkg["render"], "mask": None if masks is None else masks[n],
+                      "camera": cam, "alpha_min": alpha_min, "intrinsics": None if intrinsics is None else intrinsics[n]})
+    integrate(volume, views)
+    return volume
+
+
+@dataclass
+class Mesh:
+    vertices: torch.Tensor   # [V, 3] float32
+    normals: torch.Tensor    # [V, 3] float32, unit (towards growing distance: out of the surface) or 0
+    colors: torch.Tensor     # [V, 3] float32
+    faces: torch.Tensor      # [F, 3] int32
+
+
+def _extract_call(volume, min_weight, counts, scratch, vcap=0, fcap=0, vertices=None, normals=None, colors=None, faces=None):
+    dev = volume.device
+    out = _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
+                               counts.data_ptr(), counts.data_ptr() + 4)
+    vol = volume._struct()
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_surface_extract(C.byref(vol), float(min_weight), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
+    _capi._check(rc, "fdgs_surface_extract")
+
+
+def extract(volume: TSDFVolume, min_weight: float = 1.0) -> Mesh:
+    """The surface-nets mesh of the voxels with ``weight >= min_weight``: a count pass, one read of the two counters, exact
+    allocation, the emitting pass."""
+    dev = volume.device
+    if volume.voxels == 0:
+        return Mesh(torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.float32, device=dev),
+                    torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev))
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    scratch = torch.empty(max(int(_capi.lib.fdgs_surface_extract_scratch_bytes(*volume.dims)), 256), dtype=torch.uint8, device=dev)
+    _extract_call(volume, min_weight, counts, scratch)
+    V, F = (int(v) for v in counts.cpu())
+    mesh = Mesh(torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((V, 3), dtype=torch.float32, device=dev),
+                torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((F, 3), dtype=torch.int32, device=dev))
+    if V > 0:
+        _extract_call(volume, min_weight, counts, scratch, V, F, mesh.vertices, mesh.normals, mesh.colors, mesh.faces)
+    return mesh
+
+
+def fuse_sequence(model, cameras, pipe, bg, volume: TSDFVolume, timestamps, *, alpha_min: float = 0.5, min_weight: float = 1.0):
+    """Yields one ``Mesh`` per timestamp: the cameras moved to that time (``fdgs.playback.with_timestamp``), fused into the one
+    ``volume`` -- reset in between -- and extracted.  The cameras' intrinsics are read once, not per timestamp."""
+    from .playback import with_timestamp
+    cameras = list(cameras)
+    intrinsics = [intrinsics_of(c) for c in cameras]
+    for t in timestamps:
+        volume.reset()
+        fuse(model, [with_timestamp(c, t) for c in cameras], pipe, bg, volume, alpha_min=alpha_min, intrinsics=intrinsics)
+        yield extract(volume, min_weight)
+
+
+# ---- PLY: a triangle mesh, binary little-endian as fdgs.slice's files ----
+_VERTEX = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                    ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+_FACE = np.dtype([("n", "u1"), ("v", "<i4", (3,))])
+
+
+def save_mesh_ply(path, mesh: Mesh) -> None:
+    """Binary little-endian PLY: vertices x y z nx ny nz + uchar red green blue (the colour clamped to [0, 1], times 255, rounded),
+    faces as ``vertex_indices`` lists of three int32."""
+    cpu = lambda t: t.detach().cpu().numpy()  # noqa: E731
+    V, F = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    vert = np.zeros(V, _VERTEX)
+    xyz, nrm = cpu(mesh.vertices), cpu(mesh.normals)
+    for k, name in enumerate(("x", "y", "z")):
+        vert[name] = xyz[:, k]
+        vert["n" + name] = nrm[:, k]
+    rgb = np.floor(np.clip(np.nan_to_num(cpu(mesh.colors).astype(np.float64)), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8)
+    vert["red"], vert["green"], vert["blue"] = rgb[:, 0], rgb[:, 1], rgb[:, 2]
+    face = np.zeros(F, _FACE)
+    face["n"] = 3
+    face["v"] = cpu(mesh.faces)
+    header = "ply\nformat binary_little_endian 1.0\nelement vertex %d\n" % V
+    header += "".join("property float %s\n" % n for n in ("x", "y", "z", "nx", "ny", "nz"))
+    header += "".join("property uchar %s\n" % n for n in ("red", "green", "blue"))
+    header += "element face %d\nproperty list uchar int vertex_indices\nend_header\n" % F
+    with open(path, "wb") as fh:
+        fh.write(header.encode("ascii"))
+        fh.write(vert.tobytes())
+        fh.write(face.tobytes())
+
+
+def load_mesh_ply(path, device) -> Mesh:
+    """The mesh of a PLY in the layout ``save_mesh_ply`` writes; colours come back as ``byte / 255``."""
+    with open(path, "rb") as fh:
+        data = fh.read()
+    end = data.index(b"end_header\n") + len(b"end_header\n")
+    lines = data[:end].decode("ascii").split("\n")
+    if lines[0] != "ply" or "format binary_little_endian 1.0" not in lines:
+        raise ValueError("load_mesh_ply: %s is not a binary little-endian PLY" % path)
+    props = [ln for ln in lines if ln.startswith(("element", "property"))]
+    V = next(int(ln.split()[2]) for ln in lines if ln.startswith("element vertex"))
+    F = next((int(ln.split()[2]) for ln in lines if ln.startswith("element face")), 0)
+    want = (["element vertex %d" % V] + ["property float %s" % n for n in ("x", "y", "z", "nx", "ny", "nz")]
+            + ["property uchar %s" % n for n in ("red", "green", "blue")] + ["element face %d" % F, "property list uchar int vertex_indices"])
+    if props != want:
+        raise ValueError("load_mesh_ply: %s is not in the layout save_mesh_ply writes" % path)
+    vert = np.frombuffer(data, _VERTEX, count=V, offset=end)
+    face = np.frombuffer(data, _FACE, count=F, offset=end + V * _VERTEX.itemsize)
+    if F and not (face["n"] == 3).all():
+        raise ValueError("load_mesh_ply: only triangles are supported")
+    t = lambda a, dt: torch.from_numpy(np.array(a)).to(dt).to(device)  # noqa: E731
+    return Mesh(t(np.stack([vert["x"], vert["y"], vert["z"]], 1), torch.float32), t(np.stack([vert["nx"], vert["ny"], vert["nz"]], 1), torch.float32),
+                t(np.stack([vert["red"], vert["green"], vert["blue"]], 1).astype(np.float32) / np.float32(255.0), torch.float32),
+                t(face["v"].copy().reshape(F, 3), torch.int32))

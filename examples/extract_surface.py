@@ -1,0 +1,226 @@
+"""A coloured triangle mesh per timestamp of a 4D model: render a camera rig at N timestamps, fuse each set of depth maps into a
+TSDF volume (fdgs.surface.fuse), pull the surface out (extract, surface nets) and write it as a PLY any mesh viewer opens.
+
+    python examples/extract_surface.py --frames 4 --out meshes/surface
+    python examples/extract_surface.py --checkpoint chkpnt100.pth --workload C2 --frames 4 --out meshes/surface
+    python examples/extract_surface.py --bench     256^3 voxels, 16 views of 1352 x 1014: one call, 16 calls, the PyTorch formulation
+
+--bench: integrate moves the volume (distance, weight, colour, colour weight: 24 B per voxel) in and out once per launch; one call
+takes all 16 views in one launch, sixteen one-view calls take sixteen.  The views are prepared once (fdgs.surface.prepare_views), so
+the timed windows hold the C calls alone, 20 passes back to back.  GB/s is that volume traffic over the time (the gathers from the
+views' images come on top and are not counted).  --kernel-only one | each runs one path alone, for a kernel trace.
+"""
+import argparse, json, os, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+
+POSES = ("axis", "rig0", "rig1", "rig2", "rig3")
+
+
+def cameras_for(scene, dev, poses=POSES):
+    from fdgs import synth, train_host
+    return [train_host.SyntheticCamera(dict(scene, **synth.camera_for(p, scene["W"], scene["H"])), dev) for p in poses]
+
+
+def run(dev, frames=4, out=None, W=200, H=152, P=4000, s0=0.08, dims=64, extent=1.4, seed=0, model=None, scene=None, log=print):
+    """Fuses the rig at ``frames`` timestamps of a fdgs.synth scene (or ``model``) and returns [(timestamp, Mesh)]; with ``out`` one
+    PLY per timestamp is written to <out>_0000.ply ..."""
+    from fdgs import surface, synth, train_host
+    if scene is None:
+        scene = synth.make_scene(synth.SceneConfig("surface", P, W, H, 1, 0, s0, 1.0, True, 4, True), seed=seed)
+    if model is None:
+        model = train_host.GaussianParams(scene, dev)
+    pipe, bg = train_host.PipelineFlags(), scene["bg"].to(dev)
+    cams = cameras_for(scene, dev)
+    s = 2.0 * extent / dims
+    volume = surface.TSDFVolume((-extent, -extent, -extent), s, (dims, dims, dims), device=dev)
+    t0, t1 = model.time_duration
+    stamps = [t0 + (t1 - t0) * (k + 0.5) / frames for k in range(frames)]
+    meshes = []
+    if out:
+        os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+    for k, mesh in enumerate(surface.fuse_sequence(model, cams, pipe, bg, volume, stamps)):
+        meshes.append((stamps[k], mesh))
+        line = "t = %.4f: %d vertices, %d faces" % (stamps[k], mesh.vertices.shape[0], mesh.faces.shape[0])
+        if out:
+            path = "%s_%04d.ply" % (out, k)
+            surface.save_mesh_ply(path, mesh)
+            line = path + ": " + line
+        if log:
+            log(line)
+    return meshes
+
+
+# ---- the PyTorch formulation of the same update (float32, on the GPU), for --bench ----
+def torch_integrate(arrays, origin, s, trunc, dims, view):
+    tsdf, weight, color, cweight = arrays
+    nx, ny, nz = dims
+    dev = tsdf.device
+    ax = lambda n, o: o + (torch.arange(n, dtype=torch.float32, device=dev) + 0.5) * s  # noqa: E731
+    pz, py, px = torch.meshgrid(ax(nz, origin[2]), ax(ny, origin[1]), ax(nx, origin[0]), indexing="ij")
+    m = view["vm"]
+    x = m[0, 0] * px + m[1, 0] * py + m[2, 0] * pz + m[3, 0]
+    y = m[0, 1] * px + m[1, 1] * py + m[2, 1] * pz + m[3, 1]
+    z = m[0, 2] * px + m[1, 2] * py + m[2, 2] * pz + m[3, 2]
+    H, W = view["depth"].shape[-2:]
+    live = z > 0.2
+    zs = torch.where(live, z, torch.ones_like(z))
+    fu, fv = torch.floor(view["fl_x"] * x / zs + view["cx"]), torch.floor(view["fl_y"] * y / zs + view["cy"])
+    live &= (fu >= 0) & (fu < W) & (fv >= 0) & (fv < H)
+    pix = (torch.where(live, fv, torch.zeros_like(fv)) * W + torch.where(live, fu, torch.zeros_like(fu))).long()
+    a = view["alpha"].reshape(-1)[pix]
+    live &= a >= view["alpha_min"]
+    zp = view["depth"].reshape(-1)[pix] / torch.where(live, a, torch.ones_like(a))
+    live &= torch.isfinite(zp) & (zp > 0)
+    sdf = zp - z
+    live &= sdf >= -trunc
+    d = torch.clamp(sdf / trunc, max=1.0)
+    w = view["weight"]
+    tsdf.copy_(torch.where(live, (weight * tsdf + w * d) / (weight + w), tsdf))
+    weight.add_(live.float() * w)
+    lc = live & (d < 1)
+    img = view["image"].reshape(3, -1)
+    for c in range(3):
+        color[c].copy_(torch.where(lc, (cweight * color[c] + w * img[c][pix]) / (cweight + w), color[c]))
+    cweight.add_(lc.float() * w)
+
+
+def bench_inputs(dev, dims=256, nviews=16, W=1352, H=1014):
+    from fdgs import surface, synth
+    extent = 1.3
+    s = 2.0 * extent / dims
+    volume = surface.TSDFVolume((-extent, -extent, -extent), s, (dims, dims, dims), device=dev)
+    g = torch.Generator().manual_seed(0)
+    names = list(synth.POSES)
+    views, tviews = [], []
+    for n in range(nviews):
+        pose = dict(synth.POSES[names[n % len(names)]])
+        pose["yaw"] = pose.get("yaw", 0.0) + 0.02 * (n // len(names))
+        cam = synth.camera_for(pose, W, H)
+        z = 4.0 + 0.4 * torch.rand(1, H, W, generator=g)
+        alpha = (0.4 + 0.6 * torch.rand(1, H, W, generator=g))
+        v = {"depth": (z * alpha).to(dev), "alpha": alpha.to(dev), "image": torch.rand(3, H, W, generator=g).to(dev), "camera": cam}
+        views.append(v)
+        fx, fy, cx, cy = surface.intrinsics_of(cam)
+        tviews.append(dict(v, vm=cam["world_view_transform"].to(dev), fl_x=fx, fl_y=fy, cx=cx, cy=cy, alpha_min=0.5, weight=1.0))
+    return volume, views, tviews
+
+
+def kernel_only(dev, path, passes=10):
+    """``passes`` passes of one path and nothing else, for a kernel trace of its own: "one" = 16 views per launch, "each" = one view
+    per launch (16 launches per pass).  The views are prepared before the first launch."""
+    from fdgs import surface
+    volume, views, _ = bench_inputs(dev)
+    prepared = [surface.prepare_views(views, dev)] if path == "one" else [surface.prepare_views([v], dev) for v in views]
+    torch.cuda.synchronize(dev)
+    for _ in range(passes):
+        for p in prepared:
+            surface.integrate(volume, p)
+    torch.cuda.synchronize(dev)
+    print("%d passes of %d launch(es)" % (passes, len(prepared)))
+
+
+def bench(dev, dims=256, nviews=16, W=1352, H=1014, passes=20):
+    """Integration: the C call alone -- the views prepared once outside the timed window (``prepare_views``) -- ``passes`` passes
+    back to back between two events, three windows, the median per pass; the volume keeps accumulating (the work per voxel and view
+    does not depend on what it holds).  These are stream times of back-to-back launches, not kernel times: a kernel trace
+    (``--kernel-only one`` / ``each`` under a profiler) gives those.  ``integrate_call_with_preparation_ms`` is one
+    ``integrate(volume, views)`` on unprepared views, host work included."""
+    from fdgs import surface
+    volume, views, tviews = bench_inputs(dev, dims, nviews, W, H)
+    s = volume.voxel_size
+    one = surface.prepare_views(views, dev)
+    each = [surface.prepare_views([v], dev) for v in views]
+
+    def window(fn, reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        torch.cuda.synchronize(dev)
+        return a.elapsed_time(b) * 1e-3 / reps
+
+    def timed(fn, reps, windows=3):
+        fn()
+        torch.cuda.synchronize(dev)
+        return sorted(window(fn, reps) for _ in range(windows))
+
+    def one_by_one():
+        for p in each:
+            surface.integrate(volume, p)
+
+    def torch_all():
+        with torch.no_grad():
+            for v in tviews:
+                torch_integrate((volume.tsdf, volume.weight, volume.color, volume.cweight), volume.origin, s, volume.trunc, volume.dims, v)
+
+    t_one = timed(lambda: surface.integrate(volume, one), passes)
+    t_each = timed(one_by_one, passes)
+    t_call = timed(lambda: surface.integrate(volume, views), 1, windows=5)
+    # one pass of each path from a fresh volume: the same bits, and the PyTorch formulation's distance from them
+    volume.reset()
+    surface.integrate(volume, one)
+    seen = float((volume.weight > 0).float().mean())
+    ref = {k: v.clone() for k, v in volume.arrays().items()}
+    volume.reset()
+    one_by_one()
+    same = all(torch.equal(ref[k], v) for k, v in volume.arrays().items())
+    volume.reset()
+    torch_all()
+    gap = float((volume.tsdf - ref["tsdf"]).abs().max())
+    t_torch = timed(torch_all, 1, windows=3)
+    volume.reset()
+    surface.integrate(volume, one)
+    mesh = surface.extract(volume)
+    torch.cuda.synchronize(dev)
+    t_ext = sorted(window(lambda: surface.extract(volume), 1) for _ in range(5))
+    vol_bytes = 2 * 24 * dims ** 3
+    med = lambda v: v[len(v) // 2]   # noqa: E731
+    rng = lambda v: [round(v[0] * 1e3, 3), round(v[-1] * 1e3, 3)]   # noqa: E731
+    res = {"voxels": dims ** 3, "views": nviews, "image": [W, H], "seen_fraction": round(seen, 3), "passes_per_window": passes,
+           "integrate_one_call_ms": round(med(t_one) * 1e3, 3), "integrate_one_call_ms_range": rng(t_one),
+           "integrate_one_call_GBps_of_volume": round(vol_bytes / med(t_one) * 1e-9, 1),
+           "integrate_16_calls_ms": round(med(t_each) * 1e3, 3), "integrate_16_calls_ms_range": rng(t_each),
+           "integrate_16_calls_GBps_of_volume": round(nviews * vol_bytes / med(t_each) * 1e-9, 1),
+           "integrate_call_with_preparation_ms": round(med(t_call) * 1e3, 3), "integrate_call_with_preparation_ms_range": rng(t_call),
+           "one_call_equals_16_calls_bitwise": same,
+           "torch_formulation_ms": round(med(t_torch) * 1e3, 3), "torch_max_tsdf_gap": gap,
+           "extract_ms": round(med(t_ext) * 1e3, 3), "extract_ms_range": rng(t_ext),
+           "vertices": int(mesh.vertices.shape[0]), "faces": int(mesh.faces.shape[0])}
+    print(json.dumps(res))
+    return res
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default=None, help="a fdgs.synth workload (C1, C2, ...) instead of the small default scene")
+    ap.add_argument("--checkpoint", default=None, help="a checkpoint (fdgs.checkpoint / the reference's layout) of that workload")
+    ap.add_argument("--frames", type=int, default=4, help="timestamps, evenly spaced over the model's duration")
+    ap.add_argument("--dims", type=int, default=64, help="voxels per axis")
+    ap.add_argument("--out", default="surface", help="prefix: <out>_0000.ply ...")
+    ap.add_argument("--bench", action="store_true")
+    ap.add_argument("--kernel-only", choices=("one", "each"), default=None, help="ten passes of one integration path alone, for a kernel trace")
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    if args.kernel_only:
+        kernel_only(dev, args.kernel_only)
+        return
+    if args.bench:
+        bench(dev)
+        return
+    model = scene = None
+    if args.workload:
+        from fdgs import checkpoint, synth
+        cfg = synth.CONFIGS[args.workload]
+        scene = synth.make_scene(cfg, seed=0)
+        if args.checkpoint:
+            model, _opt, _stats, it = checkpoint.load(args.checkpoint, dev, sh_degree=cfg.sh_degree, sh_degree_t=cfg.sh_degree_t,
+                                                      time_duration=[0.0, cfg.duration], force_sh_3d=cfg.force_sh_3d)
+            print("loaded %s: %d Gaussians after %d iterations" % (args.checkpoint, model.P, it))
+    run(dev, frames=args.frames, out=args.out, dims=args.dims, model=model, scene=scene)
+
+
+if __name__ == "__main__":
+    main()

@@ -1064,6 +1064,79 @@ int fdgs_depth_normals(const fdgs_depth_in* in, float fl_x, float fl_y, float cx
 int fdgs_depth_normals_backward(const fdgs_depth_in* in, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix,
                                 const float* dL_dnormals, const fdgs_depth_grads* grads, void* stream);
 
+/* ---- a surface from depth maps: TSDF fusion and surface nets (csrc/tsdf.hip) ------------------------------------------------
+ * The volume: nx x ny x nz voxels of edge voxel_size; voxel (i, j, k) has its centre at origin + (i + .5, j + .5, k + .5) voxel_size.
+ * float32 arrays, x fastest: tsdf [nz,ny,nx], weight [nz,ny,nx], and optionally color [3,nz,ny,nx] with cweight [nz,ny,nx].  A fresh
+ * volume is all zeros (weight 0: never seen); resetting it is a memset.  tsdf holds the distance in units of `trunc`, in [-1, 1].
+ * FDGS_ERR_INVALID_ARG before any launch (all three calls): a NULL or mis-sized struct, NULL tsdf / weight, a negative size,
+ * nx ny nz >= 2^28, voxel_size or trunc not positive and finite, a non-finite origin, color and cweight not given together. */
+typedef struct fdgs_tsdf_volume
+{
+	uint32_t struct_size;     /* sizeof(fdgs_tsdf_volume)                              */
+	int32_t nx, ny, nz;
+	float origin[3];          /* the corner of voxel (0, 0, 0)                         */
+	float voxel_size;         /* s > 0                                                 */
+	float trunc;              /* truncation distance > 0                               */
+	float* tsdf;
+	float* weight;
+	float* color;             /* or NULL                                               */
+	float* cweight;           /* with color                                            */
+} fdgs_tsdf_volume;
+
+typedef struct fdgs_tsdf_view
+{
+	uint32_t struct_size;     /* sizeof(fdgs_tsdf_view)                                */
+	int32_t H, W;
+	const float* depth;       /* [H,W]  the forward's out_depth                        */
+	const float* alpha;       /* [H,W]  or NULL: the pixel depth is `depth` itself     */
+	const float* mask;        /* [H,W]  or NULL                                        */
+	const float* image;       /* [3,H,W] or NULL: this view carries no colour          */
+	const float* viewmatrix;  /* 16 floats of device memory, as fdgs_depth_normals takes it */
+	float alpha_min;          /* > 0 where alpha is given                              */
+	float fl_x, fl_y, cx, cy; /* pixel (i, j) covers [i, i + 1) x [j, j + 1)           */
+	float view_weight;        /* w > 0                                                 */
+} fdgs_tsdf_view;
+
+/* Applies `views[0 .. num_views)` in ascending order to every voxel centre c:
+ *   (x, y, z) = c in view space; skip the view if z <= 0.2 (the rasterizer's near plane);
+ *   u = fl_x x / z + cx, v = fl_y y / z + cy, the pixel is (floor(u), floor(v)); skip if it is outside the image;
+ *   skip unless alpha >= alpha_min and mask > 0 there (each where given); zp = depth / alpha (or depth); skip unless 0 < zp < inf;
+ *   sdf = zp - z; skip if sdf < -trunc; d = min(1, sdf / trunc);
+ *   tsdf = (weight tsdf + w d) / (weight + w), weight += w;   and, where the volume has colour, the view an image and d < 1, the same
+ *   running mean of the pixel's colour with cweight.
+ * One thread owns a voxel, no atomics; up to 16 views are applied per pass over the volume with the voxel in registers, and the
+ * result is bit-identical to one call per view.  A voxel no view reaches is not written.  Further INVALID_ARG: num_views < 0,
+ * NULL views with num_views > 0, and per view a wrong struct_size, H or W <= 0, H W >= 2^30, NULL depth or viewmatrix, alpha with
+ * alpha_min not positive and finite, fl_x / fl_y not positive and finite, cx / cy not finite, view_weight not positive and finite. */
+int fdgs_tsdf_integrate(const fdgs_tsdf_volume* volume, int32_t num_views, const fdgs_tsdf_view* views, void* stream);
+
+typedef struct fdgs_surface_out
+{
+	uint32_t struct_size;     /* sizeof(fdgs_surface_out)                              */
+	int32_t vertex_capacity;  /* rows of vertices / normals / colors                   */
+	int32_t face_capacity;    /* rows of faces                                         */
+	float* vertices;          /* [vertex_capacity,3] or NULL                           */
+	float* normals;           /* [vertex_capacity,3] or NULL                           */
+	float* colors;            /* [vertex_capacity,3] or NULL (0 without volume colour) */
+	int32_t* faces;           /* [face_capacity,3] vertex indices, or NULL             */
+	int32_t* n_vertices;      /* one int32 of device memory: always the full count     */
+	int32_t* n_faces;         /* likewise, in triangles                                */
+} fdgs_surface_out;
+
+/* Surface nets.  Cells are the (nx-1)(ny-1)(nz-1) cubes whose corners are voxel centres; a corner is KNOWN if weight >= min_weight
+ * and weight > 0, INSIDE if tsdf < 0; a cell is ACTIVE if all eight corners are known and not all on one side.  One vertex per active
+ * cell in ascending cell index (x fastest): the mean of the linear crossing points t = a / (a - b) of the cell's sign-changing edges,
+ * the mean of the corner colours interpolated at them, and the normalised trilinear gradient of tsdf at the cell centre (0 where its
+ * squared length is <= 1e-20).  One quad -- triangles (c0, c1, c2), (c0, c2, c3) -- per grid edge (from voxel index e along axis a)
+ * whose two ends are known and differ in sign and whose four surrounding cells exist and are active, in ascending 3 e + a, wound so
+ * that the geometric normal points from the inside end to the outside end.
+ * With vertices, normals, colors and faces all NULL the call only counts; otherwise rows below the capacities are written and the
+ * counts are still the full ones.  scratch: fdgs_surface_extract_scratch_bytes(nx, ny, nz) bytes (a cell-to-vertex int32 map and
+ * per-workgroup counts).  A volume with a dimension < 2 gives 0 and 0 without a kernel.  Further INVALID_ARG: NULL out / n_vertices /
+ * n_faces / scratch, a wrong struct_size, negative capacities, a min_weight that is NaN. */
+size_t fdgs_surface_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_weight, const fdgs_surface_out* out, void* scratch, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
