@@ -171,6 +171,21 @@ class FdgsSurfaceOut(_Sized):
                 ("normals", _fp), ("colors", _fp), ("faces", _fp), ("n_vertices", _fp), ("n_faces", _fp)]
 
 
+class FdgsMeshIn(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("V", C.c_int32), ("F", C.c_int32), ("vertices", _fp), ("normals", _fp), ("colors", _fp),
+                ("faces", _fp)]
+
+
+class FdgsMeshComponentsOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("capacity", C.c_int32), ("labelled", C.c_int32), ("vertex_component", _fp), ("n_components", _fp),
+                ("component_vertices", _fp), ("component_faces", _fp), ("rounds", C.POINTER(C.c_int32))]   # rounds: host memory
+
+
+class FdgsMeshSmoothOut(_Sized):
+    _fields_ = [("struct_size", C.c_uint32), ("iterations", C.c_int32), ("lam", C.c_float), ("mu", C.c_float), ("pin_boundary", C.c_int32),
+                ("vertices", _fp), ("normals", _fp), ("boundary", _fp)]   # lam: float lambda
+
+
 class FdgsAdamSegment(C.Structure):
     _fields_ = [("begin", C.c_int64), ("end", C.c_int64), ("lr", C.c_float), ("lr_head", C.c_float),
                 ("period", C.c_int32), ("head", C.c_int32)]
@@ -192,6 +207,8 @@ EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasteriz
             "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
             "fdgs_model_transform", "fdgs_depth_loss_num_partials", "fdgs_depth_loss", "fdgs_depth_normals", "fdgs_depth_normals_backward",
             "fdgs_tsdf_integrate", "fdgs_surface_extract_scratch_bytes", "fdgs_surface_extract",
+            "fdgs_mesh_components_scratch_bytes", "fdgs_mesh_components", "fdgs_mesh_compact_scratch_bytes", "fdgs_mesh_compact",
+            "fdgs_mesh_smooth_scratch_bytes", "fdgs_mesh_smooth",
             "fdgs_last_error", "fdgs_version")
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
@@ -388,6 +405,15 @@ def _load():
     lib.fdgs_surface_extract_scratch_bytes.restype = C.c_size_t
     lib.fdgs_surface_extract.argtypes = [C.POINTER(FdgsTsdfVolume), C.c_float, C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
     lib.fdgs_surface_extract.restype = C.c_int
+    for name in ("components", "compact", "smooth"):
+        fn = getattr(lib, "fdgs_mesh_%s_scratch_bytes" % name)
+        fn.argtypes, fn.restype = [C.c_int32, C.c_int32], C.c_size_t
+    lib.fdgs_mesh_components.argtypes = [C.POINTER(FdgsMeshIn), C.POINTER(FdgsMeshComponentsOut), C.c_void_p, C.c_void_p]
+    lib.fdgs_mesh_components.restype = C.c_int
+    lib.fdgs_mesh_compact.argtypes = [C.POINTER(FdgsMeshIn), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
+    lib.fdgs_mesh_compact.restype = C.c_int
+    lib.fdgs_mesh_smooth.argtypes = [C.POINTER(FdgsMeshIn), C.POINTER(FdgsMeshSmoothOut), C.c_void_p, C.c_void_p]
+    lib.fdgs_mesh_smooth.restype = C.c_int
     lib.fdgs_last_error.restype = C.c_char_p
     lib.fdgs_version.restype = C.c_int
     if lib.fdgs_version() != FDGS_VERSION:

@@ -1,0 +1,610 @@
+// mesh.hip -- cleaning and smoothing the meshes fdgs_surface_extract leaves on the device (gfx950): connected components
+// (fdgs_mesh_components), component filtering with order-preserving compaction (fdgs_mesh_compact) and Taubin smoothing with
+// recomputed normals (fdgs_mesh_smooth).  Conventions: include/fdgs.h.  A face with an index outside [0, V) is absent everywhere:
+// face_present() is the one place that reads a face's indices before they are used as addresses.
+//
+// Components.  A lock-free union-find over parent[V] (parent[v] <= v always; a root is its own parent):
+//   hook      one lane per face: unite (a, b) and (a, c).  unite = find both roots, compare-and-swap the larger root onto the
+//             smaller; a failed swap returns that root's new, strictly smaller parent and the retry goes on from there -- every loop
+//             here walks a strictly decreasing chain of indices, none waits for another thread.  find halves paths as it goes.
+//   (host)    reads one flag: did any face see two different roots?  No: done.  Yes: compress, hook again (the check) -- 32 at most.
+//   compress  one lane per vertex: parent[v] = its root (the only store to parent[v] in that launch)
+// One hook pass unites everything (the swap is the linearisation point), so the second finds nothing to do; the result is checked
+// on the device whatever the memory system did in between.  A component's root is its smallest index, whatever the schedule.
+//   roots / scan / rank / assign   dense ids = the flag scan of "v is a root"
+//   vertex count / face count      wave-aggregated integer atomics; all a `labelled` call runs (ids from an earlier call)
+//
+// Compaction, shaped as tsdf.hip's extraction: flags + counts per workgroup (vertices, faces), one scan launch, emit, emit.
+//
+// Smoothing.  pairs (vertex, 3 face + corner) -> radix_sort_pairs by vertex (stable: rows in ascending 3 face + corner; absent faces'
+// corners carry the key V and end up behind every row) -> row starts by binary search -> the two other corners of every incidence,
+// once -> boundary flags, once -> 2 x iterations passes between two position buffers, one lane per vertex summing its row in order
+// -> normals.  Float32 in the operation order of the written statement (built with FP contraction off).  No float atomics.
+#include "fdgs_common.h"
+#include "block_scan.h"
+#include <math.h>
+#include <stdio.h>
+
+namespace fdgs
+{
+	constexpr int MESH_THREADS = 256;
+	constexpr int MESH_SCAN_THREADS = 1024;
+	constexpr int MESH_MAX = 1 << 28;                    // V, F below it: 3 F and 3 face + corner stay int32
+	constexpr int MESH_MAX_ROUNDS = 32;
+
+	__device__ __forceinline__ bool face_present(const int32_t* __restrict__ faces, int f, int V, int& a, int& b, int& c)
+	{
+		a = faces[3 * (size_t)f + 0]; b = faces[3 * (size_t)f + 1]; c = faces[3 * (size_t)f + 2];
+		return (uint32_t)a < (uint32_t)V && (uint32_t)b < (uint32_t)V && (uint32_t)c < (uint32_t)V;
+	}
+
+	// ---- components ----
+	// parent[] is read and written by many workgroups in one launch: every access is a relaxed agent-scope atomic (no stale cache line)
+	__device__ __forceinline__ int cc_load(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+	__device__ __forceinline__ void cc_store(int32_t* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+	// the root above x.  x strictly decreases: at most x steps.  halve: x's parent becomes its grandparent (an ancestor either way)
+	template <bool HALVE>
+	__device__ __forceinline__ int cc_find(int32_t* parent, int x)
+	{
+		int p = cc_load(parent + x);
+		while (p != x)
+		{
+			const int g = cc_load(parent + p);
+			if (HALVE && g != p) cc_store(parent + x, g);
+			x = p;
+			p = g;
+		}
+		return x;
+	}
+
+	// true if a and b were under different roots when looked at
+	__device__ __forceinline__ bool cc_unite(int32_t* parent, int a, int b)
+	{
+		int ra = cc_find<true>(parent, a), rb = cc_find<true>(parent, b);
+		const bool differed = ra != rb;
+		while (ra != rb)
+		{
+			const int hi = ra > rb ? ra : rb, lo = ra > rb ? rb : ra;
+			const int old = atomicCAS(parent + hi, hi, lo);
+			if (old == hi) break;                            // hi was still a root and now hangs under lo
+			ra = cc_find<true>(parent, old);                 // old < hi: max(ra, rb) went down
+			rb = cc_find<true>(parent, lo);
+		}
+		return differed;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) cc_init_kernel(int32_t* __restrict__ parent, const int V)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v < V) parent[v] = v;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) cc_hook_kernel(const int32_t* __restrict__ faces, const int F, const int V, int32_t* parent,
+	                                                               int32_t* changed)
+	{
+		const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
+		int a, b, c;
+		if (f >= F || !face_present(faces, f, V, a, b, c)) return;
+		const bool ab = cc_unite(parent, a, b), ac = cc_unite(parent, a, c);
+		if (ab || ac) cc_store(changed, 1);
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) cc_compress_kernel(int32_t* parent, const int V)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v < V) cc_store(parent + v, cc_find<false>(parent, v));
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) cc_roots_kernel(const int32_t* __restrict__ parent, const int V, uint32_t* __restrict__ counts)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		uint32_t total;
+		block_rank<MESH_THREADS>(v < V && parent[v] == v ? 1u : 0u, s_wave, total);
+		if (threadIdx.x == 0) counts[blockIdx.x] = total;
+	}
+
+	// one workgroup per count array: exclusive scan in place, the total to totals[blockIdx.x]
+	struct ScanJobs { uint32_t* counts[2]; int n[2]; int32_t* totals[2]; };
+	__global__ void __launch_bounds__(MESH_SCAN_THREADS) mesh_scan_kernel(const ScanJobs jobs)
+	{
+		__shared__ uint32_t s_wave[MESH_SCAN_THREADS / WAVE];
+		const uint32_t sum = block_scan_counts<MESH_SCAN_THREADS>(jobs.counts[blockIdx.x], jobs.n[blockIdx.x], s_wave);
+		if (threadIdx.x == 0) *jobs.totals[blockIdx.x] = (int32_t)sum;
+	}
+
+	// the roots' dense ids, into their own rows of vertex_component
+	__global__ void __launch_bounds__(MESH_THREADS) cc_rank_kernel(const int32_t* __restrict__ parent, const int V, const uint32_t* __restrict__ counts,
+	                                                               int32_t* __restrict__ vertex_component)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		const bool root = v < V && parent[v] == v;
+		uint32_t total;
+		const uint32_t rank = counts[blockIdx.x] + block_rank<MESH_THREADS>(root ? 1u : 0u, s_wave, total);
+		if (root) vertex_component[v] = (int32_t)rank;
+	}
+
+	// counts[c] += 1 for every lane with valid set, one atomic per distinct c of the wave.  Every lane of the wave must call;
+	// each turn of the loop retires the first pending lane and all lanes with its c.
+	__device__ __forceinline__ void wave_count(int32_t* counts, int c, bool valid)
+	{
+		const int lane = threadIdx.x & (WAVE - 1);
+		unsigned long long todo = __ballot(valid);
+		while (todo)
+		{
+			const int leader = __ffsll((long long)todo) - 1;
+			const int lc = __shfl(c, leader);
+			const unsigned long long same = __ballot(valid && c == lc);
+			if (lane == leader) atomicAdd(counts + lc, (int32_t)__popcll(same));
+			todo &= ~same;
+		}
+	}
+
+	// the other vertices take their root's id (a root's row is not written here)
+	__global__ void __launch_bounds__(MESH_THREADS) cc_assign_kernel(const int32_t* __restrict__ parent, const int V, int32_t* vertex_component)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v >= V) return;
+		const int r = parent[v];
+		if (r != v) vertex_component[v] = vertex_component[r];
+	}
+
+	// vertices and faces per component; an id outside [0, cap) is counted nowhere
+	__global__ void __launch_bounds__(MESH_THREADS) cc_vertex_count_kernel(const int32_t* __restrict__ vertex_component, const int V,
+	                                                                       int32_t* component_vertices, const int cap)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		const int id = v < V ? vertex_component[v] : 0;
+		wave_count(component_vertices, id, v < V && (uint32_t)id < (uint32_t)cap);
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) cc_face_count_kernel(const int32_t* __restrict__ faces, const int F, const int V,
+	                                                                     const int32_t* __restrict__ vertex_component, int32_t* component_faces, const int cap)
+	{
+		const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
+		int a, b, c, id = 0;
+		bool valid = false;
+		if (f < F && face_present(faces, f, V, a, b, c))
+		{
+			id = vertex_component[a];
+			valid = (uint32_t)id < (uint32_t)cap;
+		}
+		wave_count(component_faces, id, valid);
+	}
+
+	// ---- compaction ----
+	struct CompactArgs
+	{
+		int V, F, C;
+		const float *vertices, *normals, *colors;
+		const int32_t *faces, *vertex_component;
+		const uint8_t* keep;
+		int32_t* map;                 // [V] old vertex -> new vertex, -1 for a dropped one
+		uint32_t *vcounts, *fcounts;  // [workgroups] survivors per workgroup -> (scan) the workgroup's first rank
+		int vcap, fcap;
+		float *out_vertices, *out_normals, *out_colors;
+		int32_t* out_faces;
+	};
+
+	__device__ __forceinline__ bool vertex_kept(const CompactArgs& a, int v)
+	{
+		const int c = a.vertex_component[v];
+		return (uint32_t)c < (uint32_t)a.C && a.keep[c] != 0;
+	}
+	__device__ __forceinline__ bool face_kept(const CompactArgs& a, int f, int& i, int& j, int& k)
+	{
+		return f < a.F && face_present(a.faces, f, a.V, i, j, k) && vertex_kept(a, i);
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) compact_count_vertices_kernel(const CompactArgs a)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		uint32_t total;
+		block_rank<MESH_THREADS>(v < a.V && vertex_kept(a, v) ? 1u : 0u, s_wave, total);
+		if (threadIdx.x == 0) a.vcounts[blockIdx.x] = total;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) compact_count_faces_kernel(const CompactArgs a)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		int i, j, k;
+		uint32_t total;
+		block_rank<MESH_THREADS>(face_kept(a, blockIdx.x * MESH_THREADS + threadIdx.x, i, j, k) ? 1u : 0u, s_wave, total);
+		if (threadIdx.x == 0) a.fcounts[blockIdx.x] = total;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) compact_vertices_kernel(const CompactArgs a)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		const bool kept = v < a.V && vertex_kept(a, v);
+		uint32_t total;
+		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank<MESH_THREADS>(kept ? 1u : 0u, s_wave, total);
+		if (v >= a.V) return;
+		a.map[v] = kept ? (int32_t)rank : -1;
+		if (!kept || rank >= (uint32_t)a.vcap) return;
+		const size_t s = 3 * (size_t)v, d = 3 * (size_t)rank;
+		if (a.out_vertices) { a.out_vertices[d] = a.vertices[s]; a.out_vertices[d + 1] = a.vertices[s + 1]; a.out_vertices[d + 2] = a.vertices[s + 2]; }
+		if (a.out_normals) { a.out_normals[d] = a.normals[s]; a.out_normals[d + 1] = a.normals[s + 1]; a.out_normals[d + 2] = a.normals[s + 2]; }
+		if (a.out_colors) { a.out_colors[d] = a.colors[s]; a.out_colors[d + 1] = a.colors[s + 1]; a.out_colors[d + 2] = a.colors[s + 2]; }
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) compact_faces_kernel(const CompactArgs a)
+	{
+		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
+		int i, j, k;
+		const bool kept = face_kept(a, blockIdx.x * MESH_THREADS + threadIdx.x, i, j, k);
+		uint32_t total;
+		const uint32_t rank = a.fcounts[blockIdx.x] + block_rank<MESH_THREADS>(kept ? 1u : 0u, s_wave, total);
+		if (!kept || rank >= (uint32_t)a.fcap) return;
+		const size_t d = 3 * (size_t)rank;
+		a.out_faces[d] = a.map[i]; a.out_faces[d + 1] = a.map[j]; a.out_faces[d + 2] = a.map[k];
+	}
+
+	// ---- smoothing ----
+	// keys[3 f + k] = corner k of face f (V for an absent face), vals[3 f + k] = 3 f + k
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_pairs_kernel(const int32_t* __restrict__ faces, const int F, const int V,
+	                                                                    uint32_t* __restrict__ keys, uint32_t* __restrict__ vals)
+	{
+		const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (f >= F) return;
+		int c[3];
+		const bool present = face_present(faces, f, V, c[0], c[1], c[2]);
+#pragma unroll
+		for (int k = 0; k < 3; k++)
+		{
+			keys[3 * (size_t)f + k] = present ? (uint32_t)c[k] : (uint32_t)V;
+			vals[3 * (size_t)f + k] = 3u * (uint32_t)f + k;
+		}
+	}
+
+	// row_start[v], v in [0, V]: the first sorted position whose key is >= v (row v is [row_start[v], row_start[v + 1]))
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_rows_kernel(const uint32_t* __restrict__ keys, const int n, const int V, int32_t* __restrict__ row_start)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v > V) return;
+		int lo = 0, hi = n;
+		while (lo < hi)
+		{
+			const int mid = lo + (hi - lo) / 2;
+			if (keys[mid] < (uint32_t)v) lo = mid + 1;
+			else hi = mid;
+		}
+		row_start[v] = lo;
+	}
+
+	// the other two corners of every incidence, in ascending corner index.  n_rows = row_start[V]: the incidences of present faces
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_others_kernel(const int32_t* __restrict__ faces, const uint32_t* __restrict__ vals,
+	                                                                     const int32_t* __restrict__ row_start, const int V, const int n, int2* __restrict__ others)
+	{
+		const int i = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (i >= n || i >= row_start[V]) return;
+		const uint32_t val = vals[i], f = val / 3u, k = val - 3u * f;
+		const int32_t* face = faces + 3 * (size_t)f;
+		others[i] = make_int2(face[k == 0 ? 1 : 0], face[k == 2 ? 1 : 2]);
+	}
+
+	// boundary[v] = 1 if some index occurs among the other corners of exactly one incidence of v's row
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_boundary_kernel(const int2* __restrict__ others, const int32_t* __restrict__ row_start, const int V,
+	                                                                       uint8_t* __restrict__ boundary)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v >= V) return;
+		const int s = row_start[v], e = row_start[v + 1];
+		bool found = false;
+		for (int i = s; i < e && !found; i++)
+		{
+			const int2 o = others[i];
+			int nx = 0, ny = 0;
+			for (int j = s; j < e; j++)
+			{
+				const int2 q = others[j];
+				nx += (q.x == o.x || q.y == o.x) ? 1 : 0;
+				ny += (q.x == o.y || q.y == o.y) ? 1 : 0;
+			}
+			found = nx == 1 || ny == 1;
+		}
+		boundary[v] = found ? 1 : 0;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_pass_kernel(const float* __restrict__ src, float* __restrict__ dst, const int2* __restrict__ others,
+	                                                                   const int32_t* __restrict__ row_start, const uint8_t* __restrict__ pinned, const int V,
+	                                                                   const float t)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v >= V) return;
+		const size_t r = 3 * (size_t)v;
+		float px = src[r], py = src[r + 1], pz = src[r + 2];
+		const int s = row_start[v], e = row_start[v + 1];
+		if (e > s && !(pinned && pinned[v]))
+		{
+			float sx = 0.f, sy = 0.f, sz = 0.f;
+			for (int i = s; i < e; i++)
+			{
+				const int2 o = others[i];
+				const size_t a = 3 * (size_t)o.x, b = 3 * (size_t)o.y;
+				sx = sx + (src[a] + src[b]);
+				sy = sy + (src[a + 1] + src[b + 1]);
+				sz = sz + (src[a + 2] + src[b + 2]);
+			}
+			const float d = (float)(2 * (e - s));
+			px = px + t * (sx / d - px);
+			py = py + t * (sy / d - py);
+			pz = pz + t * (sz / d - pz);
+		}
+		dst[r] = px; dst[r + 1] = py; dst[r + 2] = pz;
+	}
+
+	__global__ void __launch_bounds__(MESH_THREADS) smooth_normals_kernel(const float* __restrict__ pos, const int32_t* __restrict__ faces,
+	                                                                      const uint32_t* __restrict__ vals, const int32_t* __restrict__ row_start, const int V,
+	                                                                      float* __restrict__ normals)
+	{
+		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
+		if (v >= V) return;
+		float nx = 0.f, ny = 0.f, nz = 0.f;
+		for (int i = row_start[v]; i < row_start[v + 1]; i++)
+		{
+			const int32_t* face = faces + 3 * (size_t)(vals[i] / 3u);
+			const size_t a = 3 * (size_t)face[0], b = 3 * (size_t)face[1], c = 3 * (size_t)face[2];
+			const float ux = pos[b] - pos[a], uy = pos[b + 1] - pos[a + 1], uz = pos[b + 2] - pos[a + 2];
+			const float wx = pos[c] - pos[a], wy = pos[c + 1] - pos[a + 1], wz = pos[c + 2] - pos[a + 2];
+			nx = nx + (uy * wz - uz * wy);
+			ny = ny + (uz * wx - ux * wz);
+			nz = nz + (ux * wy - uy * wx);
+		}
+		const float len2 = (nx * nx + ny * ny) + nz * nz;
+		if (len2 > 0.f)
+		{
+			const float len = sqrtf(len2);
+			nx = nx / len; ny = ny / len; nz = nz / len;
+		}
+		else nx = ny = nz = 0.f;
+		const size_t r = 3 * (size_t)v;
+		normals[r] = nx; normals[r + 1] = ny; normals[r + 2] = nz;
+	}
+
+	// ---- host side ----
+	static int mesh_fail(const char* fn, const char* why)
+	{
+		char msg[256];
+		snprintf(msg, sizeof msg, "%s: %s", fn, why);
+		return set_error(FDGS_ERR_INVALID_ARG, msg);
+	}
+	static bool mesh_sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < MESH_MAX && F < MESH_MAX; }
+	static const char* mesh_in_args(const fdgs_mesh_in* m)
+	{
+		if (!m) return "mesh must not be NULL";
+		if (m->struct_size != sizeof(fdgs_mesh_in)) return "fdgs_mesh_in.struct_size is not sizeof(fdgs_mesh_in): header and library differ";
+		if (m->V < 0 || m->F < 0) return "V and F must not be negative";
+		if (!mesh_sizes_ok(m->V, m->F)) return "need V < 2^28 and F < 2^28";
+		if (m->F > 0 && !m->faces) return "faces must not be NULL with F > 0";
+		return nullptr;
+	}
+	static size_t blocks_of(size_t n) { return (n + MESH_THREADS - 1) / MESH_THREADS; }
+
+	struct ComponentsLayout { size_t parent, counts, flag, total; };
+	static ComponentsLayout components_layout(int V)
+	{
+		ComponentsLayout L;
+		size_t o = 0;
+		L.flag = o; o = align_up(o + 16);                    // a block of its own at the start: the memset's target
+		L.parent = o; o = align_up(o + (size_t)V * sizeof(int32_t));
+		L.counts = o; o = align_up(o + blocks_of((size_t)V) * sizeof(uint32_t));
+		L.total = o;
+		return L;
+	}
+	struct CompactLayout { size_t map, vcounts, fcounts, total; };
+	static CompactLayout compact_layout(int V, int F)
+	{
+		CompactLayout L;
+		size_t o = 0;
+		L.map = o; o = align_up(o + (size_t)V * sizeof(int32_t));
+		L.vcounts = o; o = align_up(o + blocks_of((size_t)V) * sizeof(uint32_t));
+		L.fcounts = o; o = align_up(o + blocks_of((size_t)F) * sizeof(uint32_t));
+		L.total = o;
+		return L;
+	}
+	struct SmoothLayout { size_t keys[2], vals[2], hist, row_start, others, tmp, boundary, total; };
+	static SmoothLayout smooth_layout(int V, int F)
+	{
+		SmoothLayout L;
+		size_t o = 0;
+		const size_t n = 3 * (size_t)F;
+		for (int k = 0; k < 2; k++) { L.keys[k] = o; o = align_up(o + n * 4); }
+		for (int k = 0; k < 2; k++) { L.vals[k] = o; o = align_up(o + n * 4); }
+		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)n) + 1) * 4);
+		L.row_start = o; o = align_up(o + ((size_t)V + 1) * sizeof(int32_t));
+		L.others = o; o = align_up(o + n * sizeof(int2));
+		L.tmp = o; o = align_up(o + 3 * (size_t)V * sizeof(float));
+		L.boundary = o; o = align_up(o + (size_t)V);
+		L.total = o;
+		return L;
+	}
+}
+
+using namespace fdgs;
+
+extern "C" size_t fdgs_mesh_components_scratch_bytes(int32_t V, int32_t F)
+{
+	return mesh_sizes_ok(V, F) ? components_layout(V).total : 0;
+}
+
+extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_components_out* out, void* scratch, void* stream_v)
+{
+	const char* fn = "fdgs_mesh_components";
+	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
+	if (!out) return mesh_fail(fn, "out must not be NULL");
+	if (out->struct_size != sizeof(fdgs_mesh_components_out))
+		return mesh_fail(fn, "fdgs_mesh_components_out.struct_size is not sizeof(fdgs_mesh_components_out): header and library differ");
+	if (out->capacity < 0) return mesh_fail(fn, "capacity must not be negative");
+	if (!out->labelled && !out->n_components) return mesh_fail(fn, "n_components must not be NULL");
+	const int V = mesh->V, F = mesh->F;
+	if (V > 0 && !out->vertex_component) return mesh_fail(fn, "vertex_component must not be NULL with V > 0");
+	if (V > 0 && !out->labelled && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	hipStream_t stream = (hipStream_t)stream_v;
+	if (out->rounds) *out->rounds = 0;
+	const int cap = out->capacity;
+	int32_t* cv = cap > 0 ? out->component_vertices : nullptr;
+	int32_t* cf = cap > 0 ? out->component_faces : nullptr;
+	const int vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
+	if (!out->labelled)
+	{
+		if (V == 0)
+			return hipMemsetAsync(out->n_components, 0, sizeof(int32_t), stream) == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+		const ComponentsLayout L = components_layout(V);
+		char* base = reinterpret_cast<char*>(scratch);
+		int32_t* flag = reinterpret_cast<int32_t*>(base + L.flag);
+		int32_t* parent = reinterpret_cast<int32_t*>(base + L.parent);
+		uint32_t* counts = reinterpret_cast<uint32_t*>(base + L.counts);
+		hipLaunchKernelGGL(cc_init_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V);
+		int rounds = 0;
+		for (bool done = F == 0; !done;)
+		{
+			if (rounds == MESH_MAX_ROUNDS) return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: no convergence within 32 hook passes");
+			int32_t changed = 0;
+			if (hipMemsetAsync(flag, 0, 16, stream) != hipSuccess) return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+			hipLaunchKernelGGL(cc_hook_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, parent, flag);
+			rounds++;
+			if (hipMemcpyAsync(&changed, flag, sizeof changed, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
+				return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: reading the convergence flag failed");
+			done = changed == 0;
+			if (!done) hipLaunchKernelGGL(cc_compress_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V);
+		}
+		if (out->rounds) *out->rounds = rounds;
+		// here every parent[v] is v's root, the smallest index of its component
+		ScanJobs jobs;
+		jobs.counts[0] = jobs.counts[1] = counts; jobs.n[0] = jobs.n[1] = vb; jobs.totals[0] = jobs.totals[1] = out->n_components;
+		hipLaunchKernelGGL(cc_roots_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, counts);
+		hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(MESH_SCAN_THREADS), 0, stream, jobs);
+		hipLaunchKernelGGL(cc_rank_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, counts, out->vertex_component);
+		hipLaunchKernelGGL(cc_assign_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, out->vertex_component);
+	}
+	if ((cv && hipMemsetAsync(cv, 0, (size_t)cap * sizeof(int32_t), stream) != hipSuccess) ||
+	    (cf && hipMemsetAsync(cf, 0, (size_t)cap * sizeof(int32_t), stream) != hipSuccess))
+		return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+	if (cv && V > 0) hipLaunchKernelGGL(cc_vertex_count_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, out->vertex_component, V, cv, cap);
+	if (cf && V > 0 && F > 0)
+		hipLaunchKernelGGL(cc_face_count_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, out->vertex_component, cf, cap);
+	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_components: launch failed");
+}
+
+extern "C" size_t fdgs_mesh_compact_scratch_bytes(int32_t V, int32_t F)
+{
+	return mesh_sizes_ok(V, F) ? compact_layout(V, F).total : 0;
+}
+
+extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex_component, const uint8_t* keep, int32_t n_components,
+                                 const fdgs_surface_out* out, void* scratch, void* stream_v)
+{
+	const char* fn = "fdgs_mesh_compact";
+	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
+	if (!out) return mesh_fail(fn, "out must not be NULL");
+	if (out->struct_size != sizeof(fdgs_surface_out)) return mesh_fail(fn, "fdgs_surface_out.struct_size is not sizeof(fdgs_surface_out): header and library differ");
+	if (!out->n_vertices || !out->n_faces) return mesh_fail(fn, "n_vertices and n_faces must not be NULL");
+	if (out->vertex_capacity < 0 || out->face_capacity < 0) return mesh_fail(fn, "capacities must not be negative");
+	if (n_components < 0) return mesh_fail(fn, "n_components must not be negative");
+	if (n_components > 0 && !keep) return mesh_fail(fn, "keep must not be NULL with n_components > 0");
+	const int V = mesh->V, F = mesh->F;
+	if (V > 0 && !vertex_component) return mesh_fail(fn, "vertex_component must not be NULL with V > 0");
+	if ((out->vertices && !mesh->vertices) || (out->normals && !mesh->normals) || (out->colors && !mesh->colors))
+		return mesh_fail(fn, "an output array needs its input array");
+	if (V > 0 && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	hipStream_t stream = (hipStream_t)stream_v;
+	if (V == 0)
+	{
+		// no vertex: every face is absent
+		if (hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream) != hipSuccess || hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream) != hipSuccess)
+			return set_error(FDGS_ERR_HIP, "fdgs_mesh_compact: memset failed");
+		return FDGS_OK;
+	}
+	const CompactLayout L = compact_layout(V, F);
+	char* base = reinterpret_cast<char*>(scratch);
+	CompactArgs a;
+	a.V = V; a.F = F; a.C = n_components;
+	a.vertices = mesh->vertices; a.normals = mesh->normals; a.colors = mesh->colors; a.faces = mesh->faces;
+	a.vertex_component = vertex_component; a.keep = keep;
+	a.map = reinterpret_cast<int32_t*>(base + L.map);
+	a.vcounts = reinterpret_cast<uint32_t*>(base + L.vcounts);
+	a.fcounts = reinterpret_cast<uint32_t*>(base + L.fcounts);
+	a.out_vertices = out->vertices; a.out_normals = out->normals; a.out_colors = out->colors; a.out_faces = out->faces;
+	const bool any_vertex = a.out_vertices || a.out_normals || a.out_colors;
+	a.vcap = any_vertex ? out->vertex_capacity : 0;
+	a.fcap = a.out_faces ? out->face_capacity : 0;
+	const int vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
+	ScanJobs jobs;
+	jobs.counts[0] = a.vcounts; jobs.n[0] = vb; jobs.totals[0] = out->n_vertices;
+	jobs.counts[1] = a.fcounts; jobs.n[1] = fb; jobs.totals[1] = out->n_faces;
+	hipLaunchKernelGGL(compact_count_vertices_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, a);
+	if (fb > 0) hipLaunchKernelGGL(compact_count_faces_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, a);
+	hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(MESH_SCAN_THREADS), 0, stream, jobs);
+	if (any_vertex || a.out_faces)
+	{
+		hipLaunchKernelGGL(compact_vertices_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, a);
+		if (a.out_faces && fb > 0) hipLaunchKernelGGL(compact_faces_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, a);
+	}
+	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_compact: launch failed");
+}
+
+extern "C" size_t fdgs_mesh_smooth_scratch_bytes(int32_t V, int32_t F)
+{
+	return mesh_sizes_ok(V, F) ? smooth_layout(V, F).total : 0;
+}
+
+extern "C" int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth_out* out, void* scratch, void* stream_v)
+{
+	const char* fn = "fdgs_mesh_smooth";
+	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
+	if (!out) return mesh_fail(fn, "out must not be NULL");
+	if (out->struct_size != sizeof(fdgs_mesh_smooth_out)) return mesh_fail(fn, "fdgs_mesh_smooth_out.struct_size is not sizeof(fdgs_mesh_smooth_out): header and library differ");
+	if (out->iterations < 0) return mesh_fail(fn, "iterations must not be negative");
+	if (out->lambda != out->lambda || out->mu != out->mu) return mesh_fail(fn, "lambda and mu must not be NaN");
+	const int V = mesh->V, F = mesh->F, iterations = out->iterations;
+	if (V > 0 && !mesh->vertices) return mesh_fail(fn, "the mesh's vertices must not be NULL with V > 0");
+	if (V > 0 && iterations > 0 && !out->vertices) return mesh_fail(fn, "out vertices must not be NULL with iterations > 0");
+	if (V > 0 && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	if (V == 0) return FDGS_OK;
+	hipStream_t stream = (hipStream_t)stream_v;
+	const SmoothLayout L = smooth_layout(V, F);
+	char* base = reinterpret_cast<char*>(scratch);
+	uint32_t* keys[2] = { reinterpret_cast<uint32_t*>(base + L.keys[0]), reinterpret_cast<uint32_t*>(base + L.keys[1]) };
+	uint32_t* vals[2] = { reinterpret_cast<uint32_t*>(base + L.vals[0]), reinterpret_cast<uint32_t*>(base + L.vals[1]) };
+	int32_t* row_start = reinterpret_cast<int32_t*>(base + L.row_start);
+	int2* others = reinterpret_cast<int2*>(base + L.others);
+	float* tmp = reinterpret_cast<float*>(base + L.tmp);
+	const int n = 3 * F, vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
+	int res = 0;
+	if (F > 0)
+	{
+		int bits = 0;                                        // the keys are 0 .. V
+		while (bits < 32 && ((uint32_t)V >> bits) != 0) bits++;
+		hipLaunchKernelGGL(smooth_pairs_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, keys[0], vals[0]);
+		if (radix_sort_pairs(keys, vals, n, 0, div_up(bits, RADIX_BITS) * RADIX_BITS, reinterpret_cast<uint32_t*>(base + L.hist), stream, &res) != hipSuccess)
+			return set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: sort failed");
+	}
+	hipLaunchKernelGGL(smooth_rows_kernel, dim3((int)blocks_of((size_t)V + 1)), dim3(MESH_THREADS), 0, stream, keys[res], n, V, row_start);
+	if (F > 0)
+		hipLaunchKernelGGL(smooth_others_kernel, dim3((int)blocks_of((size_t)n)), dim3(MESH_THREADS), 0, stream, mesh->faces, vals[res], row_start, V, n, others);
+	uint8_t* boundary = out->boundary ? out->boundary : reinterpret_cast<uint8_t*>(base + L.boundary);
+	const bool pin = out->pin_boundary != 0;
+	if (out->boundary || (pin && iterations > 0))
+		hipLaunchKernelGGL(smooth_boundary_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, others, row_start, V, boundary);
+	const float* pos = mesh->vertices;
+	for (int pass = 0; pass < 2 * iterations; pass++)
+	{
+		float* dst = (pass & 1) ? out->vertices : tmp;       // lambda: -> tmp, mu: -> out
+		hipLaunchKernelGGL(smooth_pass_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, pos, dst, others, row_start, pin ? boundary : nullptr, V,
+		                   (pass & 1) ? out->mu : out->lambda);
+		pos = dst;
+	}
+	if (iterations == 0 && out->vertices && out->vertices != mesh->vertices)
+	{
+		if (hipMemcpyAsync(out->vertices, mesh->vertices, 3 * (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
+			return set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: copy failed");
+	}
+	if (out->normals)
+		hipLaunchKernelGGL(smooth_normals_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, pos, mesh->faces, vals[res], row_start, V, out->normals);
+	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: launch failed");
+}

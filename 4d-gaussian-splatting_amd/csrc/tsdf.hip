@@ -17,6 +17,7 @@
 //   5 faces     the quads of a voxel's edges, through the map, at 2 * (quad rank)
 // A count-only call stops after 3.  Float32 in the operation order of the written statement (built with FP contraction off).
 #include "fdgs_common.h"
+#include "block_scan.h"
 #include <math.h>
 #include <stdio.h>
 
@@ -136,32 +137,6 @@ namespace fdgs
 		return idx + (m & 1) + ((m >> 1) & 1) * a.nx + (m >> 2) * a.nx * a.ny;
 	}
 
-	// exclusive rank of v among the workgroup's threads, in thread order; total: the workgroup's sum (every thread gets it)
-	__device__ __forceinline__ uint32_t block_rank(uint32_t v, uint32_t* s_wave, uint32_t& total)
-	{
-		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < WAVE; d <<= 1)
-		{
-			const uint32_t y = __shfl_up(x, d);
-			if (lane >= d) x += y;
-		}
-		__syncthreads();                                  // the previous call's readers are done with s_wave[]
-		if (lane == WAVE - 1) s_wave[wave] = x;
-		__syncthreads();
-		uint32_t before = 0;
-		total = 0;
-#pragma unroll
-		for (int w = 0; w < TSDF_THREADS / WAVE; w++)
-		{
-			const uint32_t c = s_wave[w];
-			if (w < wave) before += c;
-			total += c;
-		}
-		return before + x - v;
-	}
-
 	__global__ void __launch_bounds__(TSDF_THREADS) surf_cells_kernel(const SurfArgs a)
 	{
 		__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
@@ -186,7 +161,7 @@ namespace fdgs
 			a.map[idx] = active ? 0 : -1;
 		}
 		uint32_t total;
-		block_rank(active ? 1u : 0u, s_wave, total);
+		block_rank<TSDF_THREADS>(active ? 1u : 0u, s_wave, total);
 		if (threadIdx.x == 0) a.vcounts[blockIdx.x] = total;
 	}
 
@@ -226,7 +201,7 @@ namespace fdgs
 		int cells[3][4];
 		const uint32_t nq = surf_edges(a, blockIdx.x * TSDF_THREADS + threadIdx.x, quad, cells, inside0);
 		uint32_t total;
-		block_rank(nq, s_wave, total);
+		block_rank<TSDF_THREADS>(nq, s_wave, total);
 		if (threadIdx.x == 0) a.fcounts[blockIdx.x] = total;
 	}
 
@@ -236,34 +211,7 @@ namespace fdgs
 	                                                                      int32_t* __restrict__ n_vertices, int32_t* __restrict__ n_faces)
 	{
 		__shared__ uint32_t s_wave[SURF_SCAN_THREADS / WAVE];
-		uint32_t* counts = blockIdx.x == 0 ? vcounts : fcounts;
-		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		uint32_t carry = 0;
-		for (int base = 0; base < n; base += SURF_SCAN_THREADS)
-		{
-			const int i = base + (int)threadIdx.x;
-			const uint32_t v = i < n ? counts[i] : 0u;
-			uint32_t x = v;
-#pragma unroll
-			for (int d = 1; d < WAVE; d <<= 1)
-			{
-				const uint32_t y = __shfl_up(x, d);
-				if (lane >= d) x += y;
-			}
-			if (lane == WAVE - 1) s_wave[wave] = x;
-			__syncthreads();
-			uint32_t before = 0, total = 0;
-#pragma unroll
-			for (int w = 0; w < SURF_SCAN_THREADS / WAVE; w++)
-			{
-				const uint32_t c = s_wave[w];
-				if (w < wave) before += c;
-				total += c;
-			}
-			if (i < n) counts[i] = carry + before + x - v;
-			carry += total;
-			__syncthreads();
-		}
+		const uint32_t carry = block_scan_counts<SURF_SCAN_THREADS>(blockIdx.x == 0 ? vcounts : fcounts, n, s_wave);
 		if (threadIdx.x == 0)
 		{
 			if (blockIdx.x == 0) *n_vertices = (int32_t)carry;
@@ -277,7 +225,7 @@ namespace fdgs
 		const int idx = blockIdx.x * TSDF_THREADS + threadIdx.x;
 		const bool active = idx < a.n && a.map[idx] >= 0;
 		uint32_t total;
-		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank(active ? 1u : 0u, s_wave, total);
+		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank<TSDF_THREADS>(active ? 1u : 0u, s_wave, total);
 		if (!active) return;
 		a.map[idx] = (int32_t)rank;
 		if (rank >= (uint32_t)a.vcap) return;
@@ -352,7 +300,7 @@ namespace fdgs
 		int cells[3][4];
 		const uint32_t nq = surf_edges(a, blockIdx.x * TSDF_THREADS + threadIdx.x, quad, cells, inside0);
 		uint32_t total;
-		uint32_t rank = a.fcounts[blockIdx.x] + block_rank(nq, s_wave, total);
+		uint32_t rank = a.fcounts[blockIdx.x] + block_rank<TSDF_THREADS>(nq, s_wave, total);
 #pragma unroll
 		for (int ax = 0; ax < 3; ax++)
 		{

@@ -13,6 +13,9 @@
   sign-changing grid edge, vertices shared by construction), with normals from the distance gradient and colours from the volume.
 * ``prepare_views`` does the host side of ``integrate`` once (tensor checks, view matrices on the device, intrinsics) for callers that
   integrate the same buffers repeatedly.  ``fuse_sequence`` yields one mesh per timestamp; ``save_mesh_ply`` / ``load_mesh_ply`` write and read it.
+* ``components(mesh)``, ``clean(mesh, keep_largest=, min_faces=)`` and ``smooth(mesh)`` (csrc/mesh.hip) finish a raw mesh on the
+  device: connected components, dropping floaters with order-preserving compaction, Taubin smoothing with recomputed normals.  A face
+  with an index outside ``[0, V)`` is absent to all three.
 
 Everything runs on the current stream; ``extract`` reads two counters from the device once, to size its outputs.  No atomics: two
 runs are bit-identical.  There is no CPU path.
@@ -208,6 +211,124 @@ def fuse_sequence(model, cameras, pipe, bg, volume: TSDFVolume, timestamps, *, a
         volume.reset()
         fuse(model, [with_timestamp(c, t) for c in cameras], pipe, bg, volume, alpha_min=alpha_min, intrinsics=intrinsics)
         yield extract(volume, min_weight)
+
+
+# ---- cleaning and smoothing (csrc/mesh.hip) ----
+@dataclass
+class MeshComponents:
+    vertex_component: torch.Tensor   # [V] int32: dense ids, in ascending order of each component's smallest vertex index
+    n: int                           # the number of components
+    vertex_counts: torch.Tensor      # [n] int32
+    face_counts: torch.Tensor        # [n] int32: a face counts for the component of its first index
+    rounds: int = 0                  # hook passes the union-find took (the last one is the convergence check)
+
+
+def _mesh_struct(mesh: Mesh):
+    """(fdgs_mesh_in, device, the tensors its pointers refer to) of a mesh on the GPU."""
+    named = (("vertices", mesh.vertices), ("normals", mesh.normals), ("colors", mesh.colors), ("faces", mesh.faces))
+    for name, t in named:
+        if not t.is_cuda:
+            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        if t.device != mesh.vertices.device:
+            raise RuntimeError("fdgs: '%s' lives on %s, the vertices on %s" % (name, t.device, mesh.vertices.device))
+    V, F = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
+    for name, t in named[:3]:
+        if tuple(t.shape) != (V, 3):
+            raise ValueError("fdgs: '%s' must be [V, 3] = %s; got %s" % (name, (V, 3), tuple(t.shape)))
+    if tuple(mesh.faces.shape) != (F, 3):
+        raise ValueError("fdgs: faces must be [F, 3]; got %s" % (tuple(mesh.faces.shape),))
+    keep = [t.detach().contiguous().float() for _, t in named[:3]] + [mesh.faces.detach().contiguous().to(torch.int32)]
+    return _capi.FdgsMeshIn(V, F, *[_capi._ptr(t) for t in keep]), mesh.vertices.device, keep
+
+
+def _scratch(nbytes, dev):
+    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
+
+
+def _components_call(struct, dev, cap, vertex_component, counter, vertex_counts=None, face_counts=None, labelled=False) -> int:
+    """fdgs_mesh_components on the current stream; returns the hook passes it took.  ``labelled``: ``vertex_component`` holds an
+    earlier call's ids, only the counts are computed."""
+    rounds = C.c_int32(0)
+    out = _capi.FdgsMeshComponentsOut(int(cap), int(bool(labelled)), _capi._ptr(vertex_component), counter.data_ptr(), _capi._ptr(vertex_counts),
+                                      _capi._ptr(face_counts), C.pointer(rounds))
+    scratch = _scratch(_capi.lib.fdgs_mesh_components_scratch_bytes(struct.V, struct.F), dev)
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_mesh_components(C.byref(struct), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
+    _capi._check(rc, "fdgs_mesh_components")
+    return int(rounds.value)
+
+
+def _compact_call(struct, dev, vertex_component, keep, counts, vcap=0, fcap=0, vertices=None, normals=None, colors=None, faces=None):
+    out = _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
+                               counts.data_ptr(), counts.data_ptr() + 4)
+    scratch = _scratch(_capi.lib.fdgs_mesh_compact_scratch_bytes(struct.V, struct.F), dev)
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_mesh_compact(C.byref(struct), _capi._ptr(vertex_component), _capi._ptr(keep), int(keep.numel()), C.byref(out),
+                                         scratch.data_ptr(), _capi.current_stream_handle(dev))
+    _capi._check(rc, "fdgs_mesh_compact")
+
+
+def _smooth_call(struct, dev, iterations, lam, mu, pin_boundary, vertices=None, normals=None, boundary=None):
+    out = _capi.FdgsMeshSmoothOut(int(iterations), float(lam), float(mu), int(bool(pin_boundary)), _capi._ptr(vertices), _capi._ptr(normals),
+                                  _capi._ptr(boundary))
+    scratch = _scratch(_capi.lib.fdgs_mesh_smooth_scratch_bytes(struct.V, struct.F), dev)
+    with torch.cuda.device(dev):
+        rc = _capi.lib.fdgs_mesh_smooth(C.byref(struct), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
+    _capi._check(rc, "fdgs_mesh_smooth")
+
+
+def components(mesh: Mesh) -> MeshComponents:
+    """The connected components of the mesh's vertices under its (present) faces: labels first, one read of the one counter, exact
+    allocation of the two count arrays, the counts."""
+    struct, dev, _held = _mesh_struct(mesh)
+    V = struct.V
+    vc = torch.empty(V, dtype=torch.int32, device=dev)
+    counter = torch.zeros(1, dtype=torch.int32, device=dev)
+    rounds = _components_call(struct, dev, 0, vc, counter)
+    n = int(counter.cpu())
+    vcount, fcount = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    if n > 0:
+        _components_call(struct, dev, n, vc, counter, vcount, fcount, labelled=True)
+    return MeshComponents(vc, n, vcount, fcount, rounds)
+
+
+def clean(mesh: Mesh, *, keep_largest=None, min_faces=None) -> Mesh:
+    """The mesh without its floaters: the ``keep_largest`` components with the most faces (ties go to the smaller component id) that
+    also have at least ``min_faces`` faces -- a component must pass every criterion given.  With neither, only components without a
+    face (stray vertices) and absent faces go.  Survivors keep their order; attribute rows are copied bit for bit."""
+    struct, dev, _held = _mesh_struct(mesh)
+    comp = components(mesh)
+    keep = comp.face_counts > 0
+    if min_faces is not None:
+        keep &= comp.face_counts >= int(min_faces)
+    if keep_largest is not None:
+        if int(keep_largest) < 0:
+            raise ValueError("fdgs: keep_largest must not be negative; got %s" % (keep_largest,))
+        order = torch.sort(comp.face_counts.cpu(), descending=True, stable=True).indices[:int(keep_largest)]     # the one small read
+        largest = torch.zeros(comp.n, dtype=torch.bool)
+        largest[order] = True
+        keep &= largest.to(dev)
+    keep = keep.to(torch.uint8)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    _compact_call(struct, dev, comp.vertex_component, keep, counts)
+    V, F = (int(v) for v in counts.cpu())
+    out = Mesh(torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((V, 3), dtype=torch.float32, device=dev),
+               torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((F, 3), dtype=torch.int32, device=dev))
+    if V > 0:
+        _compact_call(struct, dev, comp.vertex_component, keep, counts, V, F, out.vertices, out.normals, out.colors, out.faces)
+    return out
+
+
+def smooth(mesh: Mesh, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, *, pin_boundary: bool = True,
+           recompute_normals: bool = True) -> Mesh:
+    """Taubin smoothing: ``iterations`` times a pass with factor ``lam``, then one with ``mu`` (negative: it undoes the shrinking), each
+    moving a vertex towards the mean of its incident faces' other corners; boundary vertices stay where they are with
+    ``pin_boundary``.  Returns a new mesh -- the normals from the smoothed faces (``recompute_normals``) or copied, the colours and
+    faces copied; the input is left untouched."""
+    struct, dev, held = _mesh_struct(mesh)
+    out = Mesh(torch.empty_like(held[0]), torch.empty_like(held[1]) if recompute_normals else held[1].clone(), held[2].clone(), held[3].clone())
+    _smooth_call(struct, dev, iterations, lam, mu, pin_boundary, out.vertices, out.normals if recompute_normals else None)
+    return out
 
 
 # ---- PLY: a triangle mesh, binary little-endian as fdgs.slice's files ----

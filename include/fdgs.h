@@ -1137,6 +1137,87 @@ typedef struct fdgs_surface_out
 size_t fdgs_surface_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_weight, const fdgs_surface_out* out, void* scratch, void* stream);
 
+/* ---- cleaning and smoothing a triangle mesh (csrc/mesh.hip) ------------------------------------------------------------------
+ * A mesh is what fdgs_surface_extract leaves on the device: vertices, normals, colors [V,3] float32 and faces [F,3] int32, with
+ * 0 <= V, F < 2^28.  A face with any index outside [0, V) is ABSENT: no call reads or writes through it, it joins nothing, it
+ * contributes to no sum and compaction drops it.  A face with repeated indices is an ordinary face.  Every integer result is a
+ * function of the input, bit for bit.  FDGS_ERR_INVALID_ARG before any launch (all three calls): a NULL or mis-sized struct, a
+ * negative count or capacity, V or F >= 2^28, NULL faces with F > 0, a NULL required output or scratch (each where its count is not
+ * zero).  Each *_scratch_bytes(V, F) is a multiple of 256, and 0 for a negative (or too large) argument. */
+typedef struct fdgs_mesh_in
+{
+	uint32_t struct_size;     /* sizeof(fdgs_mesh_in)                                  */
+	int32_t V, F;
+	const float* vertices;    /* [V,3] or NULL where the call does not need it         */
+	const float* normals;     /* [V,3] or NULL                                         */
+	const float* colors;      /* [V,3] or NULL                                         */
+	const int32_t* faces;     /* [F,3]                                                 */
+} fdgs_mesh_in;
+
+typedef struct fdgs_mesh_components_out
+{
+	uint32_t struct_size;         /* sizeof(fdgs_mesh_components_out)                  */
+	int32_t capacity;             /* rows of component_vertices / component_faces      */
+	int32_t labelled;             /* != 0: vertex_component already holds an earlier call's ids for this mesh; only the two count
+	                                 arrays are written (n_components and scratch are not used, nothing synchronises)           */
+	int32_t* vertex_component;    /* [V] dense component id of every vertex            */
+	int32_t* n_components;        /* one int32 of device memory: always the full count */
+	int32_t* component_vertices;  /* [capacity] or NULL                                */
+	int32_t* component_faces;     /* [capacity] or NULL                                */
+	int32_t* rounds;              /* HOST memory or NULL: hook passes the call took    */
+} fdgs_mesh_components_out;
+
+/* Connected components of the graph whose nodes are the V vertices and whose edges are the sides of the present faces.
+ * vertex_component: ids 0 .. C-1 in ascending order of each component's smallest vertex index (a vertex in no present face is a
+ * component of its own, with zero faces); a face is counted for the component of its first index.  Rows of the two count arrays at
+ * or beyond `capacity` are never written; *n_components is always C.
+ * A lock-free union-find: every face links its corners by a compare-and-swap of the larger root onto the smaller (a failed swap
+ * means another thread lowered that root: the retry starts from a strictly smaller index, no thread waits for another), then every
+ * vertex reads its root -- the component's smallest index, whatever the schedule.  A second hook pass that finds every face's
+ * corners under one root is the convergence check: the host reads one device flag per pass (THE CALL SYNCHRONISES `stream`); more
+ * than 32 passes give FDGS_ERR_HIP.  Dense ids by a flag scan of the roots, counts by integer atomics: exact.
+ * scratch: fdgs_mesh_components_scratch_bytes(V, F) bytes. */
+size_t fdgs_mesh_components_scratch_bytes(int32_t V, int32_t F);
+int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_components_out* out, void* scratch, void* stream);
+
+/* Keeps the components c with keep[c] != 0 (keep: n_components bytes of device memory; an id outside [0, n_components) is not
+ * kept): a vertex survives if its component is kept, a face if it is present and its first vertex's component is kept; survivors
+ * keep their relative order, faces are renumbered through the old-to-new vertex map (-1 for a dropped vertex, which only a
+ * vertex_component that contradicts the faces can produce), attribute rows are copied unchanged.  `out` as fdgs_surface_extract
+ * takes it: with all four arrays NULL the call only counts, otherwise rows below the capacities are written and the counts are the
+ * full ones.  An output array needs its input array.  No host synchronisation.  Further INVALID_ARG: NULL vertex_component with
+ * V > 0, NULL keep with n_components > 0, n_components < 0, NULL n_vertices / n_faces. */
+size_t fdgs_mesh_compact_scratch_bytes(int32_t V, int32_t F);
+int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex_component, const uint8_t* keep, int32_t n_components,
+                      const fdgs_surface_out* out, void* scratch, void* stream);
+
+typedef struct fdgs_mesh_smooth_out
+{
+	uint32_t struct_size;     /* sizeof(fdgs_mesh_smooth_out)                          */
+	int32_t iterations;       /* >= 0                                                  */
+	float lambda, mu;         /* not NaN                                               */
+	int32_t pin_boundary;
+	float* vertices;          /* [V,3] the smoothed positions (NULL allowed with iterations == 0) */
+	float* normals;           /* [V,3] or NULL                                         */
+	uint8_t* boundary;        /* [V] 1 for a boundary vertex, or NULL                  */
+} fdgs_mesh_smooth_out;
+
+/* Taubin smoothing.  The incidences (vertex, 3 face + corner) of the present faces' corners are sorted by vertex with the
+ * library's stable radix sort, so a vertex's row is in ascending 3 face + corner.  For an incidence with corner k of face f, its
+ * OTHER corners (o1, o2) are the face's remaining two in ascending corner index.  One pass with factor t, in float32 exactly as
+ * written (built with FP contraction off), n = the length of v's row:
+ *   S = 0;  for the row in order: S = S + (p[o1] + p[o2]);   m = S / (float)(2 n);   p'(v) = p(v) + t * (m - p(v))
+ * per component; n == 0 or a pinned vertex: p'(v) = p(v).  An iteration is a pass with t = lambda, then one with t = mu, each from
+ * the previous pass's positions.  v is a BOUNDARY vertex if some index occurs among the other corners of exactly one incidence of
+ * its row (an integer decision on the topology, taken once; the cost is quadratic in the row length); with pin_boundary != 0 such
+ * vertices never move.  normals: N(v) = sum over the row in order of cross(p[b] - p[a], p[c] - p[a]) of the incidence's face
+ * (a, b, c), cross = (u.y w.z - u.z w.y, u.z w.x - u.x w.z, u.x w.y - u.y w.x), from the final positions, divided by
+ * sqrt((N.x^2 + N.y^2) + N.z^2) where that is > 0, else (0, 0, 0).  iterations == 0 copies the positions (where `vertices` is given
+ * and is not the input) and recomputes normals.  Colours are not touched.  No float atomics, no host synchronisation.
+ * Further INVALID_ARG: NULL mesh vertices with V > 0, NULL out vertices with iterations > 0, negative iterations, NaN lambda / mu. */
+size_t fdgs_mesh_smooth_scratch_bytes(int32_t V, int32_t F);
+int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth_out* out, void* scratch, void* stream);
+
 /* Thread-local description of the last error on this thread ("" if none). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
