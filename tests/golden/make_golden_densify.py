@@ -54,7 +54,7 @@ def recording_normal(*a, **k):
 torch.normal = recording_normal
 
 
-def run(tag, cfg, seed, max_grad, min_opacity, extent, max_screen_size, max_grad_t, prune_only, warm_steps=2):
+def run(tag, cfg, seed, max_grad, min_opacity, extent, max_screen_size, max_grad_t, prune_only, warm_steps=2, N=2):
     scene = synth.make_scene(cfg, seed=seed)
     P, M = scene["means3D"].shape[0], scene["M"]
     g = GaussianModel(sh_degree=cfg.sh_degree, gaussian_dim=cfg.gaussian_dim, time_duration=[0.0, scene["time_duration"]],
@@ -109,12 +109,30 @@ def run(tag, cfg, seed, max_grad, min_opacity, extent, max_screen_size, max_grad
     snap("in.", out)
     RECORDED.clear()
     torch.manual_seed(4242 + seed)
-    g.densify_and_prune(max_grad, min_opacity, extent, max_screen_size, max_grad_t, prune_only=prune_only)
+    if N == 2:
+        g.densify_and_prune(max_grad, min_opacity, extent, max_screen_size, max_grad_t, prune_only=prune_only)
+    else:
+        # densify_and_prune has no N of its own, densify_and_split does: the reference's clone, split(N) and prune_points are
+        # called in densify_and_prune's order, with its gradient and its prune mask formed here
+        assert not prune_only
+        grads = torch.nan_to_num(g.xyz_gradient_accum / g.denom, nan=0.0, posinf=float("inf"))
+        grads_t = torch.nan_to_num(g.t_gradient_accum / g.denom, nan=0.0, posinf=float("inf")) if cfg.gaussian_dim == 4 else None
+        g.densify_and_clone(grads, max_grad, extent, grads_t, max_grad_t)
+        g.densify_and_split(grads, max_grad, extent, grads_t, max_grad_t, N=N)
+        mask = (g.get_opacity < min_opacity).squeeze()
+        if max_screen_size:
+            mask = mask | (g.max_radii2D > max_screen_size) | (g.get_scaling.max(dim=1).values > 0.1 * extent)
+        g.prune_points(mask)
     snap("out.", out)
+    if prune_only and max_screen_size:
+        big = (out["in.max_radii2D"] > max_screen_size)
+        print(tag, "max_screen_size prunes %d of %d" % (int(big.sum()), P))
+        assert big.any()
     for i, s in enumerate(RECORDED):
         out["normal.%d" % i] = s.numpy().copy()
     out["args"] = np.array([max_grad, min_opacity, extent, -1.0 if max_screen_size is None else max_screen_size,
                             -1.0 if max_grad_t is None else max_grad_t, float(prune_only), args.percent_dense], dtype=np.float64)
+    out["N"] = np.array(N, dtype=np.int64)
     out["cfg"] = np.array([cfg.sh_degree, cfg.sh_degree_t, cfg.gaussian_dim, int(cfg.rot_4d)], dtype=np.int64)
     np.savez_compressed(os.path.join(HERE, "densify_%s.npz" % tag), **out)
     print(tag, "P %d -> %d, %d recorded normal draws" % (P, out["out.xyz"].shape[0], len(RECORDED)))
@@ -125,3 +143,5 @@ run("rot4d", SC("d", 300, 64, 48, 3, 2, 0.05, 10.0, True, 4, False), 1, 2e-4, 0.
 run("rot4d_pruneonly", SC("d", 250, 64, 48, 3, 2, 0.05, 10.0, True, 4, False), 2, 2e-4, 0.3, 6.0, 20, 2e-4 / 40, True)
 run("dim4_norot", SC("d", 500, 64, 48, 1, 0, 0.05, 1.0, False, 4, True), 3, 2e-4, 0.3, 6.0, None, 2e-4 / 40, False)
 run("dim3", SC("d", 500, 64, 48, 2, 0, 0.05, 1.0, False, 3, False), 4, 2e-4, 0.3, 6.0, 20, None, False)
+run("rot4d_n3", SC("d", 300, 64, 48, 3, 2, 0.05, 10.0, True, 4, False), 5, 2e-4, 0.3, 6.0, 20, 2e-4 / 40, False, N=3)
+run("dim3_pruneonly_screen", SC("d", 300, 64, 48, 2, 0, 0.05, 1.0, False, 3, False), 6, 2e-4, 0.05, 6.0, 20, None, True)

@@ -9,7 +9,8 @@ import util  # noqa: F401
 from oracle import densify_oracle as do
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
-CASES = ["rot4d", "rot4d_pruneonly", "dim4_norot", "dim3"]
+# rot4d_n3: the reference's densify_and_split driven with N = 3; dim3_pruneonly_screen: prune_only with max_screen_size pruning
+CASES = ["rot4d", "rot4d_pruneonly", "dim4_norot", "dim3", "rot4d_n3", "dim3_pruneonly_screen"]
 REF2OURS = {"xyz": "_xyz", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation", "t": "_t",
             "scaling_t": "_scaling_t", "rotation_r": "_rotation_r"}
 
@@ -34,7 +35,7 @@ def golden_call(d):
     normals = [d[k] for k in sorted((k for k in d.files if k.startswith("normal.")), key=lambda s: int(s.split(".")[1]))]
     kw = dict(max_grad=float(max_grad), min_opacity=float(min_opacity), extent=float(extent),
               max_screen_size=None if mss < 0 else float(mss), max_grad_t=None if mgt < 0 else float(mgt),
-              prune_only=bool(prune_only), percent_dense=float(percent_dense), N=2, rot_4d=bool(rot_4d), gaussian_dim=gaussian_dim,
+              prune_only=bool(prune_only), percent_dense=float(percent_dense), N=int(d["N"]) if "N" in d.files else 2, rot_4d=bool(rot_4d), gaussian_dim=gaussian_dim,
               samples=normals[0] if normals else None, samples_t=normals[1] if len(normals) > 1 else None)
     return kw
 
