@@ -163,7 +163,7 @@ namespace fdgs
 	{
 		const int i = blockIdx.x * REG_THREADS + threadIdx.x;
 		if (i >= P) return;
-		const float g_rigid = g_losses[0] * scale, g_motion = g_losses[1] * scale;
+		const float g_rigid = g_losses[0], g_motion = g_losses[1];
 		const float3 vi = ld3(velocity, i);
 		// dL/dv_i: motion (d mean|v| = v / |v| / P), then the rigid pairs in which i is the query, then those in which it is the
 		// neighbour (the reverse list, in pair order)
@@ -202,15 +202,16 @@ namespace fdgs
 		float dscale_t;
 		float4 drot, drot_r;
 		cov4_backward(g.c, dSig, dscale, dscale_t, drot, drot_r);
-		d_scaling[3 * (size_t)i] += dscale.x * g.sc.x;             // d exp
-		d_scaling[3 * (size_t)i + 1] += dscale.y * g.sc.y;
-		d_scaling[3 * (size_t)i + 2] += dscale.z * g.sc.z;
-		d_scaling_t[i] += dscale_t * g.sct;
+		// scale multiplies the finished gradient (not the upstream weights): scale = s gives s x the scale = 1 result, one rounding each
+		d_scaling[3 * (size_t)i] += scale * (dscale.x * g.sc.x);             // d exp
+		d_scaling[3 * (size_t)i + 1] += scale * (dscale.y * g.sc.y);
+		d_scaling[3 * (size_t)i + 2] += scale * (dscale.z * g.sc.z);
+		d_scaling_t[i] += scale * (dscale_t * g.sct);
 		const float4 dq = act_normalize_bwd(g.q, g.inv_q, drot), dqr = act_normalize_bwd(g.qr, g.inv_qr, drot_r);
 		float* oq = d_rotation + 4 * (size_t)i;
 		float* oqr = d_rotation_r + 4 * (size_t)i;
-		oq[0] += dq.x; oq[1] += dq.y; oq[2] += dq.z; oq[3] += dq.w;
-		oqr[0] += dqr.x; oqr[1] += dqr.y; oqr[2] += dqr.z; oqr[3] += dqr.w;
+		oq[0] += scale * dq.x; oq[1] += scale * dq.y; oq[2] += scale * dq.z; oq[3] += scale * dq.w;
+		oqr[0] += scale * dqr.x; oqr[1] += scale * dqr.y; oqr[2] += scale * dqr.z; oqr[3] += scale * dqr.w;
 	}
 
 	// ---- opacity mask ----

@@ -53,8 +53,9 @@ def dt_of(t: torch.Tensor) -> torch.Tensor:
     return (t32 + 0.1) - t32
 
 
-def velocity(scaling, scaling_t, rotation, rotation_r, t, dtype=torch.float64) -> torch.Tensor:
-    """v [P, 3] from the raw parameters; differentiable in the four tensors (t only enters through dt, which has no gradient)."""
+def velocity(scaling, scaling_t, rotation, rotation_r, t, dtype=torch.float64, dt=None) -> torch.Tensor:
+    """v [P, 3] from the raw parameters; differentiable in the four tensors (t only enters through dt, which has no gradient).
+    ``dt``: a constant in place of dt_of(t), for the host test's deliberately wrong statement."""
     s = torch.exp(torch.cat([scaling, scaling_t], dim=1).to(dtype))
     ql = rotation.to(dtype)
     qr = rotation_r.to(dtype)
@@ -68,13 +69,22 @@ def velocity(scaling, scaling_t, rotation, rotation_r, t, dtype=torch.float64) -
     L = R * s.unsqueeze(1)                                      # R @ diag(s)
     sigma = L @ L.transpose(1, 2)
     c12, ct = sigma[:, 0:3, 3], sigma[:, 3, 3:4]
-    return c12 / ct * dt_of(t).to(dtype)
+    return c12 / ct * (dt_of(t).to(dtype) if dt is None else dt)
 
 
-def rigid(v: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor) -> torch.Tensor:
-    """idx [P, k] int64, d2 [P, k] (the squared distances the query returned)."""
+def valid_entries(idx: torch.Tensor, P: int) -> torch.Tensor:
+    """The entries of a neighbour table that name a Gaussian: the kernels skip every other one (n < 0 or n >= P)."""
+    return (idx >= 0) & (idx < P)
+
+
+def rigid(v: torch.Tensor, idx: torch.Tensor, d2: torch.Tensor, mask=None) -> torch.Tensor:
+    """idx [P, k] int64, d2 [P, k] (the squared distances the query returned).  ``mask`` [P, k] bool: entries that are False
+    contribute nothing and their index is not read (valid_entries: how the kernels treat an index outside [0, P))."""
     P, k = idx.shape
     w = torch.exp(-100 * d2.to(v.dtype))
+    if mask is not None:
+        idx = torch.where(mask, idx, torch.zeros_like(idx))
+        w = w * mask.to(v.dtype)
     vd = torch.norm(v[idx] - v[:, None, :], p=2, dim=-1)
     return (w * vd).sum() / k / P
 
@@ -94,12 +104,64 @@ def opa_mask(alpha: torch.Tensor, gt_alpha_mask: torch.Tensor, bounds=(1e-6, 1 -
     return (-sky * torch.log(1 - o)).mean()
 
 
-def rigid_motion_with_grads(params, idx, d2, dtype=torch.float64, g_rigid=1.0, g_motion=1.0):
+NAMES4 = ("_scaling", "_scaling_t", "_rotation", "_rotation_r")
+
+
+def rigid_motion_with_grads(params, idx, d2, dtype=torch.float64, g_rigid=1.0, g_motion=1.0, mask=None):
     """params: dict of CPU tensors _scaling, _scaling_t, _rotation, _rotation_r, _t.  Returns (L_rigid, L_motion, grads dict) of
-    g_rigid * L_rigid + g_motion * L_motion with respect to the four raw tensors, computed in ``dtype``."""
-    leaves = {n: params[n].detach().to(dtype).clone().requires_grad_(True) for n in ("_scaling", "_scaling_t", "_rotation", "_rotation_r")}
+    g_rigid * L_rigid + g_motion * L_motion with respect to the four raw tensors, computed in ``dtype``.  ``mask``: see rigid()."""
+    leaves = {n: params[n].detach().to(dtype).clone().requires_grad_(True) for n in NAMES4}
     v = velocity(leaves["_scaling"], leaves["_scaling_t"], leaves["_rotation"], leaves["_rotation_r"], params["_t"], dtype)
-    lr = rigid(v, torch.as_tensor(idx), torch.as_tensor(d2))
+    lr = rigid(v, torch.as_tensor(idx), torch.as_tensor(d2), mask)
     lm = motion(v)
     (g_rigid * lr + g_motion * lm).backward()
-    return float(lr), float(lm), {n: t.grad.detach() for n, t in leaves.items()}
+    return float(lr.detach()), float(lm.detach()), {n: t.grad.detach() for n, t in leaves.items()}
+
+
+# ---- the bar a float32 kernel's gradients are held to ----
+#
+# bar = K * max(e32, 4 eps32 max|ref64|) per tensor, absolute, with NO floor: e32 = max|float32 statement - float64 statement| of
+# that tensor on that input (both from rigid_motion_with_grads) is the measurement of what float32 can do there -- 2e-7 .. 4e-7 of
+# max|ref64| for _scaling, _rotation and _rotation_r, 1e-4 .. 2e-3 for _scaling_t, whose derivative is a cancelling sum in any
+# float32 implementation -- and K covers a kernel that evaluates in another order than torch.  K is measured, not chosen: 4 times the
+# largest |hip - ref64| / max(e32, 4 eps32 max|ref64|) seen on the GPU over all cases of tests/regularizer_cases.py, rounded up to
+# a power of two, at least 8 (BASELINE.md, "Regulariser gradients", has the ratios).
+EPS32 = float(np.finfo(np.float32).eps)
+GRAD_BAR_K = {"_scaling": 8.0, "_scaling_t": 64.0, "_rotation": 8.0, "_rotation_r": 8.0, "velocity": 8.0}
+
+
+class Bar:
+    """ref: the float64 statement; unit = max(e32, 4 eps32 max|ref|); bar = K * unit."""
+
+    def __init__(self, name, ref, f32):
+        self.name, self.ref = name, ref
+        self.ref_max = float(ref.abs().max()) if ref.numel() else 0.0
+        self.e32 = float((f32.double() - ref).abs().max()) if ref.numel() else 0.0
+        self.unit = max(self.e32, 4 * EPS32 * self.ref_max)
+        self.bar = GRAD_BAR_K[name] * self.unit
+
+    def err(self, got) -> float:
+        got = got.detach().cpu().double().reshape(self.ref.shape)
+        return float((got - self.ref).abs().max()) if torch.isfinite(got).all() else float("inf")
+
+    def ratio(self, got) -> float:
+        """err / unit (0 / 0 = 0: an exact zero reference met exactly): a kernel passes where this is <= K."""
+        e = self.err(got)
+        return e / self.unit if self.unit > 0 else (0.0 if e == 0 else float("inf"))
+
+    def accepts(self, got) -> bool:
+        return self.err(got) <= self.bar
+
+
+def grad_bar(params, idx, d2, g_rigid, g_motion, mask=None):
+    """Per tensor of NAMES4: a Bar with the float64 reference gradient of g_rigid * L_rigid + g_motion * L_motion and its bar."""
+    g64 = rigid_motion_with_grads(params, idx, d2, torch.float64, g_rigid, g_motion, mask)[2]
+    g32 = rigid_motion_with_grads(params, idx, d2, torch.float32, g_rigid, g_motion, mask)[2]
+    return {n: Bar(n, g64[n], g32[n]) for n in NAMES4}
+
+
+def velocity_bar(params):
+    """The same bar for the velocity output."""
+    args = [params[n] for n in NAMES4 + ("_t",)]
+    with torch.no_grad():
+        return Bar("velocity", velocity(*args, torch.float64), velocity(*args, torch.float32))
