@@ -1050,6 +1050,93 @@ extern "C" int fdgs_debug_radix_sort_pairs(int32_t n, int32_t bit_lo, int32_t bi
 	return FDGS_OK;
 }
 
+// Test hook (include/fdgs.h): the tile binning launchers of tilebin.hip, in the order and with the arguments the forward gives them, on
+// the caller's rectangles and depths.  scratch = the tile counters (whole uint4s), the control words, the tile-order area, R-sized keys
+// of global sort scratch.
+namespace
+{
+	struct TileBinDebugLayout { size_t counters, ctl, order, big, total; };
+	inline TileBinDebugLayout tile_bin_debug_layout(int T, int capacity)
+	{
+		TileBinDebugLayout L;
+		size_t o = 0;
+		const size_t t = (size_t)(T > 0 ? T : 1), r = (size_t)(capacity > 0 ? capacity : 1);
+		L.counters = o; o = align_up(o + bin_counter_words((int)t) * 4);
+		L.ctl = o; o = align_up(o + 16);
+		L.order = o; o = align_up(o + (3 * t + 16) * 4);
+		L.big = o; o = align_up(o + r * 8);
+		L.total = o;
+		return L;
+	}
+}
+
+extern "C" size_t fdgs_debug_tile_bin_scratch_bytes(int32_t T, int32_t capacity) { return tile_bin_debug_layout(T, capacity).total; }
+
+extern "C" int fdgs_debug_tile_bin(int32_t P, const uint16_t* rect, const float* depths, int32_t grid_x, int32_t T, int32_t sparse_cap,
+                                   int32_t capacity, int32_t max_count, uint32_t* counts_out, uint32_t* starts_out, uint32_t* ctl_out,
+                                   uint32_t* pairs, uint32_t* point_list, uint32_t* ranges, uint32_t* order_out, void* scratch, void* stream_v)
+{
+	g_err[0] = 0;
+	if (T < 1 || T >= (1 << 24)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: T = %d is not within 1 <= T < 2^24", T);
+	if (grid_x < 1 || grid_x > 65535) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: grid_x = %d is not within 1 <= grid_x <= 65535", grid_x);
+	if (P < 1 || P >= (1 << 26)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: P = %d is not within 1 <= P < 2^26", P);
+	if (capacity < 1 || sparse_cap < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: capacity = %d < 1 or sparse_cap = %d < 0", capacity, sparse_cap);
+	if (sparse_cap > 0 && (long long)sparse_cap * T > (long long)capacity)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: sparse lists need capacity >= T * sparse_cap = %lld, got %d", (long long)sparse_cap * T, capacity);
+	if (!rect || !depths || !counts_out || !starts_out || !ctl_out || !pairs || !point_list || !ranges || !order_out || !scratch)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: NULL argument");
+	hipStream_t stream = (hipStream_t)stream_v;
+	// a rectangle that leaves the grid would become an atomic outside the counters: checked here, on a host copy
+	{
+		HIP_TRY(hipStreamSynchronize(stream), "tile bin debug: synchronize");
+		ushort4* h = (ushort4*)malloc((size_t)P * sizeof(ushort4));
+		if (!h) return fail(FDGS_ERR_ALLOC, "fdgs_debug_tile_bin: no host memory for %d rectangles", P);
+		const hipError_t e = hipMemcpy(h, rect, (size_t)P * sizeof(ushort4), hipMemcpyDeviceToHost);
+		int bad = -1;
+		for (int g = 0; e == hipSuccess && g < P && bad < 0; g++)
+			if (h[g].x > h[g].z || h[g].y > h[g].w || (int)h[g].z > grid_x || (long long)h[g].w * grid_x > (long long)T) bad = g;
+		const ushort4 b = bad >= 0 ? h[bad] : make_ushort4(0, 0, 0, 0);
+		free(h);
+		HIP_TRY(e, "tile bin debug: copy of the rectangles");
+		if (bad >= 0)
+			return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_tile_bin: rectangle %d = (%d, %d, %d, %d) leaves the grid (grid_x = %d, T = %d)", bad, (int)b.x, (int)b.y,
+			            (int)b.z, (int)b.w, grid_x, T);
+	}
+	const TileBinDebugLayout L = tile_bin_debug_layout(T, capacity);
+	char* s = (char*)scratch;
+	uint32_t* counters = (uint32_t*)(s + L.counters);
+	uint32_t* ctl = (uint32_t*)(s + L.ctl);
+	uint32_t* order = (uint32_t*)(s + L.order);
+	const int lds_cap = tile_sort_lds_cap();
+	const size_t tb = (size_t)T * 4;
+	HIP_TRY(hipMemsetAsync(s, 0, L.big, stream), "tile bin debug: memset");   // counters (as preprocess_fwd leaves them), ctl, the order area
+	if (sparse_cap == 0)
+	{
+		HIP_TRY(launch_tile_count(rect, P, grid_x, T, counters, stream), "tile count");
+		HIP_TRY(hipMemcpyAsync(counts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
+		HIP_TRY(launch_tile_scan(counters, T, ctl, nullptr, 0u, order, stream), "tile scan");
+		HIP_TRY(hipMemcpyAsync(starts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
+		uint32_t h_ctl[2] = { 0u, 0u };
+		HIP_TRY(hipMemcpyAsync(h_ctl, ctl, 8, hipMemcpyDeviceToHost, stream), "tile bin debug: read ctl");
+		HIP_TRY(hipStreamSynchronize(stream), "tile bin debug: synchronize");
+		const int longest = (int)h_ctl[1];
+		HIP_TRY(launch_tile_scatter(rect, depths, P, grid_x, T, counters, pairs, ctl, (uint32_t)capacity, order, stream, 0u), "tile scatter");
+		HIP_TRY(launch_tile_sort(counters, T, longest, pairs, point_list, ranges, longest > lds_cap ? (void*)(s + L.big) : nullptr, ctl, (uint32_t)capacity, order, stream),
+		        "tile sort");
+	}
+	else
+	{
+		const int longest = max_count > 0 ? max_count : sparse_cap;   // the longest list PROVIDED FOR (Plan::sort_longest)
+		HIP_TRY(launch_tile_scatter(rect, depths, P, grid_x, T, counters, pairs, ctl, (uint32_t)capacity, nullptr, stream, (uint32_t)sparse_cap), "tile scatter");
+		HIP_TRY(hipMemcpyAsync(counts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
+		HIP_TRY(launch_tile_sort(counters, T, longest, pairs, point_list, ranges, longest > lds_cap ? (void*)(s + L.big) : nullptr, ctl, (uint32_t)capacity, nullptr, stream,
+		                         (uint32_t)sparse_cap, ctl, nullptr, 0u, order), "tile sort");
+	}
+	HIP_TRY(hipMemcpyAsync(ctl_out, ctl, 8, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
+	HIP_TRY(hipMemcpyAsync(order_out, order, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
+	return FDGS_OK;
+}
+
 extern "C" int fdgs_debug_views(int32_t P, int32_t W, int32_t H, int32_t R,
                                 const void* geom_v, const void* bin_v, const void* img_v, fdgs_debug_view* v)
 {

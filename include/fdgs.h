@@ -393,6 +393,33 @@ int fdgs_debug_clock_sample(uint64_t* out5, double span_ms, void* stream);
  * exceeds `rank_max` the LDS bitonic sort (tilebin.hip); values <= 0 restore the defaults (16384, 96).  Process-wide. */
 void fdgs_debug_tile_sort_limits(int32_t lds_cap, int32_t rank_max);
 
+/* Test hook: the tile binning of the forward (csrc/tilebin.hip) on the caller's tile rectangles and depths, without a scene in front of
+ * it and a blend behind it.  It runs the launchers the forward runs, with the arguments the forward gives them, and nothing else:
+ *   sparse_cap == 0 (compact lists): count -> scan -> scatter -> sort; the sort instances are chosen by the longest list the scan
+ *     reported (read back after a stream synchronisation), `max_count` is ignored;
+ *   sparse_cap  > 0 (sparse lists: tile t owns the slots [t * sparse_cap, (t + 1) * sparse_cap)): scatter -> sort, the sort's extra
+ *     workgroup reporting num_rendered / the longest list and writing the tile order; max_count = the longest list provided for
+ *     (<= 0: sparse_cap); capacity >= T * sparse_cap.
+ * rect [P] ushort4 (x0, y0, x1, y1: tiles [x0, x1) x [y0, y1) of a grid grid_x tiles wide; x0 == x1 or y0 == y1: none), depths [P]
+ * float, both DEVICE memory; the pair of an instance is (bits of the depth, Gaussian index).  `capacity` = the instances `pairs` and
+ * `point_list` hold, the number the kernels compare num_rendered with: with more instances than that (compact lists) scatter and
+ * sort leave both alone and every range is (0, 0).  Outputs, DEVICE memory owned by the caller, written on `stream`:
+ *   counts_out [T]      the tile counters after the count pass (sparse lists: after the scatter pass -- the tiles' true counts)
+ *   starts_out [T]      the tile counters after the scan (sparse lists: not written)
+ *   ctl_out [2]         { num_rendered, longest list }
+ *   pairs [2 capacity]  the scattered (depth bits, index) pairs, in arrival order inside every tile's slice
+ *   point_list [capacity], ranges [2 T], order_out [T] (the blend kernels' tile order)
+ * pairs, point_list and ranges are written by the kernels themselves, the others are copies out of `scratch`
+ * (fdgs_debug_tile_bin_scratch_bytes(T, capacity) bytes of device memory: counters, control words, tile-order area, global sort scratch).
+ * FDGS_ERR_INVALID_ARG, with nothing launched: T < 1, T >= 2^24, grid_x < 1, P < 1, capacity < 1, a NULL pointer, a sparse layout that
+ * does not fit `capacity`, and a rectangle that leaves the grid (x0 > x1, y0 > y1, x1 > grid_x or y1 * grid_x > T; checked on a host copy
+ * of `rect`, after a synchronisation of `stream`: a malformed input becomes an error return, never an atomic out of range).
+ * Honours fdgs_debug_tile_sort_limits. */
+size_t fdgs_debug_tile_bin_scratch_bytes(int32_t T, int32_t capacity);
+int fdgs_debug_tile_bin(int32_t P, const uint16_t* rect, const float* depths, int32_t grid_x, int32_t T, int32_t sparse_cap, int32_t capacity,
+                        int32_t max_count, uint32_t* counts_out, uint32_t* starts_out, uint32_t* ctl_out, uint32_t* pairs, uint32_t* point_list,
+                        uint32_t* ranges, uint32_t* order_out, void* scratch, void* stream);
+
 /* Test hook: the library's radix sort (csrc/radix_sort.hip, radix_sort_pairs -- the sort behind fdgs_dist2_knn3, fdgs_knn_query and
  * fdgs_rigid_motion_backward; there is no second implementation) run on the caller's n (key, value) pairs of uint32, DEVICE memory.
  * A stable LSD sort by the key bits [bit_lo, bit_hi), RADIX_BITS = 8 bits per pass: pairs with equal selected bits keep their input

@@ -58,6 +58,12 @@ def test_argument_errors_are_reported_without_touching_the_gpu():
     rc = _capi.lib.fdgs_rasterize_forward(C.byref(scene), C.byref(out), cb, None, None, C.byref(R))
     assert rc == 1 and "must not be NULL" in _capi.last_error()
     assert _capi.lib.fdgs_mark_visible(-1, None, None, None, None, None) == 1
+    # the tile binning test hook turns sizes it cannot take away before it looks at a pointer
+    for P, gx, T, what in ((1, 4, 0, "T = 0"), (1, 4, 1 << 24, "T = 16777216"), (1, 0, 8, "grid_x = 0"), (0, 4, 8, "P = 0")):
+        assert _capi.lib.fdgs_debug_tile_bin(P, None, None, gx, T, 0, 16, 0, *([None] * 9)) == 1
+        assert "fdgs_debug_tile_bin" in _capi.last_error() and what in _capi.last_error()
+    assert _capi.lib.fdgs_debug_tile_bin(1, None, None, 4, 8, 0, 16, 0, *([None] * 9)) == 1 and "NULL" in _capi.last_error()
+    assert _capi.lib.fdgs_debug_tile_bin_scratch_bytes(1200, 5000) % 256 == 0
     assert _capi.lib.fdgs_profile_read(99, None, None) == 1
 
 
