@@ -145,7 +145,7 @@ extern "C" int fdgs_adam_step(float* params, const float* grads, float* exp_avg,
 {
 	using namespace fdgs;
 	if (!params || !grads || !exp_avg || !exp_avg_sq || n < 0 || !segments || num_segments <= 0 || num_segments > ADAM_MAX_SEG || step < 1)
-		return FDGS_ERR_INVALID_ARG;
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_adam_step: a pointer is NULL, n=%lld is negative, num_segments=%d is outside 1..%d, or step=%d is below 1", (long long)n, num_segments, ADAM_MAX_SEG, step);
 	if (n == 0) return FDGS_OK;
 	AdamSegs s;
 	s.n = num_segments;
@@ -183,12 +183,12 @@ extern "C" int fdgs_adam_step(float* params, const float* grads, float* exp_avg,
 		const int bx = (int)std::min<long long>((longest / 4 + 255) / 256 + 1, 256 * 8);
 		hipLaunchKernelGGL(adam_seg_kernel, dim3(bx, num_segments), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
 		                   (long long)n, s, beta1, beta2, eps, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)));
-		return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+		return launched("fdgs_adam_step");
 	}
 	const int blocks = (int)std::min<long long>((n / 4 + 255) / 256 + 1, 256 * 16);
 	hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, params, grads, exp_avg, exp_avg_sq,
 	                   (long long)n, s, beta1, beta2, eps, (float)(1.0 / bc1), (float)(1.0 / sqrt(bc2)));
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_adam_step");
 }
 
 extern "C" int fdgs_adam_step_sh(float* params, float* exp_avg, float* exp_avg_sq, float* dL_dsh,
@@ -197,7 +197,8 @@ extern "C" int fdgs_adam_step_sh(float* params, float* exp_avg, float* exp_avg_s
                                  float lr, float lr_dc, float beta1, float beta2, float eps, int32_t step, void* stream)
 {
 	using namespace fdgs;
-	if (!params || !exp_avg || !exp_avg_sq || !stages || P < 0 || M < 0 || num_views < 1 || step < 1) return FDGS_ERR_INVALID_ARG;
+	if (!params || !exp_avg || !exp_avg_sq || !stages || P < 0 || M < 0 || num_views < 1 || step < 1)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_adam_step_sh: a pointer is NULL, P=%d or M=%d is negative, or num_views=%d or step=%d is below 1", P, M, num_views, step);
 	if (P == 0 || M == 0) return FDGS_OK;
 	const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
 	const float inv_bc1 = (float)(1.0 / bc1);
@@ -206,6 +207,8 @@ extern "C" int fdgs_adam_step_sh(float* params, float* exp_avg, float* exp_avg_s
 	k.b1 = beta1; k.b2 = beta2; k.eps = eps; k.inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
 	const hipError_t e = launch_sh_adam(P, D, D_t, M, gaussian_dim, force_sh_3d, analytic_sh_grad, num_views, stages, params, exp_avg,
 	                                    exp_avg_sq, dL_dsh, k, (hipStream_t)stream);
-	if (e == hipErrorInvalidValue) return FDGS_ERR_INVALID_ARG;   // rows not a whole number of float4s, or arrays not 16-byte aligned
-	return e == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	if (e == hipErrorInvalidValue)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_adam_step_sh: rows of M=%d coefficients must be a whole number of float4s and every array 16-byte aligned", M);
+	HIP_TRY(e, "fdgs_adam_step_sh");
+	return FDGS_OK;
 }

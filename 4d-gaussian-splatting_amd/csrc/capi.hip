@@ -21,7 +21,7 @@ using namespace fdgs;
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* fmt, ...)
+int fdgs::fail(int code, const char* fmt, ...)
 {
 	va_list ap;
 	va_start(ap, fmt);
@@ -29,19 +29,6 @@ static int fail(int code, const char* fmt, ...)
 	va_end(ap);
 	return code;
 }
-
-// for the other translation units (fdgs_common.h)
-int fdgs::set_error(int code, const char* msg)
-{
-	snprintf(g_err, sizeof g_err, "%s", msg);
-	return code;
-}
-
-#define HIP_TRY(expr, what)                                                                         \
-	do {                                                                                            \
-		hipError_t e__ = (expr);                                                                    \
-		if (e__ != hipSuccess) return fail(FDGS_ERR_HIP, "%s: %s", what, hipGetErrorString(e__));   \
-	} while (0)
 
 // ---- optional per-stage HIP-event timing (fdgs_profile_*) ----
 namespace
@@ -114,7 +101,7 @@ namespace
 extern "C" int fdgs_profile_enable(int stage_mask) { g_prof_mask.store((uint32_t)stage_mask); return FDGS_OK; }
 extern "C" int fdgs_profile_sample_every(int32_t n)
 {
-	if (n < 1) return FDGS_ERR_INVALID_ARG;
+	if (n < 1) return fail(FDGS_ERR_INVALID_ARG, "fdgs_profile_sample_every: n=%d must be at least 1", n);
 	g_prof_every.store(n);
 	for (auto& c : g_prof_calls) c.store(0u);
 	return FDGS_OK;
@@ -127,7 +114,7 @@ extern "C" int fdgs_profile_reset(void)
 }
 extern "C" int fdgs_profile_read(int stage, double* total_ms, int64_t* samples)
 {
-	if (stage < 0 || stage >= FDGS_NUM_STAGES) return FDGS_ERR_INVALID_ARG;
+	if (stage < 0 || stage >= FDGS_NUM_STAGES) return fail(FDGS_ERR_INVALID_ARG, "fdgs_profile_read: stage=%d outside 0..%d", stage, FDGS_NUM_STAGES - 1);
 	std::lock_guard<std::mutex> lk(g_prof_mu);
 	prof_flush(g_prof[stage]);
 	if (total_ms) *total_ms = g_prof[stage].total_ms;
@@ -159,15 +146,6 @@ struct StageCtx { hipStream_t stream; bool debug; };
 // tile order of the blend kernels (written by the forward's scan or sparse sort, read again by the backward); FDGS_TILE_ORDER=0 in the
 // environment: index order (A/B timing)
 static const bool g_use_tile_order = []() { const char* e = getenv("FDGS_TILE_ORDER"); return !(e && e[0] == '0'); }();
-
-// every struct of the ABI starts with its own size as the caller's header defined it: a caller built against another fdgs.h
-// is turned away here instead of the library reading past the end of a shorter struct
-#define CHECK_STRUCT(ptr, type)                                                                                           \
-	do {                                                                                                                  \
-		if ((ptr)->struct_size != (uint32_t)sizeof(type))                                                                 \
-			return fail(FDGS_ERR_INVALID_ARG, #type ".struct_size is %u, this library (FDGS_VERSION %d) expects %zu: built against another fdgs.h?", \
-			            (unsigned)(ptr)->struct_size, FDGS_VERSION, sizeof(type));                                        \
-	} while (0)
 
 // The sizes every entry point that takes a model and an image accepts.  P < 2^26: the blend kernels address the 48-byte records and the
 // 64-byte accumulator records with 32-bit byte offsets.
@@ -286,7 +264,8 @@ static std::atomic<int> g_sparse_factor{4};
 static std::atomic<long long> g_sparse_stats[3];   // forwards with sparse lists, forwards that asked for them and got compact lists (budget), bytes of the last binning buffer
 extern "C" int fdgs_set_sparse_lists_budget(int64_t min_bytes, int32_t factor)
 {
-	if (min_bytes < 0 || factor < 1) return FDGS_ERR_INVALID_ARG;
+	if (min_bytes < 0 || factor < 1)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_set_sparse_lists_budget: min_bytes=%lld must not be negative and factor=%d must be at least 1", (long long)min_bytes, factor);
 	g_sparse_min_bytes.store(min_bytes); g_sparse_factor.store(factor);
 	return FDGS_OK;
 }
@@ -1010,12 +989,12 @@ namespace
 	inline SortDebugLayout sort_debug_layout(int n)
 	{
 		SortDebugLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t p = (size_t)(n > 0 ? n : 1);
-		for (int i = 0; i < 2; i++) { L.keys[i] = o; o = align_up(o + p * 4); }
-		for (int i = 0; i < 2; i++) { L.vals[i] = o; o = align_up(o + p * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)p) + 1) * 4);
-		L.total = o;
+		for (int i = 0; i < 2; i++) L.keys[i] = c.take(p * 4);
+		for (int i = 0; i < 2; i++) L.vals[i] = c.take(p * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)p) + 1) * 4);
+		L.total = c.o;
 		return L;
 	}
 }
@@ -1059,13 +1038,13 @@ namespace
 	inline TileBinDebugLayout tile_bin_debug_layout(int T, int capacity)
 	{
 		TileBinDebugLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t t = (size_t)(T > 0 ? T : 1), r = (size_t)(capacity > 0 ? capacity : 1);
-		L.counters = o; o = align_up(o + bin_counter_words((int)t) * 4);
-		L.ctl = o; o = align_up(o + 16);
-		L.order = o; o = align_up(o + (3 * t + 16) * 4);
-		L.big = o; o = align_up(o + r * 8);
-		L.total = o;
+		L.counters = c.take(bin_counter_words((int)t) * 4);
+		L.ctl = c.take(16);
+		L.order = c.take((3 * t + 16) * 4);
+		L.big = c.take(r * 8);
+		L.total = c.o;
 		return L;
 	}
 }

@@ -20,15 +20,15 @@ namespace fdgs
 	static inline KmLayout km_layout(int N, int K)
 	{
 		KmLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t n = (size_t)(N > 0 ? N : 1), k = (size_t)(K > 0 ? K : 1);
-		L.cnorm = o; o = align_up(o + k * 4);
-		for (int i = 0; i < 2; i++) { L.keys[i] = o; o = align_up(o + n * 4); }
-		for (int i = 0; i < 2; i++) { L.vals[i] = o; o = align_up(o + n * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)n) + 1) * 4);
-		L.seg_lo = o; o = align_up(o + k * 4);
-		L.seg_hi = o; o = align_up(o + k * 4);
-		L.total = o;
+		L.cnorm = c.take(k * 4);
+		for (int i = 0; i < 2; i++) L.keys[i] = c.take(n * 4);
+		for (int i = 0; i < 2; i++) L.vals[i] = c.take(n * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)n) + 1) * 4);
+		L.seg_lo = c.take(k * 4);
+		L.seg_hi = c.take(k * 4);
+		L.total = c.o;
 		return L;
 	}
 
@@ -298,13 +298,8 @@ static const char* km_sizes_bad(int32_t N, int32_t K, int32_t D)
 extern "C" int fdgs_kmeans_assign(int32_t N, int32_t K, int32_t D, const float* x, const float* c, int32_t* index, float* dist2, void* scratch,
                                   void* stream_v)
 {
-	if (km_sizes_bad(N, K, D))
-	{
-		char msg[128];
-		snprintf(msg, sizeof msg, "fdgs_kmeans_assign: %s (N=%d K=%d D=%d)", km_sizes_bad(N, K, D), N, K, D);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
-	if (!x || !c || !index || !scratch) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_assign: x / c / index / scratch must not be NULL");
+	if (const char* bad = km_sizes_bad(N, K, D)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_assign: %s (N=%d K=%d D=%d)", bad, N, K, D);
+	if (!x || !c || !index || !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_assign: x / c / index / scratch must not be NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
 	float* cn = (float*)((char*)scratch + km_layout(N, K).cnorm);
 	hipLaunchKernelGGL(kmeans_cnorm_kernel, dim3(div_up(K, 256)), dim3(256), 0, stream, K, D, c, cn);
@@ -315,19 +310,14 @@ extern "C" int fdgs_kmeans_assign(int32_t N, int32_t K, int32_t D, const float* 
 	else if (D <= 144) hipLaunchKernelGGL(kmeans_assign_kernel<72>, grid, block, 0, stream, N, K, D, x, c, cn, index);
 	else hipLaunchKernelGGL(kmeans_assign_kernel<96>, grid, block, 0, stream, N, K, D, x, c, cn, index);
 	if (dist2) hipLaunchKernelGGL(kmeans_dist_kernel, dim3((unsigned)(((long long)N + 255) / 256)), dim3(256), 0, stream, N, K, D, x, c, index, dist2);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_kmeans_assign: a kernel launch failed");
+	return launched("fdgs_kmeans_assign");
 }
 
 extern "C" int fdgs_kmeans_update(int32_t N, int32_t K, int32_t D, const float* x, const int32_t* index, const float* w, float* c, int32_t* counts,
                                   void* scratch, void* stream_v)
 {
-	if (km_sizes_bad(N, K, D))
-	{
-		char msg[128];
-		snprintf(msg, sizeof msg, "fdgs_kmeans_update: %s (N=%d K=%d D=%d)", km_sizes_bad(N, K, D), N, K, D);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
-	if (!x || !index || !c || !scratch) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_update: x / index / c / scratch must not be NULL");
+	if (const char* bad = km_sizes_bad(N, K, D)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_update: %s (N=%d K=%d D=%d)", bad, N, K, D);
+	if (!x || !index || !c || !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_kmeans_update: x / index / c / scratch must not be NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const KmLayout L = km_layout(N, K);
 	char* s = (char*)scratch;
@@ -339,42 +329,41 @@ extern "C" int fdgs_kmeans_update(int32_t N, int32_t K, int32_t D, const float* 
 	hipLaunchKernelGGL(kmeans_pairs_kernel, dim3(nb), dim3(256), 0, stream, N, index, keys[0], vals[0]);
 	const int bits = K <= 256 ? 8 : 16;   // whole radix passes over the keys 0 .. K - 1
 	int res = 0;
-	if (radix_sort_pairs(keys, vals, N, 0, bits, (uint32_t*)(s + L.hist), stream, &res) != hipSuccess)
-		return set_error(FDGS_ERR_HIP, "fdgs_kmeans_update: the radix sort failed");
-	if (hipMemsetAsync(seg_lo, 0, (size_t)K * 4, stream) != hipSuccess || hipMemsetAsync(seg_hi, 0, (size_t)K * 4, stream) != hipSuccess)
-		return set_error(FDGS_ERR_HIP, "fdgs_kmeans_update: hipMemsetAsync failed");
+	HIP_TRY(radix_sort_pairs(keys, vals, N, 0, bits, (uint32_t*)(s + L.hist), stream, &res), "fdgs_kmeans_update: radix_sort_pairs");
+	HIP_TRY(hipMemsetAsync(seg_lo, 0, (size_t)K * 4, stream), "fdgs_kmeans_update: hipMemsetAsync");
+	HIP_TRY(hipMemsetAsync(seg_hi, 0, (size_t)K * 4, stream), "fdgs_kmeans_update: hipMemsetAsync");
 	hipLaunchKernelGGL(kmeans_segments_kernel, dim3(nb), dim3(256), 0, stream, N, K, keys[res], seg_lo, seg_hi);
 	hipLaunchKernelGGL(kmeans_update_kernel, dim3(K), dim3(KM_MAX_D), 0, stream, K, D, x, w, vals[res], seg_lo, seg_hi, c, counts);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_kmeans_update: a kernel launch failed");
+	return launched("fdgs_kmeans_update");
 }
 
 extern "C" int fdgs_quantize_columns(int32_t P, int32_t C, const float* x, const float* lo, const float* inv, int32_t qmax, void* q, void* stream_v)
 {
-	if (P < 0 || C < 1 || (int64_t)P * C >= ((int64_t)1 << 40)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: need P >= 0, C >= 1");
-	if (qmax != 255 && qmax != 65535) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: qmax must be 255 (uint8) or 65535 (uint16)");
+	if (P < 0 || C < 1 || (int64_t)P * C >= ((int64_t)1 << 40)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: need P >= 0, C >= 1");
+	if (qmax != 255 && qmax != 65535) return fail(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: qmax must be 255 (uint8) or 65535 (uint16)");
 	if (P == 0) return FDGS_OK;
-	if (!x || !lo || !inv || !q) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: x / lo / inv / q must not be NULL");
+	if (!x || !lo || !inv || !q) return fail(FDGS_ERR_INVALID_ARG, "fdgs_quantize_columns: x / lo / inv / q must not be NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const long long total = (long long)P * C;
 	const int grid = stream_grid(total, 256);
 	if (qmax == 255) hipLaunchKernelGGL(quantize_columns_kernel<uint8_t>, dim3(grid), dim3(256), 0, stream, total, C, x, lo, inv, 255.f, (uint8_t*)q);
 	else hipLaunchKernelGGL(quantize_columns_kernel<uint16_t>, dim3(grid), dim3(256), 0, stream, total, C, x, lo, inv, 65535.f, (uint16_t*)q);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_quantize_columns: the kernel launch failed");
+	return launched("fdgs_quantize_columns");
 }
 
 extern "C" int fdgs_compact_decode(int32_t P, int32_t C, int32_t bits, const void* q, const float* lo, const float* step, int32_t D, const float* rows,
                                    const int32_t* index, int32_t K, float* out, void* stream_v)
 {
 	if (P < 0 || C < 0 || D < 0 || C + (int64_t)D < 1 || C + (int64_t)D > (1 << 20))
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: need P >= 0, C >= 0, D >= 0 and 1 <= C + D <= 2^20");
-	if (bits != 8 && bits != 16 && bits != 32) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: bits must be 8, 16 or 32");
-	if (D > 0 && index && K < 1) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: an index needs K >= 1 rows");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: need P >= 0, C >= 0, D >= 0 and 1 <= C + D <= 2^20");
+	if (bits != 8 && bits != 16 && bits != 32) return fail(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: bits must be 8, 16 or 32");
+	if (D > 0 && index && K < 1) return fail(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: an index needs K >= 1 rows");
 	if (P == 0) return FDGS_OK;
 	if (!out || (C > 0 && (!q || (bits != 32 && (!lo || !step)))) || (D > 0 && !rows))
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: out / q / lo / step / rows must not be NULL where they are read");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_compact_decode: out / q / lo / step / rows must not be NULL where they are read");
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (bits == 8) launch_decode<8>(P, C, q, lo, step, D, rows, index, K, out, stream);
 	else if (bits == 16) launch_decode<16>(P, C, q, lo, step, D, rows, index, K, out, stream);
 	else launch_decode<32>(P, C, q, lo, step, D, rows, index, K, out, stream);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_compact_decode: the kernel launch failed");
+	return launched("fdgs_compact_decode");
 }

@@ -197,18 +197,18 @@ extern "C" int fdgs_densify_stats_local(int32_t P, int32_t num_views, const int3
                                         float* count, float* pgrad, float* radii_max, void* stream)
 {
 	using namespace fdgs;
-	if (P < 0 || num_views < 1 || num_views > STATS_MAX_VIEWS || !radii || !viewspace_grad) return FDGS_ERR_INVALID_ARG;
+	if (P < 0 || num_views < 1 || num_views > STATS_MAX_VIEWS || !radii || !viewspace_grad) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_stats_local: P=%d is negative, num_views=%d is outside 1..%d, or radii / viewspace_grad is NULL", P, num_views, STATS_MAX_VIEWS);
 	if (P == 0) return FDGS_OK;
-	if (!count || !pgrad || !radii_max) return FDGS_ERR_INVALID_ARG;
+	if (!count || !pgrad || !radii_max) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_stats_local: count / pgrad / radii_max must not be NULL");
 	StatsViews v;
 	v.n = num_views;
 	for (int k = 0; k < num_views; k++)
 	{
-		if (!radii[k] || !viewspace_grad[k]) return FDGS_ERR_INVALID_ARG;
+		if (!radii[k] || !viewspace_grad[k]) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_stats_local: radii / viewspace_grad of view %d is NULL", k);
 		v.radii[k] = radii[k]; v.grad[k] = viewspace_grad[k];
 	}
 	hipLaunchKernelGGL(densify_stats_local_kernel, dim3(div_up(P, 256)), dim3(256), 0, (hipStream_t)stream, P, v, count, pgrad, radii_max);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_densify_stats_local");
 }
 
 extern "C" int fdgs_densify_stats_apply(int32_t P, const float* count, const float* pgrad, const float* radii_max, const float* t_grad,
@@ -216,12 +216,12 @@ extern "C" int fdgs_densify_stats_apply(int32_t P, const float* count, const flo
                                         float* max_radii2D, void* stream)
 {
 	using namespace fdgs;
-	if (P < 0) return FDGS_ERR_INVALID_ARG;
+	if (P < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_stats_apply: P=%d is negative", P);
 	if (P == 0) return FDGS_OK;
-	if (!count || !pgrad || !radii_max || !xyz_gradient_accum || !denom || !max_radii2D || (t_grad && !t_gradient_accum)) return FDGS_ERR_INVALID_ARG;
+	if (!count || !pgrad || !radii_max || !xyz_gradient_accum || !denom || !max_radii2D || (t_grad && !t_gradient_accum)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_stats_apply: count / pgrad / radii_max / xyz_gradient_accum / denom / max_radii2D must not be NULL, and t_grad needs t_gradient_accum");
 	hipLaunchKernelGGL(densify_stats_apply_kernel, dim3(div_up(P, 256)), dim3(256), 0, (hipStream_t)stream, P, count, pgrad, radii_max, t_grad,
 	                   global_batch, xyz_gradient_accum, t_gradient_accum, denom, max_radii2D);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_densify_stats_apply");
 }
 
 extern "C" int fdgs_densify_classify(int32_t P, const float* xyz_gradient_accum, const float* denom, const float* scaling_raw,
@@ -230,14 +230,14 @@ extern "C" int fdgs_densify_classify(int32_t P, const float* xyz_gradient_accum,
                                      uint8_t* flags, void* stream)
 {
 	using namespace fdgs;
-	if (P < 0 || N < 1) return FDGS_ERR_INVALID_ARG;
+	if (P < 0 || N < 1) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_classify: P=%d is negative or N=%d is below 1", P, N);
 	if (P == 0) return FDGS_OK;
-	if (!xyz_gradient_accum || !denom || !scaling_raw || !opacity_raw || !max_radii2D || !flags) return FDGS_ERR_INVALID_ARG;
+	if (!xyz_gradient_accum || !denom || !scaling_raw || !opacity_raw || !max_radii2D || !flags) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_classify: xyz_gradient_accum / denom / scaling_raw / opacity_raw / max_radii2D / flags must not be NULL");
 	const int has_screen = max_screen_size > 0.0f ? 1 : 0;   // `if max_screen_size:` (None or 0 -> no size test)
 	hipLaunchKernelGGL(densify_classify_kernel, dim3(div_up(P, 256)), dim3(256), 0, (hipStream_t)stream, P, xyz_gradient_accum, denom,
 	                   scaling_raw, opacity_raw, max_radii2D, max_grad, min_opacity, (float)((double)percent_dense * (double)extent),
 	                   (float)(0.1 * (double)extent), max_screen_size, (float)(1.0 / (0.8 * (double)N)), has_screen, prune_only, flags);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_densify_classify");
 }
 
 extern "C" int fdgs_densify_gather(int32_t num_segments, const int32_t* row_floats, int64_t P_old, int64_t P_new,
@@ -245,15 +245,15 @@ extern "C" int fdgs_densify_gather(int32_t num_segments, const int32_t* row_floa
                                    const float* old_exp_avg_sq, float* new_params, float* new_exp_avg, float* new_exp_avg_sq, void* stream)
 {
 	using namespace fdgs;
-	if (num_segments <= 0 || num_segments > DEN_MAX_SEG || !row_floats || P_old < 0 || P_new < 0) return FDGS_ERR_INVALID_ARG;
+	if (num_segments <= 0 || num_segments > DEN_MAX_SEG || !row_floats || P_old < 0 || P_new < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_gather: num_segments=%d is outside 1..%d, row_floats is NULL, or P_old=%lld / P_new=%lld is negative", num_segments, DEN_MAX_SEG, (long long)P_old, (long long)P_new);
 	if (P_new == 0) return FDGS_OK;
-	if (!src || !kind || !old_params || !old_exp_avg || !old_exp_avg_sq || !new_params || !new_exp_avg || !new_exp_avg_sq) return FDGS_ERR_INVALID_ARG;
+	if (!src || !kind || !old_params || !old_exp_avg || !old_exp_avg_sq || !new_params || !new_exp_avg || !new_exp_avg_sq) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_gather: src / kind and the old and new params / exp_avg / exp_avg_sq must not be NULL");
 	DenSegs s;
 	s.n = num_segments;
 	s.first[0] = 0;
 	for (int k = 0; k < num_segments; k++)
 	{
-		if (row_floats[k] <= 0) return FDGS_ERR_INVALID_ARG;
+		if (row_floats[k] <= 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_gather: row_floats[%d]=%d is not positive", k, row_floats[k]);
 		s.row[k] = row_floats[k];
 		s.first[k + 1] = s.first[k] + row_floats[k];
 	}
@@ -261,7 +261,7 @@ extern "C" int fdgs_densify_gather(int32_t num_segments, const int32_t* row_floa
 	const int blocks = (int)std::min<long long>((total + 255) / 256, 256 * 32);
 	hipLaunchKernelGGL(densify_gather_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, s, (long long)P_old, (long long)P_new, src, kind,
 	                   old_params, old_exp_avg, old_exp_avg_sq, new_params, new_exp_avg, new_exp_avg_sq);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_densify_gather");
 }
 
 extern "C" int fdgs_densify_split(int32_t n_children, int32_t N, int32_t rot_4d, int32_t gaussian_dim, const int32_t* parent,
@@ -270,17 +270,17 @@ extern "C" int fdgs_densify_split(int32_t n_children, int32_t N, int32_t rot_4d,
                                   float* new_xyz, float* new_t, float* new_scaling, float* new_scaling_t, void* stream)
 {
 	using namespace fdgs;
-	if (n_children < 0 || N < 1) return FDGS_ERR_INVALID_ARG;
+	if (n_children < 0 || N < 1) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_split: n_children=%d is negative or N=%d is below 1", n_children, N);
 	if (n_children == 0) return FDGS_OK;
-	if (!parent || !samples || !xyz || !scaling || !rotation || !new_xyz || !new_scaling) return FDGS_ERR_INVALID_ARG;
-	if (gaussian_dim == 4 && (!t || !scaling_t || !new_t || !new_scaling_t)) return FDGS_ERR_INVALID_ARG;
-	if (rot_4d && (!rotation_r || gaussian_dim != 4)) return FDGS_ERR_INVALID_ARG;
-	if (!rot_4d && gaussian_dim == 4 && !samples_t) return FDGS_ERR_INVALID_ARG;
+	if (!parent || !samples || !xyz || !scaling || !rotation || !new_xyz || !new_scaling) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_split: parent / samples / xyz / scaling / rotation / new_xyz / new_scaling must not be NULL");
+	if (gaussian_dim == 4 && (!t || !scaling_t || !new_t || !new_scaling_t)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_split: gaussian_dim == 4 needs t, scaling_t, new_t and new_scaling_t");
+	if (rot_4d && (!rotation_r || gaussian_dim != 4)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_split: rot_4d needs rotation_r and gaussian_dim == 4, got gaussian_dim=%d", gaussian_dim);
+	if (!rot_4d && gaussian_dim == 4 && !samples_t) return fail(FDGS_ERR_INVALID_ARG, "fdgs_densify_split: gaussian_dim == 4 without rot_4d needs samples_t");
 	SplitArgs a;
 	a.n = n_children; a.rot_4d = rot_4d; a.gaussian_dim = gaussian_dim; a.inv_split = (float)(1.0 / (0.8 * (double)N));
 	a.parent = parent; a.samples = samples; a.samples_t = samples_t;
 	a.xyz = xyz; a.t = t; a.scaling = scaling; a.scaling_t = scaling_t; a.rot = rotation; a.rot_r = rotation_r;
 	a.nxyz = new_xyz; a.nt = new_t; a.nscaling = new_scaling; a.nscaling_t = new_scaling_t;
 	hipLaunchKernelGGL(densify_split_kernel, dim3(div_up(n_children, 256)), dim3(256), 0, (hipStream_t)stream, a);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_densify_split");
 }

@@ -17,7 +17,6 @@
 // each recomputed from the tile.  float32, in the operation order of the statement above (built with FP contraction off).
 #include "fdgs_common.h"
 #include <math.h>
-#include <stdio.h>
 
 namespace fdgs
 {
@@ -341,37 +340,30 @@ namespace fdgs
 		write_grad(g.d_alpha, i, ga, g.accumulate);
 	}
 
-	static int depth_fail(const char* fn, const char* why)
+	// FDGS_OK: the arguments are fine and `a` is filled in; otherwise the entry point `fn` fails with what is wrong with them
+	static int depth_args(const char* fn, const fdgs_depth_in* in, DepthArgs& a)
 	{
-		char msg[256];
-		snprintf(msg, sizeof msg, "%s: %s", fn, why);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
-
-	// NULL: the arguments are fine and `a` is filled in; otherwise what is wrong with them
-	static const char* depth_args(const fdgs_depth_in* in, DepthArgs& a)
-	{
-		if (!in) return "in must not be NULL";
-		if (in->struct_size != sizeof(fdgs_depth_in)) return "fdgs_depth_in.struct_size is not sizeof(fdgs_depth_in): header and library differ";
-		if (in->H <= 0 || in->W <= 0 || (int64_t)in->H * in->W >= ((int64_t)1 << 30)) return "need H, W > 0 and H * W < 2^30";
-		if (in->H >= DN_TILE * 65535) return "H must be below 16 * 65535";
-		if (!in->depth) return "depth must not be NULL";
-		if (in->alpha && !(in->alpha_min > 0.f && in->alpha_min < INFINITY)) return "alpha_min must be positive and finite (z = depth / alpha)";
+		if (!in) return fail(FDGS_ERR_INVALID_ARG, "%s: in must not be NULL", fn);
+		CHECK_STRUCT_IN(fn, in, fdgs_depth_in);
+		if (in->H <= 0 || in->W <= 0 || (int64_t)in->H * in->W >= ((int64_t)1 << 30)) return fail(FDGS_ERR_INVALID_ARG, "%s: need H, W > 0 and H * W < 2^30", fn);
+		if (in->H >= DN_TILE * 65535) return fail(FDGS_ERR_INVALID_ARG, "%s: H must be below 16 * 65535", fn);
+		if (!in->depth) return fail(FDGS_ERR_INVALID_ARG, "%s: depth must not be NULL", fn);
+		if (in->alpha && !(in->alpha_min > 0.f && in->alpha_min < INFINITY)) return fail(FDGS_ERR_INVALID_ARG, "%s: alpha_min must be positive and finite (z = depth / alpha)", fn);
 		a.H = in->H; a.W = in->W; a.HW = in->H * in->W;
 		a.depth = in->depth; a.alpha = in->alpha; a.mask = in->mask; a.alpha_min = in->alpha_min;
-		return nullptr;
+		return FDGS_OK;
 	}
 
 	// `grads` may be NULL (no gradient); g is filled in either way
-	static const char* depth_grad_args(const fdgs_depth_in* in, const fdgs_depth_grads* grads, DepthGradArgs& g)
+	static int depth_grad_args(const char* fn, const fdgs_depth_in* in, const fdgs_depth_grads* grads, DepthGradArgs& g)
 	{
 		g.d_depth = g.d_alpha = nullptr; g.g_upstream = nullptr; g.scale = 1.f; g.accumulate = 0;
-		if (!grads) return nullptr;
-		if (grads->struct_size != sizeof(fdgs_depth_grads)) return "fdgs_depth_grads.struct_size is not sizeof(fdgs_depth_grads): header and library differ";
-		if (grads->d_alpha && !in->alpha) return "d_alpha without alpha";
+		if (!grads) return FDGS_OK;
+		CHECK_STRUCT_IN(fn, grads, fdgs_depth_grads);
+		if (grads->d_alpha && !in->alpha) return fail(FDGS_ERR_INVALID_ARG, "%s: d_alpha without alpha", fn);
 		g.d_depth = grads->d_depth; g.d_alpha = grads->d_alpha; g.g_upstream = grads->g_upstream; g.scale = grads->scale;
 		g.accumulate = grads->accumulate != 0;
-		return nullptr;
+		return FDGS_OK;
 	}
 }
 
@@ -388,10 +380,10 @@ extern "C" int fdgs_depth_loss(const fdgs_depth_in* in, const float* prior, int3
 {
 	DepthArgs a;
 	DepthGradArgs g;
-	if (const char* bad = depth_args(in, a)) return depth_fail("fdgs_depth_loss", bad);
-	if (const char* bad = depth_grad_args(in, grads, g)) return depth_fail("fdgs_depth_loss", bad);
-	if (mode != FDGS_DEPTH_PEARSON && mode != FDGS_DEPTH_SSI) return depth_fail("fdgs_depth_loss", "mode must be FDGS_DEPTH_PEARSON or FDGS_DEPTH_SSI");
-	if (!prior || !partials || !out) return depth_fail("fdgs_depth_loss", "prior, partials and out must not be NULL");
+	if (const int rc = depth_args("fdgs_depth_loss", in, a)) return rc;
+	if (const int rc = depth_grad_args("fdgs_depth_loss", in, grads, g)) return rc;
+	if (mode != FDGS_DEPTH_PEARSON && mode != FDGS_DEPTH_SSI) return fail(FDGS_ERR_INVALID_ARG, "fdgs_depth_loss: mode must be FDGS_DEPTH_PEARSON or FDGS_DEPTH_SSI");
+	if (!prior || !partials || !out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_depth_loss: prior, partials and out must not be NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const int nb = div_up(a.HW, DL_CHUNK);
 	double* stats = partials;
@@ -403,15 +395,15 @@ extern "C" int fdgs_depth_loss(const fdgs_depth_in* in, const float* prior, int3
 		hipLaunchKernelGGL(depth_apply_kernel, dim3(nb), dim3(DL_THREADS), 0, stream, a, prior, mode, stats, g, rparts);
 	if (mode == FDGS_DEPTH_SSI)
 		hipLaunchKernelGGL(depth_finish_kernel, dim3(1), dim3(DL_THREADS), 0, stream, nb, rparts, mode, 1, stats, out);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_depth_loss: launch failed");
+	return launched("fdgs_depth_loss");
 }
 
-static const char* normal_cam_args(float fl_x, float fl_y, float cx, float cy, const float* viewmatrix, NormalCam& cam)
+static int normal_cam_args(const char* fn, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix, NormalCam& cam)
 {
-	if (!(fl_x > 0.f && fl_x < INFINITY) || !(fl_y > 0.f && fl_y < INFINITY)) return "fl_x and fl_y must be positive and finite";
-	if (!(fabsf(cx) < INFINITY) || !(fabsf(cy) < INFINITY)) return "cx and cy must be finite";
+	if (!(fl_x > 0.f && fl_x < INFINITY) || !(fl_y > 0.f && fl_y < INFINITY)) return fail(FDGS_ERR_INVALID_ARG, "%s: fl_x and fl_y must be positive and finite", fn);
+	if (!(fabsf(cx) < INFINITY) || !(fabsf(cy) < INFINITY)) return fail(FDGS_ERR_INVALID_ARG, "%s: cx and cy must be finite", fn);
 	cam.fl_x = fl_x; cam.fl_y = fl_y; cam.cx = cx; cam.cy = cy; cam.vm = viewmatrix;
-	return nullptr;
+	return FDGS_OK;
 }
 
 extern "C" int fdgs_depth_normals(const fdgs_depth_in* in, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix,
@@ -419,12 +411,12 @@ extern "C" int fdgs_depth_normals(const fdgs_depth_in* in, float fl_x, float fl_
 {
 	DepthArgs a;
 	NormalCam cam;
-	if (const char* bad = depth_args(in, a)) return depth_fail("fdgs_depth_normals", bad);
-	if (const char* bad = normal_cam_args(fl_x, fl_y, cx, cy, viewmatrix, cam)) return depth_fail("fdgs_depth_normals", bad);
-	if (!normals || !valid) return depth_fail("fdgs_depth_normals", "normals and valid must not be NULL");
+	if (const int rc = depth_args("fdgs_depth_normals", in, a)) return rc;
+	if (const int rc = normal_cam_args("fdgs_depth_normals", fl_x, fl_y, cx, cy, viewmatrix, cam)) return rc;
+	if (!normals || !valid) return fail(FDGS_ERR_INVALID_ARG, "fdgs_depth_normals: normals and valid must not be NULL");
 	hipLaunchKernelGGL(depth_normals_kernel, dim3(div_up(a.W, DN_TILE), div_up(a.H, DN_TILE)), dim3(DN_TILE, DN_TILE), 0, (hipStream_t)stream,
 	                   a, cam, normals, valid);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_depth_normals: launch failed");
+	return launched("fdgs_depth_normals");
 }
 
 extern "C" int fdgs_depth_normals_backward(const fdgs_depth_in* in, float fl_x, float fl_y, float cx, float cy, const float* viewmatrix,
@@ -433,13 +425,13 @@ extern "C" int fdgs_depth_normals_backward(const fdgs_depth_in* in, float fl_x, 
 	DepthArgs a;
 	DepthGradArgs g;
 	NormalCam cam;
-	if (const char* bad = depth_args(in, a)) return depth_fail("fdgs_depth_normals_backward", bad);
-	if (const char* bad = normal_cam_args(fl_x, fl_y, cx, cy, viewmatrix, cam)) return depth_fail("fdgs_depth_normals_backward", bad);
-	if (!grads) return depth_fail("fdgs_depth_normals_backward", "grads must not be NULL");
-	if (const char* bad = depth_grad_args(in, grads, g)) return depth_fail("fdgs_depth_normals_backward", bad);
-	if (!dL_dnormals) return depth_fail("fdgs_depth_normals_backward", "dL_dnormals must not be NULL");
+	if (const int rc = depth_args("fdgs_depth_normals_backward", in, a)) return rc;
+	if (const int rc = normal_cam_args("fdgs_depth_normals_backward", fl_x, fl_y, cx, cy, viewmatrix, cam)) return rc;
+	if (!grads) return fail(FDGS_ERR_INVALID_ARG, "fdgs_depth_normals_backward: grads must not be NULL");
+	if (const int rc = depth_grad_args("fdgs_depth_normals_backward", in, grads, g)) return rc;
+	if (!dL_dnormals) return fail(FDGS_ERR_INVALID_ARG, "fdgs_depth_normals_backward: dL_dnormals must not be NULL");
 	if (!g.d_depth && !g.d_alpha) return FDGS_OK;
 	hipLaunchKernelGGL(depth_normals_bwd_kernel, dim3(div_up(a.W, DN_TILE), div_up(a.H, DN_TILE)), dim3(DN_TILE, DN_TILE), 0,
 	                   (hipStream_t)stream, a, cam, dL_dnormals, g);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_depth_normals_backward: launch failed");
+	return launched("fdgs_depth_normals_backward");
 }

@@ -236,17 +236,8 @@ static int env_args(const char* fn, int32_t H, int32_t W, const float* viewmatri
 {
 	if (H <= 0 || W <= 0 || H >= 16 * 65535 || env_h <= 0 || env_w <= 0 || (int64_t)env_h * env_w >= ((int64_t)1 << 31) ||
 	    !(radius > 0.f) || fl_x == 0.f || fl_y == 0.f)
-	{
-		char msg[160];
-		snprintf(msg, sizeof msg, "%s: bad image / map size, radius or focal length", fn);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
-	if (!viewmatrix || !campos || !env)
-	{
-		char msg[160];
-		snprintf(msg, sizeof msg, "%s: missing pointer", fn);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
+		return fail(FDGS_ERR_INVALID_ARG, "%s: bad image / map size, radius or focal length", fn);
+	if (!viewmatrix || !campos || !env) return fail(FDGS_ERR_INVALID_ARG, "%s: missing pointer", fn);
 	v->H = H; v->W = W; v->eh = env_h; v->ew = env_w; v->fx = fl_x; v->fy = fl_y; v->R = radius;
 	return FDGS_OK;
 }
@@ -258,11 +249,11 @@ extern "C" int fdgs_env_composite(int32_t H, int32_t W, const float* viewmatrix,
 	EnvView v;
 	const int rc = env_args("fdgs_env_composite", H, W, viewmatrix, campos, fl_x, fl_y, env, env_h, env_w, radius, &v);
 	if (rc != FDGS_OK) return rc;
-	if (!T || !colour_in || !colour_out) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_env_composite: missing pointer");
+	if (!T || !colour_in || !colour_out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_env_composite: missing pointer");
 	v.cx = cx; v.cy = cy;
 	hipLaunchKernelGGL(env_composite_kernel, dim3(div_up(W, ENV_TILE), div_up(H, ENV_TILE)), dim3(ENV_THREADS), 0, (hipStream_t)stream_v, v,
 	                   viewmatrix, campos, env, T, colour_in, colour_out);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_env_composite");
 }
 
 extern "C" int fdgs_env_composite_backward(int32_t H, int32_t W, const float* viewmatrix, const float* campos, float fl_x, float fl_y,
@@ -273,19 +264,19 @@ extern "C" int fdgs_env_composite_backward(int32_t H, int32_t W, const float* vi
 	EnvView v;
 	const int rc = env_args("fdgs_env_composite_backward", H, W, viewmatrix, campos, fl_x, fl_y, env, env_h, env_w, radius, &v);
 	if (rc != FDGS_OK) return rc;
-	if (!T || !g_colour) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_env_composite_backward: missing pointer");
+	if (!T || !g_colour) return fail(FDGS_ERR_INVALID_ARG, "fdgs_env_composite_backward: missing pointer");
 	v.cx = cx; v.cy = cy;
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (!g_alpha && !g_env) return FDGS_OK;
 	const dim3 grid(div_up(W, ENV_TILE), div_up(H, ENV_TILE));
 	if (g_env)
 	{
-		if (!accumulate_env && hipMemsetAsync(g_env, 0, (size_t)3 * env_h * env_w * sizeof(float), stream) != hipSuccess) return FDGS_ERR_HIP;
+		if (!accumulate_env) HIP_TRY(hipMemsetAsync(g_env, 0, (size_t)3 * env_h * env_w * sizeof(float), stream), "fdgs_env_composite_backward: hipMemsetAsync");
 		hipLaunchKernelGGL(env_backward_kernel<true>, grid, dim3(ENV_THREADS), 0, stream, v, viewmatrix, campos, env, T, g_colour, g_alpha,
 		                   accumulate_alpha, g_env);
 	}
 	else
 		hipLaunchKernelGGL(env_backward_kernel<false>, grid, dim3(ENV_THREADS), 0, stream, v, viewmatrix, campos, env, T, g_colour, g_alpha,
 		                   accumulate_alpha, g_env);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_env_composite_backward");
 }

@@ -26,6 +26,39 @@ namespace fdgs
 	static inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 	static inline int div_up(int a, int b) { return (a + b - 1) / b; }
 
+	// The one error path of the entry points (defined in capi.hip): records the formatted message as this thread's fdgs_last_error()
+	// and returns code.  Every non-zero return of an entry point goes through it, so the text always belongs to the call that failed.
+	int fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+	// the end of an entry point `fn` that launched kernels: FDGS_OK, or the launch error under its name
+	static inline int launched(const char* fn)
+	{
+		const hipError_t e = hipGetLastError();
+		return e == hipSuccess ? FDGS_OK : fail(FDGS_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+	}
+	// a HIP runtime call (or a launcher that returns hipError_t) inside an entry point
+#define HIP_TRY(expr, what)                                                                                 \
+	do {                                                                                                    \
+		hipError_t e__ = (expr);                                                                            \
+		if (e__ != hipSuccess) return ::fdgs::fail(FDGS_ERR_HIP, "%s: %s", what, hipGetErrorString(e__));   \
+	} while (0)
+	// every struct of the ABI starts with its own size as the caller's header defined it: a caller built against another fdgs.h
+	// is turned away here instead of the library reading past the end of a shorter struct.  CHECK_STRUCT_IN: the message starts
+	// with the entry point's name, as the other messages of that entry point do.
+#define CHECK_STRUCT_IN(fn, ptr, type)                                                                                    \
+	do {                                                                                                                  \
+		if ((ptr)->struct_size != (uint32_t)sizeof(type))                                                                 \
+			return ::fdgs::fail(FDGS_ERR_INVALID_ARG, "%s%s" #type ".struct_size is %u, this library (FDGS_VERSION %d) expects %zu: built against another fdgs.h?", \
+			                    fn, *(fn) ? ": " : "", (unsigned)(ptr)->struct_size, FDGS_VERSION, sizeof(type));         \
+	} while (0)
+#define CHECK_STRUCT(ptr, type) CHECK_STRUCT_IN("", ptr, type)
+
+	// hands out the members of a scratch layout front to back, each at the default alignment; `o` ends as the total
+	struct ScratchCursor
+	{
+		size_t o = 0;
+		size_t take(size_t bytes) { const size_t at = o; o = align_up(o + bytes); return at; }
+	};
+
 	// Packed per-Gaussian blend record, 3 x float4 = 48 B, written by preprocess and
 	// gathered by both blend kernels (one record instead of the reference's four arrays
 	// means2D / conic_opacity / rgb / depths + the flow input):
@@ -61,15 +94,15 @@ namespace fdgs
 	static inline GeomLayout geom_layout(int P)
 	{
 		GeomLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t p = (size_t)(P > 0 ? P : 1);
-		L.records = o; o = align_up(o + p * 48);
-		L.depths = o; o = align_up(o + p * 4);
-		L.cov3D = o; o = align_up(o + p * 24);
-		L.tiles_touched = o; o = align_up(o + p * 4);
-		L.rect = o; o = align_up(o + p * 8);
-		L.clamped = o; o = align_up(o + p);
-		L.total = o;
+		L.records = c.take(p * 48);
+		L.depths = c.take(p * 4);
+		L.cov3D = c.take(p * 24);
+		L.tiles_touched = c.take(p * 4);
+		L.rect = c.take(p * 8);
+		L.clamped = c.take(p);
+		L.total = c.o;
 		return L;
 	}
 
@@ -93,16 +126,16 @@ namespace fdgs
 	static inline ImageLayout image_layout(int W, int H)
 	{
 		ImageLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t n = (size_t)W * H;
 		const size_t t = (size_t)div_up(W, TILE_X) * div_up(H, TILE_Y);
-		L.final_T = o; o = align_up(o + n * 4);
-		L.n_contrib = o; o = align_up(o + n * 4);
-		L.ranges = o; o = align_up(o + t * 8);
-		L.tile_counters = o; o = align_up(o + bin_counter_words((int)t) * 4);
-		L.bin_ctl = o; o = align_up(o + 16);
-		L.tile_order = o; o = align_up(o + (3 * t + 16) * 4);
-		L.total = o;
+		L.final_T = c.take(n * 4);
+		L.n_contrib = c.take(n * 4);
+		L.ranges = c.take(t * 8);
+		L.tile_counters = c.take(bin_counter_words((int)t) * 4);
+		L.bin_ctl = c.take(16);
+		L.tile_order = c.take((3 * t + 16) * 4);
+		L.total = c.o;
 		return L;
 	}
 
@@ -120,15 +153,14 @@ namespace fdgs
 	static inline BinLayout bin_layout(int R, bool with_big_scratch, int T)
 	{
 		BinLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t r = (size_t)(R > 0 ? R : 1);
-		L.point_list = o; o = align_up(o + r * 4);
+		L.point_list = c.take(r * 4);
 		L.cull_stride = (uint32_t)((r >> 6) + (size_t)(T > 0 ? T : 0) + 2);
-		L.cull_bits = o; o = align_up(o + (size_t)L.cull_stride * 4 * 8);
-		L.pairs = o; o = align_up(o + r * 8);
-		L.big_scratch = o;
-		if (with_big_scratch) o = align_up(o + r * 8);
-		L.total = o;
+		L.cull_bits = c.take((size_t)L.cull_stride * 4 * 8);
+		L.pairs = c.take(r * 8);
+		L.big_scratch = c.take(with_big_scratch ? r * 8 : 0);
+		L.total = c.o;
 		return L;
 	}
 
@@ -140,9 +172,6 @@ namespace fdgs
 	// SH colours of several views of the same Gaussians in one pass over the coefficients (after the views' part-1 launches)
 	hipError_t launch_colour_batch(int nviews, const fdgs_scene* const* views, const fdgs_forward_out* const* outs, char* const* geoms,
 	                               hipStream_t stream);
-
-	// records msg as fdgs_last_error() of this thread (capi.hip) and returns code
-	int set_error(int code, const char* msg);
 
 	// Stable LSD radix sort of (key,value) u32 pairs on key bits [bit_lo, bit_hi) (radix_sort.hip; used by knn.hip and regularize.hip).
 	// keys[0]/vals[0] hold the input; *result receives the index (0/1) of the buffers holding the output.

@@ -20,7 +20,6 @@
 #pragma clang fp contract(off)
 #include "fdgs_common.h"
 #include "fdgs_math.h"
-#include <stdio.h>
 
 namespace fdgs
 {
@@ -160,20 +159,20 @@ namespace fdgs
 		if (a.d_rotations_r) { float* o = a.d_rotations_r + 4 * i; o[0] += drot_r.x; o[1] += drot_r.y; o[2] += drot_r.z; o[3] += drot_r.w; }
 	}
 
-	// NULL: the arguments are fine and `a` is filled in; otherwise what is wrong with them
-	static const char* flow_args(const fdgs_flow_in* in, FlowArgs& a)
+	// FDGS_OK: the arguments are fine and `a` is filled in; otherwise the entry point `fn` fails with what is wrong with them
+	static int flow_args(const char* fn, const fdgs_flow_in* in, FlowArgs& a)
 	{
-		if (!in) return "in must not be NULL";
-		if (in->struct_size != sizeof(fdgs_flow_in)) return "fdgs_flow_in.struct_size is not sizeof(fdgs_flow_in): header and library differ";
-		if (in->P < 0) return "P must not be negative";
-		if (in->W <= 0 || in->H <= 0) return "W and H must be positive";
-		if (!in->viewmatrix || !in->projmatrix) return "viewmatrix / projmatrix must not be NULL";
-		if ((in->viewmatrix_to == nullptr) != (in->projmatrix_to == nullptr)) return "viewmatrix_to and projmatrix_to come together (both NULL: the same camera)";
-		if (in->gaussian_dim != 3 && in->gaussian_dim != 4) return "gaussian_dim must be 3 or 4";
-		if (in->rot_4d && in->gaussian_dim != 4) return "rot_4d needs gaussian_dim == 4";
-		if (in->P > 0 && !in->means3D) return "means3D must not be NULL";
+		if (!in) return fail(FDGS_ERR_INVALID_ARG, "%s: in must not be NULL", fn);
+		CHECK_STRUCT_IN(fn, in, fdgs_flow_in);
+		if (in->P < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: P must not be negative", fn);
+		if (in->W <= 0 || in->H <= 0) return fail(FDGS_ERR_INVALID_ARG, "%s: W and H must be positive", fn);
+		if (!in->viewmatrix || !in->projmatrix) return fail(FDGS_ERR_INVALID_ARG, "%s: viewmatrix / projmatrix must not be NULL", fn);
+		if ((in->viewmatrix_to == nullptr) != (in->projmatrix_to == nullptr)) return fail(FDGS_ERR_INVALID_ARG, "%s: viewmatrix_to and projmatrix_to come together (both NULL: the same camera)", fn);
+		if (in->gaussian_dim != 3 && in->gaussian_dim != 4) return fail(FDGS_ERR_INVALID_ARG, "%s: gaussian_dim must be 3 or 4", fn);
+		if (in->rot_4d && in->gaussian_dim != 4) return fail(FDGS_ERR_INVALID_ARG, "%s: rot_4d needs gaussian_dim == 4", fn);
+		if (in->P > 0 && !in->means3D) return fail(FDGS_ERR_INVALID_ARG, "%s: means3D must not be NULL", fn);
 		if (in->P > 0 && in->rot_4d && (!in->ts || !in->scales || !in->scales_t || !in->rotations || !in->rotations_r))
-			return "rot_4d needs ts / scales / scales_t / rotations / rotations_r";
+			return fail(FDGS_ERR_INVALID_ARG, "%s: rot_4d needs ts / scales / scales_t / rotations / rotations_r", fn);
 		a.P = in->P; a.W = in->W; a.H = in->H;
 		a.means3D = in->means3D; a.ts = in->ts; a.scales = in->scales; a.scales_t = in->scales_t;
 		a.rotations = in->rotations; a.rotations_r = in->rotations_r;
@@ -184,13 +183,7 @@ namespace fdgs
 		a.rot_4d = in->rot_4d != 0; a.raw = in->raw_params != 0;
 		a.flows = nullptr; a.dL_dflows = nullptr; a.scale = 0.f;
 		a.d_means3D = a.d_ts = a.d_scales = a.d_scales_t = a.d_rotations = a.d_rotations_r = nullptr;
-		return nullptr;
-	}
-	static int flow_fail(const char* fn, const char* why)
-	{
-		char msg[256];
-		snprintf(msg, sizeof msg, "%s: %s", fn, why);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
+		return FDGS_OK;
 	}
 }
 
@@ -199,27 +192,26 @@ using namespace fdgs;
 extern "C" int fdgs_gaussian_flow_forward(const fdgs_flow_in* in, float* flows, void* stream)
 {
 	FlowArgs a;
-	if (const char* bad = flow_args(in, a)) return flow_fail("fdgs_gaussian_flow_forward", bad);
+	if (const int rc = flow_args("fdgs_gaussian_flow_forward", in, a)) return rc;
 	if (a.P == 0) return FDGS_OK;
-	if (!flows) return flow_fail("fdgs_gaussian_flow_forward", "flows must not be NULL");
+	if (!flows) return fail(FDGS_ERR_INVALID_ARG, "fdgs_gaussian_flow_forward: flows must not be NULL");
 	a.flows = flows;
 	hipLaunchKernelGGL(flow_forward_kernel, dim3(div_up(a.P, FLOW_THREADS)), dim3(FLOW_THREADS), 0, (hipStream_t)stream, a);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_gaussian_flow_forward: launch failed");
+	return launched("fdgs_gaussian_flow_forward");
 }
 
 extern "C" int fdgs_gaussian_flow_backward(const fdgs_flow_in* in, const float* dL_dflows, float scale, const fdgs_flow_grads* out, void* stream)
 {
 	FlowArgs a;
-	if (const char* bad = flow_args(in, a)) return flow_fail("fdgs_gaussian_flow_backward", bad);
-	if (!out) return flow_fail("fdgs_gaussian_flow_backward", "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_flow_grads))
-		return flow_fail("fdgs_gaussian_flow_backward", "fdgs_flow_grads.struct_size is not sizeof(fdgs_flow_grads): header and library differ");
+	if (const int rc = flow_args("fdgs_gaussian_flow_backward", in, a)) return rc;
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_gaussian_flow_backward: out must not be NULL");
+	CHECK_STRUCT_IN("fdgs_gaussian_flow_backward", out, fdgs_flow_grads);
 	if (a.P == 0) return FDGS_OK;
-	if (!dL_dflows) return flow_fail("fdgs_gaussian_flow_backward", "dL_dflows must not be NULL");
+	if (!dL_dflows) return fail(FDGS_ERR_INVALID_ARG, "fdgs_gaussian_flow_backward: dL_dflows must not be NULL");
 	a.dL_dflows = dL_dflows; a.scale = scale;
 	a.d_means3D = out->d_means3D; a.d_ts = out->d_ts; a.d_scales = out->d_scales; a.d_scales_t = out->d_scales_t;
 	a.d_rotations = out->d_rotations; a.d_rotations_r = out->d_rotations_r;
 	if (!a.d_means3D && !a.d_ts && !a.d_scales && !a.d_scales_t && !a.d_rotations && !a.d_rotations_r) return FDGS_OK;
 	hipLaunchKernelGGL(flow_backward_kernel, dim3(div_up(a.P, FLOW_THREADS)), dim3(FLOW_THREADS), 0, (hipStream_t)stream, a);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_gaussian_flow_backward: launch failed");
+	return launched("fdgs_gaussian_flow_backward");
 }

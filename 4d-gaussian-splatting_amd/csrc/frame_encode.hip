@@ -222,13 +222,13 @@ using namespace fdgs;
 extern "C" int fdgs_frames_encode(const float* images, int64_t image_stride, const float* alphas, int64_t alpha_stride, int32_t B,
                                   int32_t H, int32_t W, int32_t C, uint8_t* frames, int32_t N, const int32_t* index, void* stream_v)
 {
-	if (C != 3 && C != 4) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: C must be 3 (RGB) or 4 (RGBA)");
+	if (C != 3 && C != 4) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: C must be 3 (RGB) or 4 (RGBA)");
 	const int64_t HW = (int64_t)H * W;
 	if (N <= 0 || H <= 0 || W <= 0 || B <= 0 || B > 65535 || HW > ((int64_t)1 << 31) - 4096)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
-	if (!images || !index || !frames || (C == 4 && !alphas)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: missing pointer");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
+	if (!images || !index || !frames || (C == 4 && !alphas)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: missing pointer");
 	if (image_stride < 3 * HW || (C == 4 && alpha_stride < HW))
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: image_stride must be at least 3 H W floats and alpha_stride at least H W");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode: image_stride must be at least 3 H W floats and alpha_stride at least H W");
 	if (C == 3) alphas = nullptr;
 	EncodeArgs a;
 	a.images = images; a.alphas = alphas; a.index = index; a.frames = frames;
@@ -250,7 +250,7 @@ extern "C" int fdgs_frames_encode(const float* images, int64_t image_stride, con
 		if (C == 3) hipLaunchKernelGGL((frames_encode_kernel<3, false>), grid, block, 0, stream, a);
 		else hipLaunchKernelGGL((frames_encode_kernel<4, false>), grid, block, 0, stream, a);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_frames_encode");
 }
 
 extern "C" int64_t fdgs_frames_encode_gray_scratch_bytes(int32_t B, int32_t H, int32_t W)
@@ -265,10 +265,10 @@ extern "C" int fdgs_frames_encode_gray(const float* planes, int64_t plane_stride
 {
 	const int64_t HW = (int64_t)H * W;
 	if (N <= 0 || H <= 0 || W <= 0 || B <= 0 || B > 65535 || HW > ((int64_t)1 << 31) - 4096)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
-	if (!planes || !index || !frames || !scratch) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: missing pointer");
-	if (plane_stride < HW) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: plane_stride must be at least H W floats");
-	if ((uintptr_t)scratch % 4 != 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: scratch must be dword-aligned");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
+	if (!planes || !index || !frames || !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: missing pointer");
+	if (plane_stride < HW) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: plane_stride must be at least H W floats");
+	if ((uintptr_t)scratch % 4 != 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_encode_gray: scratch must be dword-aligned");
 	const int groups = minmax_groups(HW);
 	EncodeArgs a;
 	a.images = planes; a.alphas = nullptr; a.index = index; a.frames = frames;
@@ -292,5 +292,5 @@ extern "C" int fdgs_frames_encode_gray(const float* planes, int64_t plane_stride
 		const dim3 grid((unsigned)((HW + ENCODE_THREADS - 1) / ENCODE_THREADS), (unsigned)B);
 		hipLaunchKernelGGL((frames_encode_gray_kernel<false>), grid, block, 0, stream, a);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_frames_encode_gray");
 }

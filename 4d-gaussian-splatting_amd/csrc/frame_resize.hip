@@ -399,19 +399,11 @@ extern "C" int fdgs_frames_resize(const uint8_t* src, int32_t N, int32_t Hs, int
                                   uint8_t* dst, int32_t M, int32_t Hd, int32_t Wd, const int32_t* kx, const int32_t* bx, int32_t ksize_x,
                                   const int32_t* ky, const int32_t* by, int32_t ksize_y, void* scratch, void* stream_v)
 {
-	char msg[200];
-	if (const char* bad = resize_check(N, Hs, Ws, C, B, M, Hd, Wd))
-	{
-		snprintf(msg, sizeof msg, "fdgs_frames_resize: %s", bad);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
-	if (!src || !index || !dst || !kx || !bx || !ky || !by) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: missing pointer");
+	if (const char* bad = resize_check(N, Hs, Ws, C, B, M, Hd, Wd)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: %s", bad);
+	if (!src || !index || !dst || !kx || !bx || !ky || !by) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: missing pointer");
 	if (ksize_x != resize_ksize(Ws, Wd) || ksize_y != resize_ksize(Hs, Hd))
-	{
-		snprintf(msg, sizeof msg, "fdgs_frames_resize: ksize (%d, %d) disagrees with the sizes: %d -> %d columns take %d taps, %d -> %d rows %d",
-		         ksize_x, ksize_y, Ws, Wd, resize_ksize(Ws, Wd), Hs, Hd, resize_ksize(Hs, Hd));
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: ksize (%d, %d) disagrees with the sizes: %d -> %d columns take %d taps, %d -> %d rows %d",
+		            ksize_x, ksize_y, Ws, Wd, resize_ksize(Ws, Wd), Hs, Hd, resize_ksize(Hs, Hd));
 	hipStream_t stream = (hipStream_t)stream_v;
 	const bool do_x = Ws != Wd, do_y = Hs != Hd;
 	const int vec_src = (uintptr_t)src % 4 == 0, vec_dst = (uintptr_t)dst % 4 == 0;
@@ -423,7 +415,7 @@ extern "C" int fdgs_frames_resize(const uint8_t* src, int32_t N, int32_t Hs, int
 		const int units = vec ? fb / 4 : fb;
 		const dim3 grid((unsigned)std::min(div_up(units, RS_THREADS), 4096), (unsigned)B);
 		hipLaunchKernelGGL(frames_copy_kernel, grid, block, 0, stream, src, index, dst, N, fb, vec);
-		return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+		return launched("fdgs_frames_resize");
 	}
 	const ResizePlan P = resize_plan(Hs, Ws, Hd, Wd, C, ksize_x, ksize_y);
 	if (P.fused)
@@ -438,9 +430,9 @@ extern "C" int fdgs_frames_resize(const uint8_t* src, int32_t N, int32_t Hs, int
 		const dim3 grid((unsigned)tiles, (unsigned)B);
 		if (C == 3) hipLaunchKernelGGL((frames_resize_fused_kernel<3>), grid, block, P.lds, stream, a);
 		else hipLaunchKernelGGL((frames_resize_fused_kernel<4>), grid, block, P.lds, stream, a);
-		return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+		return launched("fdgs_frames_resize");
 	}
-	if (do_x && do_y && !scratch) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: missing pointer (scratch of fdgs_frames_resize_scratch_bytes)");
+	if (do_x && do_y && !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_resize: missing pointer (scratch of fdgs_frames_resize_scratch_bytes)");
 	PassArgs h, v;
 	h.in = src; h.index = index; h.out = do_y ? (uint8_t*)scratch : dst; h.k = kx; h.bnd = bx;
 	h.N = N; h.Hi = Hs; h.Wi = Ws; h.Ho = Hs; h.Wo = Wd; h.ks = ksize_x; h.gather = 1; h.premul = 1; h.unpremul = !do_y;
@@ -460,15 +452,15 @@ extern "C" int fdgs_frames_resize(const uint8_t* src, int32_t N, int32_t Hs, int
 		if (C == 3) hipLaunchKernelGGL((frames_resize_pass_kernel<3, false>), grid, block, 0, stream, v);
 		else hipLaunchKernelGGL((frames_resize_pass_kernel<4, false>), grid, block, 0, stream, v);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_frames_resize");
 }
 
 extern "C" int fdgs_frames_composite(const uint8_t* src_rgba, int32_t N, int32_t H, int32_t W, int32_t white, int32_t keep_alpha,
                                      uint8_t* dst, void* stream_v)
 {
 	if (N <= 0 || H <= 0 || W <= 0 || (int64_t)H * W * 4 > RS_MAX_FRAME)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_composite: bad sizes (N, H, W must be positive, a frame below 2^31 - 4096 bytes)");
-	if (!src_rgba || !dst) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_composite: missing pointer");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_composite: bad sizes (N, H, W must be positive, a frame below 2^31 - 4096 bytes)");
+	if (!src_rgba || !dst) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_composite: missing pointer");
 	const long long pixels = (long long)N * H * W;
 	const int vec_src = (uintptr_t)src_rgba % 4 == 0, vec_dst = (uintptr_t)dst % 4 == 0;
 	const dim3 block(RS_THREADS), grid((unsigned)std::min<long long>((pixels + RS_THREADS - 1) / RS_THREADS, 8192));
@@ -476,5 +468,5 @@ extern "C" int fdgs_frames_composite(const uint8_t* src_rgba, int32_t N, int32_t
 	const double bg = white ? 1.0 : 0.0;
 	if (keep_alpha) hipLaunchKernelGGL((frames_composite_kernel<4>), grid, block, 0, stream, src_rgba, dst, pixels, bg, vec_src, vec_dst);
 	else hipLaunchKernelGGL((frames_composite_kernel<3>), grid, block, 0, stream, src_rgba, dst, pixels, bg, vec_src, vec_dst);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_frames_composite");
 }

@@ -112,13 +112,13 @@ using namespace fdgs;
 extern "C" int fdgs_frames_decode(const uint8_t* frames, int32_t N, int32_t H, int32_t W, int32_t C, const int32_t* index, int32_t B,
                                   float* out, int64_t out_stride, float* mask_out, int64_t mask_stride, void* stream_v)
 {
-	if (C != 3 && C != 4) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: C must be 3 (RGB) or 4 (RGBA)");
+	if (C != 3 && C != 4) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: C must be 3 (RGB) or 4 (RGBA)");
 	const int64_t HW = (int64_t)H * W;
 	if (N <= 0 || H <= 0 || W <= 0 || B <= 0 || B > 65535 || HW > ((int64_t)1 << 31) - 4096)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
-	if (!frames || !index || !out) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: missing pointer");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: bad sizes (N, H, W, B must be positive, B <= 65535, H * W <= 2^31 - 4096)");
+	if (!frames || !index || !out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: missing pointer");
 	if (out_stride < 3 * HW || (mask_out && mask_stride < HW))
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: out_stride must be at least 3 H W floats and mask_stride at least H W");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_frames_decode: out_stride must be at least 3 H W floats and mask_stride at least H W");
 	if (C == 3) mask_out = nullptr;
 	FramesArgs a;
 	a.frames = frames; a.index = index; a.out = out; a.mask = mask_out;
@@ -140,5 +140,5 @@ extern "C" int fdgs_frames_decode(const uint8_t* frames, int32_t N, int32_t H, i
 		if (C == 3) hipLaunchKernelGGL((frames_decode_kernel<3, false>), grid, block, 0, stream, a);
 		else hipLaunchKernelGGL((frames_decode_kernel<4, false>), grid, block, 0, stream, a);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_frames_decode");
 }

@@ -23,14 +23,14 @@ namespace fdgs
 	static inline KnnLayout knn_layout(int P)
 	{
 		KnnLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t p = (size_t)(P > 0 ? P : 1);
-		for (int i = 0; i < 2; i++) { L.code[i] = o; o = align_up(o + p * 4); }
-		for (int i = 0; i < 2; i++) { L.idx[i] = o; o = align_up(o + p * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)p) + 1) * 4);
-		L.boxes = o; o = align_up(o + (size_t)div_up((int)p, KNN_BOX) * 6 * 4);
-		L.bounds = o; o = align_up(o + 6 * 4);
-		L.total = o;
+		for (int i = 0; i < 2; i++) L.code[i] = c.take(p * 4);
+		for (int i = 0; i < 2; i++) L.idx[i] = c.take(p * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)p) + 1) * 4);
+		L.boxes = c.take((size_t)div_up((int)p, KNN_BOX) * 6 * 4);
+		L.bounds = c.take(6 * 4);
+		L.total = c.o;
 		return L;
 	}
 
@@ -187,9 +187,9 @@ extern "C" size_t fdgs_knn_scratch_bytes(int32_t P) { return fdgs::knn_layout(P)
 extern "C" int fdgs_dist2_knn3(int32_t P, const float* points, float* mean_dist2, void* scratch, void* stream_v)
 {
 	using namespace fdgs;
-	if (P < 0) return FDGS_ERR_INVALID_ARG;
+	if (P < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_dist2_knn3: P=%d is negative", P);
 	if (P == 0) return FDGS_OK;
-	if (!points || !mean_dist2 || !scratch) return FDGS_ERR_INVALID_ARG;
+	if (!points || !mean_dist2 || !scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_dist2_knn3: points / mean_dist2 / scratch must not be NULL");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const KnnLayout L = knn_layout(P);
 	char* s = (char*)scratch;
@@ -200,11 +200,11 @@ extern "C" int fdgs_dist2_knn3(int32_t P, const float* points, float* mean_dist2
 	hipLaunchKernelGGL(knn_bounds_kernel, dim3(1), dim3(1024), 0, stream, P, points, 0, nullptr, bounds);
 	hipLaunchKernelGGL(knn_morton_kernel, dim3(div_up(P, 256)), dim3(256), 0, stream, P, points, bounds, codes[0], idx[0]);
 	int res = 0;
-	if (radix_sort_pairs(codes, idx, P, 0, 32, (uint32_t*)(s + L.hist), stream, &res) != hipSuccess) return FDGS_ERR_HIP;
+	HIP_TRY(radix_sort_pairs(codes, idx, P, 0, 32, (uint32_t*)(s + L.hist), stream, &res), "fdgs_dist2_knn3: radix_sort_pairs");
 	const int nboxes = div_up(P, KNN_BOX);
 	hipLaunchKernelGGL(knn_box_bounds_kernel<KNN_BOX>, dim3(nboxes), dim3(KNN_THREADS), 0, stream, P, points, idx[res], boxes);
 	hipLaunchKernelGGL(knn_mean_dist_kernel, dim3(div_up(P, KNN_THREADS)), dim3(KNN_THREADS), 0, stream, P, points, idx[res], boxes, mean_dist2);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_dist2_knn3");
 }
 
 // ---- k-nearest-neighbour query: drop-in for pointops2's knnquery (utils/general_utils.py:170-184) ----------------------
@@ -230,16 +230,16 @@ namespace fdgs
 	static inline KnnQueryLayout knn_query_layout(int n, int m)
 	{
 		KnnQueryLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t pn = (size_t)(n > 0 ? n : 1), pm = (size_t)(m > 0 ? m : 1);
-		for (int i = 0; i < 2; i++) { L.scode[i] = o; o = align_up(o + pm * 4); }
-		for (int i = 0; i < 2; i++) { L.sidx[i] = o; o = align_up(o + pm * 4); }
-		for (int i = 0; i < 2; i++) { L.qcode[i] = o; o = align_up(o + pn * 4); }
-		for (int i = 0; i < 2; i++) { L.qidx[i] = o; o = align_up(o + pn * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)(pn > pm ? pn : pm)) + 1) * 4);
-		L.boxes = o; o = align_up(o + (size_t)div_up((int)pm, KNNQ_BOX) * 6 * 4);
-		L.bounds = o; o = align_up(o + 6 * 4);
-		L.total = o;
+		for (int i = 0; i < 2; i++) L.scode[i] = c.take(pm * 4);
+		for (int i = 0; i < 2; i++) L.sidx[i] = c.take(pm * 4);
+		for (int i = 0; i < 2; i++) L.qcode[i] = c.take(pn * 4);
+		for (int i = 0; i < 2; i++) L.qidx[i] = c.take(pn * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)(pn > pm ? pn : pm)) + 1) * 4);
+		L.boxes = c.take((size_t)div_up((int)pm, KNNQ_BOX) * 6 * 4);
+		L.bounds = c.take(6 * 4);
+		L.total = c.o;
 		return L;
 	}
 
@@ -372,12 +372,12 @@ extern "C" int fdgs_knn_query(int32_t b, int32_t n, int32_t m, int32_t k, const 
                               void* scratch, void* stream_v)
 {
 	using namespace fdgs;
-	if (b < 0 || n < 0 || m < 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: negative size");
-	if (k < 1 || k > FDGS_KNN_MAX_K) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: k must be in [1, 64]");
+	if (b < 0 || n < 0 || m < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: negative size");
+	if (k < 1 || k > FDGS_KNN_MAX_K) return fail(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: k must be in [1, 64]");
 	if ((int64_t)div_up(m > 0 ? m : 1, KNNQ_BOX) > (int64_t)KNNQ_MASK_WORDS * 32)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: more than 16777216 sources per batch");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: more than 16777216 sources per batch");
 	if (b == 0 || n == 0) return FDGS_OK;
-	if (!x || !idx || !dist2 || !scratch || (m > 0 && !src)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: missing pointer");
+	if (!x || !idx || !dist2 || !scratch || (m > 0 && !src)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_knn_query: missing pointer");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const KnnQueryLayout L = knn_query_layout(n, m);
 	char* s = (char*)scratch;
@@ -395,12 +395,12 @@ extern "C" int fdgs_knn_query(int32_t b, int32_t n, int32_t m, int32_t k, const 
 		if (m > 0)
 		{
 			hipLaunchKernelGGL(knn_morton_kernel, dim3(div_up(m, 256)), dim3(256), 0, stream, m, sb, bounds, scode[0], sidx[0]);
-			if (radix_sort_pairs(scode, sidx, m, 0, 32, (uint32_t*)(s + L.hist), stream, &sres) != hipSuccess) return FDGS_ERR_HIP;
+			HIP_TRY(radix_sort_pairs(scode, sidx, m, 0, 32, (uint32_t*)(s + L.hist), stream, &sres), "fdgs_knn_query: radix_sort_pairs");
 			hipLaunchKernelGGL(knn_box_bounds_kernel<KNNQ_BOX>, dim3(div_up(m, KNNQ_BOX)), dim3(KNN_THREADS), 0, stream, m, sb, sidx[sres],
 			                   (float*)(s + L.boxes));
 		}
 		hipLaunchKernelGGL(knn_morton_kernel, dim3(div_up(n, 256)), dim3(256), 0, stream, n, xb, bounds, qcode[0], qidx[0]);
-		if (radix_sort_pairs(qcode, qidx, n, 0, 32, (uint32_t*)(s + L.hist), stream, &qres) != hipSuccess) return FDGS_ERR_HIP;
+		HIP_TRY(radix_sort_pairs(qcode, qidx, n, 0, 32, (uint32_t*)(s + L.hist), stream, &qres), "fdgs_knn_query: radix_sort_pairs");
 		int64_t* ib = idx + (size_t)bb * n * k;
 		float* db = dist2 + (size_t)bb * n * k;
 		if (k <= 4) knn_query_launch<4>(n, m, k, xb, sb, L, s, qres, sres, ib, db, stream);
@@ -410,14 +410,14 @@ extern "C" int fdgs_knn_query(int32_t b, int32_t n, int32_t m, int32_t k, const 
 		else if (k <= 32) knn_query_launch<32>(n, m, k, xb, sb, L, s, qres, sres, ib, db, stream);
 		else knn_query_launch<64>(n, m, k, xb, sb, L, s, qres, sres, ib, db, stream);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_knn_query");
 }
 
 // Test hook (include/fdgs.h): where the stages above lie in the scratch buffer of a finished call.  Host arithmetic only.
 extern "C" int fdgs_debug_knn_stage_offsets(int32_t query, int32_t n, int32_t m, int64_t* offsets)
 {
 	using namespace fdgs;
-	if (!offsets || n < 0 || m < 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_debug_knn_stage_offsets: bad arguments");
+	if (!offsets || n < 0 || m < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_debug_knn_stage_offsets: bad arguments");
 	if (query)
 	{
 		const KnnQueryLayout L = knn_query_layout(n, m);

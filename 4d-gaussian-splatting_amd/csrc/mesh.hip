@@ -255,14 +255,7 @@ namespace fdgs
 	{
 		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
 		if (v > V) return;
-		int lo = 0, hi = n;
-		while (lo < hi)
-		{
-			const int mid = lo + (hi - lo) / 2;
-			if (keys[mid] < (uint32_t)v) lo = mid + 1;
-			else hi = mid;
-		}
-		row_start[v] = lo;
+		row_start[v] = lower_bound_u32(keys, n, (uint32_t)v);
 	}
 
 	// the other two corners of every incidence, in ascending corner index.  n_rows = row_start[V]: the incidences of present faces
@@ -360,38 +353,38 @@ namespace fdgs
 	static ComponentsLayout components_layout(int V)
 	{
 		ComponentsLayout L;
-		size_t o = 0;
-		L.flag = o; o = align_up(o + 16);                    // a block of its own at the start: the memset's target
-		L.parent = o; o = align_up(o + (size_t)V * sizeof(int32_t));
-		L.counts = o; o = align_up(o + blocks_of((size_t)V) * sizeof(uint32_t));
-		L.total = o;
+		ScratchCursor c;
+		L.flag = c.take(16);                    // a block of its own at the start: the memset's target
+		L.parent = c.take((size_t)V * sizeof(int32_t));
+		L.counts = c.take(blocks_of((size_t)V) * sizeof(uint32_t));
+		L.total = c.o;
 		return L;
 	}
 	struct CompactLayout { size_t map, vcounts, fcounts, total; };
 	static CompactLayout compact_layout(int V, int F)
 	{
 		CompactLayout L;
-		size_t o = 0;
-		L.map = o; o = align_up(o + (size_t)V * sizeof(int32_t));
-		L.vcounts = o; o = align_up(o + blocks_of((size_t)V) * sizeof(uint32_t));
-		L.fcounts = o; o = align_up(o + blocks_of((size_t)F) * sizeof(uint32_t));
-		L.total = o;
+		ScratchCursor c;
+		L.map = c.take((size_t)V * sizeof(int32_t));
+		L.vcounts = c.take(blocks_of((size_t)V) * sizeof(uint32_t));
+		L.fcounts = c.take(blocks_of((size_t)F) * sizeof(uint32_t));
+		L.total = c.o;
 		return L;
 	}
 	struct SmoothLayout { size_t keys[2], vals[2], hist, row_start, others, tmp, boundary, total; };
 	static SmoothLayout smooth_layout(int V, int F)
 	{
 		SmoothLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t n = 3 * (size_t)F;
-		for (int k = 0; k < 2; k++) { L.keys[k] = o; o = align_up(o + n * 4); }
-		for (int k = 0; k < 2; k++) { L.vals[k] = o; o = align_up(o + n * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)n) + 1) * 4);
-		L.row_start = o; o = align_up(o + ((size_t)V + 1) * sizeof(int32_t));
-		L.others = o; o = align_up(o + n * sizeof(int2));
-		L.tmp = o; o = align_up(o + 3 * (size_t)V * sizeof(float));
-		L.boundary = o; o = align_up(o + (size_t)V);
-		L.total = o;
+		for (int k = 0; k < 2; k++) L.keys[k] = c.take(n * 4);
+		for (int k = 0; k < 2; k++) L.vals[k] = c.take(n * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)n) + 1) * 4);
+		L.row_start = c.take(((size_t)V + 1) * sizeof(int32_t));
+		L.others = c.take(n * sizeof(int2));
+		L.tmp = c.take(3 * (size_t)V * sizeof(float));
+		L.boundary = c.take((size_t)V);
+		L.total = c.o;
 		return L;
 	}
 }
@@ -406,15 +399,14 @@ extern "C" size_t fdgs_mesh_components_scratch_bytes(int32_t V, int32_t F)
 extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_components_out* out, void* scratch, void* stream_v)
 {
 	const char* fn = "fdgs_mesh_components";
-	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
-	if (!out) return mesh_fail(fn, "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_mesh_components_out))
-		return mesh_fail(fn, "fdgs_mesh_components_out.struct_size is not sizeof(fdgs_mesh_components_out): header and library differ");
-	if (out->capacity < 0) return mesh_fail(fn, "capacity must not be negative");
-	if (!out->labelled && !out->n_components) return mesh_fail(fn, "n_components must not be NULL");
+	if (const int rc = mesh_in_args(fn, mesh)) return rc;
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
+	CHECK_STRUCT_IN(fn, out, fdgs_mesh_components_out);
+	if (out->capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: capacity must not be negative", fn);
+	if (!out->labelled && !out->n_components) return fail(FDGS_ERR_INVALID_ARG, "%s: n_components must not be NULL", fn);
 	const int V = mesh->V, F = mesh->F;
-	if (V > 0 && !out->vertex_component) return mesh_fail(fn, "vertex_component must not be NULL with V > 0");
-	if (V > 0 && !out->labelled && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	if (V > 0 && !out->vertex_component) return fail(FDGS_ERR_INVALID_ARG, "%s: vertex_component must not be NULL with V > 0", fn);
+	if (V > 0 && !out->labelled && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (out->rounds) *out->rounds = 0;
 	const int cap = out->capacity;
@@ -424,7 +416,10 @@ extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_co
 	if (!out->labelled)
 	{
 		if (V == 0)
-			return hipMemsetAsync(out->n_components, 0, sizeof(int32_t), stream) == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+		{
+			HIP_TRY(hipMemsetAsync(out->n_components, 0, sizeof(int32_t), stream), "fdgs_mesh_components: memset");
+			return FDGS_OK;
+		}
 		const ComponentsLayout L = components_layout(V);
 		char* base = reinterpret_cast<char*>(scratch);
 		int32_t* flag = reinterpret_cast<int32_t*>(base + L.flag);
@@ -434,13 +429,13 @@ extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_co
 		int rounds = 0;
 		for (bool done = F == 0; !done;)
 		{
-			if (rounds == MESH_MAX_ROUNDS) return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: no convergence within 32 hook passes");
+			if (rounds == MESH_MAX_ROUNDS) return fail(FDGS_ERR_HIP, "fdgs_mesh_components: no convergence within 32 hook passes");
 			int32_t changed = 0;
-			if (hipMemsetAsync(flag, 0, 16, stream) != hipSuccess) return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+			HIP_TRY(hipMemsetAsync(flag, 0, 16, stream), "fdgs_mesh_components: memset");
 			hipLaunchKernelGGL(cc_hook_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, parent, flag);
 			rounds++;
-			if (hipMemcpyAsync(&changed, flag, sizeof changed, hipMemcpyDeviceToHost, stream) != hipSuccess || hipStreamSynchronize(stream) != hipSuccess)
-				return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: reading the convergence flag failed");
+			HIP_TRY(hipMemcpyAsync(&changed, flag, sizeof changed, hipMemcpyDeviceToHost, stream), "fdgs_mesh_components: reading the convergence flag");
+			HIP_TRY(hipStreamSynchronize(stream), "fdgs_mesh_components: reading the convergence flag");
 			done = changed == 0;
 			if (!done) hipLaunchKernelGGL(cc_compress_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V);
 		}
@@ -453,13 +448,12 @@ extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_co
 		hipLaunchKernelGGL(cc_rank_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, counts, out->vertex_component);
 		hipLaunchKernelGGL(cc_assign_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, out->vertex_component);
 	}
-	if ((cv && hipMemsetAsync(cv, 0, (size_t)cap * sizeof(int32_t), stream) != hipSuccess) ||
-	    (cf && hipMemsetAsync(cf, 0, (size_t)cap * sizeof(int32_t), stream) != hipSuccess))
-		return set_error(FDGS_ERR_HIP, "fdgs_mesh_components: memset failed");
+	if (cv) HIP_TRY(hipMemsetAsync(cv, 0, (size_t)cap * sizeof(int32_t), stream), "fdgs_mesh_components: memset");
+	if (cf) HIP_TRY(hipMemsetAsync(cf, 0, (size_t)cap * sizeof(int32_t), stream), "fdgs_mesh_components: memset");
 	if (cv && V > 0) hipLaunchKernelGGL(cc_vertex_count_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, out->vertex_component, V, cv, cap);
 	if (cf && V > 0 && F > 0)
 		hipLaunchKernelGGL(cc_face_count_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, out->vertex_component, cf, cap);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_components: launch failed");
+	return launched("fdgs_mesh_components");
 }
 
 extern "C" size_t fdgs_mesh_compact_scratch_bytes(int32_t V, int32_t F)
@@ -471,24 +465,24 @@ extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex
                                  const fdgs_surface_out* out, void* scratch, void* stream_v)
 {
 	const char* fn = "fdgs_mesh_compact";
-	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
-	if (!out) return mesh_fail(fn, "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_surface_out)) return mesh_fail(fn, "fdgs_surface_out.struct_size is not sizeof(fdgs_surface_out): header and library differ");
-	if (!out->n_vertices || !out->n_faces) return mesh_fail(fn, "n_vertices and n_faces must not be NULL");
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return mesh_fail(fn, "capacities must not be negative");
-	if (n_components < 0) return mesh_fail(fn, "n_components must not be negative");
-	if (n_components > 0 && !keep) return mesh_fail(fn, "keep must not be NULL with n_components > 0");
+	if (const int rc = mesh_in_args(fn, mesh)) return rc;
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
+	CHECK_STRUCT_IN(fn, out, fdgs_surface_out);
+	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "%s: n_vertices and n_faces must not be NULL", fn);
+	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: capacities must not be negative", fn);
+	if (n_components < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: n_components must not be negative", fn);
+	if (n_components > 0 && !keep) return fail(FDGS_ERR_INVALID_ARG, "%s: keep must not be NULL with n_components > 0", fn);
 	const int V = mesh->V, F = mesh->F;
-	if (V > 0 && !vertex_component) return mesh_fail(fn, "vertex_component must not be NULL with V > 0");
+	if (V > 0 && !vertex_component) return fail(FDGS_ERR_INVALID_ARG, "%s: vertex_component must not be NULL with V > 0", fn);
 	if ((out->vertices && !mesh->vertices) || (out->normals && !mesh->normals) || (out->colors && !mesh->colors))
-		return mesh_fail(fn, "an output array needs its input array");
-	if (V > 0 && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+		return fail(FDGS_ERR_INVALID_ARG, "%s: an output array needs its input array", fn);
+	if (V > 0 && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (V == 0)
 	{
 		// no vertex: every face is absent
-		if (hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream) != hipSuccess || hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream) != hipSuccess)
-			return set_error(FDGS_ERR_HIP, "fdgs_mesh_compact: memset failed");
+		HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_mesh_compact: memset");
+		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_mesh_compact: memset");
 		return FDGS_OK;
 	}
 	const CompactLayout L = compact_layout(V, F);
@@ -516,7 +510,7 @@ extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex
 		hipLaunchKernelGGL(compact_vertices_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, a);
 		if (a.out_faces && fb > 0) hipLaunchKernelGGL(compact_faces_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, a);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_compact: launch failed");
+	return launched("fdgs_mesh_compact");
 }
 
 extern "C" size_t fdgs_mesh_smooth_scratch_bytes(int32_t V, int32_t F)
@@ -527,15 +521,15 @@ extern "C" size_t fdgs_mesh_smooth_scratch_bytes(int32_t V, int32_t F)
 extern "C" int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth_out* out, void* scratch, void* stream_v)
 {
 	const char* fn = "fdgs_mesh_smooth";
-	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
-	if (!out) return mesh_fail(fn, "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_mesh_smooth_out)) return mesh_fail(fn, "fdgs_mesh_smooth_out.struct_size is not sizeof(fdgs_mesh_smooth_out): header and library differ");
-	if (out->iterations < 0) return mesh_fail(fn, "iterations must not be negative");
-	if (out->lambda != out->lambda || out->mu != out->mu) return mesh_fail(fn, "lambda and mu must not be NaN");
+	if (const int rc = mesh_in_args(fn, mesh)) return rc;
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
+	CHECK_STRUCT_IN(fn, out, fdgs_mesh_smooth_out);
+	if (out->iterations < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: iterations must not be negative", fn);
+	if (out->lambda != out->lambda || out->mu != out->mu) return fail(FDGS_ERR_INVALID_ARG, "%s: lambda and mu must not be NaN", fn);
 	const int V = mesh->V, F = mesh->F, iterations = out->iterations;
-	if (V > 0 && !mesh->vertices) return mesh_fail(fn, "the mesh's vertices must not be NULL with V > 0");
-	if (V > 0 && iterations > 0 && !out->vertices) return mesh_fail(fn, "out vertices must not be NULL with iterations > 0");
-	if (V > 0 && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	if (V > 0 && !mesh->vertices) return fail(FDGS_ERR_INVALID_ARG, "%s: the mesh's vertices must not be NULL with V > 0", fn);
+	if (V > 0 && iterations > 0 && !out->vertices) return fail(FDGS_ERR_INVALID_ARG, "%s: out vertices must not be NULL with iterations > 0", fn);
+	if (V > 0 && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	if (V == 0) return FDGS_OK;
 	hipStream_t stream = (hipStream_t)stream_v;
 	const SmoothLayout L = smooth_layout(V, F);
@@ -552,8 +546,7 @@ extern "C" int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth
 		int bits = 0;                                        // the keys are 0 .. V
 		while (bits < 32 && ((uint32_t)V >> bits) != 0) bits++;
 		hipLaunchKernelGGL(smooth_pairs_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, keys[0], vals[0]);
-		if (radix_sort_pairs(keys, vals, n, 0, div_up(bits, RADIX_BITS) * RADIX_BITS, reinterpret_cast<uint32_t*>(base + L.hist), stream, &res) != hipSuccess)
-			return set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: sort failed");
+		HIP_TRY(radix_sort_pairs(keys, vals, n, 0, div_up(bits, RADIX_BITS) * RADIX_BITS, reinterpret_cast<uint32_t*>(base + L.hist), stream, &res), "fdgs_mesh_smooth: sort");
 	}
 	hipLaunchKernelGGL(smooth_rows_kernel, dim3((int)blocks_of((size_t)V + 1)), dim3(MESH_THREADS), 0, stream, keys[res], n, V, row_start);
 	if (F > 0)
@@ -571,11 +564,8 @@ extern "C" int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth
 		pos = dst;
 	}
 	if (iterations == 0 && out->vertices && out->vertices != mesh->vertices)
-	{
-		if (hipMemcpyAsync(out->vertices, mesh->vertices, 3 * (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess)
-			return set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: copy failed");
-	}
+		HIP_TRY(hipMemcpyAsync(out->vertices, mesh->vertices, 3 * (size_t)V * sizeof(float), hipMemcpyDeviceToDevice, stream), "fdgs_mesh_smooth: copy");
 	if (out->normals)
 		hipLaunchKernelGGL(smooth_normals_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, pos, mesh->faces, vals[res], row_start, V, out->normals);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_smooth: launch failed");
+	return launched("fdgs_mesh_smooth");
 }

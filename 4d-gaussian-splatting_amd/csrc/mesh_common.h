@@ -3,7 +3,6 @@
 #pragma once
 #include "fdgs_common.h"
 #include "block_scan.h"
-#include <stdio.h>
 
 namespace fdgs
 {
@@ -30,21 +29,15 @@ namespace fdgs
 		return lo;
 	}
 
-	static int mesh_fail(const char* fn, const char* why)
-	{
-		char msg[256];
-		snprintf(msg, sizeof msg, "%s: %s", fn, why);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
-	}
 	static bool mesh_sizes_ok(int64_t V, int64_t F) { return V >= 0 && F >= 0 && V < MESH_MAX && F < MESH_MAX; }
-	static const char* mesh_in_args(const fdgs_mesh_in* m)
+	static int mesh_in_args(const char* fn, const fdgs_mesh_in* m)
 	{
-		if (!m) return "mesh must not be NULL";
-		if (m->struct_size != sizeof(fdgs_mesh_in)) return "fdgs_mesh_in.struct_size is not sizeof(fdgs_mesh_in): header and library differ";
-		if (m->V < 0 || m->F < 0) return "V and F must not be negative";
-		if (!mesh_sizes_ok(m->V, m->F)) return "need V < 2^28 and F < 2^28";
-		if (m->F > 0 && !m->faces) return "faces must not be NULL with F > 0";
-		return nullptr;
+		if (!m) return fail(FDGS_ERR_INVALID_ARG, "%s: mesh must not be NULL", fn);
+		CHECK_STRUCT_IN(fn, m, fdgs_mesh_in);
+		if (m->V < 0 || m->F < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: V and F must not be negative", fn);
+		if (!mesh_sizes_ok(m->V, m->F)) return fail(FDGS_ERR_INVALID_ARG, "%s: need V < 2^28 and F < 2^28", fn);
+		if (m->F > 0 && !m->faces) return fail(FDGS_ERR_INVALID_ARG, "%s: faces must not be NULL with F > 0", fn);
+		return FDGS_OK;
 	}
 	static size_t blocks_of(size_t n) { return (n + MESH_THREADS - 1) / MESH_THREADS; }
 }

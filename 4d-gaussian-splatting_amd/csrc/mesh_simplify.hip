@@ -319,25 +319,25 @@ namespace fdgs
 	static SimplifyLayout simplify_layout(int V, int F)
 	{
 		SimplifyLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const size_t n = 3 * (size_t)F;
-		for (int k = 0; k < 2; k++) { L.vkeys[k] = o; o = align_up(o + (size_t)V * 4); }
-		for (int k = 0; k < 2; k++) { L.vvals[k] = o; o = align_up(o + (size_t)V * 4); }
-		for (int k = 0; k < 2; k++) { L.fkeys[k] = o; o = align_up(o + n * 4); }
-		for (int k = 0; k < 2; k++) { L.fvals[k] = o; o = align_up(o + n * 4); }
+		for (int k = 0; k < 2; k++) L.vkeys[k] = c.take((size_t)V * 4);
+		for (int k = 0; k < 2; k++) L.vvals[k] = c.take((size_t)V * 4);
+		for (int k = 0; k < 2; k++) L.fkeys[k] = c.take(n * 4);
+		for (int k = 0; k < 2; k++) L.fvals[k] = c.take(n * 4);
 		int sb = sort_blocks(V);
 		if (sort_blocks(F) > sb) sb = sort_blocks(F);
 		if (sort_blocks((int)n) > sb) sb = sort_blocks((int)n);
-		L.hist = o; o = align_up(o + (size_t)RADIX * ((size_t)sb + 1) * 4);
-		L.map = o; o = align_up(o + (size_t)V * sizeof(int32_t));
-		L.cluster_start = o; o = align_up(o + (size_t)V * sizeof(int32_t));
-		L.mean = o; o = align_up(o + 3 * (size_t)V * sizeof(float));
-		L.row_start = o; o = align_up(o + ((size_t)V + 1) * sizeof(int32_t));
-		for (int k = 0; k < 3; k++) { L.canon[k] = o; o = align_up(o + (size_t)F * 4); }
-		L.keep = o; o = align_up(o + (size_t)F);
-		L.vcounts = o; o = align_up(o + blocks_of((size_t)V) * sizeof(uint32_t));
-		L.fcounts = o; o = align_up(o + blocks_of((size_t)F) * sizeof(uint32_t));
-		L.total = o;
+		L.hist = c.take((size_t)RADIX * ((size_t)sb + 1) * 4);
+		L.map = c.take((size_t)V * sizeof(int32_t));
+		L.cluster_start = c.take((size_t)V * sizeof(int32_t));
+		L.mean = c.take(3 * (size_t)V * sizeof(float));
+		L.row_start = c.take(((size_t)V + 1) * sizeof(int32_t));
+		for (int k = 0; k < 3; k++) L.canon[k] = c.take((size_t)F * 4);
+		L.keep = c.take((size_t)F);
+		L.vcounts = c.take(blocks_of((size_t)V) * sizeof(uint32_t));
+		L.fcounts = c.take(blocks_of((size_t)F) * sizeof(uint32_t));
+		L.total = c.o;
 		return L;
 	}
 	static int bits_of(uint32_t largest_key)
@@ -360,31 +360,30 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
                                   void* stream_v)
 {
 	const char* fn = "fdgs_mesh_simplify";
-	if (const char* bad = mesh_in_args(mesh)) return mesh_fail(fn, bad);
-	if (!params) return mesh_fail(fn, "params must not be NULL");
-	if (params->struct_size != sizeof(fdgs_mesh_simplify_params))
-		return mesh_fail(fn, "fdgs_mesh_simplify_params.struct_size is not sizeof(fdgs_mesh_simplify_params): header and library differ");
-	if (!out) return mesh_fail(fn, "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_surface_out)) return mesh_fail(fn, "fdgs_surface_out.struct_size is not sizeof(fdgs_surface_out): header and library differ");
-	if (!(params->cell > 0.f) || !finite_f(params->cell)) return mesh_fail(fn, "cell must be positive and finite");
-	if (!finite_f(params->origin[0]) || !finite_f(params->origin[1]) || !finite_f(params->origin[2])) return mesh_fail(fn, "origin must be finite");
-	if (params->nx < 1 || params->ny < 1 || params->nz < 1) return mesh_fail(fn, "the grid dimensions nx, ny, nz must be at least 1");
+	if (const int rc = mesh_in_args(fn, mesh)) return rc;
+	if (!params) return fail(FDGS_ERR_INVALID_ARG, "%s: params must not be NULL", fn);
+	CHECK_STRUCT_IN(fn, params, fdgs_mesh_simplify_params);
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
+	CHECK_STRUCT_IN(fn, out, fdgs_surface_out);
+	if (!(params->cell > 0.f) || !finite_f(params->cell)) return fail(FDGS_ERR_INVALID_ARG, "%s: cell must be positive and finite", fn);
+	if (!finite_f(params->origin[0]) || !finite_f(params->origin[1]) || !finite_f(params->origin[2])) return fail(FDGS_ERR_INVALID_ARG, "%s: origin must be finite", fn);
+	if (params->nx < 1 || params->ny < 1 || params->nz < 1) return fail(FDGS_ERR_INVALID_ARG, "%s: the grid dimensions nx, ny, nz must be at least 1", fn);
 	const int64_t ncells = (int64_t)params->nx * params->ny;     // < 2^62
-	if (ncells > SIMPLIFY_MAX_CELLS || ncells * params->nz > SIMPLIFY_MAX_CELLS) return mesh_fail(fn, "the grid must not have more than 2^30 cells");
-	if (!(params->stabilise >= 0.f)) return mesh_fail(fn, "stabilise must not be negative or NaN");
-	if (params->placement != FDGS_SIMPLIFY_MEAN && params->placement != FDGS_SIMPLIFY_QUADRIC) return mesh_fail(fn, "placement must be 0 (mean) or 1 (quadric)");
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return mesh_fail(fn, "capacities must not be negative");
-	if (!out->n_vertices || !out->n_faces) return mesh_fail(fn, "n_vertices and n_faces must not be NULL");
+	if (ncells > SIMPLIFY_MAX_CELLS || ncells * params->nz > SIMPLIFY_MAX_CELLS) return fail(FDGS_ERR_INVALID_ARG, "%s: the grid must not have more than 2^30 cells", fn);
+	if (!(params->stabilise >= 0.f)) return fail(FDGS_ERR_INVALID_ARG, "%s: stabilise must not be negative or NaN", fn);
+	if (params->placement != FDGS_SIMPLIFY_MEAN && params->placement != FDGS_SIMPLIFY_QUADRIC) return fail(FDGS_ERR_INVALID_ARG, "%s: placement must be 0 (mean) or 1 (quadric)", fn);
+	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: capacities must not be negative", fn);
+	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "%s: n_vertices and n_faces must not be NULL", fn);
 	const int V = mesh->V, F = mesh->F;
-	if (V > 0 && !mesh->vertices) return mesh_fail(fn, "the mesh's vertices must not be NULL with V > 0");
-	if ((out->normals && !mesh->normals) || (out->colors && !mesh->colors)) return mesh_fail(fn, "an output array needs its input array");
-	if (V > 0 && !scratch) return mesh_fail(fn, "scratch must not be NULL with V > 0");
+	if (V > 0 && !mesh->vertices) return fail(FDGS_ERR_INVALID_ARG, "%s: the mesh's vertices must not be NULL with V > 0", fn);
+	if ((out->normals && !mesh->normals) || (out->colors && !mesh->colors)) return fail(FDGS_ERR_INVALID_ARG, "%s: an output array needs its input array", fn);
+	if (V > 0 && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (V == 0 || F == 0)
 	{
 		// no vertex: every face is absent
-		if ((V == 0 && hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream) != hipSuccess) || hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream) != hipSuccess)
-			return set_error(FDGS_ERR_HIP, "fdgs_mesh_simplify: memset failed");
+		if (V == 0) HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_mesh_simplify: memset");
+		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_mesh_simplify: memset");
 		if (V == 0) return FDGS_OK;
 	}
 	const SimplifyLayout L = simplify_layout(V, F);
@@ -410,14 +409,14 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 	const int vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
 	const dim3 T(MESH_THREADS);
 	uint32_t* hist = u32(L.hist);
-	const char* sort_failed = "fdgs_mesh_simplify: sort failed";
+	const char* sort = "fdgs_mesh_simplify: sort";
 
 	// clusters
 	uint32_t* vkeys[2] = { u32(L.vkeys[0]), u32(L.vkeys[1]) };
 	uint32_t* vvals[2] = { u32(L.vvals[0]), u32(L.vvals[1]) };
 	int vres = 0;
 	hipLaunchKernelGGL(simplify_cells_kernel, dim3(vb), T, 0, stream, a, vkeys[0], vvals[0]);
-	if (radix_sort_pairs(vkeys, vvals, V, 0, bits_of(a.ncells), hist, stream, &vres) != hipSuccess) return set_error(FDGS_ERR_HIP, sort_failed);
+	HIP_TRY(radix_sort_pairs(vkeys, vvals, V, 0, bits_of(a.ncells), hist, stream, &vres), sort);
 	const uint32_t *cell_keys = vkeys[vres], *cell_vals = vvals[vres];
 	hipLaunchKernelGGL(simplify_heads_kernel, dim3(vb), T, 0, stream, a, cell_keys);
 	hipLaunchKernelGGL(simplify_scan_kernel, dim3(1), dim3(MESH_SCAN_THREADS), 0, stream, a.vcounts, vb, out->n_vertices);
@@ -433,7 +432,7 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 		for (int component = 2; component >= 0; component--)
 		{
 			int res = 0;
-			if (radix_sort_pairs(keys, vals, F, 0, bits, hist, stream, &res) != hipSuccess) return set_error(FDGS_ERR_HIP, sort_failed);
+			HIP_TRY(radix_sort_pairs(keys, vals, F, 0, bits, hist, stream, &res), sort);
 			if (res) { uint32_t* t = keys[0]; keys[0] = keys[1]; keys[1] = t; t = vals[0]; vals[0] = vals[1]; vals[1] = t; }
 			if (component > 0) hipLaunchKernelGGL(simplify_gather_kernel, dim3(fb), T, 0, stream, a.canon[component - 1], vals[0], F, keys[0]);
 		}
@@ -456,12 +455,12 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 			if (F > 0)
 			{
 				hipLaunchKernelGGL(simplify_incidences_kernel, dim3(fb), T, 0, stream, a, keys[0], vals[0]);
-				if (radix_sort_pairs(keys, vals, n, 0, bits_of((uint32_t)V), hist, stream, &res) != hipSuccess) return set_error(FDGS_ERR_HIP, sort_failed);
+				HIP_TRY(radix_sort_pairs(keys, vals, n, 0, bits_of((uint32_t)V), hist, stream, &res), sort);
 			}
 			hipLaunchKernelGGL(simplify_rows_kernel, dim3((int)blocks_of((size_t)V + 1)), T, 0, stream, a, keys[res], n, row_start);
 			hipLaunchKernelGGL(simplify_quadric_kernel, dim3(vb), T, 0, stream, a, cell_keys, vals[res], row_start);
 		}
 	}
 	if (a.out_faces && F > 0) hipLaunchKernelGGL(simplify_emit_faces_kernel, dim3(fb), T, 0, stream, a);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_mesh_simplify: launch failed");
+	return launched("fdgs_mesh_simplify");
 }

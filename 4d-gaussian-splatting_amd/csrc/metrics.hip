@@ -267,13 +267,13 @@ extern "C" int fdgs_eval_metrics(const float* img, const float* gt, int32_t C, i
 {
 	using namespace fdgs;
 	using namespace fdgs::metrics;
-	if (!img || !gt || !scratch || !out4) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: missing pointer");
-	if (C <= 0 || H <= 0 || W <= 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: C, H and W must be positive");
-	if ((size_t)C * H * W > (size_t)INT32_MAX) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: image too large");
+	if (!img || !gt || !scratch || !out4) return fail(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: missing pointer");
+	if (C <= 0 || H <= 0 || W <= 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: C, H and W must be positive");
+	if ((size_t)C * H * W > (size_t)INT32_MAX) return fail(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: image too large");
 	const bool ms = !(flags & FDGS_METRICS_NO_MSSSIM);
 	if (ms && (H < MIN_SIDE || W < MIN_SIDE))
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: MS-SSIM with 5 scales and an 11-tap window needs both image sides "
-		                                       ">= 176 pixels (H // 16 > 10 and W // 16 > 10)");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_eval_metrics: MS-SSIM with 5 scales and an 11-tap window needs both image sides "
+		                                  ">= 176 pixels (H // 16 > 10 and W // 16 > 10)");
 	const Layout L = layout_of(C, H, W, ms);
 	char* base = static_cast<char*>(scratch);
 	const hipStream_t st = (hipStream_t)stream;
@@ -292,5 +292,5 @@ extern "C" int fdgs_eval_metrics(const float* img, const float* gt, int32_t C, i
 		pl.part[s] = part; pl.ntiles[s] = nt; pl.H[s] = Hs; pl.W[s] = Ws;
 	}
 	hipLaunchKernelGGL(metrics_finish_kernel, dim3(1), dim3(FT), 0, st, pl, out4);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_eval_metrics: kernel launch failed");
+	return launched("fdgs_eval_metrics");
 }

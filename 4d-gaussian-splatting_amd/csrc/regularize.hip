@@ -20,16 +20,16 @@ namespace fdgs
 	static inline RegLayout reg_layout(int P, int k)
 	{
 		RegLayout L;
-		size_t o = 0;
+		ScratchCursor c;
 		const int p = P > 0 ? P : 1;
 		const size_t pk = (size_t)p * (size_t)(k > 0 ? k : 1);
-		L.parts = o; o = align_up(o + (size_t)2 * div_up(p, REG_THREADS) * 4);
-		for (int i = 0; i < 2; i++) { L.keys[i] = o; o = align_up(o + pk * 4); }
-		for (int i = 0; i < 2; i++) { L.vals[i] = o; o = align_up(o + pk * 4); }
-		L.hist = o; o = align_up(o + (size_t)RADIX * (sort_blocks((int)pk) + 1) * 4);
-		L.seg_lo = o; o = align_up(o + (size_t)p * 4);
-		L.seg_hi = o; o = align_up(o + (size_t)p * 4);
-		L.total = o;
+		L.parts = c.take((size_t)2 * div_up(p, REG_THREADS) * 4);
+		for (int i = 0; i < 2; i++) L.keys[i] = c.take(pk * 4);
+		for (int i = 0; i < 2; i++) L.vals[i] = c.take(pk * 4);
+		L.hist = c.take((size_t)RADIX * (sort_blocks((int)pk) + 1) * 4);
+		L.seg_lo = c.take((size_t)p * 4);
+		L.seg_hi = c.take((size_t)p * 4);
+		L.total = c.o;
 		return L;
 	}
 
@@ -254,10 +254,10 @@ extern "C" int fdgs_rigid_motion_forward(int32_t P, int32_t k, const float* scal
                                          const float* rotation_r, const float* t, const int64_t* knn_idx, const float* knn_d2, float* velocity,
                                          float* losses, void* scratch, void* stream_v)
 {
-	if (!reg_args_ok(P, k)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: need P >= 0, k >= 1, P * k < 2^31");
-	if (P == 0) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: no Gaussians (the reference's mean is undefined)");
+	if (!reg_args_ok(P, k)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: need P >= 0, k >= 1, P * k < 2^31");
+	if (P == 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: no Gaussians (the reference's mean is undefined)");
 	if (!scaling || !scaling_t || !rotation || !rotation_r || !t || !knn_idx || !knn_d2 || !velocity || !losses || !scratch)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: missing pointer");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_forward: missing pointer");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const RegLayout L = reg_layout(P, k);
 	float* parts = (float*)((char*)scratch + L.parts);
@@ -267,7 +267,7 @@ extern "C" int fdgs_rigid_motion_forward(int32_t P, int32_t k, const float* scal
 	hipLaunchKernelGGL(reg_rigid_kernel, dim3(nb), dim3(REG_THREADS), 0, stream, P, k, velocity, knn_idx, knn_d2, parts);
 	const RegDivs divs = { { (float)k, 1.f }, { (float)P, (float)P } };   // (sum / k) / N  and  sum / N
 	hipLaunchKernelGGL(reg_reduce_kernel, dim3(1), dim3(REG_THREADS), 0, stream, nb, 2, parts, divs, losses);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_rigid_motion_forward");
 }
 
 extern "C" int fdgs_rigid_motion_backward(int32_t P, int32_t k, const float* scaling, const float* scaling_t, const float* rotation,
@@ -275,11 +275,11 @@ extern "C" int fdgs_rigid_motion_backward(int32_t P, int32_t k, const float* sca
                                           const float* velocity, const float* g_losses, float scale, float* d_scaling, float* d_scaling_t,
                                           float* d_rotation, float* d_rotation_r, void* scratch, void* stream_v)
 {
-	if (!reg_args_ok(P, k)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_backward: need P >= 0, k >= 1, P * k < 2^31");
+	if (!reg_args_ok(P, k)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_backward: need P >= 0, k >= 1, P * k < 2^31");
 	if (P == 0) return FDGS_OK;
 	if (!scaling || !scaling_t || !rotation || !rotation_r || !t || !knn_idx || !knn_d2 || !velocity || !g_losses || !d_scaling ||
 	    !d_scaling_t || !d_rotation || !d_rotation_r || !scratch)
-		return set_error(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_backward: missing pointer");
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_rigid_motion_backward: missing pointer");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const RegLayout L = reg_layout(P, k);
 	char* s = (char*)scratch;
@@ -292,14 +292,14 @@ extern "C" int fdgs_rigid_motion_backward(int32_t P, int32_t k, const float* sca
 	int bits = 0;
 	while (bits < 32 && ((uint64_t)1 << bits) <= (uint64_t)P) bits++;      // keys are 0 .. P
 	int res = 0;
-	if (radix_sort_pairs(keys, vals, PK, 0, bits, (uint32_t*)(s + L.hist), stream, &res) != hipSuccess) return FDGS_ERR_HIP;
-	if (hipMemsetAsync(seg_lo, 0, (size_t)P * 4, stream) != hipSuccess || hipMemsetAsync(seg_hi, 0, (size_t)P * 4, stream) != hipSuccess)
-		return FDGS_ERR_HIP;
+	HIP_TRY(radix_sort_pairs(keys, vals, PK, 0, bits, (uint32_t*)(s + L.hist), stream, &res), "fdgs_rigid_motion_backward: radix_sort_pairs");
+	HIP_TRY(hipMemsetAsync(seg_lo, 0, (size_t)P * 4, stream), "fdgs_rigid_motion_backward: hipMemsetAsync");
+	HIP_TRY(hipMemsetAsync(seg_hi, 0, (size_t)P * 4, stream), "fdgs_rigid_motion_backward: hipMemsetAsync");
 	hipLaunchKernelGGL(reg_segments_kernel, dim3(div_up(PK, 256)), dim3(256), 0, stream, P, PK, keys[res], seg_lo, seg_hi);
 	hipLaunchKernelGGL(reg_backward_kernel, dim3(div_up(P, REG_THREADS)), dim3(REG_THREADS), 0, stream, P, k, scaling, scaling_t, rotation,
 	                   rotation_r, t, knn_idx, knn_d2, velocity, vals[res], seg_lo, seg_hi, g_losses, scale, d_scaling, d_scaling_t, d_rotation,
 	                   d_rotation_r);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_rigid_motion_backward");
 }
 
 extern "C" int fdgs_opa_mask_num_partials(int32_t H, int32_t W)
@@ -310,8 +310,8 @@ extern "C" int fdgs_opa_mask_num_partials(int32_t H, int32_t W)
 extern "C" int fdgs_opa_mask_loss(int32_t H, int32_t W, const float* alpha, int32_t alpha_is_T, const float* mask, const float* g_upstream,
                                   float scale, float* grad, int32_t accumulate, float* partials, float* loss, void* stream_v)
 {
-	if (H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_opa_mask_loss: bad image size");
-	if (!alpha || !mask || !partials || !loss) return set_error(FDGS_ERR_INVALID_ARG, "fdgs_opa_mask_loss: missing pointer");
+	if (H <= 0 || W <= 0 || (int64_t)H * W >= ((int64_t)1 << 31)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_opa_mask_loss: bad image size");
+	if (!alpha || !mask || !partials || !loss) return fail(FDGS_ERR_INVALID_ARG, "fdgs_opa_mask_loss: missing pointer");
 	hipStream_t stream = (hipStream_t)stream_v;
 	const int HW = H * W, nb = div_up(HW, REG_THREADS);
 	// torch.clamp(alpha, 1e-6, 1 - 1e-6) on a float32 tensor: both bounds rounded to float
@@ -319,5 +319,5 @@ extern "C" int fdgs_opa_mask_loss(int32_t H, int32_t W, const float* alpha, int3
 	                   g_upstream, scale, grad, accumulate, partials);
 	const RegDivs divs = { { 1.f, 1.f }, { (float)HW, 1.f } };
 	hipLaunchKernelGGL(reg_reduce_kernel, dim3(1), dim3(REG_THREADS), 0, stream, nb, 1, partials, divs, loss);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_opa_mask_loss");
 }

@@ -324,14 +324,15 @@ extern "C" int fdgs_l1_ssim_value_and_grad(const float* img, const float* gt, in
 {
 	using namespace fdgs;
 	static_assert(FT == STX && FT == STY, "the fused kernel shares the tile's partial-sum layout with the two-kernel path");
-	if (!img || !gt || !upstream || !dL_dimg || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
+	if (!img || !gt || !upstream || !dL_dimg || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_l1_ssim_value_and_grad: a pointer is NULL, or one of C=%d H=%d W=%d is not positive", C, H, W);
 	const float n = (float)C * (float)H * (float)W;
 	const float w_l1 = (1.0f - lambda_dssim) / n, w_ssim = -lambda_dssim / n;
 	const dim3 grid(grid_of(div_up(W, FT) * div_up(H, FT) * C)), block(STHREADS, 1, 1);
 	static const bool wpe2 = []() { const char* e = getenv("FDGS_SSIM_FUSED_WPE"); return e && e[0] == '2'; }();
 	if (wpe2) hipLaunchKernelGGL(ssim_fused_kernel_wpe2, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, upstream, w_l1, w_ssim, dL_dimg, partial_l1, partial_ssim);
 	else hipLaunchKernelGGL(ssim_fused_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, upstream, w_l1, w_ssim, dL_dimg, partial_l1, partial_ssim);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_l1_ssim_value_and_grad");
 }
 
 extern "C" int fdgs_l1_ssim_forward(const float* img, const float* gt, int32_t C, int32_t H, int32_t W,
@@ -339,10 +340,11 @@ extern "C" int fdgs_l1_ssim_forward(const float* img, const float* gt, int32_t C
                                     float* partial_l1, float* partial_ssim, void* stream)
 {
 	using namespace fdgs;
-	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
+	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !partial_l1 || !partial_ssim || C <= 0 || H <= 0 || W <= 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_l1_ssim_forward: a pointer is NULL, or one of C=%d H=%d W=%d is not positive", C, H, W);
 	const dim3 grid(grid_of(div_up(W, STX) * div_up(H, STY) * C)), block(STHREADS, 1, 1);
 	hipLaunchKernelGGL(ssim_fwd_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, dm_dmu1, dm_de11, dm_de12, partial_l1, partial_ssim);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_l1_ssim_forward");
 }
 
 extern "C" int fdgs_l1_ssim_backward(const float* img, const float* gt, int32_t C, int32_t H, int32_t W,
@@ -350,12 +352,13 @@ extern "C" int fdgs_l1_ssim_backward(const float* img, const float* gt, int32_t 
                                      const float* upstream, float lambda_dssim, float* dL_dimg, void* stream)
 {
 	using namespace fdgs;
-	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !upstream || !dL_dimg || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
+	if (!img || !gt || !dm_dmu1 || !dm_de11 || !dm_de12 || !upstream || !dL_dimg || C <= 0 || H <= 0 || W <= 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_l1_ssim_backward: a pointer is NULL, or one of C=%d H=%d W=%d is not positive", C, H, W);
 	const float n = (float)C * (float)H * (float)W;
 	const float w_l1 = (1.0f - lambda_dssim) / n, w_ssim = -lambda_dssim / n;
 	const dim3 grid(grid_of(div_up(W, STX) * div_up(H, STY) * C)), block(STHREADS, 1, 1);
 	hipLaunchKernelGGL(ssim_bwd_kernel, grid, block, 0, (hipStream_t)stream, img, gt, C, H, W, dm_dmu1, dm_de11, dm_de12, upstream, w_l1, w_ssim, dL_dimg);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_l1_ssim_backward");
 }
 
 namespace fdgs
@@ -404,21 +407,23 @@ extern "C" int fdgs_l1_ssim_loss(const float* partial_l1, const float* partial_s
                                  float lambda_dssim, float* loss_l1_ssim, void* stream)
 {
 	using namespace fdgs;
-	if (!partial_l1 || !partial_ssim || !loss_l1_ssim || num_partials <= 0 || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
+	if (!partial_l1 || !partial_ssim || !loss_l1_ssim || num_partials <= 0 || C <= 0 || H <= 0 || W <= 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_l1_ssim_loss: a pointer is NULL, or one of num_partials=%d C=%d H=%d W=%d is not positive", num_partials, C, H, W);
 	const float inv_n = 1.0f / ((float)C * (float)H * (float)W);
 	hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partial_l1, partial_ssim, num_partials, inv_n, lambda_dssim, loss_l1_ssim, 0ll);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_l1_ssim_loss");
 }
 
 extern "C" int fdgs_l1_ssim_loss_batch(const float* partials, int32_t num_views, int32_t num_partials, int32_t C, int32_t H, int32_t W,
                                        float lambda_dssim, float* losses, void* stream)
 {
 	using namespace fdgs;
-	if (!partials || !losses || num_views <= 0 || num_partials <= 0 || C <= 0 || H <= 0 || W <= 0) return FDGS_ERR_INVALID_ARG;
+	if (!partials || !losses || num_views <= 0 || num_partials <= 0 || C <= 0 || H <= 0 || W <= 0)
+		return fail(FDGS_ERR_INVALID_ARG, "fdgs_l1_ssim_loss_batch: a pointer is NULL, or one of num_views=%d num_partials=%d C=%d H=%d W=%d is not positive", num_views, num_partials, C, H, W);
 	const float inv_n = 1.0f / ((float)C * (float)H * (float)W);
 	hipLaunchKernelGGL(l1_ssim_finish_kernel, dim3(num_views), dim3(1024), 0, (hipStream_t)stream, partials, partials + num_partials, num_partials, inv_n,
 	                   lambda_dssim, losses, 2ll * num_partials);
-	return hipGetLastError() == hipSuccess ? FDGS_OK : FDGS_ERR_HIP;
+	return launched("fdgs_l1_ssim_loss_batch");
 }
 
 extern "C" int fdgs_l1_ssim_num_partials(int32_t C, int32_t H, int32_t W)

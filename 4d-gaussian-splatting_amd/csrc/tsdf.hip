@@ -19,7 +19,6 @@
 #include "fdgs_common.h"
 #include "block_scan.h"
 #include <math.h>
-#include <stdio.h>
 
 namespace fdgs
 {
@@ -314,45 +313,52 @@ namespace fdgs
 		}
 	}
 
-	static int tsdf_fail(const char* fn, const char* why)
+	// scratch of fdgs_surface_extract for n voxels: the cells' vertex indices and the per-block vertex / face counts
+	struct SurfaceLayout { size_t map, vcounts, fcounts, total; };
+	static SurfaceLayout surface_layout(size_t n)
 	{
-		char msg[256];
-		snprintf(msg, sizeof msg, "%s: %s", fn, why);
-		return set_error(FDGS_ERR_INVALID_ARG, msg);
+		SurfaceLayout L;
+		ScratchCursor c;
+		const size_t nb = (n + TSDF_THREADS - 1) / TSDF_THREADS;
+		L.map = c.take(n * sizeof(int32_t));
+		L.vcounts = c.take(nb * sizeof(uint32_t));
+		L.fcounts = c.take(nb * sizeof(uint32_t));
+		L.total = c.o;
+		return L;
 	}
 	static bool finite_f(float v) { return fabsf(v) < INFINITY; }
 	static bool positive_f(float v) { return v > 0.f && v < INFINITY; }
 
-	// NULL: the volume is fine and `v` is filled in; otherwise what is wrong with it
-	static const char* tsdf_volume_args(const fdgs_tsdf_volume* in, TsdfVol& v)
+	// FDGS_OK: the volume is fine and `v` is filled in; otherwise the entry point `fn` fails with what is wrong with it
+	static int tsdf_volume_args(const char* fn, const fdgs_tsdf_volume* in, TsdfVol& v)
 	{
-		if (!in) return "volume must not be NULL";
-		if (in->struct_size != sizeof(fdgs_tsdf_volume)) return "fdgs_tsdf_volume.struct_size is not sizeof(fdgs_tsdf_volume): header and library differ";
-		if (in->nx < 0 || in->ny < 0 || in->nz < 0) return "nx, ny, nz must not be negative";
-		if ((int64_t)in->nx * in->ny >= TSDF_MAX_VOXELS || (int64_t)in->nx * in->ny * in->nz >= TSDF_MAX_VOXELS) return "need nx * ny * nz < 2^28";
-		if (!in->tsdf || !in->weight) return "tsdf and weight must not be NULL";
-		if (!positive_f(in->voxel_size)) return "voxel_size (s) must be positive and finite";
-		if (!positive_f(in->trunc)) return "trunc must be positive and finite";
-		if (!finite_f(in->origin[0]) || !finite_f(in->origin[1]) || !finite_f(in->origin[2])) return "origin must be finite";
-		if ((in->color != nullptr) != (in->cweight != nullptr)) return "color and cweight must be given together";
+		if (!in) return fail(FDGS_ERR_INVALID_ARG, "%s: volume must not be NULL", fn);
+		CHECK_STRUCT_IN(fn, in, fdgs_tsdf_volume);
+		if (in->nx < 0 || in->ny < 0 || in->nz < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: nx, ny, nz must not be negative", fn);
+		if ((int64_t)in->nx * in->ny >= TSDF_MAX_VOXELS || (int64_t)in->nx * in->ny * in->nz >= TSDF_MAX_VOXELS) return fail(FDGS_ERR_INVALID_ARG, "%s: need nx * ny * nz < 2^28", fn);
+		if (!in->tsdf || !in->weight) return fail(FDGS_ERR_INVALID_ARG, "%s: tsdf and weight must not be NULL", fn);
+		if (!positive_f(in->voxel_size)) return fail(FDGS_ERR_INVALID_ARG, "%s: voxel_size (s) must be positive and finite", fn);
+		if (!positive_f(in->trunc)) return fail(FDGS_ERR_INVALID_ARG, "%s: trunc must be positive and finite", fn);
+		if (!finite_f(in->origin[0]) || !finite_f(in->origin[1]) || !finite_f(in->origin[2])) return fail(FDGS_ERR_INVALID_ARG, "%s: origin must be finite", fn);
+		if ((in->color != nullptr) != (in->cweight != nullptr)) return fail(FDGS_ERR_INVALID_ARG, "%s: color and cweight must be given together", fn);
 		v.nx = in->nx; v.ny = in->ny; v.nz = in->nz; v.n = in->nx * in->ny * in->nz;
 		v.ox = in->origin[0]; v.oy = in->origin[1]; v.oz = in->origin[2]; v.s = in->voxel_size; v.trunc = in->trunc;
 		v.tsdf = in->tsdf; v.weight = in->weight; v.color = in->color; v.cweight = in->cweight;
-		return nullptr;
+		return FDGS_OK;
 	}
 
-	static const char* tsdf_view_args(const fdgs_tsdf_view& in, TsdfView& v)
+	static int tsdf_view_args(const char* fn, const fdgs_tsdf_view& in, TsdfView& v)
 	{
-		if (in.struct_size != sizeof(fdgs_tsdf_view)) return "fdgs_tsdf_view.struct_size is not sizeof(fdgs_tsdf_view): header and library differ";
-		if (in.H <= 0 || in.W <= 0 || (int64_t)in.H * in.W >= ((int64_t)1 << 30)) return "a view needs H, W > 0 and H * W < 2^30";
-		if (!in.depth || !in.viewmatrix) return "a view's depth and viewmatrix must not be NULL";
-		if (in.alpha && !positive_f(in.alpha_min)) return "alpha_min must be positive and finite (zp = depth / alpha)";
-		if (!positive_f(in.fl_x) || !positive_f(in.fl_y)) return "fl_x and fl_y must be positive and finite";
-		if (!finite_f(in.cx) || !finite_f(in.cy)) return "cx and cy must be finite";
-		if (!positive_f(in.view_weight)) return "view_weight must be positive and finite";
+		CHECK_STRUCT_IN(fn, &in, fdgs_tsdf_view);
+		if (in.H <= 0 || in.W <= 0 || (int64_t)in.H * in.W >= ((int64_t)1 << 30)) return fail(FDGS_ERR_INVALID_ARG, "%s: a view needs H, W > 0 and H * W < 2^30", fn);
+		if (!in.depth || !in.viewmatrix) return fail(FDGS_ERR_INVALID_ARG, "%s: a view's depth and viewmatrix must not be NULL", fn);
+		if (in.alpha && !positive_f(in.alpha_min)) return fail(FDGS_ERR_INVALID_ARG, "%s: alpha_min must be positive and finite (zp = depth / alpha)", fn);
+		if (!positive_f(in.fl_x) || !positive_f(in.fl_y)) return fail(FDGS_ERR_INVALID_ARG, "%s: fl_x and fl_y must be positive and finite", fn);
+		if (!finite_f(in.cx) || !finite_f(in.cy)) return fail(FDGS_ERR_INVALID_ARG, "%s: cx and cy must be finite", fn);
+		if (!positive_f(in.view_weight)) return fail(FDGS_ERR_INVALID_ARG, "%s: view_weight must be positive and finite", fn);
 		v.H = in.H; v.W = in.W; v.depth = in.depth; v.alpha = in.alpha; v.mask = in.mask; v.image = in.image; v.vm = in.viewmatrix;
 		v.alpha_min = in.alpha_min; v.fl_x = in.fl_x; v.fl_y = in.fl_y; v.cx = in.cx; v.cy = in.cy; v.weight = in.view_weight;
-		return nullptr;
+		return FDGS_OK;
 	}
 }
 
@@ -361,11 +367,11 @@ using namespace fdgs;
 extern "C" int fdgs_tsdf_integrate(const fdgs_tsdf_volume* volume, int32_t num_views, const fdgs_tsdf_view* views, void* stream)
 {
 	TsdfVol vol;
-	if (const char* bad = tsdf_volume_args(volume, vol)) return tsdf_fail("fdgs_tsdf_integrate", bad);
-	if (num_views < 0 || (num_views > 0 && !views)) return tsdf_fail("fdgs_tsdf_integrate", "num_views must not be negative, views not NULL");
+	if (const int rc = tsdf_volume_args("fdgs_tsdf_integrate", volume, vol)) return rc;
+	if (num_views < 0 || (num_views > 0 && !views)) return fail(FDGS_ERR_INVALID_ARG, "fdgs_tsdf_integrate: num_views must not be negative, views not NULL");
 	TsdfView probe;
 	for (int n = 0; n < num_views; n++)
-		if (const char* bad = tsdf_view_args(views[n], probe)) return tsdf_fail("fdgs_tsdf_integrate", bad);
+		if (const int rc = tsdf_view_args("fdgs_tsdf_integrate", views[n], probe)) return rc;
 	if (vol.n == 0 || num_views == 0) return FDGS_OK;
 	const int blocks = div_up(vol.n, TSDF_THREADS);
 	const dim3 grid(blocks < TSDF_MAX_BLOCKS ? blocks : TSDF_MAX_BLOCKS);
@@ -373,48 +379,47 @@ extern "C" int fdgs_tsdf_integrate(const fdgs_tsdf_volume* volume, int32_t num_v
 	{
 		TsdfViews chunk;
 		chunk.n = num_views - first < TSDF_CHUNK ? num_views - first : TSDF_CHUNK;
-		for (int n = 0; n < TSDF_CHUNK; n++) tsdf_view_args(views[first + (n < chunk.n ? n : 0)], chunk.v[n]);   // (unused slots: a valid view)
+		for (int n = 0; n < TSDF_CHUNK; n++) (void)tsdf_view_args("fdgs_tsdf_integrate", views[first + (n < chunk.n ? n : 0)], chunk.v[n]);   // (checked above; unused slots: a valid view)
 		hipLaunchKernelGGL(tsdf_integrate_kernel, grid, dim3(TSDF_THREADS), 0, (hipStream_t)stream, vol, chunk);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_tsdf_integrate: launch failed");
+	return launched("fdgs_tsdf_integrate");
 }
 
 extern "C" size_t fdgs_surface_extract_scratch_bytes(int32_t nx, int32_t ny, int32_t nz)
 {
 	if (nx < 2 || ny < 2 || nz < 2 || (int64_t)nx * ny >= TSDF_MAX_VOXELS || (int64_t)nx * ny * nz >= TSDF_MAX_VOXELS) return 0;
-	const size_t n = (size_t)nx * ny * nz, nb = (n + TSDF_THREADS - 1) / TSDF_THREADS;
-	return align_up(n * sizeof(int32_t)) + 2 * align_up(nb * sizeof(uint32_t));
+	return surface_layout((size_t)nx * ny * nz).total;
 }
 
 extern "C" int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_weight, const fdgs_surface_out* out, void* scratch, void* stream_v)
 {
 	TsdfVol vol;
-	if (const char* bad = tsdf_volume_args(volume, vol)) return tsdf_fail("fdgs_surface_extract", bad);
-	if (!out) return tsdf_fail("fdgs_surface_extract", "out must not be NULL");
-	if (out->struct_size != sizeof(fdgs_surface_out))
-		return tsdf_fail("fdgs_surface_extract", "fdgs_surface_out.struct_size is not sizeof(fdgs_surface_out): header and library differ");
-	if (!out->n_vertices || !out->n_faces) return tsdf_fail("fdgs_surface_extract", "n_vertices and n_faces must not be NULL");
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return tsdf_fail("fdgs_surface_extract", "capacities must not be negative");
-	if (min_weight != min_weight) return tsdf_fail("fdgs_surface_extract", "min_weight must not be NaN");
+	if (const int rc = tsdf_volume_args("fdgs_surface_extract", volume, vol)) return rc;
+	if (!out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: out must not be NULL");
+	CHECK_STRUCT_IN("fdgs_surface_extract", out, fdgs_surface_out);
+	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: n_vertices and n_faces must not be NULL");
+	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: capacities must not be negative");
+	if (min_weight != min_weight) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: min_weight must not be NaN");
 	hipStream_t stream = (hipStream_t)stream_v;
 	if (vol.nx < 2 || vol.ny < 2 || vol.nz < 2)
 	{
 		// no cell: nothing is launched that indexes the volume
-		if (hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream) != hipSuccess || hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream) != hipSuccess)
-			return set_error(FDGS_ERR_HIP, "fdgs_surface_extract: memset failed");
+		HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_surface_extract: memset");
+		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_surface_extract: memset");
 		return FDGS_OK;
 	}
-	if (!scratch) return tsdf_fail("fdgs_surface_extract", "scratch must not be NULL");
+	if (!scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: scratch must not be NULL");
 	const int nb = div_up(vol.n, TSDF_THREADS);
 	SurfArgs a;
 	a.nx = vol.nx; a.ny = vol.ny; a.nz = vol.nz; a.n = vol.n;
 	a.ox = vol.ox; a.oy = vol.oy; a.oz = vol.oz; a.s = vol.s;
 	a.tsdf = vol.tsdf; a.weight = vol.weight; a.color = vol.color;
 	a.min_weight = min_weight;
+	const SurfaceLayout L = surface_layout((size_t)vol.n);
 	char* base = reinterpret_cast<char*>(scratch);
-	a.map = reinterpret_cast<int32_t*>(base);
-	a.vcounts = reinterpret_cast<uint32_t*>(base + align_up((size_t)vol.n * sizeof(int32_t)));
-	a.fcounts = reinterpret_cast<uint32_t*>(base + align_up((size_t)vol.n * sizeof(int32_t)) + align_up((size_t)nb * sizeof(uint32_t)));
+	a.map = reinterpret_cast<int32_t*>(base + L.map);
+	a.vcounts = reinterpret_cast<uint32_t*>(base + L.vcounts);
+	a.fcounts = reinterpret_cast<uint32_t*>(base + L.fcounts);
 	a.vertices = out->vertices; a.normals = out->normals; a.colors = out->colors; a.faces = out->faces;
 	const bool any_vertex = a.vertices || a.normals || a.colors;
 	a.vcap = any_vertex ? out->vertex_capacity : 0;
@@ -427,5 +432,5 @@ extern "C" int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_we
 		hipLaunchKernelGGL(surf_vertices_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
 		if (a.faces) hipLaunchKernelGGL(surf_faces_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
 	}
-	return hipGetLastError() == hipSuccess ? FDGS_OK : set_error(FDGS_ERR_HIP, "fdgs_surface_extract: launch failed");
+	return launched("fdgs_surface_extract");
 }

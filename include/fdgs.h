@@ -1303,7 +1303,9 @@ size_t fdgs_mesh_simplify_scratch_bytes(int32_t V, int32_t F);
 int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simplify_params* params, const fdgs_surface_out* out, void* scratch,
                        void* stream);
 
-/* Thread-local description of the last error on this thread ("" if none). */
+/* Thread-local description of the last error on this thread ("" if none).  Every non-zero return of an entry point writes its
+ * own message first: the text belongs to the calling thread's most recent non-zero return.  After a call that returned FDGS_OK it
+ * is unspecified (an earlier failure's text may still be there). */
 const char* fdgs_last_error(void);
 int fdgs_version(void);
 

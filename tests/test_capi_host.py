@@ -231,3 +231,100 @@ def test_register_budgets_of_the_built_kernels():
         for name, (n, spills) in hits.items():
             assert n <= most and spills == 0, "%s: %d VGPRs, %d spills (budget %d = %d waves per SIMD)" % (name, n, spills, most, waves)
             assert 512 // ((n + 7) // 8 * 8) >= waves, (name, n)
+
+
+# (entry point, arguments it rejects before its first HIP call, text its message must carry).  The first block: every entry point
+# that used to return a bare code without a message -- its new message names it.  The second: one entry point of each other
+# translation unit, with the text it always had.
+_N = None
+_REJECTED = [
+    ("fdgs_l1_ssim_value_and_grad", (_N, _N, 0, 0, 0, _N, 0.2, _N, _N, _N, _N), "fdgs_l1_ssim_value_and_grad"),
+    ("fdgs_l1_ssim_forward", (_N, _N, 0, 0, 0, _N, _N, _N, _N, _N, _N), "fdgs_l1_ssim_forward"),
+    ("fdgs_l1_ssim_backward", (_N, _N, 0, 0, 0, _N, _N, _N, _N, 0.2, _N, _N), "fdgs_l1_ssim_backward"),
+    ("fdgs_l1_ssim_loss", (_N, _N, 0, 3, 16, 16, 0.2, _N, _N), "fdgs_l1_ssim_loss"),
+    ("fdgs_l1_ssim_loss_batch", (_N, 0, 1, 3, 16, 16, 0.2, _N, _N), "fdgs_l1_ssim_loss_batch"),
+    ("fdgs_densify_stats_local", (-1, 1, _N, _N, _N, _N, _N, _N), "fdgs_densify_stats_local"),
+    ("fdgs_densify_stats_local", (8, 1, _N, _N, _N, _N, _N, _N), "fdgs_densify_stats_local"),
+    ("fdgs_densify_stats_apply", (-1, _N, _N, _N, _N, 1.0, _N, _N, _N, _N, _N), "fdgs_densify_stats_apply"),
+    ("fdgs_densify_stats_apply", (8, _N, _N, _N, _N, 1.0, _N, _N, _N, _N, _N), "fdgs_densify_stats_apply"),
+    ("fdgs_densify_classify", (-1, _N, _N, _N, _N, _N, 1.0, 1.0, 1.0, 1.0, 1.0, 2, 0, _N, _N), "fdgs_densify_classify"),
+    ("fdgs_densify_classify", (8, _N, _N, _N, _N, _N, 1.0, 1.0, 1.0, 1.0, 1.0, 2, 0, _N, _N), "fdgs_densify_classify"),
+    ("fdgs_densify_gather", (0, _N, 0, 0) + (_N,) * 9, "fdgs_densify_gather"),
+    ("fdgs_densify_split", (-1, 2, 0, 4) + (_N,) * 14, "fdgs_densify_split"),
+    ("fdgs_densify_split", (8, 2, 0, 4) + (_N,) * 14, "fdgs_densify_split"),
+    ("fdgs_dist2_knn3", (-1, _N, _N, _N, _N), "fdgs_dist2_knn3"),
+    ("fdgs_dist2_knn3", (8, _N, _N, _N, _N), "fdgs_dist2_knn3"),
+    ("fdgs_adam_step", (_N, _N, _N, _N, 0, _N, 0, 0.9, 0.999, 1e-15, 1, _N), "fdgs_adam_step"),
+    ("fdgs_adam_step_sh", (_N, _N, _N, _N, -1, 0, 0, 0, 4, 0, 0, 1, _N, 1e-3, 1e-3, 0.9, 0.999, 1e-15, 1, _N), "fdgs_adam_step_sh"),
+    ("fdgs_profile_read", (99, _N, _N), "fdgs_profile_read"),
+    ("fdgs_profile_sample_every", (0,), "fdgs_profile_sample_every"),
+    ("fdgs_set_sparse_lists_budget", (-1, 1), "fdgs_set_sparse_lists_budget"),
+
+    ("fdgs_mark_visible", (-1, _N, _N, _N, _N, _N), "P < 0"),
+    ("fdgs_rigid_motion_forward", (0, 1) + (_N,) * 11, "fdgs_rigid_motion_forward: no Gaussians"),
+    ("fdgs_opa_mask_loss", (0, 0, _N, 0, _N, _N, 1.0, _N, 0, _N, _N, _N), "fdgs_opa_mask_loss: bad image size"),
+    ("fdgs_env_composite", (0, 0, _N, _N, 1.0, 1.0, 0.0, 0.0, _N, 1, 1, 1.0, _N, _N, _N, _N), "fdgs_env_composite: bad image / map size"),
+    ("fdgs_eval_metrics", (_N, _N, 3, 16, 16, 0, _N, _N, _N), "fdgs_eval_metrics: missing pointer"),
+    ("fdgs_frames_decode", (_N, 1, 1, 1, 5, _N, 1, _N, 0, _N, 0, _N), "fdgs_frames_decode: C must be 3"),
+    ("fdgs_frames_encode", (_N, 0, _N, 0, 1, 1, 1, 5, _N, 1, _N, _N), "fdgs_frames_encode: C must be 3"),
+    ("fdgs_frames_resize", (_N, 1, 1, 1, 5, _N, 1, _N, 1, 1, 1, _N, _N, 1, _N, _N, 1, _N, _N), "fdgs_frames_resize: C must be 3"),
+    ("fdgs_knn_query", (-1, 0, 0, 1, _N, _N, _N, _N, _N, _N), "fdgs_knn_query: negative size"),
+    ("fdgs_kmeans_assign", (0, 1, 1, _N, _N, _N, _N, _N, _N), "fdgs_kmeans_assign: N must be at least 1 (N=0 K=1 D=1)"),
+    ("fdgs_gaussian_flow_forward", (_N, _N, _N), "fdgs_gaussian_flow_forward: in must not be NULL"),
+    ("fdgs_depth_normals", (_N, 1.0, 1.0, 0.0, 0.0, _N, _N, _N, _N), "fdgs_depth_normals: in must not be NULL"),
+    ("fdgs_tsdf_integrate", (_N, 0, _N, _N), "fdgs_tsdf_integrate: volume must not be NULL"),
+    ("fdgs_surface_extract", (_N, 0.0, _N, _N, _N), "fdgs_surface_extract: volume must not be NULL"),
+    ("fdgs_mesh_smooth", (_N, _N, _N, _N), "fdgs_mesh_smooth: mesh must not be NULL"),
+    ("fdgs_mesh_simplify", (_N, _N, _N, _N, _N), "fdgs_mesh_simplify: mesh must not be NULL"),
+]
+
+
+@pytest.mark.parametrize("row", range(len(_REJECTED)), ids=lambda i: "%s-%d" % (_REJECTED[i][0], i))
+def test_every_rejection_carries_its_own_message(row):
+    """fdgs_last_error() describes the call that failed, not an earlier one: after the rasterizer's "bad sizes" failure on the same
+    thread, every rejected call leaves its own text.  All of these are turned away before anything touches the GPU."""
+    from fdgs import _capi
+    name, args, text = _REJECTED[row]
+    scene, out, R = _capi.FdgsScene(), _capi.FdgsForwardOut(), C.c_int32(0)
+    scene.P, scene.W, scene.H = 10, 0, 16
+    cb = _capi.ALLOC_FN(lambda u, w, n: None)
+    assert _capi.lib.fdgs_rasterize_forward(C.byref(scene), C.byref(out), cb, None, None, C.byref(R)) == 1
+    assert "bad sizes" in _capi.last_error()   # the poison
+    assert getattr(_capi.lib, name)(*args) == 1
+    err = _capi.last_error()
+    print(name, "->", err)
+    assert text in err and "bad sizes" not in err
+
+
+def test_every_nonzero_return_goes_through_fail():
+    """No source line under csrc/ returns an error code directly: fdgs::fail (capi.hip) writes the message and returns the code, and
+    nothing else does.  The helpers it replaced are gone."""
+    src = os.path.join(ROOT, "4d-gaussian-splatting_amd", "csrc")
+    files = sorted(f for f in os.listdir(src) if f.endswith((".hip", ".h")))
+    assert "capi.hip" in files and "fdgs_common.h" in files and len(files) >= 30
+    for f in files:
+        with open(os.path.join(src, f)) as fh:
+            text = fh.read()
+        if f == "capi.hip":   # the definition of fail is the one place a code may be returned from
+            m = re.search(r"^int fdgs::fail\(int code, const char\* fmt, \.\.\.\)\n\{\n.*?^\}\n", text, flags=re.S | re.M)
+            assert m and "return code;" in m.group(0)
+            text = text.replace(m.group(0), "")
+        assert "return FDGS_ERR_" not in text, f
+        for gone in ("set_error", "mesh_fail", "tsdf_fail", "flow_fail", "depth_fail"):
+            assert gone not in text, (f, gone)
+
+
+def test_scratch_sizes_did_not_move():
+    """Every exported *_bytes / *_scratch* function returns what the build before the layouts were rewritten returned
+    (tests/golden/scratch_sizes.json, recorded from that build by tests/golden/make_golden_scratch_sizes.py)."""
+    import json
+    from fdgs import _capi
+    with open(os.path.join(ROOT, "tests", "golden", "scratch_sizes.json")) as f:
+        table = json.load(f)
+    with open(os.path.join(ROOT, "include", "fdgs.h")) as f:
+        declared = set(re.findall(r"\b(fdgs_\w*(?:_bytes|scratch)\w*)\s*\(", re.sub(r"/\*.*?\*/", "", f.read(), flags=re.S)))
+    assert declared == set(table) and len(declared) == 19
+    for name, rows in table.items():
+        assert len(rows) >= 6
+        for args, want in rows:
+            assert int(getattr(_capi.lib, name)(*args)) == want, (name, args)
