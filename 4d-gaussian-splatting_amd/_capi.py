@@ -201,23 +201,108 @@ class FdgsAdamSegment(C.Structure):
 
 ALLOC_FN = C.CFUNCTYPE(C.c_void_p, C.c_void_p, C.c_int, C.c_size_t)
 
-# every symbol include/fdgs.h declares
-EXPORTED = ("fdgs_rasterize_forward", "fdgs_forward_lazy_status", "fdgs_rasterize_backward", "fdgs_preprocess_batch", "fdgs_sh_backward_batch", "fdgs_mark_visible", "fdgs_geometry_bytes",
-            "fdgs_image_bytes", "fdgs_binning_bytes", "fdgs_debug_views", "fdgs_debug_activations", "fdgs_debug_radix_sort_scratch_bytes", "fdgs_debug_radix_sort_pairs", "fdgs_debug_knn_stage_offsets", "fdgs_debug_tile_sort_limits", "fdgs_debug_tile_bin_scratch_bytes", "fdgs_debug_tile_bin", "fdgs_debug_block_reaches", "fdgs_debug_run_ahead_stats", "fdgs_set_run_ahead", "fdgs_set_sparse_lists_budget", "fdgs_debug_sparse_lists_stats", "fdgs_debug_clock_sample", "fdgs_sh_flush", "fdgs_profile_enable", "fdgs_profile_sample_every", "fdgs_profile_read",
-            "fdgs_profile_reset", "fdgs_stage_name", "fdgs_l1_ssim_forward", "fdgs_l1_ssim_backward", "fdgs_l1_ssim_loss", "fdgs_l1_ssim_loss_batch",
-            "fdgs_l1_ssim_num_partials", "fdgs_l1_ssim_value_and_grad", "fdgs_adam_step", "fdgs_adam_step_sh", "fdgs_densify_classify", "fdgs_densify_gather", "fdgs_densify_split", "fdgs_densify_stats_local", "fdgs_densify_stats_apply", "fdgs_knn_scratch_bytes", "fdgs_dist2_knn3",
-            "fdgs_knn_query_scratch_bytes", "fdgs_knn_query", "fdgs_rigid_motion_scratch_bytes", "fdgs_rigid_motion_forward",
-            "fdgs_rigid_motion_backward", "fdgs_opa_mask_num_partials", "fdgs_opa_mask_loss", "fdgs_env_composite", "fdgs_env_composite_backward",
-            "fdgs_eval_metrics_scratch_bytes", "fdgs_eval_metrics", "fdgs_frames_decode", "fdgs_frames_encode",
-            "fdgs_frames_encode_gray_scratch_bytes", "fdgs_frames_encode_gray", "fdgs_frames_resize", "fdgs_frames_resize_scratch_bytes",
-            "fdgs_debug_frames_resize_path", "fdgs_frames_composite", "fdgs_time_slice_scratch_bytes", "fdgs_time_slice",
-            "fdgs_gaussian_flow_forward", "fdgs_gaussian_flow_backward", "fdgs_contribution", "fdgs_feature_blend", "fdgs_feature_blend_backward", "fdgs_camera_backward_scratch", "fdgs_camera_backward",
-            "fdgs_kmeans_scratch_bytes", "fdgs_kmeans_assign", "fdgs_kmeans_update", "fdgs_quantize_columns", "fdgs_compact_decode",
-            "fdgs_model_transform", "fdgs_depth_loss_num_partials", "fdgs_depth_loss", "fdgs_depth_normals", "fdgs_depth_normals_backward",
-            "fdgs_tsdf_integrate", "fdgs_surface_extract_scratch_bytes", "fdgs_surface_extract",
-            "fdgs_mesh_components_scratch_bytes", "fdgs_mesh_components", "fdgs_mesh_compact_scratch_bytes", "fdgs_mesh_compact",
-            "fdgs_mesh_smooth_scratch_bytes", "fdgs_mesh_smooth", "fdgs_mesh_simplify_scratch_bytes", "fdgs_mesh_simplify",
-            "fdgs_last_error", "fdgs_version")
+_i, _i64, _f, _p, _sz = C.c_int32, C.c_int64, C.c_float, C.c_void_p, C.c_size_t
+_P = C.POINTER
+_mesh_scratch = (_sz, [_i, _i])
+# every symbol include/fdgs.h declares: name -> (restype, argtypes).  The one place a new entry point is bound (EXPORTED and _load follow it)
+SIGNATURES = {
+    "fdgs_rasterize_forward": (C.c_int, [_P(FdgsScene), _P(FdgsForwardOut), ALLOC_FN, _p, _p, _P(_i)]),
+    "fdgs_forward_lazy_status": (C.c_int, [_i, _p, _P(_i), _P(_i), _P(_i), _i, _P(_i)]),
+    "fdgs_rasterize_backward": (C.c_int, [_P(FdgsScene), _P(FdgsBackwardIn), _P(FdgsBackwardOut), _p]),
+    "fdgs_preprocess_batch": (C.c_int, [_i, _P(_P(FdgsScene)), _P(_P(FdgsForwardOut)), ALLOC_FN, _P(_p), _p]),
+    "fdgs_sh_backward_batch": (C.c_int, [_i, _P(_P(FdgsScene)), _P(_P(FdgsBackwardIn)), _P(_P(FdgsBackwardOut)), _p]),
+    "fdgs_mark_visible": (C.c_int, [_i] + [_p] * 5),
+    "fdgs_geometry_bytes": (_sz, [_i]),
+    "fdgs_image_bytes": (_sz, [_i, _i]),
+    "fdgs_binning_bytes": (_sz, [_i] * 3),
+    "fdgs_debug_views": (C.c_int, [_i] * 4 + [_p] * 3 + [_P(FdgsDebugView)]),
+    "fdgs_debug_activations": (C.c_int, [_i] + [_p] * 11),
+    "fdgs_debug_radix_sort_scratch_bytes": (_sz, [_i]),
+    "fdgs_debug_radix_sort_pairs": (C.c_int, [_i] * 3 + [_p] * 4),
+    "fdgs_debug_knn_stage_offsets": (C.c_int, [_i] * 3 + [_P(_i64)]),
+    "fdgs_debug_tile_sort_limits": (None, [_i, _i]),
+    "fdgs_debug_tile_bin_scratch_bytes": (_sz, [_i, _i]),
+    "fdgs_debug_tile_bin": (C.c_int, [_i, _p, _p] + [_i] * 5 + [_p] * 9),
+    "fdgs_debug_block_reaches": (C.c_int, [_i, _p, _p, _p]),
+    "fdgs_debug_run_ahead_stats": (None, [_P(_i64)]),
+    "fdgs_set_run_ahead": (None, [_i]),
+    "fdgs_set_sparse_lists_budget": (C.c_int, [_i64, _i]),
+    "fdgs_debug_sparse_lists_stats": (None, [_P(_i64)]),
+    "fdgs_debug_clock_sample": (C.c_int, [_p, C.c_double, _p]),
+    "fdgs_sh_flush": (C.c_int, [_i] * 8 + [_p, _p, _i, _p]),
+    "fdgs_profile_enable": (C.c_int, [C.c_int]),
+    "fdgs_profile_sample_every": (C.c_int, [_i]),
+    "fdgs_profile_read": (C.c_int, [C.c_int, _P(C.c_double), _P(_i64)]),
+    "fdgs_profile_reset": (C.c_int, []),
+    "fdgs_stage_name": (C.c_char_p, [C.c_int]),
+    "fdgs_l1_ssim_forward": (C.c_int, [_p, _p, _i, _i, _i] + [_p] * 6),
+    "fdgs_l1_ssim_backward": (C.c_int, [_p, _p, _i, _i, _i] + [_p] * 4 + [_f, _p, _p]),
+    "fdgs_l1_ssim_loss": (C.c_int, [_p, _p] + [_i] * 4 + [_f, _p, _p]),
+    "fdgs_l1_ssim_loss_batch": (C.c_int, [_p] + [_i] * 5 + [_f, _p, _p]),
+    "fdgs_l1_ssim_num_partials": (C.c_int, [_i] * 3),
+    "fdgs_l1_ssim_value_and_grad": (C.c_int, [_p, _p, _i, _i, _i, _p, _f] + [_p] * 4),
+    "fdgs_adam_step": (C.c_int, [_p] * 4 + [_i64, _P(FdgsAdamSegment), _i, _f, _f, _f, _i, _p]),
+    "fdgs_adam_step_sh": (C.c_int, [_p] * 4 + [_i] * 8 + [_p] + [_f] * 5 + [_i, _p]),
+    "fdgs_densify_classify": (C.c_int, [_i] + [_p] * 5 + [_f] * 5 + [_i, _i, _p, _p]),
+    "fdgs_densify_gather": (C.c_int, [_i, _P(_i), _i64, _i64] + [_p] * 9),
+    "fdgs_densify_split": (C.c_int, [_i] * 4 + [_p] * 14),
+    "fdgs_densify_stats_local": (C.c_int, [_i, _i, _P(_p), _P(_p)] + [_p] * 4),
+    "fdgs_densify_stats_apply": (C.c_int, [_i] + [_p] * 4 + [_f] + [_p] * 5),
+    "fdgs_knn_scratch_bytes": (_sz, [_i]),
+    "fdgs_dist2_knn3": (C.c_int, [_i] + [_p] * 4),
+    "fdgs_knn_query_scratch_bytes": (_sz, [_i, _i]),
+    "fdgs_knn_query": (C.c_int, [_i] * 4 + [_p] * 6),
+    "fdgs_rigid_motion_scratch_bytes": (_sz, [_i, _i]),
+    "fdgs_rigid_motion_forward": (C.c_int, [_i, _i] + [_p] * 11),
+    "fdgs_rigid_motion_backward": (C.c_int, [_i, _i] + [_p] * 9 + [_f] + [_p] * 6),
+    "fdgs_opa_mask_num_partials": (C.c_int, [_i, _i]),
+    "fdgs_opa_mask_loss": (C.c_int, [_i, _i, _p, _i, _p, _p, _f, _p, _i, _p, _p, _p]),
+    "fdgs_env_composite": (C.c_int, [_i, _i, _p, _p] + [_f] * 4 + [_p, _i, _i, _f] + [_p] * 4),
+    "fdgs_env_composite_backward": (C.c_int, [_i, _i, _p, _p] + [_f] * 4 + [_p, _i, _i, _f, _p, _p, _p, _i, _p, _i, _p]),
+    "fdgs_eval_metrics_scratch_bytes": (C.c_int, [_i] * 3),
+    "fdgs_eval_metrics": (C.c_int, [_p, _p] + [_i] * 4 + [_p] * 3),
+    "fdgs_frames_decode": (C.c_int, [_p] + [_i] * 4 + [_p, _i, _p, _i64, _p, _i64, _p]),
+    "fdgs_frames_encode": (C.c_int, [_p, _i64, _p, _i64] + [_i] * 4 + [_p, _i, _p, _p]),
+    "fdgs_frames_encode_gray_scratch_bytes": (_i64, [_i] * 3),
+    "fdgs_frames_encode_gray": (C.c_int, [_p, _i64] + [_i] * 3 + [_p, _i, _p, _p, _p]),
+    "fdgs_frames_resize": (C.c_int, [_p] + [_i] * 4 + [_p, _i, _p] + [_i] * 3 + [_p, _p, _i, _p, _p, _i, _p, _p]),
+    "fdgs_frames_resize_scratch_bytes": (_i64, [_i] * 6),
+    "fdgs_debug_frames_resize_path": (None, [_i]),
+    "fdgs_frames_composite": (C.c_int, [_p] + [_i] * 5 + [_p, _p]),
+    "fdgs_time_slice_scratch_bytes": (_sz, [_i]),
+    "fdgs_time_slice": (C.c_int, [_P(FdgsSliceIn), _P(FdgsSliceOut), _p, _p]),
+    "fdgs_gaussian_flow_forward": (C.c_int, [_P(FdgsFlowIn), _p, _p]),
+    "fdgs_gaussian_flow_backward": (C.c_int, [_P(FdgsFlowIn), _p, _f, _P(FdgsFlowGrads), _p]),
+    "fdgs_contribution": (C.c_int, [_P(FdgsContributionIn), _P(FdgsContributionOut), _p]),
+    "fdgs_feature_blend": (C.c_int, [_P(FdgsFeatureIn), _p, _p]),
+    "fdgs_feature_blend_backward": (C.c_int, [_P(FdgsFeatureIn), _p, _p, _p]),
+    "fdgs_camera_backward_scratch": (_sz, [_i]),
+    "fdgs_camera_backward": (C.c_int, [_P(FdgsScene), _P(FdgsBackwardIn), _p, _P(FdgsCameraGrads), _p, _sz, _p]),
+    "fdgs_kmeans_scratch_bytes": (_sz, [_i, _i]),
+    "fdgs_kmeans_assign": (C.c_int, [_i] * 3 + [_p] * 6),
+    "fdgs_kmeans_update": (C.c_int, [_i] * 3 + [_p] * 7),
+    "fdgs_quantize_columns": (C.c_int, [_i, _i, _p, _p, _p, _i, _p, _p]),
+    "fdgs_compact_decode": (C.c_int, [_i] * 3 + [_p] * 3 + [_i, _p, _p, _i, _p, _p]),
+    "fdgs_model_transform": (C.c_int, [_P(FdgsTransformIn), _P(FdgsTransformOut), _p]),
+    "fdgs_depth_loss_num_partials": (C.c_int, [_i, _i]),
+    "fdgs_depth_loss": (C.c_int, [_P(FdgsDepthIn), _p, _i, _P(FdgsDepthGrads), _p, _p, _p]),
+    "fdgs_depth_normals": (C.c_int, [_P(FdgsDepthIn)] + [_f] * 4 + [_p] * 4),
+    "fdgs_depth_normals_backward": (C.c_int, [_P(FdgsDepthIn)] + [_f] * 4 + [_p, _p, _P(FdgsDepthGrads), _p]),
+    "fdgs_tsdf_integrate": (C.c_int, [_P(FdgsTsdfVolume), _i, _P(FdgsTsdfView), _p]),
+    "fdgs_surface_extract_scratch_bytes": (_sz, [_i] * 3),
+    "fdgs_surface_extract": (C.c_int, [_P(FdgsTsdfVolume), _f, _P(FdgsSurfaceOut), _p, _p]),
+    "fdgs_mesh_components_scratch_bytes": _mesh_scratch,
+    "fdgs_mesh_components": (C.c_int, [_P(FdgsMeshIn), _P(FdgsMeshComponentsOut), _p, _p]),
+    "fdgs_mesh_compact_scratch_bytes": _mesh_scratch,
+    "fdgs_mesh_compact": (C.c_int, [_P(FdgsMeshIn), _p, _p, _i, _P(FdgsSurfaceOut), _p, _p]),
+    "fdgs_mesh_smooth_scratch_bytes": _mesh_scratch,
+    "fdgs_mesh_smooth": (C.c_int, [_P(FdgsMeshIn), _P(FdgsMeshSmoothOut), _p, _p]),
+    "fdgs_mesh_simplify_scratch_bytes": _mesh_scratch,
+    "fdgs_mesh_simplify": (C.c_int, [_P(FdgsMeshIn), _P(FdgsMeshSimplifyParams), _P(FdgsSurfaceOut), _p, _p]),
+    "fdgs_last_error": (C.c_char_p, []),
+    "fdgs_version": (C.c_int, []),
+}
+EXPORTED = tuple(SIGNATURES)
 NUM_STAGES = 12
 # offsets[] of fdgs_debug_knn_stage_offsets (include/fdgs.h FDGS_KNN_STAGE_*)
 KNN_STAGE_BOUNDS, KNN_STAGE_BOXES, KNN_STAGE_SRC_CODES, KNN_STAGE_SRC_ORDER, KNN_STAGE_QUERY_CODES, KNN_STAGE_QUERY_ORDER, \
@@ -230,206 +315,9 @@ def _load():
             "libfdgs.so not found at %s -- build it with 4d-gaussian-splatting_amd/csrc/build.sh "
             "(or __graft_entry__.build()); there is no CPU / PyTorch fallback." % LIB_PATH)
     lib = C.CDLL(LIB_PATH)
-    lib.fdgs_rasterize_forward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsForwardOut), ALLOC_FN, C.c_void_p,
-                                           C.c_void_p, C.POINTER(C.c_int32)]
-    lib.fdgs_rasterize_forward.restype = C.c_int
-    lib.fdgs_forward_lazy_status.argtypes = [C.c_int32, C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32),
-                                             C.c_int32, C.POINTER(C.c_int32)]
-    lib.fdgs_forward_lazy_status.restype = C.c_int
-    lib.fdgs_rasterize_backward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsBackwardIn),
-                                            C.POINTER(FdgsBackwardOut), C.c_void_p]
-    lib.fdgs_rasterize_backward.restype = C.c_int
-    lib.fdgs_preprocess_batch.argtypes = [C.c_int32, C.POINTER(C.POINTER(FdgsScene)), C.POINTER(C.POINTER(FdgsForwardOut)), ALLOC_FN,
-                                          C.POINTER(C.c_void_p), C.c_void_p]
-    lib.fdgs_preprocess_batch.restype = C.c_int
-    lib.fdgs_sh_backward_batch.argtypes = [C.c_int32, C.POINTER(C.POINTER(FdgsScene)), C.POINTER(C.POINTER(FdgsBackwardIn)),
-                                           C.POINTER(C.POINTER(FdgsBackwardOut)), C.c_void_p]
-    lib.fdgs_sh_backward_batch.restype = C.c_int
-    lib.fdgs_mark_visible.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_mark_visible.restype = C.c_int
-    lib.fdgs_geometry_bytes.argtypes = [C.c_int32]
-    lib.fdgs_geometry_bytes.restype = C.c_size_t
-    lib.fdgs_image_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_image_bytes.restype = C.c_size_t
-    lib.fdgs_binning_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.fdgs_binning_bytes.restype = C.c_size_t
-    lib.fdgs_debug_views.argtypes = [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.POINTER(FdgsDebugView)]
-    lib.fdgs_debug_views.restype = C.c_int
-    lib.fdgs_debug_activations.argtypes = [C.c_int32] + [C.c_void_p] * 11
-    lib.fdgs_debug_activations.restype = C.c_int
-    lib.fdgs_debug_tile_sort_limits.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_debug_tile_sort_limits.restype = None
-    lib.fdgs_debug_tile_bin_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_debug_tile_bin_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_debug_tile_bin.argtypes = [C.c_int32, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p] * 9
-    lib.fdgs_debug_tile_bin.restype = C.c_int
-    lib.fdgs_debug_block_reaches.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_debug_block_reaches.restype = C.c_int
-    lib.fdgs_debug_run_ahead_stats.argtypes = [C.POINTER(C.c_int64)]
-    lib.fdgs_debug_run_ahead_stats.restype = None
-    lib.fdgs_set_run_ahead.argtypes = [C.c_int32]
-    lib.fdgs_set_run_ahead.restype = None
-    lib.fdgs_set_sparse_lists_budget.argtypes = [C.c_int64, C.c_int32]
-    lib.fdgs_set_sparse_lists_budget.restype = C.c_int
-    lib.fdgs_debug_sparse_lists_stats.argtypes = [C.POINTER(C.c_int64)]
-    lib.fdgs_debug_sparse_lists_stats.restype = None
-    lib.fdgs_debug_clock_sample.argtypes = [C.c_void_p, C.c_double, C.c_void_p]
-    lib.fdgs_debug_clock_sample.restype = C.c_int
-    lib.fdgs_sh_flush.argtypes = [C.c_int32] * 8 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.fdgs_sh_flush.restype = C.c_int
-    lib.fdgs_profile_enable.argtypes = [C.c_int]
-    lib.fdgs_profile_enable.restype = C.c_int
-    lib.fdgs_profile_sample_every.argtypes = [C.c_int32]
-    lib.fdgs_profile_sample_every.restype = C.c_int
-    lib.fdgs_profile_read.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int64)]
-    lib.fdgs_profile_read.restype = C.c_int
-    lib.fdgs_profile_reset.restype = C.c_int
-    lib.fdgs_stage_name.argtypes = [C.c_int]
-    lib.fdgs_stage_name.restype = C.c_char_p
-    lib.fdgs_l1_ssim_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_l1_ssim_forward.restype = C.c_int
-    lib.fdgs_l1_ssim_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
-                                          C.c_void_p, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p]
-    lib.fdgs_l1_ssim_backward.restype = C.c_int
-    lib.fdgs_l1_ssim_loss.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
-    lib.fdgs_l1_ssim_loss.restype = C.c_int
-    lib.fdgs_l1_ssim_loss_batch.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]
-    lib.fdgs_l1_ssim_loss_batch.restype = C.c_int
-    lib.fdgs_l1_ssim_value_and_grad.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_float, C.c_void_p, C.c_void_p,
-                                                C.c_void_p, C.c_void_p]
-    lib.fdgs_l1_ssim_value_and_grad.restype = C.c_int
-    lib.fdgs_l1_ssim_num_partials.argtypes = [C.c_int32, C.c_int32, C.c_int32]
-    lib.fdgs_l1_ssim_num_partials.restype = C.c_int
-    lib.fdgs_adam_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                   C.POINTER(FdgsAdamSegment), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_int32,
-                                   C.c_void_p]
-    lib.fdgs_adam_step.restype = C.c_int
-    lib.fdgs_adam_step_sh.argtypes = [C.c_void_p] * 4 + [C.c_int32] * 8 + [C.c_void_p] + [C.c_float] * 5 + [C.c_int32, C.c_void_p]
-    lib.fdgs_adam_step_sh.restype = C.c_int
-    lib.fdgs_densify_classify.argtypes = [C.c_int32] + [C.c_void_p] * 5 + [C.c_float] * 5 + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.fdgs_densify_classify.restype = C.c_int
-    lib.fdgs_densify_gather.argtypes = [C.c_int32, C.POINTER(C.c_int32), C.c_int64, C.c_int64] + [C.c_void_p] * 9
-    lib.fdgs_densify_gather.restype = C.c_int
-    lib.fdgs_densify_split.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 14
-    lib.fdgs_densify_split.restype = C.c_int
-    lib.fdgs_densify_stats_local.argtypes = [C.c_int32, C.c_int32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p,
-                                             C.c_void_p, C.c_void_p]
-    lib.fdgs_densify_stats_local.restype = C.c_int
-    lib.fdgs_densify_stats_apply.argtypes = [C.c_int32] + [C.c_void_p] * 4 + [C.c_float] + [C.c_void_p] * 5
-    lib.fdgs_densify_stats_apply.restype = C.c_int
-    lib.fdgs_knn_scratch_bytes.argtypes = [C.c_int32]
-    lib.fdgs_knn_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_dist2_knn3.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_dist2_knn3.restype = C.c_int
-    lib.fdgs_knn_query_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_knn_query_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_knn_query.argtypes = [C.c_int32] * 4 + [C.c_void_p] * 6
-    lib.fdgs_knn_query.restype = C.c_int
-    lib.fdgs_debug_radix_sort_scratch_bytes.argtypes = [C.c_int32]
-    lib.fdgs_debug_radix_sort_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_debug_radix_sort_pairs.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 4
-    lib.fdgs_debug_radix_sort_pairs.restype = C.c_int
-    lib.fdgs_debug_knn_stage_offsets.argtypes = [C.c_int32] * 3 + [C.POINTER(C.c_int64)]
-    lib.fdgs_debug_knn_stage_offsets.restype = C.c_int
-    lib.fdgs_rigid_motion_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_rigid_motion_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_rigid_motion_forward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 11
-    lib.fdgs_rigid_motion_forward.restype = C.c_int
-    lib.fdgs_rigid_motion_backward.argtypes = [C.c_int32, C.c_int32] + [C.c_void_p] * 9 + [C.c_float] + [C.c_void_p] * 6
-    lib.fdgs_rigid_motion_backward.restype = C.c_int
-    lib.fdgs_opa_mask_num_partials.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_opa_mask_num_partials.restype = C.c_int
-    lib.fdgs_opa_mask_loss.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p,
-                                       C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_opa_mask_loss.restype = C.c_int
-    lib.fdgs_env_composite.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [C.c_void_p, C.c_int32, C.c_int32,
-                                                                                            C.c_float] + [C.c_void_p] * 4
-    lib.fdgs_env_composite.restype = C.c_int
-    lib.fdgs_env_composite_backward.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p] + [C.c_float] * 4 + [
-        C.c_void_p, C.c_int32, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
-    lib.fdgs_env_composite_backward.restype = C.c_int
-    lib.fdgs_eval_metrics_scratch_bytes.argtypes = [C.c_int32] * 3
-    lib.fdgs_eval_metrics_scratch_bytes.restype = C.c_int
-    lib.fdgs_eval_metrics.argtypes = [C.c_void_p, C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p] * 3
-    lib.fdgs_eval_metrics.restype = C.c_int
-    lib.fdgs_frames_decode.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
-    lib.fdgs_frames_decode.restype = C.c_int
-    lib.fdgs_frames_encode.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.fdgs_frames_encode.restype = C.c_int
-    lib.fdgs_frames_encode_gray_scratch_bytes.argtypes = [C.c_int32] * 3
-    lib.fdgs_frames_encode_gray_scratch_bytes.restype = C.c_int64
-    lib.fdgs_frames_encode_gray.argtypes = [C.c_void_p, C.c_int64] + [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_frames_encode_gray.restype = C.c_int
-    lib.fdgs_frames_resize.argtypes = [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p] + [C.c_int32] * 3 + [
-        C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.fdgs_frames_resize.restype = C.c_int
-    lib.fdgs_frames_resize_scratch_bytes.argtypes = [C.c_int32] * 6
-    lib.fdgs_frames_resize_scratch_bytes.restype = C.c_int64
-    lib.fdgs_debug_frames_resize_path.argtypes = [C.c_int32]
-    lib.fdgs_debug_frames_resize_path.restype = None
-    lib.fdgs_frames_composite.argtypes = [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p]
-    lib.fdgs_frames_composite.restype = C.c_int
-    lib.fdgs_time_slice_scratch_bytes.argtypes = [C.c_int32]
-    lib.fdgs_time_slice_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_time_slice.argtypes = [C.POINTER(FdgsSliceIn), C.POINTER(FdgsSliceOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_time_slice.restype = C.c_int
-    lib.fdgs_gaussian_flow_forward.argtypes = [C.POINTER(FdgsFlowIn), C.c_void_p, C.c_void_p]
-    lib.fdgs_gaussian_flow_forward.restype = C.c_int
-    lib.fdgs_gaussian_flow_backward.argtypes = [C.POINTER(FdgsFlowIn), C.c_void_p, C.c_float, C.POINTER(FdgsFlowGrads), C.c_void_p]
-    lib.fdgs_gaussian_flow_backward.restype = C.c_int
-    lib.fdgs_contribution.argtypes = [C.POINTER(FdgsContributionIn), C.POINTER(FdgsContributionOut), C.c_void_p]
-    lib.fdgs_contribution.restype = C.c_int
-    lib.fdgs_feature_blend.argtypes = [C.POINTER(FdgsFeatureIn), C.c_void_p, C.c_void_p]
-    lib.fdgs_feature_blend.restype = C.c_int
-    lib.fdgs_feature_blend_backward.argtypes = [C.POINTER(FdgsFeatureIn), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_feature_blend_backward.restype = C.c_int
-    lib.fdgs_camera_backward_scratch.argtypes = [C.c_int32]
-    lib.fdgs_camera_backward_scratch.restype = C.c_size_t
-    lib.fdgs_camera_backward.argtypes = [C.POINTER(FdgsScene), C.POINTER(FdgsBackwardIn), C.c_void_p, C.POINTER(FdgsCameraGrads), C.c_void_p,
-                                         C.c_size_t, C.c_void_p]
-    lib.fdgs_camera_backward.restype = C.c_int
-    lib.fdgs_kmeans_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_kmeans_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_kmeans_assign.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 6
-    lib.fdgs_kmeans_assign.restype = C.c_int
-    lib.fdgs_kmeans_update.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 7
-    lib.fdgs_kmeans_update.restype = C.c_int
-    lib.fdgs_quantize_columns.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.fdgs_quantize_columns.restype = C.c_int
-    lib.fdgs_compact_decode.argtypes = [C.c_int32] * 3 + [C.c_void_p] * 3 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
-    lib.fdgs_compact_decode.restype = C.c_int
-    lib.fdgs_model_transform.argtypes = [C.POINTER(FdgsTransformIn), C.POINTER(FdgsTransformOut), C.c_void_p]
-    lib.fdgs_model_transform.restype = C.c_int
-    lib.fdgs_depth_loss_num_partials.argtypes = [C.c_int32, C.c_int32]
-    lib.fdgs_depth_loss_num_partials.restype = C.c_int
-    lib.fdgs_depth_loss.argtypes = [C.POINTER(FdgsDepthIn), C.c_void_p, C.c_int32, C.POINTER(FdgsDepthGrads), C.c_void_p, C.c_void_p, C.c_void_p]
-    lib.fdgs_depth_loss.restype = C.c_int
-    lib.fdgs_depth_normals.argtypes = [C.POINTER(FdgsDepthIn)] + [C.c_float] * 4 + [C.c_void_p] * 4
-    lib.fdgs_depth_normals.restype = C.c_int
-    lib.fdgs_depth_normals_backward.argtypes = [C.POINTER(FdgsDepthIn)] + [C.c_float] * 4 + [C.c_void_p, C.c_void_p, C.POINTER(FdgsDepthGrads),
-                                                                                             C.c_void_p]
-    lib.fdgs_depth_normals_backward.restype = C.c_int
-    lib.fdgs_tsdf_integrate.argtypes = [C.POINTER(FdgsTsdfVolume), C.c_int32, C.POINTER(FdgsTsdfView), C.c_void_p]
-    lib.fdgs_tsdf_integrate.restype = C.c_int
-    lib.fdgs_surface_extract_scratch_bytes.argtypes = [C.c_int32] * 3
-    lib.fdgs_surface_extract_scratch_bytes.restype = C.c_size_t
-    lib.fdgs_surface_extract.argtypes = [C.POINTER(FdgsTsdfVolume), C.c_float, C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_surface_extract.restype = C.c_int
-    for name in ("components", "compact", "smooth", "simplify"):
-        fn = getattr(lib, "fdgs_mesh_%s_scratch_bytes" % name)
-        fn.argtypes, fn.restype = [C.c_int32, C.c_int32], C.c_size_t
-    lib.fdgs_mesh_components.argtypes = [C.POINTER(FdgsMeshIn), C.POINTER(FdgsMeshComponentsOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_mesh_components.restype = C.c_int
-    lib.fdgs_mesh_compact.argtypes = [C.POINTER(FdgsMeshIn), C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_mesh_compact.restype = C.c_int
-    lib.fdgs_mesh_smooth.argtypes = [C.POINTER(FdgsMeshIn), C.POINTER(FdgsMeshSmoothOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_mesh_smooth.restype = C.c_int
-    lib.fdgs_mesh_simplify.argtypes = [C.POINTER(FdgsMeshIn), C.POINTER(FdgsMeshSimplifyParams), C.POINTER(FdgsSurfaceOut), C.c_void_p, C.c_void_p]
-    lib.fdgs_mesh_simplify.restype = C.c_int
-    lib.fdgs_last_error.restype = C.c_char_p
-    lib.fdgs_version.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if lib.fdgs_version() != FDGS_VERSION:
         raise ImportError("%s is version %d, this binding was written for FDGS_VERSION %d (include/fdgs.h): rebuild the library "
                           "(4d-gaussian-splatting_amd/csrc/build.sh)" % (LIB_PATH, lib.fdgs_version(), FDGS_VERSION))
@@ -443,14 +331,49 @@ def last_error() -> str:
     return lib.fdgs_last_error().decode()
 
 
-def _check(rc: int, what: str):
+def _check(rc: int, what: str, arg_error=Exception):
+    """``arg_error``: what an argument error (code 1) raises; modules whose own checks raise ValueError pass that."""
     if rc != 0:
         msg = last_error()
         if rc == 1:
             # argument errors keep the reference's Python-level wording / type
             # (gaussian_renderer/diff_gaussian_rasterization.py:271-280 raise plain Exception)
-            raise Exception(msg)
+            raise arg_error(msg)
         raise RuntimeError("%s failed (code %d): %s" % (what, rc, msg))
+
+
+def current_stream_handle(device):
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def call(name, dev, *args, guard=True, stream=None, arg_error=Exception):
+    """The one way a launching entry point is called: ``lib.<name>(*args, stream)`` with ``dev`` current and ``stream`` the current
+    stream of ``dev`` (the last argument of every such entry point), then ``_check``.  ``guard=False``: the caller is inside
+    ``torch.cuda.device(dev)`` already (several calls under one guard, a ``torch.cuda.stream`` block) and it is not entered again.
+    ``stream``: a handle of the caller's instead (``ClockSample``'s own stream; one look-up for back-to-back calls).  The two entry
+    points that take their stream in the middle are written out below: ``rasterize_forward``, ``forward_lazy_status``."""
+    fn = getattr(lib, name)
+    if stream is None:
+        stream = current_stream_handle(dev)
+    if guard:
+        with torch.cuda.device(dev):
+            rc = fn(*args, stream)
+    else:
+        rc = fn(*args, stream)
+    if rc != 0:
+        _check(rc, name, arg_error)
+
+
+def need_gpu(t, name, what=None):
+    """The one refusal of a CPU tensor; ``what``: what the message calls it where that is not "tensor '<name>'"."""
+    if not t.is_cuda:
+        raise RuntimeError("fdgs: %s must live on the GPU (got %s); there is no CPU path" % (what or "tensor '%s'" % name, t.device))
+
+
+def scratch(nbytes, dev, floor=0):
+    """``nbytes`` of device scratch as a uint8 tensor; ``floor``: the least it allocates (an entry point that wants a pointer even
+    where it needs no bytes)."""
+    return torch.empty(max(int(nbytes), floor), dtype=torch.uint8, device=dev)
 
 
 def _ptr(t):
@@ -463,8 +386,7 @@ def _ptr(t):
 def _dev_f32(t, name):
     if t is None or t.numel() == 0:
         return None
-    if not t.is_cuda:
-        raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+    need_gpu(t, name)
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
@@ -477,8 +399,7 @@ def _common_device(named):
     for name, t in named:
         if t is None or t.numel() == 0:
             continue
-        if not t.is_cuda:
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        need_gpu(t, name)
         if dev is not None and t.device != dev:
             raise RuntimeError("fdgs: '%s' lives on %s, the forward's buffers on %s" % (name, t.device, dev))
         dev = t.device
@@ -493,9 +414,7 @@ def debug_activations(opacity_raw=None, scales_raw=None, scales_t_raw=None, rota
     ins = [_dev_f32(t, "raw parameter") for t in ins]
     outs = [None if t is None else torch.empty_like(t) for t in ins]
     P = int(ref.shape[0])
-    with torch.cuda.device(ref.device):
-        rc = lib.fdgs_debug_activations(P, *[_ptr(t) for t in ins], *[_ptr(t) for t in outs], current_stream_handle(ref.device))
-    _check(rc, "fdgs_debug_activations")
+    call("fdgs_debug_activations", ref.device, P, *[_ptr(t) for t in ins], *[_ptr(t) for t in outs])
     return tuple(outs)
 
 
@@ -506,11 +425,8 @@ def sh_flush(stages, dL_dsh, sh_degree, sh_degree_t, gaussian_dim, force_sh_3d, 
     P, M = int(dL_dsh.shape[0]), int(dL_dsh.shape[1])
     if stages.dim() != 3 or stages.shape[1] != P or stages.shape[2] != 8 or not stages.is_contiguous() or stages.dtype != torch.float32:
         raise RuntimeError("fdgs: stages must be a contiguous float32 tensor [num_views, %d, 8]" % P)
-    with torch.cuda.device(dL_dsh.device):
-        rc = lib.fdgs_sh_flush(P, int(sh_degree), int(sh_degree_t), M, int(gaussian_dim), int(bool(force_sh_3d)),
-                               int(bool(analytic_sh_grad)), int(stages.shape[0]), stages.data_ptr(), dL_dsh.data_ptr(), int(bool(accumulate)),
-                               current_stream_handle(dL_dsh.device))
-    _check(rc, "fdgs_sh_flush")
+    call("fdgs_sh_flush", dL_dsh.device, P, int(sh_degree), int(sh_degree_t), M, int(gaussian_dim), int(bool(force_sh_3d)),
+         int(bool(analytic_sh_grad)), int(stages.shape[0]), stages.data_ptr(), dL_dsh.data_ptr(), int(bool(accumulate)))
 
 
 def adam_step_sh(params, exp_avg, exp_avg_sq, stages, sh_degree, sh_degree_t, gaussian_dim, force_sh_3d, analytic_sh_grad,
@@ -523,14 +439,18 @@ def adam_step_sh(params, exp_avg, exp_avg_sq, stages, sh_degree, sh_degree_t, ga
     ptrs = [params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr()] + ([dL_dsh.data_ptr()] if dL_dsh is not None else [])
     if (3 * M) % 4 != 0 or any(q % 16 for q in ptrs):
         return False
-    with torch.cuda.device(params.device):
-        rc = lib.fdgs_adam_step_sh(params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
-                                   dL_dsh.data_ptr() if dL_dsh is not None else None, P, int(sh_degree), int(sh_degree_t), M,
-                                   int(gaussian_dim), int(bool(force_sh_3d)), int(bool(analytic_sh_grad)), int(stages.shape[0]),
-                                   stages.data_ptr(), float(lr), float(lr_dc), float(beta1), float(beta2), float(eps), int(step),
-                                   current_stream_handle(params.device))
-    _check(rc, "fdgs_adam_step_sh")
+    call("fdgs_adam_step_sh", params.device, params.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(),
+         dL_dsh.data_ptr() if dL_dsh is not None else None, P, int(sh_degree), int(sh_degree_t), M, int(gaussian_dim),
+         int(bool(force_sh_3d)), int(bool(analytic_sh_grad)), int(stages.shape[0]), stages.data_ptr(), float(lr), float(lr_dc),
+         float(beta1), float(beta2), float(eps), int(step))
     return True
+
+
+def rasterize_forward(dev, scene, out, alloc, num_rendered):
+    """fdgs_rasterize_forward on the current stream of ``dev`` (its stream argument is not the last one); ``num_rendered``: a c_int32."""
+    with torch.cuda.device(dev):
+        rc = lib.fdgs_rasterize_forward(C.byref(scene), C.byref(out), alloc, None, current_stream_handle(dev), C.byref(num_rendered))
+    _check(rc, "fdgs_rasterize_forward")
 
 
 def forward_lazy_status(device, wait=True):
@@ -568,9 +488,7 @@ class ClockSample:
         self.out = torch.zeros(5, dtype=torch.int64, device=device)
 
     def start(self, span_ms: float):
-        with torch.cuda.device(self.dev):
-            rc = lib.fdgs_debug_clock_sample(self.out.data_ptr(), float(span_ms), C.c_void_p(self.stream.cuda_stream))
-        _check(rc, "fdgs_debug_clock_sample")
+        call("fdgs_debug_clock_sample", self.dev, self.out.data_ptr(), float(span_ms), stream=C.c_void_p(self.stream.cuda_stream))
 
     def ghz(self):
         self.stream.synchronize()
@@ -592,9 +510,7 @@ class ClockPair:
         self.n = 0
 
     def mark(self):
-        with torch.cuda.device(self.dev):
-            rc = lib.fdgs_debug_clock_sample(self.out[self.n].data_ptr(), 0.002, current_stream_handle(self.dev))
-        _check(rc, "fdgs_debug_clock_sample")
+        call("fdgs_debug_clock_sample", self.dev, self.out[self.n].data_ptr(), 0.002)
         self.n += 1
 
     def ghz(self):
@@ -605,10 +521,6 @@ class ClockPair:
         if w1 <= w0 or khz <= 0:
             return None
         return (s1 - s0) / (w1 - w0) * khz * 1e-6
-
-
-def current_stream_handle(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def profile_enable(on: bool = True, stages=None, every: int = 1):

@@ -37,20 +37,11 @@ DEFAULT_BITS = {"_xyz": 32, "_t": 16, "_scaling": 16, "_scaling_t": 16, "_opacit
 _QUATERNIONS = ("_rotation", "_rotation_r")
 
 
-def _need_gpu(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
-
-
 def _rows_f32(t: torch.Tensor, name: str) -> torch.Tensor:
-    _need_gpu(t, name)
+    _capi.need_gpu(t, name)
     if t.dim() != 2:
         raise ValueError("fdgs.compress: %s must be a matrix [rows, columns], got %s" % (name, tuple(t.shape)))
     return t.detach().to(torch.float32).contiguous()
-
-
-def _scratch(N: int, K: int, device) -> torch.Tensor:
-    return torch.empty((max(int(_capi.lib.fdgs_kmeans_scratch_bytes(int(N), int(K))), 1),), dtype=torch.uint8, device=device)
 
 
 def assign(x: torch.Tensor, codebook: torch.Tensor, *, want_dist: bool = False, scratch: Optional[torch.Tensor] = None):
@@ -62,11 +53,9 @@ def assign(x: torch.Tensor, codebook: torch.Tensor, *, want_dist: bool = False, 
         raise ValueError("fdgs.compress.assign: x is [%d, %d] on %s, the codebook %s on %s" % (N, D, x.device, tuple(c.shape), c.device))
     index = torch.empty((N,), dtype=torch.int32, device=x.device)
     dist = torch.empty((N,), dtype=torch.float32, device=x.device) if want_dist else None
-    scratch = _scratch(N, K, x.device) if scratch is None else scratch
-    with torch.cuda.device(x.device):
-        rc = _capi.lib.fdgs_kmeans_assign(N, K, D, _capi._ptr(x), _capi._ptr(c), _capi._ptr(index), _capi._ptr(dist), scratch.data_ptr(),
-                                          _capi.current_stream_handle(x.device))
-    _capi._check(rc, "fdgs_kmeans_assign")
+    if scratch is None:
+        scratch = _capi.scratch(_capi.lib.fdgs_kmeans_scratch_bytes(N, K), x.device, floor=1)
+    _capi.call("fdgs_kmeans_assign", x.device, N, K, D, _capi._ptr(x), _capi._ptr(c), _capi._ptr(index), _capi._ptr(dist), scratch.data_ptr())
     return index, dist
 
 
@@ -76,8 +65,8 @@ def update(x: torch.Tensor, index: torch.Tensor, codebook: torch.Tensor, *, weig
     ``x`` with ``index == k``; a cluster without rows or without weight keeps its row.  Returns the rows per cluster, int32 [K].
     Bitwise reproducible."""
     x = _rows_f32(x, "x")
-    _need_gpu(codebook, "codebook")
-    _need_gpu(index, "index")
+    _capi.need_gpu(codebook, "codebook")
+    _capi.need_gpu(index, "index")
     N, D, K = int(x.shape[0]), int(x.shape[1]), int(codebook.shape[0])
     if codebook.dtype != torch.float32 or not codebook.is_contiguous() or codebook.dim() != 2 or int(codebook.shape[1]) != D:
         raise ValueError("fdgs.compress.update: the codebook must be a contiguous float32 [K, %d] tensor" % D)
@@ -89,11 +78,10 @@ def update(x: torch.Tensor, index: torch.Tensor, codebook: torch.Tensor, *, weig
         if w is None or w.numel() != N:
             raise ValueError("fdgs.compress.update: weights must have %d elements" % N)
     counts = torch.empty((K,), dtype=torch.int32, device=x.device)
-    scratch = _scratch(N, K, x.device) if scratch is None else scratch
-    with torch.cuda.device(x.device):
-        rc = _capi.lib.fdgs_kmeans_update(N, K, D, _capi._ptr(x), _capi._ptr(index), _capi._ptr(w), _capi._ptr(codebook), _capi._ptr(counts),
-                                          scratch.data_ptr(), _capi.current_stream_handle(x.device))
-    _capi._check(rc, "fdgs_kmeans_update")
+    if scratch is None:
+        scratch = _capi.scratch(_capi.lib.fdgs_kmeans_scratch_bytes(N, K), x.device, floor=1)
+    _capi.call("fdgs_kmeans_update", x.device, N, K, D, _capi._ptr(x), _capi._ptr(index), _capi._ptr(w), _capi._ptr(codebook),
+               _capi._ptr(counts), scratch.data_ptr())
     return counts
 
 
@@ -114,7 +102,7 @@ def kmeans(x: torch.Tensor, K: int, *, iters: int = 10, weights: Optional[torch.
     else:
         perm = torch.randperm(N, generator=torch.Generator().manual_seed(int(seed)))
         codebook = x[perm[torch.arange(K) % N].to(x.device)].contiguous()
-    scratch = _scratch(N, K, x.device)
+    scratch = _capi.scratch(_capi.lib.fdgs_kmeans_scratch_bytes(N, K), x.device, floor=1)
     for _ in range(int(iters)):
         index, _d = assign(x, codebook, scratch=scratch)
         update(x, index, codebook, weights=weights, scratch=scratch)
@@ -143,10 +131,7 @@ def quantize_columns(x: torch.Tensor, lo, inv, bits: int) -> torch.Tensor:
     lo_d = torch.as_tensor(np.asarray(lo, np.float32).reshape(C)).to(x.device)
     inv_d = torch.as_tensor(np.asarray(inv, np.float32).reshape(C)).to(x.device)
     q = torch.empty((P, C), dtype=torch.uint8 if bits == 8 else torch.int16, device=x.device)
-    with torch.cuda.device(x.device):
-        rc = _capi.lib.fdgs_quantize_columns(P, C, _capi._ptr(x), lo_d.data_ptr(), inv_d.data_ptr(), (1 << bits) - 1, _capi._ptr(q),
-                                             _capi.current_stream_handle(x.device))
-    _capi._check(rc, "fdgs_quantize_columns")
+    _capi.call("fdgs_quantize_columns", x.device, P, C, _capi._ptr(x), lo_d.data_ptr(), inv_d.data_ptr(), (1 << bits) - 1, _capi._ptr(q))
     return q
 
 
@@ -154,7 +139,7 @@ def decode_into(out: torch.Tensor, P: int, C: int, bits: int, q: Optional[torch.
                 rows: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None) -> None:
     """Fills ``out`` (contiguous float32, P * (C + D) elements, GPU) row by row: the C columns of ``q`` [P, C] -- uint8 / 16-bit /
     float32 by ``bits``, dequantised as ``lo + q * step`` -- then row ``index[p]`` (int32; None: row p) of ``rows`` [K, D]."""
-    _need_gpu(out, "out")
+    _capi.need_gpu(out, "out")
     D = 0 if rows is None else int(rows.shape[1])
     if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != int(P) * (int(C) + D):
         raise ValueError("fdgs.compress.decode_into: out must be a contiguous float32 tensor of %d elements" % (int(P) * (int(C) + D)))
@@ -170,11 +155,8 @@ def decode_into(out: torch.Tensor, P: int, C: int, bits: int, q: Optional[torch.
     if int(bits) != 32 and int(C) > 0:
         lo_d = torch.as_tensor(np.asarray(lo, np.float32).reshape(int(C))).to(dev)
         step_d = torch.as_tensor(np.asarray(step, np.float32).reshape(int(C))).to(dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_compact_decode(int(P), int(C), int(bits), _capi._ptr(q), _capi._ptr(lo_d), _capi._ptr(step_d), D, _capi._ptr(rows),
-                                           _capi._ptr(index), 0 if rows is None else int(rows.shape[0]), out.data_ptr(),
-                                           _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_compact_decode")
+    _capi.call("fdgs_compact_decode", dev, int(P), int(C), int(bits), _capi._ptr(q), _capi._ptr(lo_d), _capi._ptr(step_d), D, _capi._ptr(rows),
+               _capi._ptr(index), 0 if rows is None else int(rows.shape[0]), out.data_ptr())
 
 
 @dataclass
@@ -200,7 +182,7 @@ def compress(model, *, codebook_size: Optional[int] = 4096, iters: int = 10, wei
     ``init``) plus uint16 indices; ``codebook_size = None`` keeps the rows as float32.  Every other segment is stored with
     ``bits[name]`` in {8, 16, 32} over its columns' [min, max] (quaternions: normalised, over [-1, 1]); 32 keeps the float32 values bit
     for bit.  ``bits`` overrides ``DEFAULT_BITS`` per name."""
-    _need_gpu(model.flat, "model.flat")
+    _capi.need_gpu(model.flat, "model.flat")
     P, M = int(model.P), int(model.M)
     if P < 1:
         raise ValueError("fdgs.compress: the model has no Gaussians")

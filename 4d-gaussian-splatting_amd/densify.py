@@ -18,10 +18,6 @@ from . import _capi
 CLONE, SPLIT, PRUNE, PRUNE_CHILD = 1, 2, 4, 8
 
 
-def _p(t):
-    return None if t is None else t.data_ptr()
-
-
 @torch.no_grad()
 def densify_and_prune(model, optimizer, stats, max_grad: float, min_opacity: float, extent: float,
                       max_screen_size: Optional[float], max_grad_t: Optional[float] = None, prune_only: bool = False,
@@ -35,14 +31,11 @@ def densify_and_prune(model, optimizer, stats, max_grad: float, min_opacity: flo
     if not model.flat.is_cuda:
         raise RuntimeError("fdgs: densify_and_prune needs the model on the GPU; there is no CPU path")
     P = model.P
-    st = _capi.current_stream_handle(dev)
+    _p = _capi._ptr
     flags = torch.empty(P, dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_densify_classify(P, _p(stats.xyz_gradient_accum), _p(stats.denom), _p(model._scaling), _p(model._opacity),
-                                             _p(stats.max_radii2D), float(max_grad), float(min_opacity), float(extent),
-                                             float(max_screen_size) if max_screen_size else -1.0, float(percent_dense), int(N),
-                                             int(bool(prune_only)), _p(flags), st)
-    _capi._check(rc, "fdgs_densify_classify")
+    _capi.call("fdgs_densify_classify", dev, P, _p(stats.xyz_gradient_accum), _p(stats.denom), _p(model._scaling), _p(model._opacity),
+               _p(stats.max_radii2D), float(max_grad), float(min_opacity), float(extent), float(max_screen_size) if max_screen_size else -1.0,
+               float(percent_dense), int(N), int(bool(prune_only)), _p(flags))
 
     # ---- index plan (host plumbing: three nonzero() calls) ----
     pruned = (flags & PRUNE) != 0
@@ -82,20 +75,15 @@ def densify_and_prune(model, optimizer, stats, max_grad: float, min_opacity: flo
     new_flat, new_m, new_v = (torch.empty(P_new * per, **f) for _ in range(3))
     rows_arr = (C.c_int32 * len(model.row_floats()))(*model.row_floats())
     old_flat, old = model.flat, {n: model.params[n] for n in model.NAMES}
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_densify_gather(len(model.row_floats()), rows_arr, P, P_new, _p(src), _p(kind), _p(old_flat),
-                                           _p(optimizer.exp_avg), _p(optimizer.exp_avg_sq), _p(new_flat), _p(new_m), _p(new_v), st)
-    _capi._check(rc, "fdgs_densify_gather")
+    _capi.call("fdgs_densify_gather", dev, len(model.row_floats()), rows_arr, P, P_new, _p(src), _p(kind), _p(old_flat), _p(optimizer.exp_avg),
+               _p(optimizer.exp_avg_sq), _p(new_flat), _p(new_m), _p(new_v))
     model._bind(new_flat, torch.zeros(P_new * per, **f), P_new)
     if n_child:
         first = n_orig + n_clone
         parent32 = child_parent.to(torch.int32).contiguous()
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_densify_split(
-                n_child, int(N), int(model.rot_4d), int(model.gaussian_dim), _p(parent32), _p(child_samples), _p(child_samples_t),
-                _p(old["_xyz"]), _p(old["_t"]), _p(old["_scaling"]), _p(old["_scaling_t"]), _p(old["_rotation"]), _p(old["_rotation_r"]),
-                _p(model._xyz[first:]), _p(model._t[first:]), _p(model._scaling[first:]), _p(model._scaling_t[first:]), st)
-        _capi._check(rc, "fdgs_densify_split")
+        _capi.call("fdgs_densify_split", dev, n_child, int(N), int(model.rot_4d), int(model.gaussian_dim), _p(parent32), _p(child_samples),
+                   _p(child_samples_t), _p(old["_xyz"]), _p(old["_t"]), _p(old["_scaling"]), _p(old["_scaling_t"]), _p(old["_rotation"]),
+                   _p(old["_rotation_r"]), _p(model._xyz[first:]), _p(model._t[first:]), _p(model._scaling[first:]), _p(model._scaling_t[first:]))
     optimizer.rebind(new_m, new_v)
 
     # ---- statistics: restart from zero after a densification (densification_postfix), masked after prune_only ----

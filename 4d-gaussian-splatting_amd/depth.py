@@ -27,8 +27,7 @@ def _plane(t, name, like=None):
     """A [1, H, W] (or [H, W]) image as a detached contiguous float32 GPU tensor; None stays None."""
     if t is None:
         return None
-    if not t.is_cuda:
-        raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+    _capi.need_gpu(t, name)
     if like is not None and (t.numel() != like.numel() or t.shape[-2:] != like.shape[-2:]):
         raise ValueError("fdgs: '%s' must have the depth's [1, H, W] shape %s; got %s" % (name, tuple(like.shape), tuple(t.shape)))
     return t.detach().contiguous().float()
@@ -60,10 +59,8 @@ class _DepthLoss(torch.autograd.Function):
         grads = _capi.FdgsDepthGrads(_capi._ptr(g_d), _capi._ptr(g_a), None, 1.0, 0) if (need_d or need_a) else None
         parts = torch.empty(_capi.lib.fdgs_depth_loss_num_partials(din.H, din.W), dtype=torch.float64, device=dev)
         out = torch.empty(4, dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_depth_loss(C.byref(din), p.data_ptr(), MODES[mode], None if grads is None else C.byref(grads),
-                                           parts.data_ptr(), out.data_ptr(), _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_depth_loss")
+        _capi.call("fdgs_depth_loss", dev, C.byref(din), p.data_ptr(), MODES[mode], None if grads is None else C.byref(grads),
+                   parts.data_ptr(), out.data_ptr())
         ctx.save_for_backward(g_d, g_a)
         ctx.shapes = (depth.shape, None if alpha is None else alpha.shape)
         ctx.dtypes = (depth.dtype, None if alpha is None else alpha.dtype)
@@ -110,10 +107,7 @@ class _DepthNormals(torch.autograd.Function):
         vm = _vm(viewmatrix, dev)
         normals = torch.empty((3, din.H, din.W), dtype=torch.float32, device=dev)
         valid = torch.empty((1, din.H, din.W), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_depth_normals(C.byref(din), fx, fy, cx, cy, _capi._ptr(vm), normals.data_ptr(), valid.data_ptr(),
-                                              _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_depth_normals")
+        _capi.call("fdgs_depth_normals", dev, C.byref(din), fx, fy, cx, cy, _capi._ptr(vm), normals.data_ptr(), valid.data_ptr())
         ctx.save_for_backward(d, a, m, vm)
         ctx.intr, ctx.alpha_min = (fx, fy, cx, cy), float(alpha_min)
         ctx.shapes = (depth.shape, None if alpha is None else alpha.shape)
@@ -133,10 +127,7 @@ class _DepthNormals(torch.autograd.Function):
         g_d = torch.empty_like(d) if need_d else None
         g_a = torch.empty_like(a) if need_a else None
         grads = _capi.FdgsDepthGrads(_capi._ptr(g_d), _capi._ptr(g_a), None, 1.0, 0)
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_depth_normals_backward(C.byref(din), *ctx.intr, _capi._ptr(vm), g.data_ptr(), C.byref(grads),
-                                                       _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_depth_normals_backward")
+        _capi.call("fdgs_depth_normals_backward", dev, C.byref(din), *ctx.intr, _capi._ptr(vm), g.data_ptr(), C.byref(grads))
         gd = None if g_d is None else g_d.view(ctx.shapes[0]).to(ctx.dtypes[0])
         ga = None if g_a is None else g_a.view(ctx.shapes[1]).to(ctx.dtypes[1])
         return gd, ga, None, None, None, None

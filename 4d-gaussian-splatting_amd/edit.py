@@ -231,15 +231,10 @@ def _arguments(sim, gaussian_dim, rot_4d, M, inputs, outputs):
     return a_in, _capi.FdgsTransformOut(*[p(t) for t in outputs])
 
 
-def _launch(a_in, a_out, dev):
-    """fdgs_model_transform on the current stream of ``dev``."""
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_model_transform(C.byref(a_in), C.byref(a_out), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_model_transform")
-
-
 def _enqueue(sim, gaussian_dim, rot_4d, M, inputs, outputs):
-    _launch(*_arguments(sim, gaussian_dim, rot_4d, M, inputs, outputs), inputs[0].device)
+    """fdgs_model_transform on the current stream of the inputs' device."""
+    a_in, a_out = _arguments(sim, gaussian_dim, rot_4d, M, inputs, outputs)
+    _capi.call("fdgs_model_transform", inputs[0].device, C.byref(a_in), C.byref(a_out))
 
 
 def transform(model, sim, *, inplace=False):
@@ -272,8 +267,7 @@ def transform(model, sim, *, inplace=False):
     else:
         feats = _features_of(model)
     xyz = model._xyz
-    if not xyz.is_cuda:
-        raise RuntimeError("fdgs: the model must live on the GPU (got %s); there is no CPU path" % xyz.device)
+    _capi.need_gpu(xyz, "_xyz", what="the model")
     P, M = int(xyz.shape[0]), int(feats.shape[1])
     if M not in SH_M:
         raise ValueError("transform: %d SH coefficients per Gaussian; supported: %s" % (M, (SH_M,)))

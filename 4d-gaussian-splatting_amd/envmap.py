@@ -58,11 +58,8 @@ def composite_(colour, T, env_map, cam, radius: float = ENV_RADIUS, out=None):
     H, W, dev = int(colour.shape[-2]), int(colour.shape[-1]), colour.device
     out = colour if out is None else out
     vm, cp, fx, fy, cx, cy = _cam_args(cam, dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_env_composite(H, W, vm.data_ptr(), cp.data_ptr(), fx, fy, cx, cy, env_map.data_ptr(), int(env_map.shape[1]),
-                                          int(env_map.shape[2]), float(radius), T.data_ptr(), colour.data_ptr(), out.data_ptr(),
-                                          _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_env_composite")
+    _capi.call("fdgs_env_composite", dev, H, W, vm.data_ptr(), cp.data_ptr(), fx, fy, cx, cy, env_map.data_ptr(), int(env_map.shape[1]),
+               int(env_map.shape[2]), float(radius), T.data_ptr(), colour.data_ptr(), out.data_ptr())
     return out
 
 
@@ -73,13 +70,10 @@ def composite_backward(T, g_colour, env_map, cam, g_alpha=None, accumulate_alpha
     _check_env(env_map)
     H, W, dev = int(g_colour.shape[-2]), int(g_colour.shape[-1]), g_colour.device
     vm, cp, fx, fy, cx, cy = _cam_args(cam, dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_env_composite_backward(H, W, vm.data_ptr(), cp.data_ptr(), fx, fy, cx, cy, env_map.data_ptr(),
-                                                   int(env_map.shape[1]), int(env_map.shape[2]), float(radius), T.data_ptr(),
-                                                   g_colour.data_ptr(), None if g_alpha is None else g_alpha.data_ptr(),
-                                                   int(bool(accumulate_alpha)), None if g_env is None else g_env.data_ptr(),
-                                                   int(bool(accumulate_env)), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_env_composite_backward")
+    _capi.call("fdgs_env_composite_backward", dev, H, W, vm.data_ptr(), cp.data_ptr(), fx, fy, cx, cy, env_map.data_ptr(),
+               int(env_map.shape[1]), int(env_map.shape[2]), float(radius), T.data_ptr(), g_colour.data_ptr(),
+               None if g_alpha is None else g_alpha.data_ptr(), int(bool(accumulate_alpha)), None if g_env is None else g_env.data_ptr(),
+               int(bool(accumulate_env)))
 
 
 class _EnvComposite(torch.autograd.Function):
@@ -136,7 +130,5 @@ class EnvMapAdam:
         self.step_count += 1
         n = p.numel()
         seg = (_capi.FdgsAdamSegment * 1)(_capi.FdgsAdamSegment(0, n, self.lr, self.lr, 0, 0))
-        with torch.cuda.device(p.device):
-            rc = _capi.lib.fdgs_adam_step(p.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n, seg, 1,
-                                          self.betas[0], self.betas[1], self.eps, self.step_count, _capi.current_stream_handle(p.device))
-        _capi._check(rc, "fdgs_adam_step")
+        _capi.call("fdgs_adam_step", p.device, p.data_ptr(), self.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), n, seg, 1,
+                   self.betas[0], self.betas[1], self.eps, self.step_count)

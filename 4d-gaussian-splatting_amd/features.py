@@ -50,8 +50,8 @@ def blend_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int, featu
     constants: this call is not recorded by autograd (``render_features`` is)."""
     named = [("geom", geom), ("binb", binb), ("img", img), ("features", features), ("out", out)]
     for name, t in named:   # the device check comes first: nothing here runs on the CPU (an empty model leaves scratch buffers out)
-        if t is not None and not t.is_cuda and (t.numel() > 0 or name in ("features", "out")):
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        if t is not None and (t.numel() > 0 or name in ("features", "out")):
+            _capi.need_gpu(t, name)
     features = as_feature_matrix(features.detach(), P)
     Cn = int(features.shape[1])
     _check_f32(features, "features", (P, Cn))
@@ -64,9 +64,7 @@ def blend_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int, featu
         _check_f32(out, "out", (Cn, H, W))
     cin = _capi.FdgsFeatureIn(int(P), int(W), int(H), Cn, _capi._ptr(geom), _capi._ptr(binb), _capi._ptr(img), int(num_rendered),
                               features.data_ptr() if P > 0 else out.data_ptr())   # (P == 0: no row is read; the library wants a pointer)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_feature_blend(C.byref(cin), out.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_feature_blend")
+    _capi.call("fdgs_feature_blend", dev, C.byref(cin), out.data_ptr())
     return out
 
 
@@ -76,8 +74,8 @@ def blend_backward_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: i
     Geometry is held constant: this is the whole gradient of a feature image, and it reaches the features only."""
     named = [("geom", geom), ("binb", binb), ("img", img), ("dL_dout", dL_dout), ("d_features", d_features)]
     for name, t in named:
-        if t is not None and not t.is_cuda and (t.numel() > 0 or name in ("dL_dout", "d_features")):
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        if t is not None and (t.numel() > 0 or name in ("dL_dout", "d_features")):
+            _capi.need_gpu(t, name)
     if d_features.dim() != 2 or int(d_features.shape[0]) != int(P):
         raise ValueError("fdgs.features: d_features must be [P,C] with P = %d, got %s" % (P, tuple(d_features.shape)))
     Cn = int(d_features.shape[1])
@@ -88,9 +86,7 @@ def blend_backward_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: i
     if P == 0:
         return d_features   # an empty model: nothing to add to
     cin = _capi.FdgsFeatureIn(int(P), int(W), int(H), Cn, _capi._ptr(geom), _capi._ptr(binb), _capi._ptr(img), int(num_rendered), None)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_feature_blend_backward(C.byref(cin), dL_dout.data_ptr(), d_features.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_feature_blend_backward")
+    _capi.call("fdgs_feature_blend_backward", dev, C.byref(cin), dL_dout.data_ptr(), d_features.data_ptr())
     return d_features
 
 
@@ -125,8 +121,7 @@ def render_features(camera, model, pipe, features: torch.Tensor, *, bg_color: Op
     from .importance import _forward
     P = int(model.get_xyz.shape[0])
     dev = model.get_xyz.device
-    if not features.is_cuda:
-        raise RuntimeError("fdgs: tensor 'features' must live on the GPU (got %s); there is no CPU path" % (features.device,))
+    _capi.need_gpu(features, "features")
     F = as_feature_matrix(features, P)
     if F.dtype != torch.float32:
         raise ValueError("fdgs.features: features must be float32, got %s" % (F.dtype,))

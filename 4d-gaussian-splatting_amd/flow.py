@@ -42,17 +42,14 @@ class _GaussianFlow(torch.autograd.Function):
     def forward(ctx, means3D, ts, scales, scales_t, rotations, rotations_r, cam, cam_to, rot_4d, gaussian_dim, raw, scaling_modifier):
         given = (means3D, ts, scales, scales_t, rotations, rotations_r)
         names = ("means3D", "ts", "scales", "scales_t", "rotations", "rotations_r")
-        if not means3D.is_cuda:
-            raise RuntimeError("fdgs: tensor 'means3D' must live on the GPU (got %s); there is no CPU path" % means3D.device)
+        _capi.need_gpu(means3D, "means3D")
         # without rot_4d the kernels read the mean only
         tensors = [_capi._dev_f32(t.detach(), n) if (t is not None and (rot_4d or n == "means3D")) else None for t, n in zip(given, names)]
         dev = means3D.device
         P = int(means3D.shape[0])
         flows = torch.empty((P, 2), dtype=torch.float32, device=dev)
         a, keep = _flow_in(cam, cam_to, tensors, rot_4d, gaussian_dim, raw, scaling_modifier)
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_gaussian_flow_forward(C.byref(a), flows.data_ptr(), _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_gaussian_flow_forward")
+        _capi.call("fdgs_gaussian_flow_forward", dev, C.byref(a), flows.data_ptr())
         del keep
         ctx.cams, ctx.settings = (cam, cam_to), (rot_4d, gaussian_dim, raw, scaling_modifier)
         ctx.shapes = [None if t is None else t.shape for t in given]
@@ -73,9 +70,7 @@ class _GaussianFlow(torch.autograd.Function):
             g_in = _capi._dev_f32(dL_dflows, "dL_dflows")
             a, keep = _flow_in(ctx.cams[0], ctx.cams[1], tensors, rot_4d, gaussian_dim, raw, scaling_modifier)
             out = _capi.FdgsFlowGrads(*[_capi._ptr(g) for g in grads])
-            with torch.cuda.device(dev):
-                rc = _capi.lib.fdgs_gaussian_flow_backward(C.byref(a), g_in.data_ptr(), 1.0, C.byref(out), _capi.current_stream_handle(dev))
-            _capi._check(rc, "fdgs_gaussian_flow_backward")
+            _capi.call("fdgs_gaussian_flow_backward", dev, C.byref(a), g_in.data_ptr(), 1.0, C.byref(out))
             del keep
         shaped = [None if g is None else g.reshape(s) for g, s in zip(grads, ctx.shapes)]
         return tuple(shaped) + (None,) * 6

@@ -70,12 +70,8 @@ def decode_frames(frames_u8: torch.Tensor, index: torch.Tensor, out: torch.Tenso
         if C != 4:
             raise ValueError("fdgs.frames: mask_out needs RGBA frames (C = 4), got C = %d" % C)
         mask_stride = strided(mask_out, "mask_out", 1)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_frames_decode(frames_u8.data_ptr(), N, H, W, C, index.data_ptr(), B, out.data_ptr(), out_stride,
-                                          None if mask_out is None else mask_out.data_ptr(), mask_stride, _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_frames_decode")
+    _capi.call("fdgs_frames_decode", dev, frames_u8.data_ptr(), N, H, W, C, index.data_ptr(), B, out.data_ptr(), out_stride,
+               None if mask_out is None else mask_out.data_ptr(), mask_stride, arg_error=ValueError)
     return out
 
 
@@ -390,12 +386,8 @@ def encode_frames(images: torch.Tensor, index: torch.Tensor, frames_u8: torch.Te
         alphas = alphas.detach() if isinstance(alphas, torch.Tensor) else alphas
         astride = _batch_stride(alphas, "alphas", B, 1, H, W, frames_u8.device)
     dev = frames_u8.device
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_frames_encode(images.data_ptr(), stride, None if alphas is None else alphas.data_ptr(), astride, B, H, W, C,
-                                          frames_u8.data_ptr(), N, index.data_ptr(), _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_frames_encode")
+    _capi.call("fdgs_frames_encode", dev, images.data_ptr(), stride, None if alphas is None else alphas.data_ptr(), astride, B, H, W, C,
+               frames_u8.data_ptr(), N, index.data_ptr(), arg_error=ValueError)
     return frames_u8
 
 
@@ -404,7 +396,7 @@ def gray_scratch(B: int, H: int, W: int, device) -> torch.Tensor:
     nbytes = _capi.lib.fdgs_frames_encode_gray_scratch_bytes(int(B), int(H), int(W))
     if nbytes < 0:
         raise ValueError("fdgs.frames: invalid plane shape %s" % ((B, H, W),))
-    return torch.empty(nbytes // 4, dtype=torch.float32, device=device)
+    return _capi.scratch(nbytes, device).view(torch.float32)
 
 
 def encode_gray(planes: torch.Tensor, index: torch.Tensor, frames_u8: torch.Tensor, scratch: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -425,12 +417,8 @@ def encode_gray(planes: torch.Tensor, index: torch.Tensor, frames_u8: torch.Tens
         scratch = gray_scratch(B, H, W, dev)
     elif scratch.device != dev or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
         raise ValueError("fdgs.frames: scratch must be a contiguous tensor of at least %d bytes on %s" % (need, dev))
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_frames_encode_gray(planes.data_ptr(), stride, B, H, W, frames_u8.data_ptr(), N, index.data_ptr(),
-                                               scratch.data_ptr(), _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_frames_encode_gray")
+    _capi.call("fdgs_frames_encode_gray", dev, planes.data_ptr(), stride, B, H, W, frames_u8.data_ptr(), N, index.data_ptr(), scratch.data_ptr(),
+               arg_error=ValueError)
     return frames_u8
 
 

@@ -60,7 +60,7 @@ class _Scratch:
             if t is not None and t.numel() >= int(nbytes):
                 return t.data_ptr()
         try:
-            t = torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=self.device)
+            t = _capi.scratch(nbytes, self.device, floor=1)
         except Exception:  # out of memory: report NULL to the C side, which returns FDGS_ERR_ALLOC
             return None
         self.buf[int(which)] = t
@@ -161,11 +161,10 @@ class _NativeRasterizer:
                                    int(preprocessed["tile_cull"] if preprocessed is not None else bool(tile_cull)), int(bool(lazy)),
                                    int(bool(sparse_lists)), colour_stream.cuda_stream if colour_stream is not None else None)
         R = C.c_int32(0)
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_rasterize_forward(C.byref(scene), C.byref(out), scratch.callback, None,
-                                                  _capi.current_stream_handle(dev), C.byref(R))
-        geom, binb, img = scratch.release()
-        _capi._check(rc, "fdgs_rasterize_forward")
+        try:
+            _capi.rasterize_forward(dev, scene, out, scratch.callback, R)
+        finally:
+            geom, binb, img = scratch.release()
         del keep
         return (int(R.value), out_color, out_flow, out_depth, out_T, radii, geom, binb, img, covs_com, out_means3D)
 
@@ -195,9 +194,7 @@ class _NativeRasterizer:
         users = (C.c_void_p * B)(*[v + 1 for v in range(B)])
         # one callback for the batch: the user word says which view's buffer is asked for
         cb = _capi.ALLOC_FN(lambda user, which, nbytes: handles[int(user) - 1]["scratch"]._alloc(None, which, nbytes))
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_preprocess_batch(B, scenes, outs, cb, users, _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_preprocess_batch")
+        _capi.call("fdgs_preprocess_batch", dev, B, scenes, outs, cb, users)
         return handles
 
     def sh_backward_batch(self, pendings):
@@ -207,9 +204,18 @@ class _NativeRasterizer:
         scenes = (C.POINTER(_capi.FdgsScene) * B)(*[C.pointer(p["scene"]) for p in pendings])
         ins = (C.POINTER(_capi.FdgsBackwardIn) * B)(*[C.pointer(p["bin"]) for p in pendings])
         outs = (C.POINTER(_capi.FdgsBackwardOut) * B)(*[C.pointer(p["bout"]) for p in pendings])
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_sh_backward_batch(B, scenes, ins, outs, _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_sh_backward_batch")
+        _capi.call("fdgs_sh_backward_batch", dev, B, scenes, ins, outs)
+
+    @staticmethod
+    def _backward_call(dev, scene, bin_, bout, grad_accum, guard=True):
+        """fdgs_rasterize_backward.  A failed call may have left partial sums behind: ``grad_accum`` -- the caller's persistent accumulator,
+        or None -- gets its "all zero on entry" invariant back before the error goes up."""
+        try:
+            _capi.call("fdgs_rasterize_backward", dev, C.byref(scene), C.byref(bin_), C.byref(bout), guard=guard)
+        except Exception:
+            if grad_accum is not None:
+                grad_accum.zero_()
+            raise
 
     def backward_begin(self, *args, **kw):
         """The blend backward of one view only (fdgs_backward_out.stage_mask = 5); same arguments as
@@ -222,12 +228,7 @@ class _NativeRasterizer:
         binding's 12-tuple."""
         dev = pending["dev"]
         pending["bout"].stage_mask = 2
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_rasterize_backward(C.byref(pending["scene"]), C.byref(pending["bin"]), C.byref(pending["bout"]),
-                                                   _capi.current_stream_handle(dev))
-        if rc != 0 and pending["clean"]:
-            pending["grad_accum"].zero_()
-        _capi._check(rc, "fdgs_rasterize_backward")
+        self._backward_call(dev, pending["scene"], pending["bin"], pending["bout"], pending["grad_accum"])
         g = pending["g"]
         return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
                 g["dL_dflows"], g["dL_dts"], g["dL_dscales"], g["dL_dscales_t"], g["dL_drotations"], g["dL_drotations_r"])
@@ -252,12 +253,10 @@ class _NativeRasterizer:
                 t = torch.empty(shape, dtype=torch.float32, device=dev)
             g[name] = t
         nbytes = int(_capi.lib.fdgs_camera_backward_scratch(scene.P))
-        scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        scratch = _capi.scratch(nbytes, dev)
         cg = _capi.FdgsCameraGrads(*[_capi._ptr(g[n]) for n in names], float(scale), int(bool(accumulate)))
-        with torch.cuda.device(dev):
-            rc = _capi.lib.fdgs_camera_backward(C.byref(scene), C.byref(pending["bin"]), _capi._ptr(pending["grad_accum"]), C.byref(cg),
-                                                scratch.data_ptr(), nbytes, _capi.current_stream_handle(dev))
-        _capi._check(rc, "fdgs_camera_backward")
+        _capi.call("fdgs_camera_backward", dev, C.byref(scene), C.byref(pending["bin"]), _capi._ptr(pending["grad_accum"]), C.byref(cg),
+                   scratch.data_ptr(), nbytes)
         return g
 
     def rasterize_gaussians_backward(self, bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales,
@@ -342,12 +341,8 @@ class _NativeRasterizer:
             if sh_stage is None or grad_accum is None:
                 raise RuntimeError("fdgs: backward_begin needs sh_stage and a grad_accum of the view's own")
             bout.stage_mask = 5   # blend backward only; the SH backward is left to sh_backward_batch
-            with torch.cuda.device(dev):
-                rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout), _capi.current_stream_handle(dev))
-            if rc != 0:
-                grad_accum.zero_()
-            _capi._check(rc, "fdgs_rasterize_backward")
-            return {"scene": scene, "keep": keep, "bin": bin_, "bout": bout, "g": g, "dev": dev, "clean": clean, "grad_accum": grad_accum,
+            self._backward_call(dev, scene, bin_, bout, grad_accum)
+            return {"scene": scene, "keep": keep, "bin": bin_, "bout": bout, "g": g, "dev": dev, "grad_accum": grad_accum,
                     "alive": (gin, radii_c, om_c, geomBuffer, binningBuffer, imageBuffer, sh_stage)}
         adam_keep = None
 
@@ -362,31 +357,23 @@ class _NativeRasterizer:
                                         float(ga["eps"]), int(ga["step"]))
             bout.adam = C.pointer(st)
             return (st, ga)
-        with torch.cuda.device(dev):
+        with torch.cuda.device(dev):   # one guard for the two halves of a split backward
             if after_sh is None and camera is None:
                 adam_keep = attach_adam()
-                rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
-                                                       _capi.current_stream_handle(dev))
+                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
             else:
                 bout.stage_mask = 1
-                rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
-                                                       _capi.current_stream_handle(dev))
-                if rc == 0:
-                    if after_sh is not None:
-                        after_sh()
-                    if camera is not None:
-                        camera["grads"] = self.camera_backward({"dev": dev, "scene": scene, "bin": bin_, "grad_accum": g["grad_accum"]},
-                                                               want=camera.get("want", (True, True, True, True)), scale=camera.get("scale", 1.0),
-                                                               out=camera.get("out"), accumulate=camera.get("accumulate", False))
-                    bout.stage_mask = 2
-                    adam_keep = attach_adam()
-                    rc = _capi.lib.fdgs_rasterize_backward(C.byref(scene), C.byref(bin_), C.byref(bout),
-                                                           _capi.current_stream_handle(dev))
+                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
+                if after_sh is not None:
+                    after_sh()
+                if camera is not None:
+                    camera["grads"] = self.camera_backward({"dev": dev, "scene": scene, "bin": bin_, "grad_accum": g["grad_accum"]},
+                                                           want=camera.get("want", (True, True, True, True)), scale=camera.get("scale", 1.0),
+                                                           out=camera.get("out"), accumulate=camera.get("accumulate", False))
+                bout.stage_mask = 2
+                adam_keep = attach_adam()
+                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
         del adam_keep
-        if rc != 0 and clean:
-            # a failed call may have left partial sums behind: restore the caller's "all zero on entry" invariant
-            grad_accum.zero_()
-        _capi._check(rc, "fdgs_rasterize_backward")
         del keep
         return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
                 g["dL_dflows"], g["dL_dts"], g["dL_dscales"], g["dL_dscales_t"], g["dL_drotations"],
@@ -403,10 +390,7 @@ class _NativeRasterizer:
         v = _capi._dev_f32(viewmatrix, "viewmatrix")
         p = _capi._dev_f32(projmatrix, "projmatrix")
         if P:
-            with torch.cuda.device(dev):
-                rc = _capi.lib.fdgs_mark_visible(P, m.data_ptr(), v.data_ptr(), _capi._ptr(p), present.data_ptr(),
-                                                 _capi.current_stream_handle(dev))
-            _capi._check(rc, "fdgs_mark_visible")
+            _capi.call("fdgs_mark_visible", dev, P, m.data_ptr(), v.data_ptr(), _capi._ptr(p), present.data_ptr())
         return present
 
 

@@ -124,7 +124,6 @@ class DensificationStats:
         radii = [r["radii"].contiguous() for r in results]
         grads = [r["viewspace_grad"].contiguous() for r in results]
         tmp = torch.empty((3, P), dtype=torch.float32, device=dev)   # count, pgrad | radii_max
-        st = _capi.current_stream_handle(dev)
         with torch.cuda.device(dev):
             # the kernel takes at most 16 views per call: larger per-rank batches go in groups, combined like the ranks are
             GROUP = 16
@@ -134,8 +133,7 @@ class DensificationStats:
                 rp = (C.c_void_p * n)(*[t.data_ptr() for t in rad])
                 gp = (C.c_void_p * n)(*[t.data_ptr() for t in grd])
                 dst = tmp if g0 == 0 else torch.empty_like(tmp)
-                rc = _capi.lib.fdgs_densify_stats_local(P, n, rp, gp, dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), st)
-                _capi._check(rc, "fdgs_densify_stats_local")
+                _capi.call("fdgs_densify_stats_local", dev, P, n, rp, gp, dst[0].data_ptr(), dst[1].data_ptr(), dst[2].data_ptr(), guard=False)
                 if g0 > 0:
                     tmp[:2] += dst[:2]
                     torch.maximum(tmp[2], dst[2], out=tmp[2])
@@ -144,11 +142,9 @@ class DensificationStats:
                 dist.all_reduce(tmp[:2], op=dist.ReduceOp.SUM)
                 dist.all_reduce(tmp[2], op=dist.ReduceOp.MAX)
             tg = None if t_grad is None else t_grad.contiguous()
-            rc = _capi.lib.fdgs_densify_stats_apply(P, tmp[0].data_ptr(), tmp[1].data_ptr(), tmp[2].data_ptr(),
-                                                    None if tg is None else tg.data_ptr(), float(global_batch),
-                                                    self.xyz_gradient_accum.data_ptr(), self.t_gradient_accum.data_ptr(),
-                                                    self.denom.data_ptr(), self.max_radii2D.data_ptr(), st)
-            _capi._check(rc, "fdgs_densify_stats_apply")
+            _capi.call("fdgs_densify_stats_apply", dev, P, tmp[0].data_ptr(), tmp[1].data_ptr(), tmp[2].data_ptr(),
+                       None if tg is None else tg.data_ptr(), float(global_batch), self.xyz_gradient_accum.data_ptr(),
+                       self.t_gradient_accum.data_ptr(), self.denom.data_ptr(), self.max_radii2D.data_ptr(), guard=False)
 
 
 def psnr(img: torch.Tensor, gt: torch.Tensor) -> torch.Tensor:

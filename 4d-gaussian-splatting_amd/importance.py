@@ -140,8 +140,7 @@ def contribution_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int
     for name, (t, dtype, n) in outs.items():
         if t is None:
             continue
-        if not t.is_cuda:
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        _capi.need_gpu(t, name)
         if t.dtype != dtype or t.numel() != n or not t.is_contiguous():
             raise RuntimeError("fdgs: %s must be a contiguous %s tensor with %d elements" % (name, dtype, n))
         if dev is None:
@@ -161,9 +160,7 @@ def contribution_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int
     cout = _capi.FdgsContributionOut(*ptrs)
     if P == 0 and ptrs[4] is None:
         return   # an empty model: nothing to accumulate into and no map to fill
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_contribution(C.byref(cin), C.byref(cout), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_contribution")
+    _capi.call("fdgs_contribution", dev, C.byref(cin), C.byref(cout))
 
 
 @torch.no_grad()
@@ -236,11 +233,8 @@ def prune_by_contribution(model, optimizer, stats: ContributionStats, *, keep_fr
     rows = model.row_floats()
     rows_arr = (C.c_int32 * len(rows))(*rows)
     old_flat = model.flat
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_densify_gather(len(rows), rows_arr, P, P_new, src.data_ptr(), kind.data_ptr(), old_flat.data_ptr(),
-                                           optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), new_flat.data_ptr(),
-                                           new_m.data_ptr(), new_v.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_densify_gather")
+    _capi.call("fdgs_densify_gather", dev, len(rows), rows_arr, P, P_new, src.data_ptr(), kind.data_ptr(), old_flat.data_ptr(),
+               optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), new_flat.data_ptr(), new_m.data_ptr(), new_v.data_ptr())
     model._bind(new_flat, torch.zeros(P_new * per, **f), P_new)
     optimizer.rebind(new_m, new_v)
     _follow(dens_stats, stats, sel)

@@ -15,10 +15,8 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     means = torch.zeros(P, dtype=torch.float32, device=dev)           # torch::full({P}, 0.0), spatial.cu:21
     if P == 0:
         return means
-    scratch = torch.empty(_capi.lib.fdgs_knn_scratch_bytes(P), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_dist2_knn3(P, pts.data_ptr(), means.data_ptr(), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_dist2_knn3")
+    scratch = _capi.scratch(_capi.lib.fdgs_knn_scratch_bytes(P), dev)
+    _capi.call("fdgs_dist2_knn3", dev, P, pts.data_ptr(), means.data_ptr(), scratch.data_ptr())
     return means
 
 
@@ -50,9 +48,7 @@ def knn(x: torch.Tensor, src: torch.Tensor, k: int, transpose: bool = False):
     dist2 = torch.empty((b, n, k), dtype=torch.float32, device=dev)
     if b == 0 or n == 0:
         return idx, dist2
-    scratch = torch.empty(_capi.lib.fdgs_knn_query_scratch_bytes(n, m), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_knn_query(b, n, m, k, xq.data_ptr(), sq.data_ptr() if m > 0 else None, idx.data_ptr(), dist2.data_ptr(),
-                                      scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_knn_query")
+    scratch = _capi.scratch(_capi.lib.fdgs_knn_query_scratch_bytes(n, m), dev)
+    _capi.call("fdgs_knn_query", dev, b, n, m, k, xq.data_ptr(), sq.data_ptr() if m > 0 else None, idx.data_ptr(), dist2.data_ptr(),
+               scratch.data_ptr())
     return idx, dist2

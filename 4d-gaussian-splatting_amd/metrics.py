@@ -26,7 +26,7 @@ def _scratch(dev, Cn, H, W):
     key = (dev, torch.cuda.current_stream(dev).cuda_stream)
     buf = _SCRATCH.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = _SCRATCH[key] = torch.empty(max(nbytes, 256), dtype=torch.uint8, device=dev)
+        buf = _SCRATCH[key] = _capi.scratch(nbytes, dev, floor=256)
     return buf
 
 
@@ -58,13 +58,8 @@ def image_metrics(img: torch.Tensor, gt: torch.Tensor, clamp: bool = True, msssi
     elif out.dtype != torch.float32 or out.numel() != 4 or not out.is_contiguous() or out.device != dev:
         raise ValueError("fdgs.metrics: out must be a contiguous float32 tensor of 4 elements on %s" % dev)
     flags = (CLAMP if clamp else 0) | (0 if msssim else NO_MSSSIM)
-    with torch.cuda.device(dev):
-        scratch = _scratch(dev, Cn, H, W)
-        rc = _capi.lib.fdgs_eval_metrics(a.data_ptr(), b.data_ptr(), Cn, H, W, flags, scratch.data_ptr(), out.data_ptr(),
-                                         _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_eval_metrics")
+    scratch = _scratch(dev, Cn, H, W)
+    _capi.call("fdgs_eval_metrics", dev, a.data_ptr(), b.data_ptr(), Cn, H, W, flags, scratch.data_ptr(), out.data_ptr(), arg_error=ValueError)
     return out
 
 

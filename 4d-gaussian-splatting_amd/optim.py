@@ -406,8 +406,5 @@ class Adam(torch.optim.Optimizer):
         n = p.numel()
         seg = (_capi.FdgsAdamSegment * 1)(_capi.FdgsAdamSegment(0, n, float(grp["lr"]), float(grp["lr"]), 0, 0))
         g = p.grad.contiguous()
-        with torch.cuda.device(p.device):
-            rc = _capi.lib.fdgs_adam_step(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), n, seg, 1,
-                                          float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), int(float(st["step"])),
-                                          _capi.current_stream_handle(p.device))
-        _capi._check(rc, "fdgs_adam_step")
+        _capi.call("fdgs_adam_step", p.device, p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(), n, seg, 1,
+                   float(grp["betas"][0]), float(grp["betas"][1]), float(grp["eps"]), int(float(st["step"])))

@@ -272,13 +272,11 @@ class StepPipeline:
             st.reg_idx, st.reg_d2 = knn(m._xyz.detach()[None], m._xyz.detach()[None], k)
             st.reg_vel = torch.empty((P, 3), dtype=torch.float32, device=self.dev)
             st.reg_losses = torch.empty(2, dtype=torch.float32, device=self.dev)
-            st.reg_scratch = torch.empty(_capi.lib.fdgs_rigid_motion_scratch_bytes(P, k), dtype=torch.uint8, device=self.dev)
+            st.reg_scratch = _capi.scratch(_capi.lib.fdgs_rigid_motion_scratch_bytes(P, k), self.dev)
             st.reg_w = torch.tensor([self.lam_rigid, self.lam_motion], dtype=torch.float32, device=self.dev)
-            rc = _capi.lib.fdgs_rigid_motion_forward(P, k, m._scaling.data_ptr(), m._scaling_t.data_ptr(), m._rotation.data_ptr(),
-                                                     m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(),
-                                                     st.reg_vel.data_ptr(), st.reg_losses.data_ptr(), st.reg_scratch.data_ptr(),
-                                                     _capi.current_stream_handle(self.dev))
-        _capi._check(rc, "fdgs_rigid_motion_forward")
+            _capi.call("fdgs_rigid_motion_forward", self.dev, P, k, m._scaling.data_ptr(), m._scaling_t.data_ptr(), m._rotation.data_ptr(),
+                       m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(), st.reg_vel.data_ptr(),
+                       st.reg_losses.data_ptr(), st.reg_scratch.data_ptr(), guard=False)   # (the stream block has made the device current)
         self.last_terms["rigid"], self.last_terms["motion"] = st.reg_losses[0], st.reg_losses[1]
 
     def _terms_backward(self, st):
@@ -289,12 +287,10 @@ class StepPipeline:
             return
         m, g = self.model, self.sink
         with torch.cuda.stream(self.sB):
-            rc = _capi.lib.fdgs_rigid_motion_backward(m.P, self.rigid_k, m._scaling.data_ptr(), m._scaling_t.data_ptr(), m._rotation.data_ptr(),
-                                                      m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(),
-                                                      st.reg_vel.data_ptr(), st.reg_w.data_ptr(), 1.0, g["dL_dscales"].data_ptr(),
-                                                      g["dL_dscales_t"].data_ptr(), g["dL_drotations"].data_ptr(), g["dL_drotations_r"].data_ptr(),
-                                                      st.reg_scratch.data_ptr(), _capi.current_stream_handle(self.dev))
-        _capi._check(rc, "fdgs_rigid_motion_backward")
+            _capi.call("fdgs_rigid_motion_backward", self.dev, m.P, self.rigid_k, m._scaling.data_ptr(), m._scaling_t.data_ptr(),
+                       m._rotation.data_ptr(), m._rotation_r.data_ptr(), m._t.data_ptr(), st.reg_idx.data_ptr(), st.reg_d2.data_ptr(),
+                       st.reg_vel.data_ptr(), st.reg_w.data_ptr(), 1.0, g["dL_dscales"].data_ptr(), g["dL_dscales_t"].data_ptr(),
+                       g["dL_drotations"].data_ptr(), g["dL_drotations_r"].data_ptr(), st.reg_scratch.data_ptr(), guard=False)
         st.reg_done = True
 
     def _opa_grad(self, st, b, T):
@@ -309,9 +305,8 @@ class StepPipeline:
             self.last_terms["opa_mask"] = st.opa_vals
         mask = self._masks[b].to(self.dev, torch.float32).contiguous()
         g_alpha = torch.empty((1, H, W), dtype=torch.float32, device=self.dev)
-        rc = _capi.lib.fdgs_opa_mask_loss(H, W, T.data_ptr(), 1, mask.data_ptr(), st.up.data_ptr(), self.lam_opa, g_alpha.data_ptr(), 0,
-                                          st.opa_parts.data_ptr(), st.opa_vals[b:].data_ptr(), _capi.current_stream_handle(self.dev))
-        _capi._check(rc, "fdgs_opa_mask_loss")
+        _capi.call("fdgs_opa_mask_loss", self.dev, H, W, T.data_ptr(), 1, mask.data_ptr(), st.up.data_ptr(), self.lam_opa, g_alpha.data_ptr(), 0,
+                   st.opa_parts.data_ptr(), st.opa_vals[b:].data_ptr(), guard=False)   # (stream B's block is open around the caller)
         st.keep_masks.append((mask, g_alpha))
         return g_alpha
 

@@ -140,16 +140,12 @@ def resize_frames(frames_u8: torch.Tensor, size: Sequence[int], index: Optional[
     if need > 0:
         scratch = _scratch.get(str(dev))
         if scratch is None or scratch.numel() < need:
-            scratch = _scratch[str(dev)] = torch.empty(need, dtype=torch.uint8, device=dev)
+            scratch = _scratch[str(dev)] = _capi.scratch(need, dev)
     kx, bx, ksx = _device_tables(Ws, Wd, dev)
     ky, by, ksy = _device_tables(Hs, Hd, dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_frames_resize(frames_u8.data_ptr(), N, Hs, Ws, C, index.data_ptr(), B, out.data_ptr(), int(out.shape[0]), Hd, Wd,
-                                          kx.data_ptr(), bx.data_ptr(), ksx, ky.data_ptr(), by.data_ptr(), ksy,
-                                          None if scratch is None else scratch.data_ptr(), _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_frames_resize")
+    _capi.call("fdgs_frames_resize", dev, frames_u8.data_ptr(), N, Hs, Ws, C, index.data_ptr(), B, out.data_ptr(), int(out.shape[0]), Hd, Wd,
+               kx.data_ptr(), bx.data_ptr(), ksx, ky.data_ptr(), by.data_ptr(), ksy, None if scratch is None else scratch.data_ptr(),
+               arg_error=ValueError)
     return out
 
 
@@ -171,12 +167,8 @@ def composite(frames_rgba: torch.Tensor, white: bool, keep_alpha: bool = False, 
             or tuple(out.shape[1:]) != (H, W, Co) or out.shape[0] < N):
         raise ValueError("fdgs.resize: out must be a contiguous uint8 tensor [M >= %d, %d, %d, %d] on %s, got %s" % (
             N, H, W, Co, dev, tuple(getattr(out, "shape", ()))))
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_frames_composite(frames_rgba.data_ptr(), N, H, W, int(bool(white)), int(bool(keep_alpha)), out.data_ptr(),
-                                             _capi.current_stream_handle(dev))
-    if rc == 1:
-        raise ValueError(_capi.last_error())
-    _capi._check(rc, "fdgs_frames_composite")
+    _capi.call("fdgs_frames_composite", dev, frames_rgba.data_ptr(), N, H, W, int(bool(white)), int(bool(keep_alpha)), out.data_ptr(),
+               arg_error=ValueError)
     return out[:N]
 
 

@@ -55,8 +55,7 @@ def time_slice(model, timestamp, scaling_modifier=1.0, *, decompose=False, capac
     if int(model.gaussian_dim) != 4:
         raise ValueError("time_slice: the model is 3D (gaussian_dim == %d): it has no time to slice" % int(model.gaussian_dim))
     xyz = model._xyz
-    if not xyz.is_cuda:
-        raise RuntimeError("fdgs: the model must live on the GPU (got %s); there is no CPU path" % xyz.device)
+    _capi.need_gpu(xyz, "_xyz", what="the model")
     dev = xyz.device
     P = int(xyz.shape[0])
     cap = P if capacity is None else int(capacity)
@@ -94,14 +93,12 @@ def _enqueue(inputs, settings, cap, outputs, n_live):
     means3D, feats = inputs[0], inputs[1]
     dev, P = means3D.device, int(means3D.shape[0])
     D, D_t, mod, prefilter_var, timestamp, duration, rot_4d, force_sh_3d = settings
-    scratch = torch.empty((max(int(_capi.lib.fdgs_time_slice_scratch_bytes(P)), 1),), dtype=torch.uint8, device=dev)
+    scratch = _capi.scratch(_capi.lib.fdgs_time_slice_scratch_bytes(P), dev, floor=1)
     p = _capi._ptr
     a_in = _capi.FdgsSliceIn(P, int(D), int(D_t), int(feats.shape[1]) if P else 0, *[p(t) for t in inputs], float(mod), float(prefilter_var),
                              float(timestamp), float(duration), int(bool(rot_4d)), int(bool(force_sh_3d)))
     a_out = _capi.FdgsSliceOut(int(cap), *[p(t) for t in outputs], n_live.data_ptr())
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_time_slice(C.byref(a_in), C.byref(a_out), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_time_slice")
+    _capi.call("fdgs_time_slice", dev, C.byref(a_in), C.byref(a_out), scratch.data_ptr())
 
 
 def _rasterize(slice: TimeSlice, camera, bg):

@@ -74,8 +74,7 @@ def _field(view, key, default=None):
 def _image(t, name, dev, shape=None):
     if t is None:
         return None
-    if not t.is_cuda:
-        raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+    _capi.need_gpu(t, name)
     if t.device != dev:
         raise RuntimeError("fdgs: '%s' lives on %s, the volume on %s" % (name, t.device, dev))
     t = t.detach().contiguous().float()
@@ -142,9 +141,7 @@ def integrate(volume: TSDFVolume, views) -> None:
     if volume.voxels == 0 or len(views) == 0:
         return
     vol = volume._struct()
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_tsdf_integrate(C.byref(vol), len(views), views.structs, _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_tsdf_integrate")
+    _capi.call("fdgs_tsdf_integrate", dev, C.byref(vol), len(views), views.structs)
 
 
 @torch.no_grad()
@@ -175,14 +172,30 @@ class Mesh:
     faces: torch.Tensor      # [F, 3] int32
 
 
+def _empty_mesh(V, F, dev) -> Mesh:
+    return Mesh(*[torch.empty((V, 3), dtype=torch.float32, device=dev) for _ in range(3)], torch.empty((F, 3), dtype=torch.int32, device=dev))
+
+
+def _surface_out(counts, vcap=0, fcap=0, vertices=None, normals=None, colors=None, faces=None):
+    """fdgs_surface_out: the two counters in ``counts`` and, for an emitting pass, the four arrays with their capacities."""
+    return _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
+                                counts.data_ptr(), counts.data_ptr() + 4)
+
+
+def _two_pass(call, counts, dev) -> Mesh:
+    """What every mesh-producing entry point asks for: ``call()`` counts, one read of the two counters, exact allocation,
+    ``call(vcap, fcap, vertices, normals, colors, faces)`` emits."""
+    call()
+    V, F = (int(v) for v in counts.cpu())
+    mesh = _empty_mesh(V, F, dev)
+    if V > 0:
+        call(V, F, mesh.vertices, mesh.normals, mesh.colors, mesh.faces)
+    return mesh
+
+
 def _extract_call(volume, min_weight, counts, scratch, vcap=0, fcap=0, vertices=None, normals=None, colors=None, faces=None):
-    dev = volume.device
-    out = _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
-                               counts.data_ptr(), counts.data_ptr() + 4)
-    vol = volume._struct()
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_surface_extract(C.byref(vol), float(min_weight), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_surface_extract")
+    vol, sout = volume._struct(), _surface_out(counts, vcap, fcap, vertices, normals, colors, faces)
+    _capi.call("fdgs_surface_extract", volume.device, C.byref(vol), float(min_weight), C.byref(sout), scratch.data_ptr())
 
 
 def extract(volume: TSDFVolume, min_weight: float = 1.0) -> Mesh:
@@ -190,17 +203,10 @@ def extract(volume: TSDFVolume, min_weight: float = 1.0) -> Mesh:
     allocation, the emitting pass."""
     dev = volume.device
     if volume.voxels == 0:
-        return Mesh(torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.float32, device=dev),
-                    torch.empty((0, 3), dtype=torch.float32, device=dev), torch.empty((0, 3), dtype=torch.int32, device=dev))
+        return _empty_mesh(0, 0, dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    scratch = torch.empty(max(int(_capi.lib.fdgs_surface_extract_scratch_bytes(*volume.dims)), 256), dtype=torch.uint8, device=dev)
-    _extract_call(volume, min_weight, counts, scratch)
-    V, F = (int(v) for v in counts.cpu())
-    mesh = Mesh(torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((V, 3), dtype=torch.float32, device=dev),
-                torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((F, 3), dtype=torch.int32, device=dev))
-    if V > 0:
-        _extract_call(volume, min_weight, counts, scratch, V, F, mesh.vertices, mesh.normals, mesh.colors, mesh.faces)
-    return mesh
+    scratch = _capi.scratch(_capi.lib.fdgs_surface_extract_scratch_bytes(*volume.dims), dev, floor=256)
+    return _two_pass(lambda *out: _extract_call(volume, min_weight, counts, scratch, *out), counts, dev)
 
 
 def fuse_sequence(model, cameras, pipe, bg, volume: TSDFVolume, timestamps, *, alpha_min: float = 0.5, min_weight: float = 1.0):
@@ -229,8 +235,7 @@ def _mesh_struct(mesh: Mesh):
     """(fdgs_mesh_in, device, the tensors its pointers refer to) of a mesh on the GPU."""
     named = (("vertices", mesh.vertices), ("normals", mesh.normals), ("colors", mesh.colors), ("faces", mesh.faces))
     for name, t in named:
-        if not t.is_cuda:
-            raise RuntimeError("fdgs: tensor '%s' must live on the GPU (got %s); there is no CPU path" % (name, t.device))
+        _capi.need_gpu(t, name)
         if t.device != mesh.vertices.device:
             raise RuntimeError("fdgs: '%s' lives on %s, the vertices on %s" % (name, t.device, mesh.vertices.device))
     V, F = int(mesh.vertices.shape[0]), int(mesh.faces.shape[0])
@@ -243,40 +248,29 @@ def _mesh_struct(mesh: Mesh):
     return _capi.FdgsMeshIn(V, F, *[_capi._ptr(t) for t in keep]), mesh.vertices.device, keep
 
 
-def _scratch(nbytes, dev):
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-
-
 def _components_call(struct, dev, cap, vertex_component, counter, vertex_counts=None, face_counts=None, labelled=False) -> int:
     """fdgs_mesh_components on the current stream; returns the hook passes it took.  ``labelled``: ``vertex_component`` holds an
     earlier call's ids, only the counts are computed."""
     rounds = C.c_int32(0)
     out = _capi.FdgsMeshComponentsOut(int(cap), int(bool(labelled)), _capi._ptr(vertex_component), counter.data_ptr(), _capi._ptr(vertex_counts),
                                       _capi._ptr(face_counts), C.pointer(rounds))
-    scratch = _scratch(_capi.lib.fdgs_mesh_components_scratch_bytes(struct.V, struct.F), dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_mesh_components(C.byref(struct), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_mesh_components")
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_components_scratch_bytes(struct.V, struct.F), dev, floor=256)
+    _capi.call("fdgs_mesh_components", dev, C.byref(struct), C.byref(out), scratch.data_ptr())
     return int(rounds.value)
 
 
 def _compact_call(struct, dev, vertex_component, keep, counts, vcap=0, fcap=0, vertices=None, normals=None, colors=None, faces=None):
-    out = _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
-                               counts.data_ptr(), counts.data_ptr() + 4)
-    scratch = _scratch(_capi.lib.fdgs_mesh_compact_scratch_bytes(struct.V, struct.F), dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_mesh_compact(C.byref(struct), _capi._ptr(vertex_component), _capi._ptr(keep), int(keep.numel()), C.byref(out),
-                                         scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_mesh_compact")
+    sout = _surface_out(counts, vcap, fcap, vertices, normals, colors, faces)
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_compact_scratch_bytes(struct.V, struct.F), dev, floor=256)
+    _capi.call("fdgs_mesh_compact", dev, C.byref(struct), _capi._ptr(vertex_component), _capi._ptr(keep), int(keep.numel()), C.byref(sout),
+               scratch.data_ptr())
 
 
 def _smooth_call(struct, dev, iterations, lam, mu, pin_boundary, vertices=None, normals=None, boundary=None):
     out = _capi.FdgsMeshSmoothOut(int(iterations), float(lam), float(mu), int(bool(pin_boundary)), _capi._ptr(vertices), _capi._ptr(normals),
                                   _capi._ptr(boundary))
-    scratch = _scratch(_capi.lib.fdgs_mesh_smooth_scratch_bytes(struct.V, struct.F), dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_mesh_smooth(C.byref(struct), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_mesh_smooth")
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_smooth_scratch_bytes(struct.V, struct.F), dev, floor=256)
+    _capi.call("fdgs_mesh_smooth", dev, C.byref(struct), C.byref(out), scratch.data_ptr())
 
 
 def components(mesh: Mesh) -> MeshComponents:
@@ -312,13 +306,7 @@ def clean(mesh: Mesh, *, keep_largest=None, min_faces=None) -> Mesh:
         keep &= largest.to(dev)
     keep = keep.to(torch.uint8)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
-    _compact_call(struct, dev, comp.vertex_component, keep, counts)
-    V, F = (int(v) for v in counts.cpu())
-    out = Mesh(torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((V, 3), dtype=torch.float32, device=dev),
-               torch.empty((V, 3), dtype=torch.float32, device=dev), torch.empty((F, 3), dtype=torch.int32, device=dev))
-    if V > 0:
-        _compact_call(struct, dev, comp.vertex_component, keep, counts, V, F, out.vertices, out.normals, out.colors, out.faces)
-    return out
+    return _two_pass(lambda *out: _compact_call(struct, dev, comp.vertex_component, keep, counts, *out), counts, dev)
 
 
 def smooth(mesh: Mesh, iterations: int = 10, lam: float = 0.5, mu: float = -0.53, *, pin_boundary: bool = True,
@@ -342,13 +330,10 @@ def _simplify_call(struct, dev, origin, cell, dims, placement, stabilise, counts
                    colors=None, faces=None, vertex_map=None):
     params = _capi.FdgsMeshSimplifyParams(*[int(d) for d in dims], *[float(o) for o in origin], float(cell), int(placement), float(stabilise),
                                           _capi._ptr(vertex_map))
-    out = _capi.FdgsSurfaceOut(int(vcap), int(fcap), _capi._ptr(vertices), _capi._ptr(normals), _capi._ptr(colors), _capi._ptr(faces),
-                               counts.data_ptr(), counts.data_ptr() + 4)
+    sout = _surface_out(counts, vcap, fcap, vertices, normals, colors, faces)
     if scratch is None:
-        scratch = _scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev)
-    with torch.cuda.device(dev):
-        rc = _capi.lib.fdgs_mesh_simplify(C.byref(struct), C.byref(params), C.byref(out), scratch.data_ptr(), _capi.current_stream_handle(dev))
-    _capi._check(rc, "fdgs_mesh_simplify")
+        scratch = _capi.scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev, floor=256)
+    _capi.call("fdgs_mesh_simplify", dev, C.byref(struct), C.byref(params), C.byref(sout), scratch.data_ptr())
 
 
 def _bounds(vertices):
@@ -401,14 +386,9 @@ def simplify(mesh: Mesh, cell: float, *, origin=None, placement: str = "quadric"
     V = struct.V
     vmap = torch.empty(V, dtype=torch.int32, device=dev) if return_map else None
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    scratch = _scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev)
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev, floor=256)
     args = (struct, dev, start, cell, dims, _PLACEMENTS[placement], stabilise, counts, scratch)
-    _simplify_call(*args, vertex_map=vmap)
-    nv, nf = (int(v) for v in counts.cpu())
-    out = Mesh(torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nv, 3), dtype=torch.float32, device=dev),
-               torch.empty((nv, 3), dtype=torch.float32, device=dev), torch.empty((nf, 3), dtype=torch.int32, device=dev))
-    if nv > 0:
-        _simplify_call(*args, nv, nf, out.vertices, out.normals, out.colors, out.faces)
+    out = _two_pass(lambda *o: _simplify_call(*args, *o, vertex_map=None if o else vmap), counts, dev)   # the counting pass writes the map
     return (out, vmap) if return_map else out
 
 
@@ -424,7 +404,7 @@ def cell_for_target(mesh: Mesh, target_faces: int, probes: int = 12) -> float:
     if not (diagonal > 0 and np.isfinite(diagonal)):
         return 1.0                                        # nothing, or one point: every grid gives no face
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
-    scratch = _scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev)
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(struct.V, struct.F), dev, floor=256)
 
     def faces_at(cell):
         _simplify_call(struct, dev, bounds[0], cell, _grid_dims(bounds[1] - bounds[0], cell), _capi.FDGS_SIMPLIFY_MEAN, 0.0, counts, scratch)

@@ -421,12 +421,9 @@ class FlatAdam:
             for i, s in enumerate(self.segments):
                 arr[i] = _capi.FdgsAdamSegment(s["begin"] - begin, s["end"] - begin, s["lr"], s["lr_head"], s["period"], s["head"])
             self._native = arr
-            with torch.cuda.device(m.flat.device):
-                rc = _capi.lib.fdgs_adam_step(m.flat.data_ptr() + 4 * begin, m.flat_grad.data_ptr() + 4 * begin,
-                                              self.exp_avg.data_ptr() + 4 * begin, self.exp_avg_sq.data_ptr() + 4 * begin, n,
-                                              arr, len(self.segments), self.betas[0], self.betas[1], self.eps,
-                                              self.step_count, _capi.current_stream_handle(m.flat.device))
-            _capi._check(rc, "fdgs_adam_step")
+            _capi.call("fdgs_adam_step", m.flat.device, m.flat.data_ptr() + 4 * begin, m.flat_grad.data_ptr() + 4 * begin,
+                       self.exp_avg.data_ptr() + 4 * begin, self.exp_avg_sq.data_ptr() + 4 * begin, n, arr, len(self.segments),
+                       self.betas[0], self.betas[1], self.eps, self.step_count)
             return
         if self._lr_vec is None:
             self._lr_vec = self.lr_vector()

@@ -9,7 +9,7 @@ stream over at least one second of work after a warm-up, three times; the median
 the call with SH rows minus the call without them (the C entry always runs the geometry pass); the argument structs are built once,
 outside the timed loop.
 """
-import argparse, json, math, os, sys
+import argparse, ctypes, json, math, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import torch
@@ -24,7 +24,7 @@ def rot_axis(axis, angle):
 
 
 def bench(dev):
-    from fdgs import edit, synth, train_host
+    from fdgs import _capi, edit, synth, train_host
     scene = synth.make_scene(synth.CONFIGS["C3"], seed=0)
     model = train_host.GaussianParams(scene, dev)
     P, M = model.P, model.M
@@ -37,14 +37,14 @@ def bench(dev):
     geom_bytes, sh_bytes = 2 * 4 * 16 * P, 2 * 12 * M * P
 
     # the argument structs once: what is timed is the C call (two launches), not the float64 host set-up of the matrices
-    args_geometry = edit._arguments(sim, 4, True, M, src[:6] + [None], dst[:6] + [None])
-    args_both = edit._arguments(sim, 4, True, M, src, dst)
+    args_geometry = [ctypes.byref(a) for a in edit._arguments(sim, 4, True, M, src[:6] + [None], dst[:6] + [None])]
+    args_both = [ctypes.byref(a) for a in edit._arguments(sim, 4, True, M, src, dst)]
 
     def geometry():
-        edit._launch(*args_geometry, dev)
+        _capi.call("fdgs_model_transform", dev, *args_geometry)
 
     def both():
-        edit._launch(*args_both, dev)
+        _capi.call("fdgs_model_transform", dev, *args_both)
 
     def call():   # the whole Python call, host set-up and output allocation included
         edit.transform(model, sim)

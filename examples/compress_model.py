@@ -41,13 +41,13 @@ def cdist_argmin(x, c, chunk=16384):
 
 
 def bench(dev, N=300_000, D=141, K=4096):
-    from fdgs import compress
+    from fdgs import _capi, compress
     g = torch.Generator().manual_seed(0)
     centres = torch.randn(K, D, generator=g)
     x = (centres[torch.randint(0, K, (N,), generator=g)] + 0.5 * torch.randn(N, D, generator=g)).to(dev)
     c = x[torch.randperm(N, generator=g)[:K].to(dev)].contiguous()
     w = torch.rand(N, generator=g).to(dev)
-    scratch = compress._scratch(N, K, dev)
+    scratch = _capi.scratch(_capi.lib.fdgs_kmeans_scratch_bytes(N, K), dev, floor=1)
     res = {"N": N, "D": D, "K": K, "runs": 3}
     t, rng = median3(lambda: compress.assign(x, c, scratch=scratch), 5)
     res["assign_ms"], res["assign_ms_range"], res["assign_tflops"] = t * 1e3, [rng[0] * 1e3, rng[1] * 1e3], 2.0 * N * K * D / t * 1e-12

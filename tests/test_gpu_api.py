@@ -1061,3 +1061,29 @@ def test_sh_kernels_pinned_bits(gpu_device, request, D, D_t, M, sh3d, misaligned
             assert bad.size == 0, "%s %s: %d of %d words differ, first at %s: %08x != %08x" % (
                 name, k, len(bad), a.size, tuple(bad[0]), a[tuple(bad[0])], b[tuple(bad[0])])
     _GSH.check_contents(inp, got)
+
+
+def test_launches_follow_the_current_stream(gpu_device):
+    """A launch goes onto the current stream of its tensors' device (_capi.call): two calls made inside a side stream's block, with their
+    results copied to pinned memory on that stream, are complete once that stream alone is -- while the default stream is still busy
+    with work enqueued before them, which a launch that had gone there would have to wait behind."""
+    from fdgs.knn import distCUDA2
+    from fdgs.loss import opa_mask_loss
+    g = torch.Generator().manual_seed(3)
+    pts = torch.randn(64, 3, generator=g).to(gpu_device)
+    alpha = torch.rand(1, 16, 16, generator=g).to(gpu_device)
+    mask = (torch.rand(1, 16, 16, generator=g) > 0.5).float().to(gpu_device)
+    host = torch.full((65,), float("nan")).pin_memory()
+    busy = torch.zeros(1 << 25, device=gpu_device)
+    side = torch.cuda.Stream(gpu_device)
+    torch.cuda.synchronize(gpu_device)
+    for _ in range(20):
+        busy.add_(1.0)                       # a few milliseconds of default-stream work
+    with torch.cuda.stream(side):
+        host[:64].copy_(distCUDA2(pts), non_blocking=True)
+        host[64:].copy_(opa_mask_loss(alpha, mask).reshape(1), non_blocking=True)
+    side.synchronize()
+    got = host.clone()
+    torch.cuda.synchronize(gpu_device)
+    want = torch.cat([distCUDA2(pts), opa_mask_loss(alpha, mask).reshape(1)]).cpu()
+    assert torch.equal(got, want) and bool(torch.isfinite(want).all()) and float(want[:64].min()) > 0.0

@@ -93,7 +93,7 @@ def main():
     out = {"voxels": args.dims ** 3, "vertices": V, "faces": F, "reps": args.reps,
            "scratch_MB": round(_capi.lib.fdgs_mesh_simplify_scratch_bytes(V, F) / 2 ** 20, 1)}
     struct, _, _held = surface._mesh_struct(mesh)
-    scratch = surface._scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(V, F), dev)
+    scratch = _capi.scratch(_capi.lib.fdgs_mesh_simplify_scratch_bytes(V, F), dev, floor=256)
     counts = torch.zeros(2, dtype=torch.int32, device=dev)
     for voxels in (2, 4):
         h = voxels * volume.voxel_size
