@@ -364,10 +364,11 @@ def call(name, dev, *args, guard=True, stream=None, arg_error=Exception):
         _check(rc, name, arg_error)
 
 
-def need_gpu(t, name, what=None):
-    """The one refusal of a CPU tensor; ``what``: what the message calls it where that is not "tensor '<name>'"."""
+def need_gpu(t, name, what=None, got=True):
+    """The one refusal of a CPU tensor; ``what``: what the message calls it where that is not "tensor '<name>'"; ``got=False``: the
+    rasterizer's older wording, which does not say where the tensor is."""
     if not t.is_cuda:
-        raise RuntimeError("fdgs: %s must live on the GPU (got %s); there is no CPU path" % (what or "tensor '%s'" % name, t.device))
+        raise RuntimeError("fdgs: %s must live on the GPU%s; there is no CPU path" % (what or "tensor '%s'" % name, " (got %s)" % t.device if got else ""))
 
 
 def scratch(nbytes, dev, floor=0):

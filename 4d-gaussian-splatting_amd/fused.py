@@ -16,19 +16,10 @@ Covers the default pipeline (in-kernel covariance and SH, rot_4d or not) and the
 rasterized over black, then ``fdgs.envmap.env_composite``); the Python covariance / SH branches go through ``render()``.  Same
 result dict as ``render()``.
 """
-import math
-
 import torch
 
-from .gaussian_renderer.diff_gaussian_rasterization import GaussianRasterizationSettings, _C, _is_given, camera_tensors, detached_settings
-
-
-def _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, flows=None):
-    e = torch.Tensor([])
-    return (rs.bg, means3D, e, e if flows is None else flows, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
-            rs.scale_modifier, e, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-            rs.image_height, rs.image_width, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp,
-            rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, rs.prefiltered, rs.debug)
+from .gaussian_renderer.diff_gaussian_rasterization import (_C, backward_args, camera_gradients, camera_inputs, camera_tensors, forward_args,
+                                                             image_gradients, shaped, time_inputs, view_settings)
 
 
 def raw_forward(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var,
@@ -37,7 +28,8 @@ def raw_forward(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, ro
     per-Gaussian ``flow_2d`` input [P, 2] (default: none, the flow image is zero).
     ``preprocessed``: the view's handle from ``raw_preprocess_batch``; ``tile_cull``: fdgs_forward_out.tile_cull; ``lazy``:
     fdgs_forward_out.lazy (num_rendered comes back as -1, the host does not wait); ``sparse_lists``: fdgs_forward_out.sparse_lists; ``colour_stream``: fdgs_forward_out.colour_stream (a torch.cuda.Stream)."""
-    args = _raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, flows)
+    args = forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var,
+                        **({} if flows is None else {"flow_2d": flows}))
     return _C.rasterize_gaussians(*args, raw_params=True, split_colour=split_colour, preprocessed=preprocessed, tile_cull=tile_cull, lazy=lazy,
                                   sparse_lists=sparse_lists, colour_stream=colour_stream)
 
@@ -46,7 +38,7 @@ def raw_preprocess_batch(settings, means3D, sh, opacity_raw, ts, scaling_raw, sc
                          tile_cull=False):
     """View-batched preprocess on RAW parameters (fdgs_preprocess_batch): ``settings`` = the views' raster settings (the views of
     one optimizer step share every parameter tensor).  One handle per view for ``raw_forward(..., preprocessed=handle)``."""
-    views = [_raw_forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var)
+    views = [forward_args(rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var)
              for rs in settings]
     return _C.preprocess_batch(views, raw_params=True, tile_cull=tile_cull)
 
@@ -59,11 +51,8 @@ def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_r
     ``_C.backward_finish``.  ``per_view_outputs=False``: dL_dcolors / dL_dcov3D / dL_dflows are not written (None in the tuple).
     ``geometry_adam``: see ``_C.rasterize_gaussians_backward`` (the geometry parameters' Adam step inside the geometry backward);
     ``camera``: as there (the camera gradients, computed between the two halves of the backward)."""
-    e = torch.Tensor([])
-    args = (rs.bg, means3D, out_means3D, radii, e, e if flows is None else flows, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
-            rotation_r_raw, rs.scale_modifier, e, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx,
-            rs.tanfovy, g_color, g_depth, g_alpha, g_flow, sh, rs.sh_degree, rs.sh_degree_t, rs.campos,
-            rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, geom, R, binb, img, rs.debug)
+    args = backward_args(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
+                         prefilter_var, geom, R, binb, img, g_color, g_depth, g_alpha, g_flow, **({} if flows is None else {"flow_2d": flows}))
     if begin_only:
         return _C.backward_begin(*args, raw_params=True, grad_out=sink, accumulate=accumulate, grad_accum=grad_accum, sh_stage=sh_stage,
                                  per_view_outputs=per_view_outputs)
@@ -72,94 +61,92 @@ def raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_r
                                            camera=camera)
 
 
-_BLACK = {}
+def raw_tensors(pc):
+    """(xyz, features, opacity, t, scaling, scaling_t, rotation, rotation_r, prefilter_var): the raw parameters of ``pc`` (the reference's
+    attribute names) as the kernels take them."""
+    ts, scaling_t, rotation_r, prefilter_var = time_inputs(pc, lambda name: getattr(pc, "_" + name))
+    return (pc._xyz, pc.get_features, pc._opacity, ts, pc._scaling, scaling_t, pc._rotation, rotation_r, prefilter_var)
 
 
-def _black(device):
-    """A zero background per device, made once (and waited for once: it is read on whichever stream renders)."""
-    z = _BLACK.get(device)
-    if z is None:
-        z = _BLACK[device] = torch.zeros(3, dtype=torch.float32, device=device)
-        torch.cuda.current_stream(device).synchronize()
-    return z
+def _raw_view(viewpoint_camera, pc, pipe, bg_color, scaling_modifier):
+    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
+        raise ValueError("render_raw covers the default pipeline only; use render() for the Python covariance / SH branches")
+    return view_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier) + (raw_tensors(pc),)
 
 
 def raw_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
-    """GaussianRasterizationSettings + the raw parameter tensors of ``pc`` for the default pipeline (with ``pipe.env_map_res`` the
-    background is black whatever ``bg_color`` says: the environment map is composited behind the Gaussians afterwards)."""
-    if pipe.compute_cov3D_python or pipe.convert_SHs_python:
-        raise ValueError("render_raw covers the default pipeline only; use render() for the Python covariance / SH branches")
-    if getattr(pipe, "env_map_res", 0):
-        bg_color = _black(pc._xyz.device)   # the environment is composited behind a black background (gaussian_renderer/__init__.py:41)
-    rs = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color, scale_modifier=scaling_modifier, viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform, sh_degree=pc.active_sh_degree,
-        sh_degree_t=pc.active_sh_degree_t, campos=viewpoint_camera.camera_center, timestamp=viewpoint_camera.timestamp,
-        time_duration=pc.time_duration[1] - pc.time_duration[0], rot_4d=pc.rot_4d, gaussian_dim=pc.gaussian_dim,
-        force_sh_3d=pc.force_sh_3d, prefiltered=False, debug=pipe.debug)
-    e = torch.Tensor([])
-    is_4d = pc.gaussian_dim == 4
-    ts = pc._t if is_4d else e
-    scaling_t = pc._scaling_t if is_4d else e
-    rotation_r = pc._rotation_r if (is_4d and pc.rot_4d) else e
-    prefilter_var = pc.prefilter_var if (is_4d and pc.prefilter_var > 0.0) else -1.0
-    return rs, (pc._xyz, pc.get_features, pc._opacity, ts, pc._scaling, scaling_t, pc._rotation, rotation_r, prefilter_var)
+    """GaussianRasterizationSettings + the raw parameter tensors of ``pc`` for the default pipeline (``view_settings`` and
+    ``raw_tensors``)."""
+    rs, _timestamp_tensor, tensors = _raw_view(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    return rs, tensors
 
 
 class _RasterizeRaw(torch.autograd.Function):
+    """The rasterizer on a model's RAW parameters (fdgs_scene.raw_params: activations inside the kernels).  ``grad_to`` says where the
+    parameter gradients go: None -- back to autograd; ``(sink, accumulate)`` -- into the caller's buffers (see the module docstring);
+    an ``fdgs.optim.Adam`` that owns the parameters -- into the flat gradient bucket behind ``p.grad`` and its SH stage, asked for at
+    backward time (``backward_begin(rs)``).  An input whose gradient went there gets None from autograd.  ``lazy``: the forward does
+    not wait for num_rendered (such a forward never hands its lists out: they may as well sit at fixed offsets -- no count / scan
+    launch).  ``cam``: () or (viewmatrix, projmatrix, campos, timestamp tensor or None) as explicit inputs: a camera under optimisation."""
+
     @staticmethod
     def forward(ctx, means3D, means2D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw,
-                prefilter_var, raster_settings, grad_sink, accumulate, tile_cull=False, flows=None, *cam):
-        # cam: () or (viewmatrix, projmatrix, campos, timestamp tensor or None) as explicit inputs: a camera under optimisation
-        rs = raster_settings
+                prefilter_var, rs, grad_to, tile_cull, lazy=False, flows=None, *cam):
         ctx.cam_meta = None
         if cam:
-            rs = detached_settings(rs._replace(viewmatrix=cam[0], projmatrix=cam[1], campos=cam[2]), cam[3])
-            ctx.cam_meta = [None if t is None else (t.shape, t.dtype) for t in cam]
+            rs = camera_inputs(ctx, rs, *cam)
         (R, color, flow, depth, T, radii, geom, binb, img, covs_com, out_means3D) = raw_forward(
             rs, means3D, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw, rotation_r_raw, prefilter_var, tile_cull=tile_cull,
-            flows=flows)
-        ctx.rs, ctx.R, ctx.prefilter_var, ctx.sink, ctx.accumulate = rs, R, prefilter_var, grad_sink, bool(accumulate)
+            lazy=lazy, sparse_lists=lazy, flows=flows)
+        ctx.rs, ctx.R, ctx.prefilter_var, ctx.grad_to = rs, R, prefilter_var, grad_to
         ctx.has_flows = flows is not None
         ctx.save_for_backward(means3D, out_means3D, scaling_raw, rotation_raw, radii, sh, opacity_raw, ts, scaling_t_raw,
                               rotation_r_raw, geom, binb, img, *((flows,) if flows is not None else ()))
         ctx.mark_non_differentiable(radii)
         ctx.set_materialize_grads(False)  # unused outputs -> None gradients -> colour-only backward
+        if not (grad_to is None or isinstance(grad_to, tuple)):
+            grad_to.note_forward(R < 0)
         return color, radii, depth, 1 - T, flow
 
     @staticmethod
     def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_flow):
-        rs = ctx.rs
+        rs, grad_to = ctx.rs, ctx.grad_to
         (means3D, out_means3D, scaling_raw, rotation_raw, radii, sh, opacity_raw, ts, scaling_t_raw, rotation_r_raw,
          geom, binb, img) = ctx.saved_tensors[:13]
         flows = ctx.saved_tensors[13] if ctx.has_flows else None
-        sink = ctx.sink
+        grads = image_gradients(rs, means3D.device, g_color, g_depth, g_alpha, g_flow)
+        sink, accumulate, gacc, stage = None, False, None, None
+        if isinstance(grad_to, tuple):
+            sink, accumulate = grad_to
+        elif grad_to is not None:
+            if not (grad_to.is_homed() and grad_to.features().data_ptr() == sh.data_ptr()):
+                # the forward was handed the optimizer's bucket views (plain tensors, no requires_grad): returning gradients for them
+                # would be dropped by autograd without a word and no parameter would receive anything
+                raise RuntimeError("fdgs render(): the optimizer's parameters or Adam state were replaced between this view's forward and its "
+                                   "backward (densification / prune / load_state_dict); the gradients of this view have nowhere to go -- "
+                                   "run backward() before editing the optimizer, as the reference's loop does (train.py:160-249)")
+            sink, accumulate, gacc, stage = grad_to.backward_begin(rs)
         camera = {"want": tuple(bool(n) for n in ctx.needs_input_grad[15:19])} if ctx.cam_meta is not None else None
         (d_means2D, _d_colors, d_opacity, d_means3D, _d_cov3D, d_sh, d_flows, d_ts, d_scales, d_scales_t, d_rot,
          d_rot_r) = raw_backward(rs, means3D, out_means3D, radii, sh, opacity_raw, ts, scaling_raw, scaling_t_raw, rotation_raw,
-                                 rotation_r_raw, ctx.prefilter_var, geom, ctx.R, binb, img, g_color, g_depth, g_alpha, g_flow,
-                                 sink, ctx.accumulate, flows=flows, camera=camera)
-
-        cam_grads = ()
-        if camera is not None:
-            for need, name, meta in zip(camera["want"], ("viewmatrix", "projmatrix", "campos", "timestamp"), ctx.cam_meta):
-                g = camera["grads"].get(name) if (need and meta is not None) else None
-                cam_grads += (None if g is None else g.reshape(meta[0]).to(meta[1]),)
+                                 rotation_r_raw, ctx.prefilter_var, geom, ctx.R, binb, img, *grads, sink, bool(accumulate),
+                                 grad_accum=gacc, sh_stage=stage, flows=flows, camera=camera)
 
         def ret(name, given, g):
-            if not _is_given(given):
-                return None
-            if sink and sink.get(name) is not None:
-                return None  # already written into the caller's buffer
-            return g.reshape(given.shape)
+            if (sink and sink.get(name) is not None) or (stage is not None and name == "dL_dsh"):
+                return None  # already written into the caller's buffer / staged
+            return shaped(given, g)
 
+        tail = ()
+        if ctx.has_flows or camera:
+            tail = (d_flows.reshape(flows.shape) if ctx.has_flows else None,)
+        if camera:
+            tail += camera_gradients(ctx, camera["want"], camera)
         return (ret("dL_dmeans3D", means3D, d_means3D), d_means2D, ret("dL_dsh", sh, d_sh),
                 ret("dL_dopacity", opacity_raw, d_opacity), ret("dL_dts", ts, d_ts),
                 ret("dL_dscales", scaling_raw, d_scales), ret("dL_dscales_t", scaling_t_raw, d_scales_t),
                 ret("dL_drotations", rotation_raw, d_rot), ret("dL_drotations_r", rotation_r_raw, d_rot_r),
-                None, None, None, None, None) + ((d_flows.reshape(flows.shape),) if ctx.has_flows else ((None,) if camera else ())) + cam_grads
+                None, None, None, None, None) + tail
 
 
 def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, grad_sink=None, accumulate=False, tile_cull=False,
@@ -171,27 +158,20 @@ def render_raw(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modif
     zeros and ``"flow"`` is the blended image ``sum_i flow_i alpha_i T_i`` in pixels, NOT divided by alpha (divide by ``"alpha"`` for
     the mean motion of what a pixel shows).  A loss on ``"flow"`` reaches the parameters through the rasterizer and through the flow
     itself, both by autograd: not together with ``grad_sink``."""
-    rs, (xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var) = raw_settings(
-        viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
+    rs, timestamp_tensor, (xyz, *tensors) = _raw_view(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     screenspace_points = torch.zeros_like(xyz, requires_grad=True)
     # a camera under optimisation (fdgs.camera.LearnableCamera): its tensors become inputs of the autograd function
-    cam_time = viewpoint_camera.timestamp
-    cam, camera_grad = camera_tensors(rs, cam_time if isinstance(cam_time, torch.Tensor) else None)
-    cam = cam if camera_grad else ()
-    if isinstance(cam_time, torch.Tensor) and not camera_grad:
-        rs = rs._replace(timestamp=float(cam_time.detach()))
-    if flow_to is None:
-        color, radii, depth, alpha, flow = _RasterizeRaw.apply(
-            xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
-            prefilter_var, rs, grad_sink, accumulate, tile_cull, *((None,) + cam if cam else ()))
-    else:
+    cam, camera_grad = camera_tensors(rs, timestamp_tensor)
+    flows = None
+    if flow_to is not None:
         if grad_sink:
             raise ValueError("render_raw: flow_to with grad_sink is not supported: the gradients of the flow arrive through autograd")
         from .flow import model_flow
         flows = model_flow(viewpoint_camera, flow_to, pc, raw=True, scaling_modifier=scaling_modifier)
-        color, radii, depth, alpha, flow = _RasterizeRaw.apply(
-            xyz, screenspace_points, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r,
-            prefilter_var, rs, grad_sink, accumulate, tile_cull, flows, *cam)
+    extra = (flows,) + (cam if camera_grad else ()) if (camera_grad or flows is not None) else ()
+    color, radii, depth, alpha, flow = _RasterizeRaw.apply(
+        xyz, screenspace_points, *tensors, rs, (grad_sink, accumulate) if (grad_sink is not None or accumulate) else None, tile_cull, False,
+        *extra)
     if getattr(pipe, "env_map_res", 0):
         from .envmap import env_composite
         if getattr(pc, "env_map", None) is None:

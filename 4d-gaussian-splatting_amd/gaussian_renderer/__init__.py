@@ -7,12 +7,10 @@ of the reference; the rasterizer underneath is the MI355X-native one
 members that are read).  Unlike the reference, the device is taken from the
 model (``pc.get_xyz.device``) instead of the literal "cuda".
 """
-import math
-
 import torch
 from torch.nn import functional as F
 
-from .diff_gaussian_rasterization import GaussianRasterizationSettings, GaussianRasterizer, camera_tensors
+from .diff_gaussian_rasterization import GaussianRasterizer, camera_tensors, view_settings
 from ..sh_utils import eval_sh, eval_shfs_4d
 
 
@@ -28,61 +26,13 @@ render_options = {"tile_cull": False, "fast_path": True}
 _RAW_ATTRS = ("_xyz", "_scaling", "_rotation", "_opacity", "_features_dc", "_features_rest")
 
 
-class _RasterizeModel(torch.autograd.Function):
-    """The rasterizer on a reference-style model's RAW parameters (fdgs_scene.raw_params: activations inside the kernels).
-    With an ``fdgs.optim.Adam`` that owns the parameters (``opt``), the backward writes the parameter gradients straight into the
-    optimizer's flat gradient bucket behind ``p.grad`` and returns nothing for them; otherwise it returns them to autograd."""
-
-    @staticmethod
-    def forward(ctx, means2D, xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var, rs, opt, tile_cull, lazy):
-        from ..fused import raw_forward
-        (R, color, flow, depth, T, radii, geom, binb, img, _covs, out_means3D) = raw_forward(
-            rs, xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var, tile_cull=tile_cull, lazy=lazy,
-            sparse_lists=lazy)   # (a lazy forward never hands its lists out: they may as well sit at fixed offsets -- no count / scan launch)
-        ctx.rs, ctx.R, ctx.prefilter_var, ctx.opt = rs, R, prefilter_var, opt
-        ctx.save_for_backward(xyz, out_means3D, scaling, rotation, radii, feats, opacity, ts, scaling_t, rotation_r, geom, binb, img)
-        ctx.mark_non_differentiable(radii)
-        ctx.set_materialize_grads(False)   # outputs nobody differentiates arrive as None: colour-only backward
-        if opt is not None:
-            opt.note_forward(R < 0)
-        return color, radii, depth, 1 - T, flow
-
-    @staticmethod
-    def backward(ctx, g_color, g_radii, g_depth, g_alpha, g_flow):
-        from ..fused import raw_backward
-        from .diff_gaussian_rasterization import _is_given
-        rs, opt = ctx.rs, ctx.opt
-        (xyz, out_means3D, scaling, rotation, radii, feats, opacity, ts, scaling_t, rotation_r, geom, binb, img) = ctx.saved_tensors
-        if g_color is None and g_depth is None and g_alpha is None and g_flow is None:
-            g_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=xyz.device)
-        sunk = opt is not None and opt.is_homed() and opt.features().data_ptr() == feats.data_ptr()
-        if opt is not None and not sunk:
-            # the forward was handed the optimizer's bucket views (plain tensors, no requires_grad): returning gradients for them
-            # would be dropped by autograd without a word and no parameter would receive anything
-            raise RuntimeError("fdgs render(): the optimizer's parameters or Adam state were replaced between this view's forward and its "
-                               "backward (densification / prune / load_state_dict); the gradients of this view have nowhere to go -- "
-                               "run backward() before editing the optimizer, as the reference's loop does (train.py:160-249)")
-        if sunk:
-            sink, accumulate, gacc, stage = opt.backward_begin(rs)
-            grads = raw_backward(rs, xyz, out_means3D, radii, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, ctx.prefilter_var,
-                                 geom, ctx.R, binb, img, g_color, g_depth, g_alpha, g_flow, sink, accumulate, grad_accum=gacc, sh_stage=stage)
-            return (grads[0],) + (None,) * 13
-        (d_means2D, _dc, d_opacity, d_means3D, _dcov, d_sh, _df, d_ts, d_scales, d_scales_t, d_rot, d_rot_r) = raw_backward(
-            rs, xyz, out_means3D, radii, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, ctx.prefilter_var, geom, ctx.R, binb, img,
-            g_color, g_depth, g_alpha, g_flow, None, False)
-
-        def shaped(given, g):
-            return g.reshape(given.shape) if _is_given(given) else None
-
-        return (d_means2D, d_means3D, shaped(feats, d_sh), shaped(opacity, d_opacity), shaped(ts, d_ts), shaped(scaling, d_scales),
-                shaped(scaling_t, d_scales_t), shaped(rotation, d_rot), shaped(rotation_r, d_rot_r), None, None, None, None, None)
-
-
-def _fast_path(viewpoint_camera, pc, pipe, raster_settings, means2D):
+def _fast_path(pc, pipe, raster_settings, means2D):
     """A reference-style model (raw ``_scaling`` / ``_rotation`` / ``_opacity`` / ``_features_dc`` / ``_features_rest`` ... attributes,
     scene/gaussian_model.py:70-80) on the default pipeline: the kernels take the RAW parameters and apply the activations of
-    :179-209 themselves (no exp / sigmoid / normalize kernels forward and backward); with ``fdgs.optim.Adam`` as ``pc.optimizer``
-    also no ``torch.cat`` of the SH coefficients and no gradient accumulation pass (see fdgs/optim.py).  None: not applicable."""
+    :179-209 themselves (no exp / sigmoid / normalize kernels forward and backward; ``fdgs.fused._RasterizeRaw``).  With an
+    ``fdgs.optim.Adam`` that owns the parameters as ``pc.optimizer`` also no ``torch.cat`` of the SH coefficients and no gradient
+    accumulation pass: the backward writes the parameter gradients straight into the optimizer's flat gradient bucket behind ``p.grad``
+    and returns nothing for them (see fdgs/optim.py).  None: not applicable."""
     if pipe.compute_cov3D_python or pipe.convert_SHs_python or pipe.debug or not render_options["fast_path"]:
         return None
     if not all(isinstance(getattr(pc, a, None), torch.Tensor) for a in _RAW_ATTRS):
@@ -95,20 +45,14 @@ def _fast_path(viewpoint_camera, pc, pipe, raster_settings, means2D):
         return None
     if is_4d and pc.rot_4d and not isinstance(getattr(pc, "_rotation_r", None), torch.Tensor):
         return None
+    from ..fused import _RasterizeRaw, raw_tensors
     from ..optim import Adam as _FdgsAdam
-    e = torch.Tensor([])
     opt = getattr(pc, "optimizer", None)
-    prefilter_var = pc.prefilter_var if (is_4d and pc.prefilter_var > 0.0) else -1.0
     if isinstance(opt, _FdgsAdam) and opt.ensure_homed() and opt._homed["xyz"][0] is xyz:
-        tensors = opt.model_tensors(pc.gaussian_dim, pc.rot_4d)
-        lazy = opt.lazy_forward
+        tensors, lazy = opt.model_tensors(pc), opt.lazy_forward
     else:
-        opt, lazy = None, False
-        tensors = (xyz, pc.get_features, pc._opacity, pc._t if is_4d else e, pc._scaling, pc._scaling_t if is_4d else e, pc._rotation,
-                   pc._rotation_r if (is_4d and pc.rot_4d) else e)
-    (x, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r) = tensors
-    return _RasterizeModel.apply(means2D, x, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var,
-                                 raster_settings, opt, bool(render_options["tile_cull"]), lazy)
+        tensors, opt, lazy = raw_tensors(pc), None, False
+    return _RasterizeRaw.apply(tensors[0], means2D, *tensors[1:], raster_settings, opt, bool(render_options["tile_cull"]), lazy)
 
 
 def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=1.0, override_color=None, *, flow_to=None):
@@ -130,34 +74,13 @@ def render(viewpoint_camera, pc, pipe, bg_color: torch.Tensor, scaling_modifier=
 
     # a camera under optimisation (fdgs.camera.LearnableCamera): its matrices are differentiable torch expressions and its timestamp a
     # 0-d tensor; the rasterizer returns their gradients when they require one
-    cam_time = viewpoint_camera.timestamp
-    timestamp_tensor = cam_time if isinstance(cam_time, torch.Tensor) else None
-    raster_settings = GaussianRasterizationSettings(
-        image_height=int(viewpoint_camera.image_height),
-        image_width=int(viewpoint_camera.image_width),
-        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5),
-        tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
-        bg=bg_color if not pipe.env_map_res else torch.zeros(3, device=device),
-        scale_modifier=scaling_modifier,
-        viewmatrix=viewpoint_camera.world_view_transform,
-        projmatrix=viewpoint_camera.full_proj_transform,
-        sh_degree=pc.active_sh_degree,
-        sh_degree_t=pc.active_sh_degree_t,
-        campos=viewpoint_camera.camera_center,
-        timestamp=cam_time if timestamp_tensor is None else float(cam_time.detach()),
-        time_duration=pc.time_duration[1] - pc.time_duration[0],
-        rot_4d=pc.rot_4d,
-        gaussian_dim=pc.gaussian_dim,
-        force_sh_3d=pc.force_sh_3d,
-        prefiltered=False,
-        debug=pipe.debug,
-    )
+    raster_settings, timestamp_tensor = view_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier)
     rasterizer = GaussianRasterizer(raster_settings=raster_settings, timestamp_tensor=timestamp_tensor)
     _, camera_grad = camera_tensors(raster_settings, timestamp_tensor)
 
     # (the fast path has no flow input and no camera gradients: with flow_to, or a camera tensor that requires a gradient, the model goes
     # through the reference's own sequence below)
-    fast = _fast_path(viewpoint_camera, pc, pipe, raster_settings, screenspace_points) if (override_color is None and flow_to is None and not camera_grad) else None
+    fast = _fast_path(pc, pipe, raster_settings, screenspace_points) if (override_color is None and flow_to is None and not camera_grad) else None
     if fast is not None:
         rendered_image, radii, depth, alpha, flow = fast
         return _finish(viewpoint_camera, pc, pipe, screenspace_points, rendered_image, radii, depth, alpha, flow, None)

@@ -12,6 +12,7 @@ ABI of ``include/fdgs.h``.  No rasterization arithmetic happens in Python and
 there is no CPU fallback.
 """
 import ctypes as C
+import math
 from typing import NamedTuple
 
 import torch
@@ -38,6 +39,15 @@ def analytic_sh_gradients() -> bool:
 
 def _is_given(t) -> bool:
     return t is not None and t.numel() > 0
+
+
+def _need_gpu(means3D):
+    _capi.need_gpu(means3D, "means3D", "means3D", got=False)
+
+
+# the backward's 12 results in the binding's order (rasterize_points.h:51-89); also the keys of ``grad_out``
+_GRADS = ("dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dflows", "dL_dts", "dL_dscales",
+          "dL_dscales_t", "dL_drotations", "dL_drotations_r")
 
 
 class _Scratch:
@@ -114,6 +124,15 @@ class _NativeRasterizer:
         s.analytic_sh_grad = int(_ANALYTIC_SH_GRAD)
         return s, keep
 
+    @staticmethod
+    def _view(dev, scene, keep, tile_cull):
+        """One view's scene with the per-Gaussian forward outputs and scratch of its own: what ``preprocess_batch`` hands out per view."""
+        fo = dict(dtype=torch.float32, device=dev)
+        return {"scene": scene, "keep": keep, "radii": torch.empty((scene.P,), dtype=torch.int32, device=dev),
+                "out_means3D": torch.empty((scene.P, 3), **fo),
+                "covs_com": torch.empty((scene.P, 6), **fo),  # owning, not a from_blob alias of the scratch (rasterize_points.cu:144-147)
+                "scratch": _Scratch(dev), "tile_cull": bool(tile_cull)}
+
     def rasterize_gaussians(self, bg, means3D, colors, flows, opacity, ts, scales, scales_t, rotations, rotations_r,
                             scale_modifier, cov3D_precomp, prefilter_var, viewmatrix, projmatrix, tan_fovx, tan_fovy,
                             image_height, image_width, sh, degree, degree_t, campos, timestamp, time_duration, rot_4d,
@@ -129,36 +148,28 @@ class _NativeRasterizer:
         ``sparse_lists`` (with ``lazy``): fdgs_forward_out.sparse_lists -- every tile's list at a fixed offset of the binning buffer, no
         count / scan launches; ``colour_stream`` (with ``split_colour``): the torch.cuda.Stream the colour launch goes onto instead of
         the library's own (fdgs_forward_out.colour_stream)."""
-        if not means3D.is_cuda:
-            raise RuntimeError("fdgs: means3D must live on the GPU; there is no CPU path")
+        _need_gpu(means3D)
         dev = means3D.device
         if preprocessed is not None:
             # ``preprocessed``: this view's handle from preprocess_batch (same arguments): geometry and SH colours are already
             # enqueued on this stream; the call continues with the tile binning and the blend
-            scene, keep = preprocessed["scene"], preprocessed["keep"]
+            view = preprocessed
         else:
-            scene, keep = self._scene(bg, means3D, colors, flows, opacity, ts, scales, scales_t, rotations, rotations_r,
-                                      scale_modifier, cov3D_precomp, prefilter_var, viewmatrix, projmatrix, tan_fovx,
-                                      tan_fovy, image_height, image_width, sh, degree, degree_t, campos, timestamp,
-                                      time_duration, rot_4d, gaussian_dim, force_sh_3d, prefiltered, debug, raw_params)
-        P, H, W = scene.P, scene.H, scene.W
+            view = self._view(dev, *self._scene(bg, means3D, colors, flows, opacity, ts, scales, scales_t, rotations, rotations_r,
+                                                scale_modifier, cov3D_precomp, prefilter_var, viewmatrix, projmatrix, tan_fovx,
+                                                tan_fovy, image_height, image_width, sh, degree, degree_t, campos, timestamp,
+                                                time_duration, rot_4d, gaussian_dim, force_sh_3d, prefiltered, debug, raw_params), tile_cull)
+        scene, keep, radii, out_means3D, covs_com, scratch = (view[k] for k in ("scene", "keep", "radii", "out_means3D", "covs_com", "scratch"))
+        H, W = scene.H, scene.W
         fo = dict(dtype=torch.float32, device=dev)
         # every output is fully written by the kernels: torch.empty, not torch.full (rasterize_points.cu:80-85)
         out_color = torch.empty((3, H, W), **fo)
         out_flow = torch.empty((2, H, W), **fo)
         out_depth = torch.empty((1, H, W), **fo)
         out_T = torch.empty((1, H, W), **fo)
-        if preprocessed is not None:
-            radii, out_means3D, covs_com, scratch = (preprocessed[k] for k in ("radii", "out_means3D", "covs_com", "scratch"))
-        else:
-            radii = torch.empty((P,), dtype=torch.int32, device=dev)
-            out_means3D = torch.empty((P, 3), **fo)
-            covs_com = torch.empty((P, 6), **fo)  # owning, not a from_blob alias of the scratch (rasterize_points.cu:144-147)
-            scratch = _Scratch(dev)
         out = _capi.FdgsForwardOut(out_color.data_ptr(), out_flow.data_ptr(), out_depth.data_ptr(), out_T.data_ptr(),
                                    _capi._ptr(radii), _capi._ptr(out_means3D), _capi._ptr(covs_com),
-                                   int(preprocessed is not None), int(bool(split_colour)),
-                                   int(preprocessed["tile_cull"] if preprocessed is not None else bool(tile_cull)), int(bool(lazy)),
+                                   int(preprocessed is not None), int(bool(split_colour)), int(view["tile_cull"]), int(bool(lazy)),
                                    int(bool(sparse_lists)), colour_stream.cuda_stream if colour_stream is not None else None)
         R = C.c_int32(0)
         try:
@@ -173,17 +184,11 @@ class _NativeRasterizer:
         ``rasterize_gaussians`` for the views of ONE optimizer step (same Gaussian tensors, own camera / timestamp).  The
         geometry runs per view, the SH colours of all views in one pass over the coefficients.  Returns one handle per view;
         ``rasterize_gaussians(*views[v], raw_params=..., preprocessed=handles[v])`` then completes view v on the same stream."""
+        _need_gpu(views[0][1])
         dev = views[0][1].device
-        if not views[0][1].is_cuda:
-            raise RuntimeError("fdgs: means3D must live on the GPU; there is no CPU path")
         handles = []
         for a in views:
-            scene, keep = self._scene(*a, raw_params)
-            P = scene.P
-            fo = dict(dtype=torch.float32, device=dev)
-            h = {"scene": scene, "keep": keep, "radii": torch.empty((P,), dtype=torch.int32, device=dev),
-                 "out_means3D": torch.empty((P, 3), **fo), "covs_com": torch.empty((P, 6), **fo), "scratch": _Scratch(dev),
-                 "tile_cull": bool(tile_cull)}
+            h = self._view(dev, *self._scene(*a, raw_params), tile_cull)
             h["scratch"].reuse = True
             h["out"] = _capi.FdgsForwardOut(None, None, None, None, _capi._ptr(h["radii"]), _capi._ptr(h["out_means3D"]),
                                             _capi._ptr(h["covs_com"]), 0, 0, int(bool(tile_cull)), 0, 0, None)
@@ -207,83 +212,31 @@ class _NativeRasterizer:
         _capi.call("fdgs_sh_backward_batch", dev, B, scenes, ins, outs)
 
     @staticmethod
-    def _backward_call(dev, scene, bin_, bout, grad_accum, guard=True):
-        """fdgs_rasterize_backward.  A failed call may have left partial sums behind: ``grad_accum`` -- the caller's persistent accumulator,
-        or None -- gets its "all zero on entry" invariant back before the error goes up."""
+    def _backward_call(p, stage_mask, guard=True):
+        """fdgs_rasterize_backward, the stages ``stage_mask`` (fdgs_backward_out.stage_mask; 0: all) of the pending backward ``p``.  A failed
+        call may have left partial sums behind: the caller's persistent accumulator, if there is one, gets its "all zero on entry"
+        invariant back before the error goes up."""
+        p["bout"].stage_mask = stage_mask
         try:
-            _capi.call("fdgs_rasterize_backward", dev, C.byref(scene), C.byref(bin_), C.byref(bout), guard=guard)
+            _capi.call("fdgs_rasterize_backward", p["dev"], C.byref(p["scene"]), C.byref(p["bin"]), C.byref(p["bout"]), guard=guard)
         except Exception:
-            if grad_accum is not None:
-                grad_accum.zero_()
+            if p["persistent"] is not None:
+                p["persistent"].zero_()
             raise
 
-    def backward_begin(self, *args, **kw):
-        """The blend backward of one view only (fdgs_backward_out.stage_mask = 5); same arguments as
-        ``rasterize_gaussians_backward`` (``sh_stage`` and a ``grad_accum`` of the view's own are required).  Returns the pending
-        call for ``sh_backward_batch`` / ``backward_finish``."""
-        return self.rasterize_gaussians_backward(*args, _phase="begin", **kw)
+    @staticmethod
+    def _result(p):
+        """The binding's 12-tuple of a pending backward."""
+        return tuple(p["g"][k] for k in _GRADS)
 
-    def backward_finish(self, pending):
-        """The geometry backward (stage_mask = 2) of a view begun with ``backward_begin``, after ``sh_backward_batch``; returns the
-        binding's 12-tuple."""
-        dev = pending["dev"]
-        pending["bout"].stage_mask = 2
-        self._backward_call(dev, pending["scene"], pending["bin"], pending["bout"], pending["grad_accum"])
-        g = pending["g"]
-        return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
-                g["dL_dflows"], g["dL_dts"], g["dL_dscales"], g["dL_dscales_t"], g["dL_drotations"], g["dL_drotations_r"])
-
-    def camera_backward(self, pending, want=(True, True, True, True), scale=1.0, out=None, accumulate=False):
-        """The camera gradients of a view (fdgs_camera_backward) between the two halves of its backward: ``pending`` is what
-        ``backward_begin`` returned (or the split backward's own state), the blend backward is enqueued, the geometry backward
-        (``backward_finish``) is not.  ``want``: which of (viewmatrix, projmatrix, campos, timestamp) to compute; ``out``: optional dict
-        of preallocated float32 tensors under those names ([4,4], [4,4], [3], [1]); ``accumulate``: add to their contents; ``scale``
-        multiplies the result.  Returns {name: tensor or None}.  Only reads the accumulator records."""
-        dev, scene = pending["dev"], pending["scene"]
-        names, shapes = ("viewmatrix", "projmatrix", "campos", "timestamp"), ((4, 4), (4, 4), (3,), (1,))
-        g = {}
-        for name, shape, w in zip(names, shapes, want):
-            t = out.get(name) if out else None
-            if t is not None:
-                if t.numel() != (16, 16, 3, 1)[names.index(name)] or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
-                    raise RuntimeError("fdgs: camera_backward out[%r] must be a contiguous float32 GPU tensor of shape %s" % (name, shape))
-            elif w:
-                if accumulate:
-                    raise RuntimeError("fdgs: camera_backward accumulate=True needs out[%r]" % name)
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            g[name] = t
-        nbytes = int(_capi.lib.fdgs_camera_backward_scratch(scene.P))
-        scratch = _capi.scratch(nbytes, dev)
-        cg = _capi.FdgsCameraGrads(*[_capi._ptr(g[n]) for n in names], float(scale), int(bool(accumulate)))
-        _capi.call("fdgs_camera_backward", dev, C.byref(scene), C.byref(pending["bin"]), _capi._ptr(pending["grad_accum"]), C.byref(cg),
-                   scratch.data_ptr(), nbytes)
-        return g
-
-    def rasterize_gaussians_backward(self, bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales,
-                                     scales_t, rotations, rotations_r, scale_modifier, cov3D_precomp, prefilter_var,
-                                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
-                                     dL_dout_mask, dL_dout_flow, sh, degree, degree_t, campos, timestamp,
-                                     time_duration, rot_4d, gaussian_dim, force_sh_3d, geomBuffer, R, binningBuffer,
-                                     imageBuffer, debug, *, raw_params=False, grad_out=None, accumulate=False, grad_accum=None,
-                                     after_sh=None, sh_stage=None, per_view_outputs=True, geometry_adam=None, camera=None, _phase=None):
-        """37 positional arguments and the 12-tuple result of the reference binding (rasterize_points.h:51-89).
-        Keyword-only extensions: ``raw_params`` as in the forward; ``grad_out`` maps gradient names
-        (dL_dmeans3D, dL_dsh, dL_dopacity, dL_dts, dL_dscales, dL_dscales_t, dL_drotations, dL_drotations_r) to
-        preallocated contiguous tensors the kernels write into (e.g. views of a flat gradient bucket);
-        ``accumulate``: the kernels ADD into those parameter gradients instead of overwriting them;
-        ``grad_accum``: a persistent all-zero [P,16] float32 scratch tensor owned by the caller -- the call then skips
-        its memset and leaves the tensor all zero again (fdgs_backward_out.grad_accum_clean);
-        ``after_sh``: a callable invoked between the blend + SH backward and the geometry backward (two native calls,
-        fdgs_backward_out.stage_mask): dL_dsh is final at that point, so a data-parallel caller can start its all-reduce;
-        ``sh_stage``: a [P,8] float32 scratch tensor -> deferred SH gradient (fdgs_backward_out.sh_stage): dL_dsh is not
-        touched by this call, ``_capi.sh_flush`` builds it from the stages of all views of the step;
-        ``per_view_outputs=False``: dL_dcolors, dL_dcov3D and dL_dflows are not written (NULL at the C ABI) and come back as None;
-        ``geometry_adam``: a callable evaluated right before the geometry backward is enqueued (after ``after_sh``) that returns None or
-        dict(flat, exp_avg, exp_avg_sq, lr={means3D, opacities, ts, scales, scales_t, rotations, rotations_r}, betas, eps, step): the
-        geometry backward then also takes the Adam step of the geometry parameters (fdgs_backward_out.adam; raw_params only);
-        ``camera``: a dict (optional keys want, scale, out, accumulate: ``camera_backward``'s arguments) -> the backward runs as blend + SH
-        backward, ``camera_backward``, geometry backward, and
-        leaves the four camera gradients in ``camera["grads"]`` (the per-Gaussian gradients are bit for bit those of the unsplit call)."""
+    def _prepare_backward(self, bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
+                          scale_modifier, cov3D_precomp, prefilter_var, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
+                          dL_dout_depth, dL_dout_mask, dL_dout_flow, sh, degree, degree_t, campos, timestamp, time_duration, rot_4d,
+                          gaussian_dim, force_sh_3d, geomBuffer, R, binningBuffer, imageBuffer, debug, *, raw_params=False, grad_out=None,
+                          accumulate=False, grad_accum=None, sh_stage=None, per_view_outputs=True):
+        """Validates, allocates and builds the structs of one view's backward; nothing is enqueued.  Returns the pending call every
+        phase takes: scene / bin / bout, the gradient tensors ``g``, the accumulator in use (``grad_accum``; ``persistent``: the
+        caller's, or None) and what has to stay alive until the last phase is enqueued."""
         dev = means3D.device
         # The reference always receives four dense tensors (autograd materialises zeros).  Here an image gradient may
         # be None = "no upstream gradient": the kernels then skip that term (colour-only backward when only
@@ -326,9 +279,6 @@ class _NativeRasterizer:
             raise RuntimeError("fdgs: accumulate=True needs grad_out buffers that already hold gradients")
         if not per_view_outputs:
             g["dL_dcolors"] = g["dL_dcov3D"] = g["dL_dflows"] = None
-        ptrs = [_capi._ptr(g[k]) for k in (
-            "dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dcov3D", "dL_dsh", "dL_dflows", "dL_dts",
-            "dL_dscales", "dL_dscales_t", "dL_drotations", "dL_drotations_r")]
         clean = 0
         if grad_accum is not None:
             if grad_accum.numel() != P * 16 or grad_accum.dtype != torch.float32 or not grad_accum.is_contiguous():
@@ -336,53 +286,119 @@ class _NativeRasterizer:
             g["grad_accum"], clean = grad_accum, 1
         if sh_stage is not None and (sh_stage.numel() != P * 8 or sh_stage.dtype != torch.float32 or not sh_stage.is_contiguous()):
             raise RuntimeError("fdgs: sh_stage must be a contiguous float32 tensor with %d elements" % (P * 8))
-        bout = _capi.FdgsBackwardOut(*ptrs, int(bool(accumulate)), _capi._ptr(g["grad_accum"]), clean, _capi._ptr(sh_stage), 0)
-        if _phase == "begin":
-            if sh_stage is None or grad_accum is None:
-                raise RuntimeError("fdgs: backward_begin needs sh_stage and a grad_accum of the view's own")
-            bout.stage_mask = 5   # blend backward only; the SH backward is left to sh_backward_batch
-            self._backward_call(dev, scene, bin_, bout, grad_accum)
-            return {"scene": scene, "keep": keep, "bin": bin_, "bout": bout, "g": g, "dev": dev, "grad_accum": grad_accum,
-                    "alive": (gin, radii_c, om_c, geomBuffer, binningBuffer, imageBuffer, sh_stage)}
-        adam_keep = None
+        bout = _capi.FdgsBackwardOut(*[_capi._ptr(g[k]) for k in _GRADS], int(bool(accumulate)), _capi._ptr(g["grad_accum"]), clean,
+                                     _capi._ptr(sh_stage), 0)
+        return {"scene": scene, "keep": keep, "bin": bin_, "bout": bout, "g": g, "dev": dev, "grad_accum": g["grad_accum"],
+                "persistent": grad_accum, "alive": (gin, radii_c, om_c, geomBuffer, binningBuffer, imageBuffer, sh_stage)}
 
-        def attach_adam():
-            ga = geometry_adam() if geometry_adam is not None else None
-            if ga is None:
-                return None
-            lr = ga["lr"]
-            st = _capi.FdgsGeometryAdam(_capi._ptr(ga["flat"]), _capi._ptr(ga["exp_avg"]), _capi._ptr(ga["exp_avg_sq"]), float(lr["means3D"]),
-                                        float(lr["opacities"]), float(lr.get("ts", 0.0)), float(lr["scales"]), float(lr.get("scales_t", 0.0)),
-                                        float(lr["rotations"]), float(lr.get("rotations_r", 0.0)), float(ga["betas"][0]), float(ga["betas"][1]),
-                                        float(ga["eps"]), int(ga["step"]))
-            bout.adam = C.pointer(st)
-            return (st, ga)
-        with torch.cuda.device(dev):   # one guard for the two halves of a split backward
+    def backward_begin(self, *args, **kw):
+        """The blend backward of one view only (fdgs_backward_out.stage_mask = 5; the SH backward is left to ``sh_backward_batch``); the
+        37 positional arguments of ``rasterize_gaussians_backward`` and its keywords raw_params, grad_out, accumulate, per_view_outputs,
+        ``sh_stage`` and a ``grad_accum`` of the view's own (both required).  Returns the pending call for ``sh_backward_batch`` /
+        ``camera_backward`` / ``backward_finish``."""
+        p = self._prepare_backward(*args, **kw)
+        if kw.get("sh_stage") is None or kw.get("grad_accum") is None:
+            raise RuntimeError("fdgs: backward_begin needs sh_stage and a grad_accum of the view's own")
+        self._backward_call(p, 5)
+        return p
+
+    def backward_finish(self, pending):
+        """The geometry backward (stage_mask = 2) of a view begun with ``backward_begin``, after ``sh_backward_batch``; returns the
+        binding's 12-tuple."""
+        self._backward_call(pending, 2)
+        return self._result(pending)
+
+    def camera_backward(self, pending, want=(True, True, True, True), scale=1.0, out=None, accumulate=False):
+        """The camera gradients of a view (fdgs_camera_backward) between the two halves of its backward: ``pending`` is what
+        ``backward_begin`` returned (or the split backward's own), the blend backward is enqueued, the geometry backward
+        (``backward_finish``) is not.  ``want``: which of (viewmatrix, projmatrix, campos, timestamp) to compute; ``out``: optional dict
+        of preallocated float32 tensors under those names ([4,4], [4,4], [3], [1]); ``accumulate``: add to their contents; ``scale``
+        multiplies the result.  Returns {name: tensor or None}.  Only reads the accumulator records."""
+        dev, scene = pending["dev"], pending["scene"]
+        names, shapes = ("viewmatrix", "projmatrix", "campos", "timestamp"), ((4, 4), (4, 4), (3,), (1,))
+        g = {}
+        for name, shape, w in zip(names, shapes, want):
+            t = out.get(name) if out else None
+            if t is not None:
+                if t.numel() != (16, 16, 3, 1)[names.index(name)] or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda:
+                    raise RuntimeError("fdgs: camera_backward out[%r] must be a contiguous float32 GPU tensor of shape %s" % (name, shape))
+            elif w:
+                if accumulate:
+                    raise RuntimeError("fdgs: camera_backward accumulate=True needs out[%r]" % name)
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            g[name] = t
+        nbytes = int(_capi.lib.fdgs_camera_backward_scratch(scene.P))
+        scratch = _capi.scratch(nbytes, dev)
+        cg = _capi.FdgsCameraGrads(*[_capi._ptr(g[n]) for n in names], float(scale), int(bool(accumulate)))
+        _capi.call("fdgs_camera_backward", dev, C.byref(scene), C.byref(pending["bin"]), _capi._ptr(pending["grad_accum"]), C.byref(cg),
+                   scratch.data_ptr(), nbytes)
+        return g
+
+    @staticmethod
+    def _attach_adam(p, geometry_adam):
+        """The geometry parameters' Adam step for the geometry backward of ``p`` (fdgs_backward_out.adam), asked for right before that
+        backward is enqueued; what has to outlive the call."""
+        ga = geometry_adam() if geometry_adam is not None else None
+        if ga is None:
+            return None
+        lr = ga["lr"]
+        st = _capi.FdgsGeometryAdam(_capi._ptr(ga["flat"]), _capi._ptr(ga["exp_avg"]), _capi._ptr(ga["exp_avg_sq"]), float(lr["means3D"]),
+                                    float(lr["opacities"]), float(lr.get("ts", 0.0)), float(lr["scales"]), float(lr.get("scales_t", 0.0)),
+                                    float(lr["rotations"]), float(lr.get("rotations_r", 0.0)), float(ga["betas"][0]), float(ga["betas"][1]),
+                                    float(ga["eps"]), int(ga["step"]))
+        p["bout"].adam = C.pointer(st)
+        return (st, ga)
+
+    def rasterize_gaussians_backward(self, bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales,
+                                     scales_t, rotations, rotations_r, scale_modifier, cov3D_precomp, prefilter_var,
+                                     viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color, dL_dout_depth,
+                                     dL_dout_mask, dL_dout_flow, sh, degree, degree_t, campos, timestamp,
+                                     time_duration, rot_4d, gaussian_dim, force_sh_3d, geomBuffer, R, binningBuffer,
+                                     imageBuffer, debug, *, raw_params=False, grad_out=None, accumulate=False, grad_accum=None,
+                                     after_sh=None, sh_stage=None, per_view_outputs=True, geometry_adam=None, camera=None):
+        """37 positional arguments and the 12-tuple result of the reference binding (rasterize_points.h:51-89).
+        Keyword-only extensions: ``raw_params`` as in the forward; ``grad_out`` maps gradient names
+        (dL_dmeans3D, dL_dsh, dL_dopacity, dL_dts, dL_dscales, dL_dscales_t, dL_drotations, dL_drotations_r) to
+        preallocated contiguous tensors the kernels write into (e.g. views of a flat gradient bucket);
+        ``accumulate``: the kernels ADD into those parameter gradients instead of overwriting them;
+        ``grad_accum``: a persistent all-zero [P,16] float32 scratch tensor owned by the caller -- the call then skips
+        its memset and leaves the tensor all zero again (fdgs_backward_out.grad_accum_clean);
+        ``after_sh``: a callable invoked between the blend + SH backward and the geometry backward (two native calls,
+        fdgs_backward_out.stage_mask): dL_dsh is final at that point, so a data-parallel caller can start its all-reduce;
+        ``sh_stage``: a [P,8] float32 scratch tensor -> deferred SH gradient (fdgs_backward_out.sh_stage): dL_dsh is not
+        touched by this call, ``_capi.sh_flush`` builds it from the stages of all views of the step;
+        ``per_view_outputs=False``: dL_dcolors, dL_dcov3D and dL_dflows are not written (NULL at the C ABI) and come back as None;
+        ``geometry_adam``: a callable evaluated right before the geometry backward is enqueued (after ``after_sh``) that returns None or
+        dict(flat, exp_avg, exp_avg_sq, lr={means3D, opacities, ts, scales, scales_t, rotations, rotations_r}, betas, eps, step): the
+        geometry backward then also takes the Adam step of the geometry parameters (fdgs_backward_out.adam; raw_params only);
+        ``camera``: a dict (optional keys want, scale, out, accumulate: ``camera_backward``'s arguments) -> the backward runs as blend + SH
+        backward, ``camera_backward``, geometry backward, and
+        leaves the four camera gradients in ``camera["grads"]`` (the per-Gaussian gradients are bit for bit those of the unsplit call)."""
+        p = self._prepare_backward(bg, means3D, out_means3D, radii, colors, flows_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
+                                   scale_modifier, cov3D_precomp, prefilter_var, viewmatrix, projmatrix, tan_fovx, tan_fovy, dL_dout_color,
+                                   dL_dout_depth, dL_dout_mask, dL_dout_flow, sh, degree, degree_t, campos, timestamp, time_duration, rot_4d,
+                                   gaussian_dim, force_sh_3d, geomBuffer, R, binningBuffer, imageBuffer, debug, raw_params=raw_params,
+                                   grad_out=grad_out, accumulate=accumulate, grad_accum=grad_accum, sh_stage=sh_stage,
+                                   per_view_outputs=per_view_outputs)
+        with torch.cuda.device(p["dev"]):   # one guard for the two halves of a split backward
             if after_sh is None and camera is None:
-                adam_keep = attach_adam()
-                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
+                adam_keep = self._attach_adam(p, geometry_adam)
+                self._backward_call(p, 0, guard=False)
             else:
-                bout.stage_mask = 1
-                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
+                self._backward_call(p, 1, guard=False)
                 if after_sh is not None:
                     after_sh()
                 if camera is not None:
-                    camera["grads"] = self.camera_backward({"dev": dev, "scene": scene, "bin": bin_, "grad_accum": g["grad_accum"]},
-                                                           want=camera.get("want", (True, True, True, True)), scale=camera.get("scale", 1.0),
+                    camera["grads"] = self.camera_backward(p, want=camera.get("want", (True, True, True, True)), scale=camera.get("scale", 1.0),
                                                            out=camera.get("out"), accumulate=camera.get("accumulate", False))
-                bout.stage_mask = 2
-                adam_keep = attach_adam()
-                self._backward_call(dev, scene, bin_, bout, grad_accum, guard=False)
+                adam_keep = self._attach_adam(p, geometry_adam)
+                self._backward_call(p, 2, guard=False)
         del adam_keep
-        del keep
-        return (g["dL_dmeans2D"], g["dL_dcolors"], g["dL_dopacity"], g["dL_dmeans3D"], g["dL_dcov3D"], g["dL_dsh"],
-                g["dL_dflows"], g["dL_dts"], g["dL_dscales"], g["dL_dscales_t"], g["dL_drotations"],
-                g["dL_drotations_r"])
+        return self._result(p)
 
     def mark_visible(self, means3D, viewmatrix, projmatrix):
         """rasterize_points.cu:272-291: bool[P], True where view-space z > 0.2."""
-        if not means3D.is_cuda:
-            raise RuntimeError("fdgs: means3D must live on the GPU; there is no CPU path")
+        _need_gpu(means3D)
         dev = means3D.device
         P = int(means3D.shape[0])
         present = torch.zeros((P,), dtype=torch.bool, device=dev)
@@ -395,6 +411,26 @@ class _NativeRasterizer:
 
 
 _C = _NativeRasterizer()
+_E = torch.Tensor([])   # an absent tensor: empty, on the CPU == a NULL pointer (gaussian_renderer/diff_gaussian_rasterization.py:282-300)
+
+
+def forward_args(rs, means3D, sh, opacities, ts, scales, scales_t, rotations, rotations_r, prefilter_var, colors_precomp=_E, flow_2d=_E,
+                 cov3Ds_precomp=_E):
+    """The 30 positional arguments of ``_C.rasterize_gaussians`` (and of a view of ``_C.preprocess_batch``): the one place that knows
+    their order.  ``rs``: GaussianRasterizationSettings with a float timestamp."""
+    return (rs.bg, means3D, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations, rotations_r, rs.scale_modifier,
+            cov3Ds_precomp, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, rs.image_height, rs.image_width, sh,
+            rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d,
+            rs.prefiltered, rs.debug)
+
+
+def backward_args(rs, means3D, out_means3D, radii, sh, opacities, ts, scales, scales_t, rotations, rotations_r, prefilter_var, geom, R, binb,
+                  img, g_color, g_depth, g_alpha, g_flow, colors_precomp=_E, flow_2d=_E, cov3Ds_precomp=_E):
+    """The 37 positional arguments of ``_C.rasterize_gaussians_backward`` / ``_C.backward_begin``, likewise."""
+    return (rs.bg, means3D, out_means3D, radii, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
+            rs.scale_modifier, cov3Ds_precomp, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy, g_color, g_depth,
+            g_alpha, g_flow, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim,
+            rs.force_sh_3d, geom, R, binb, img, rs.debug)
 
 
 def cpu_deep_copy_tuple(input_tuple):
@@ -436,14 +472,81 @@ class GaussianRasterizationSettings(NamedTuple):
     debug: bool
 
 
+_BLACK = {}
+
+
+def _black(device):
+    """A zero background per device, made once (and on a GPU waited for once: it is read on whichever stream renders)."""
+    z = _BLACK.get(device)
+    if z is None:
+        z = _BLACK[device] = torch.zeros(3, dtype=torch.float32, device=device)
+        if z.is_cuda:
+            torch.cuda.current_stream(device).synchronize()
+    return z
+
+
+def view_settings(viewpoint_camera, pc, pipe, bg_color, scaling_modifier=1.0):
+    """(GaussianRasterizationSettings, timestamp tensor or None) of ``pc`` seen by ``viewpoint_camera``.  With ``pipe.env_map_res`` the
+    background is black whatever ``bg_color`` says: the environment map is composited behind the Gaussians afterwards
+    (gaussian_renderer/__init__.py:41).  The timestamp of a camera under optimisation (fdgs.camera.LearnableCamera) is a 0-d tensor: the
+    settings carry its value as a float, the tensor is returned for the camera path, which gives it its gradient."""
+    cam_time = viewpoint_camera.timestamp
+    timestamp_tensor = cam_time if isinstance(cam_time, torch.Tensor) else None
+    return GaussianRasterizationSettings(
+        image_height=int(viewpoint_camera.image_height), image_width=int(viewpoint_camera.image_width),
+        tanfovx=math.tan(viewpoint_camera.FoVx * 0.5), tanfovy=math.tan(viewpoint_camera.FoVy * 0.5),
+        bg=_black(pc.get_xyz.device) if getattr(pipe, "env_map_res", 0) else bg_color, scale_modifier=scaling_modifier,
+        viewmatrix=viewpoint_camera.world_view_transform, projmatrix=viewpoint_camera.full_proj_transform,
+        sh_degree=pc.active_sh_degree, sh_degree_t=pc.active_sh_degree_t, campos=viewpoint_camera.camera_center,
+        timestamp=cam_time if timestamp_tensor is None else float(cam_time.detach()),
+        time_duration=pc.time_duration[1] - pc.time_duration[0], rot_4d=pc.rot_4d, gaussian_dim=pc.gaussian_dim,
+        force_sh_3d=pc.force_sh_3d, prefiltered=False, debug=pipe.debug), timestamp_tensor
+
+
+def time_inputs(pc, get):
+    """(t, scaling_t, rotation_r, prefilter_var) as the kernels take them from ``pc``: ``t`` / ``scaling_t`` only from a 4D model,
+    ``rotation_r`` only with ``rot_4d``, else absent; ``prefilter_var`` positive only for a 4D model, else -1.  ``get(name)`` fetches one of
+    the three where the caller keeps them: raw attributes, an optimizer's bucket views, activated getters."""
+    is_4d = pc.gaussian_dim == 4
+    return (get("t") if is_4d else _E, get("scaling_t") if is_4d else _E, get("rotation_r") if (is_4d and pc.rot_4d) else _E,
+            pc.prefilter_var if (is_4d and pc.prefilter_var > 0.0) else -1.0)
+
+
+def shaped(given, g):
+    """gradient reshaped like its input, or None when that optional input was absent"""
+    return g.reshape(given.shape) if _is_given(given) else None
+
+
+def image_gradients(rs, device, g_color, g_depth, g_alpha, g_flow):
+    """The four upstream gradients for the native backward: None = "no upstream gradient" (outputs nobody differentiates arrive as
+    None, see the native binding).  All four None: only an output without a gradient path (covs_com) was differentiated -- the
+    reference ignores that gradient, the images contribute zeros."""
+    if g_color is None and g_depth is None and g_alpha is None and g_flow is None:
+        g_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=device)
+    return g_color, g_depth, g_alpha, g_flow
+
+
+def camera_inputs(ctx, rs, viewmatrix, projmatrix, campos, timestamp_tensor):
+    """Forward half of the camera path: the camera tensors are explicit inputs of the autograd function; the settings take them
+    detached and ``ctx`` remembers how to shape their gradients."""
+    ctx.cam_meta = [None if t is None else (t.shape, t.dtype) for t in (viewmatrix, projmatrix, campos, timestamp_tensor)]
+    return detached_settings(rs._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos), timestamp_tensor)
+
+
+def camera_gradients(ctx, needs, camera):
+    """Backward half: ``camera`` is the dict the native backward left ``camera["grads"]`` in (fdgs_camera_backward, run between the
+    blend + SH backward and the geometry backward); ``needs``: the four inputs' needs_input_grad."""
+    out = ()
+    for need, name, meta in zip(needs, ("viewmatrix", "projmatrix", "campos", "timestamp"), ctx.cam_meta):
+        g = camera["grads"].get(name) if (need and meta is not None) else None
+        out += (None if g is None else g.reshape(meta[0]).to(meta[1]),)
+    return out
+
+
 def _rg_forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
                 rotations_r, cov3Ds_precomp, prefilter_var, rs):
-    native_args = (
-        rs.bg, means3D, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations, rotations_r,
-        rs.scale_modifier, cov3Ds_precomp, prefilter_var, rs.viewmatrix, rs.projmatrix, rs.tanfovx, rs.tanfovy,
-        rs.image_height, rs.image_width, sh, rs.sh_degree, rs.sh_degree_t, rs.campos, rs.timestamp,
-        rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d, rs.prefiltered, rs.debug,
-    )
+    native_args = forward_args(rs, means3D, sh, opacities, ts, scales, scales_t, rotations, rotations_r, prefilter_var, colors_precomp,
+                               flow_2d, cov3Ds_precomp)
     (num_rendered, color, flow, depth, T, radii, geomBuffer, binningBuffer, imgBuffer, covs_com,
      out_means3D) = _call_native(_C.rasterize_gaussians, native_args, rs.debug, "snapshot_fw.dump", "forward")
 
@@ -462,25 +565,14 @@ def _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow, camera=
     rs = ctx.raster_settings
     (colors_precomp, means3D, out_means3D, scales, rotations, cov3Ds_precomp, radii, sh, flow_2d, opacities, ts,
      scales_t, rotations_r, geomBuffer, binningBuffer, imgBuffer) = ctx.saved_tensors
-    if grad_out_color is None and grad_depth is None and grad_alpha is None and grad_flow is None:
-        # only covs_com was differentiated: the reference ignores that gradient, the images contribute zeros
-        grad_out_color = torch.zeros((3, rs.image_height, rs.image_width), dtype=torch.float32, device=means3D.device)
-    native_args = (
-        rs.bg, means3D, out_means3D, radii, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
-        rotations_r, rs.scale_modifier, cov3Ds_precomp, ctx.prefilter_var, rs.viewmatrix, rs.projmatrix,
-        rs.tanfovx, rs.tanfovy, grad_out_color, grad_depth, grad_alpha, grad_flow, sh, rs.sh_degree,
-        rs.sh_degree_t, rs.campos, rs.timestamp, rs.time_duration, rs.rot_4d, rs.gaussian_dim, rs.force_sh_3d,
-        geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer, rs.debug,
-    )
+    native_args = backward_args(rs, means3D, out_means3D, radii, sh, opacities, ts, scales, scales_t, rotations, rotations_r,
+                                ctx.prefilter_var, geomBuffer, ctx.num_rendered, binningBuffer, imgBuffer,
+                                *image_gradients(rs, means3D.device, grad_out_color, grad_depth, grad_alpha, grad_flow),
+                                colors_precomp, flow_2d, cov3Ds_precomp)
     fn = _C.rasterize_gaussians_backward if camera is None else (lambda *a: _C.rasterize_gaussians_backward(*a, camera=camera))
     (grad_means2D, grad_colors_precomp, grad_opacities, grad_means3D, grad_cov3Ds_precomp, grad_sh, grad_flows,
      grad_ts, grad_scales, grad_scales_t, grad_rotations, grad_rotations_r) = _call_native(
         fn, native_args, rs.debug, "snapshot_bw.dump", "backward")
-
-    def shaped(given, g):
-        """gradient reshaped like its input, or None when that optional input was absent"""
-        return g.reshape(given.shape) if _is_given(given) else None
-
     # order = forward's inputs (gaussian_renderer/diff_gaussian_rasterization.py:208-225)
     return (
         grad_means3D, grad_means2D, shaped(sh, grad_sh), shaped(colors_precomp, grad_colors_precomp),
@@ -523,21 +615,15 @@ class _RasterizeGaussiansCamera(torch.autograd.Function):
     @staticmethod
     def forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
                 rotations_r, cov3Ds_precomp, prefilter_var, raster_settings, viewmatrix, projmatrix, campos, timestamp_tensor):
-        rs = detached_settings(raster_settings._replace(viewmatrix=viewmatrix, projmatrix=projmatrix, campos=campos), timestamp_tensor)
-        ctx.cam_meta = [None if t is None else (t.shape, t.dtype) for t in (viewmatrix, projmatrix, campos, timestamp_tensor)]
         return _rg_forward(ctx, means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,
-                           rotations_r, cov3Ds_precomp, prefilter_var, rs)
+                           rotations_r, cov3Ds_precomp, prefilter_var,
+                           camera_inputs(ctx, raster_settings, viewmatrix, projmatrix, campos, timestamp_tensor))
 
     @staticmethod
     def backward(ctx, grad_out_color, grad_radii, grad_depth, grad_alpha, grad_flow, grad_covs_com):
         needs = ctx.needs_input_grad[14:18]
         camera = {"want": tuple(bool(n) for n in needs)}
-        per_gaussian = _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow, camera=camera)
-        out = []
-        for need, name, meta in zip(needs, ("viewmatrix", "projmatrix", "campos", "timestamp"), ctx.cam_meta):
-            g = camera["grads"].get(name) if (need and meta is not None) else None
-            out.append(None if g is None else g.reshape(meta[0]).to(meta[1]))
-        return per_gaussian + tuple(out)
+        return _rg_backward(ctx, grad_out_color, grad_depth, grad_alpha, grad_flow, camera=camera) + camera_gradients(ctx, needs, camera)
 
 
 def rasterize_gaussians(means3D, means2D, sh, colors_precomp, flow_2d, opacities, ts, scales, scales_t, rotations,

@@ -110,23 +110,16 @@ def _forward(model, camera, pipe, bg, tile_cull, scaling_modifier=1.0):
     """A waiting (non-lazy) forward of ``model`` seen from ``camera``; the native binding's 11-tuple."""
     from .fused import raw_forward, raw_settings
     if all(isinstance(getattr(model, a, None), torch.Tensor) for a in _RAW_ATTRS):
-        rs, (xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var) = raw_settings(camera, model, pipe, bg,
-                                                                                                                   scaling_modifier)
-        return raw_forward(rs, xyz, feats, opacity, ts, scaling, scaling_t, rotation, rotation_r, prefilter_var, tile_cull=tile_cull)
+        rs, tensors = raw_settings(camera, model, pipe, bg, scaling_modifier)
+        return raw_forward(rs, *tensors, tile_cull=tile_cull)
     # a model that only has the reference's post-activation getters
-    from .gaussian_renderer.diff_gaussian_rasterization import _C
+    from .gaussian_renderer.diff_gaussian_rasterization import _C, forward_args, time_inputs, view_settings
     if pipe.compute_cov3D_python or pipe.convert_SHs_python:
         raise ValueError("fdgs.importance covers the default pipeline only (in-kernel covariance and SH)")
-    e = torch.Tensor([])
-    is_4d = model.gaussian_dim == 4
-    prefilter_var = model.prefilter_var if (is_4d and model.prefilter_var > 0.0) else -1.0
-    return _C.rasterize_gaussians(
-        bg, model.get_xyz, e, e, model.get_opacity, model.get_t if is_4d else e, model.get_scaling, model.get_scaling_t if is_4d else e,
-        model.get_rotation, model.get_rotation_r if (is_4d and model.rot_4d) else e, scaling_modifier, e, prefilter_var, camera.world_view_transform,
-        camera.full_proj_transform, math.tan(camera.FoVx * 0.5), math.tan(camera.FoVy * 0.5), int(camera.image_height),
-        int(camera.image_width), model.get_features, model.active_sh_degree, model.active_sh_degree_t, camera.camera_center,
-        camera.timestamp, model.time_duration[1] - model.time_duration[0], model.rot_4d, model.gaussian_dim, model.force_sh_3d, False,
-        pipe.debug, tile_cull=tile_cull)
+    rs, _timestamp_tensor = view_settings(camera, model, pipe, bg, scaling_modifier)
+    ts, scaling_t, rotation_r, prefilter_var = time_inputs(model, lambda name: getattr(model, "get_" + name))
+    return _C.rasterize_gaussians(*forward_args(rs, model.get_xyz, model.get_features, model.get_opacity, ts, model.get_scaling, scaling_t,
+                                                model.get_rotation, rotation_r, prefilter_var), tile_cull=tile_cull)
 
 
 def contribution_pass(P: int, W: int, H: int, geom, binb, img, num_rendered: int, *, pix_weight=None, weight_sum=None, weight_max=None,

@@ -191,14 +191,13 @@ class Adam(torch.optim.Optimizer):
         """The contiguous ``[P, M, 3]`` SH coefficient array the model's ``_features_dc`` / ``_features_rest`` are views of."""
         return self._features
 
-    def model_tensors(self, gaussian_dim: int, rot_4d: bool):
-        """(xyz, features, opacity, t, scaling, scaling_t, rotation, rotation_r): the homed raw parameter tensors for the kernels."""
-        e = torch.Tensor([])
+    def model_tensors(self, pc):
+        """(xyz, features, opacity, t, scaling, scaling_t, rotation, rotation_r, prefilter_var): the homed raw parameter tensors of the
+        model ``pc`` for the kernels (``fdgs.fused.raw_tensors`` on the bucket views)."""
+        from .gaussian_renderer.diff_gaussian_rasterization import _E, time_inputs
         v = self._views
-        is_4d = gaussian_dim == 4
-        return (v["xyz"][0], self._features, v["opacity"][0], v["t"][0] if is_4d and "t" in v else e, v["scaling"][0],
-                v["scaling_t"][0] if is_4d and "scaling_t" in v else e, v["rotation"][0],
-                v["rotation_r"][0] if is_4d and rot_4d and "rotation_r" in v else e)
+        ts, scaling_t, rotation_r, prefilter_var = time_inputs(pc, lambda name: v[name][0] if name in v else _E)
+        return (v["xyz"][0], self._features, v["opacity"][0], ts, v["scaling"][0], scaling_t, v["rotation"][0], rotation_r, prefilter_var)
 
     @torch.no_grad()
     def backward_begin(self, rs):
