@@ -11,10 +11,10 @@
 //   compress  one lane per vertex: parent[v] = its root (the only store to parent[v] in that launch)
 // One hook pass unites everything (the swap is the linearisation point), so the second finds nothing to do; the result is checked
 // on the device whatever the memory system did in between.  A component's root is its smallest index, whatever the schedule.
-//   roots / scan / rank / assign   dense ids = the flag scan of "v is a root"
+//   roots (count / scan / emit) / assign   dense ids = the compaction (compact.h) of "v is a root"
 //   vertex count / face count      wave-aggregated integer atomics; all a `labelled` call runs (ids from an earlier call)
 //
-// Compaction, shaped as tsdf.hip's extraction: flags + counts per workgroup (vertices, faces), one scan launch, emit, emit.
+// Compaction, shaped as tsdf.hip's extraction: two passes of compact.h (vertices, faces) that share their scan launch.
 //
 // Smoothing.  pairs (vertex, 3 face + corner) -> radix_sort_pairs by vertex (stable: rows in ascending 3 face + corner; absent faces'
 // corners carry the key V and end up behind every row) -> row starts by binary search -> the two other corners of every incidence,
@@ -85,35 +85,17 @@ namespace fdgs
 		if (v < V) cc_store(parent + v, cc_find<false>(parent, v));
 	}
 
-	__global__ void __launch_bounds__(MESH_THREADS) cc_roots_kernel(const int32_t* __restrict__ parent, const int V, uint32_t* __restrict__ counts)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
-		uint32_t total;
-		block_rank<MESH_THREADS>(v < V && parent[v] == v ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) counts[blockIdx.x] = total;
-	}
-
-	// one workgroup per count array: exclusive scan in place, the total to totals[blockIdx.x]
-	struct ScanJobs { uint32_t* counts[2]; int n[2]; int32_t* totals[2]; };
-	__global__ void __launch_bounds__(MESH_SCAN_THREADS) mesh_scan_kernel(const ScanJobs jobs)
-	{
-		__shared__ uint32_t s_wave[MESH_SCAN_THREADS / WAVE];
-		const uint32_t sum = block_scan_counts<MESH_SCAN_THREADS>(jobs.counts[blockIdx.x], jobs.n[blockIdx.x], s_wave);
-		if (threadIdx.x == 0) *jobs.totals[blockIdx.x] = (int32_t)sum;
-	}
-
 	// the roots' dense ids, into their own rows of vertex_component
-	__global__ void __launch_bounds__(MESH_THREADS) cc_rank_kernel(const int32_t* __restrict__ parent, const int V, const uint32_t* __restrict__ counts,
-	                                                               int32_t* __restrict__ vertex_component)
+	struct CcRoots
 	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
-		const bool root = v < V && parent[v] == v;
-		uint32_t total;
-		const uint32_t rank = counts[blockIdx.x] + block_rank<MESH_THREADS>(root ? 1u : 0u, s_wave, total);
-		if (root) vertex_component[v] = (int32_t)rank;
-	}
+		const int32_t* parent;
+		int V;
+		int32_t* vertex_component;
+		struct Item {};
+		__host__ __device__ int size() const { return V; }
+		__device__ uint32_t count(int v, Item&, bool) const { return parent[v] == v ? 1u : 0u; }
+		__device__ void emit(int v, uint32_t root, uint32_t rank, const Item&) const { if (root) vertex_component[v] = (int32_t)rank; }
+	};
 
 	// counts[c] += 1 for every lane with valid set, one atomic per distinct c of the wave.  Every lane of the wave must call;
 	// each turn of the loop retires the first pending lane and all lanes with its c.
@@ -171,7 +153,6 @@ namespace fdgs
 		const int32_t *faces, *vertex_component;
 		const uint8_t* keep;
 		int32_t* map;                 // [V] old vertex -> new vertex, -1 for a dropped one
-		uint32_t *vcounts, *fcounts;  // [workgroups] survivors per workgroup -> (scan) the workgroup's first rank
 		int vcap, fcap;
 		float *out_vertices, *out_normals, *out_colors;
 		int32_t* out_faces;
@@ -182,56 +163,36 @@ namespace fdgs
 		const int c = a.vertex_component[v];
 		return (uint32_t)c < (uint32_t)a.C && a.keep[c] != 0;
 	}
-	__device__ __forceinline__ bool face_kept(const CompactArgs& a, int f, int& i, int& j, int& k)
+	struct CompactVertices
 	{
-		return f < a.F && face_present(a.faces, f, a.V, i, j, k) && vertex_kept(a, i);
-	}
+		CompactArgs a;
+		struct Item {};
+		__host__ __device__ int size() const { return a.V; }
+		__device__ uint32_t count(int v, Item&, bool) const { return vertex_kept(a, v) ? 1u : 0u; }
+		__device__ void emit(int v, uint32_t kept, uint32_t rank, const Item&) const
+		{
+			a.map[v] = kept ? (int32_t)rank : -1;
+			if (!kept || rank >= (uint32_t)a.vcap) return;
+			const size_t s = 3 * (size_t)v, d = 3 * (size_t)rank;
+			if (a.out_vertices) { a.out_vertices[d] = a.vertices[s]; a.out_vertices[d + 1] = a.vertices[s + 1]; a.out_vertices[d + 2] = a.vertices[s + 2]; }
+			if (a.out_normals) { a.out_normals[d] = a.normals[s]; a.out_normals[d + 1] = a.normals[s + 1]; a.out_normals[d + 2] = a.normals[s + 2]; }
+			if (a.out_colors) { a.out_colors[d] = a.colors[s]; a.out_colors[d + 1] = a.colors[s + 1]; a.out_colors[d + 2] = a.colors[s + 2]; }
+		}
+	};
 
-	__global__ void __launch_bounds__(MESH_THREADS) compact_count_vertices_kernel(const CompactArgs a)
+	struct CompactFaces
 	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
-		uint32_t total;
-		block_rank<MESH_THREADS>(v < a.V && vertex_kept(a, v) ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) a.vcounts[blockIdx.x] = total;
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) compact_count_faces_kernel(const CompactArgs a)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		int i, j, k;
-		uint32_t total;
-		block_rank<MESH_THREADS>(face_kept(a, blockIdx.x * MESH_THREADS + threadIdx.x, i, j, k) ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) a.fcounts[blockIdx.x] = total;
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) compact_vertices_kernel(const CompactArgs a)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
-		const bool kept = v < a.V && vertex_kept(a, v);
-		uint32_t total;
-		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank<MESH_THREADS>(kept ? 1u : 0u, s_wave, total);
-		if (v >= a.V) return;
-		a.map[v] = kept ? (int32_t)rank : -1;
-		if (!kept || rank >= (uint32_t)a.vcap) return;
-		const size_t s = 3 * (size_t)v, d = 3 * (size_t)rank;
-		if (a.out_vertices) { a.out_vertices[d] = a.vertices[s]; a.out_vertices[d + 1] = a.vertices[s + 1]; a.out_vertices[d + 2] = a.vertices[s + 2]; }
-		if (a.out_normals) { a.out_normals[d] = a.normals[s]; a.out_normals[d + 1] = a.normals[s + 1]; a.out_normals[d + 2] = a.normals[s + 2]; }
-		if (a.out_colors) { a.out_colors[d] = a.colors[s]; a.out_colors[d + 1] = a.colors[s + 1]; a.out_colors[d + 2] = a.colors[s + 2]; }
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) compact_faces_kernel(const CompactArgs a)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		int i, j, k;
-		const bool kept = face_kept(a, blockIdx.x * MESH_THREADS + threadIdx.x, i, j, k);
-		uint32_t total;
-		const uint32_t rank = a.fcounts[blockIdx.x] + block_rank<MESH_THREADS>(kept ? 1u : 0u, s_wave, total);
-		if (!kept || rank >= (uint32_t)a.fcap) return;
-		const size_t d = 3 * (size_t)rank;
-		a.out_faces[d] = a.map[i]; a.out_faces[d + 1] = a.map[j]; a.out_faces[d + 2] = a.map[k];
-	}
+		CompactArgs a;
+		struct Item { int i, j, k; };
+		__host__ __device__ int size() const { return a.F; }
+		__device__ uint32_t count(int f, Item& c, bool) const { return face_present(a.faces, f, a.V, c.i, c.j, c.k) && vertex_kept(a, c.i) ? 1u : 0u; }
+		__device__ void emit(int, uint32_t kept, uint32_t rank, const Item& c) const
+		{
+			if (!kept || rank >= (uint32_t)a.fcap) return;
+			const size_t d = 3 * (size_t)rank;
+			a.out_faces[d] = a.map[c.i]; a.out_faces[d + 1] = a.map[c.j]; a.out_faces[d + 2] = a.map[c.k];
+		}
+	};
 
 	// ---- smoothing ----
 	// keys[3 f + k] = corner k of face f (V for an absent face), vals[3 f + k] = 3 f + k
@@ -248,14 +209,6 @@ namespace fdgs
 			keys[3 * (size_t)f + k] = present ? (uint32_t)c[k] : (uint32_t)V;
 			vals[3 * (size_t)f + k] = 3u * (uint32_t)f + k;
 		}
-	}
-
-	// row_start[v], v in [0, V]: the first sorted position whose key is >= v (row v is [row_start[v], row_start[v + 1]))
-	__global__ void __launch_bounds__(MESH_THREADS) smooth_rows_kernel(const uint32_t* __restrict__ keys, const int n, const int V, int32_t* __restrict__ row_start)
-	{
-		const int v = blockIdx.x * MESH_THREADS + threadIdx.x;
-		if (v > V) return;
-		row_start[v] = lower_bound_u32(keys, n, (uint32_t)v);
 	}
 
 	// the other two corners of every incidence, in ascending corner index.  n_rows = row_start[V]: the incidences of present faces
@@ -441,11 +394,7 @@ extern "C" int fdgs_mesh_components(const fdgs_mesh_in* mesh, const fdgs_mesh_co
 		}
 		if (out->rounds) *out->rounds = rounds;
 		// here every parent[v] is v's root, the smallest index of its component
-		ScanJobs jobs;
-		jobs.counts[0] = jobs.counts[1] = counts; jobs.n[0] = jobs.n[1] = vb; jobs.totals[0] = jobs.totals[1] = out->n_components;
-		hipLaunchKernelGGL(cc_roots_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, counts);
-		hipLaunchKernelGGL(mesh_scan_kernel, dim3(1), dim3(MESH_SCAN_THREADS), 0, stream, jobs);
-		hipLaunchKernelGGL(cc_rank_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, counts, out->vertex_component);
+		compact_enqueue(Compaction<CcRoots>{ { parent, V, out->vertex_component }, counts, out->n_components, 1u, true }, stream);
 		hipLaunchKernelGGL(cc_assign_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, parent, V, out->vertex_component);
 	}
 	if (cv) HIP_TRY(hipMemsetAsync(cv, 0, (size_t)cap * sizeof(int32_t), stream), "fdgs_mesh_components: memset");
@@ -466,10 +415,8 @@ extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex
 {
 	const char* fn = "fdgs_mesh_compact";
 	if (const int rc = mesh_in_args(fn, mesh)) return rc;
-	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
-	CHECK_STRUCT_IN(fn, out, fdgs_surface_out);
-	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "%s: n_vertices and n_faces must not be NULL", fn);
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: capacities must not be negative", fn);
+	SurfaceOut so;
+	if (const int rc = surface_out_args(fn, out, so)) return rc;
 	if (n_components < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: n_components must not be negative", fn);
 	if (n_components > 0 && !keep) return fail(FDGS_ERR_INVALID_ARG, "%s: keep must not be NULL with n_components > 0", fn);
 	const int V = mesh->V, F = mesh->F;
@@ -478,13 +425,7 @@ extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex
 		return fail(FDGS_ERR_INVALID_ARG, "%s: an output array needs its input array", fn);
 	if (V > 0 && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	hipStream_t stream = (hipStream_t)stream_v;
-	if (V == 0)
-	{
-		// no vertex: every face is absent
-		HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_mesh_compact: memset");
-		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_mesh_compact: memset");
-		return FDGS_OK;
-	}
+	if (V == 0) return surface_out_empty(fn, out, stream);        // no vertex: every face is absent
 	const CompactLayout L = compact_layout(V, F);
 	char* base = reinterpret_cast<char*>(scratch);
 	CompactArgs a;
@@ -492,24 +433,11 @@ extern "C" int fdgs_mesh_compact(const fdgs_mesh_in* mesh, const int32_t* vertex
 	a.vertices = mesh->vertices; a.normals = mesh->normals; a.colors = mesh->colors; a.faces = mesh->faces;
 	a.vertex_component = vertex_component; a.keep = keep;
 	a.map = reinterpret_cast<int32_t*>(base + L.map);
-	a.vcounts = reinterpret_cast<uint32_t*>(base + L.vcounts);
-	a.fcounts = reinterpret_cast<uint32_t*>(base + L.fcounts);
 	a.out_vertices = out->vertices; a.out_normals = out->normals; a.out_colors = out->colors; a.out_faces = out->faces;
-	const bool any_vertex = a.out_vertices || a.out_normals || a.out_colors;
-	a.vcap = any_vertex ? out->vertex_capacity : 0;
-	a.fcap = a.out_faces ? out->face_capacity : 0;
-	const int vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
-	ScanJobs jobs;
-	jobs.counts[0] = a.vcounts; jobs.n[0] = vb; jobs.totals[0] = out->n_vertices;
-	jobs.counts[1] = a.fcounts; jobs.n[1] = fb; jobs.totals[1] = out->n_faces;
-	hipLaunchKernelGGL(compact_count_vertices_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, a);
-	if (fb > 0) hipLaunchKernelGGL(compact_count_faces_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, a);
-	hipLaunchKernelGGL(mesh_scan_kernel, dim3(2), dim3(MESH_SCAN_THREADS), 0, stream, jobs);
-	if (any_vertex || a.out_faces)
-	{
-		hipLaunchKernelGGL(compact_vertices_kernel, dim3(vb), dim3(MESH_THREADS), 0, stream, a);
-		if (a.out_faces && fb > 0) hipLaunchKernelGGL(compact_faces_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, a);
-	}
+	a.vcap = so.vcap; a.fcap = so.fcap;
+	// the faces go through the map the vertex emit writes: asked for faces alone, the vertices are emitted too (into no array)
+	compact_enqueue(Compaction<CompactVertices>{ { a }, reinterpret_cast<uint32_t*>(base + L.vcounts), out->n_vertices, 1u, so.any_vertex || a.out_faces },
+	                Compaction<CompactFaces>{ { a }, reinterpret_cast<uint32_t*>(base + L.fcounts), out->n_faces, 1u, a.out_faces != nullptr }, stream);
 	return launched("fdgs_mesh_compact");
 }
 
@@ -548,7 +476,8 @@ extern "C" int fdgs_mesh_smooth(const fdgs_mesh_in* mesh, const fdgs_mesh_smooth
 		hipLaunchKernelGGL(smooth_pairs_kernel, dim3(fb), dim3(MESH_THREADS), 0, stream, mesh->faces, F, V, keys[0], vals[0]);
 		HIP_TRY(radix_sort_pairs(keys, vals, n, 0, div_up(bits, RADIX_BITS) * RADIX_BITS, reinterpret_cast<uint32_t*>(base + L.hist), stream, &res), "fdgs_mesh_smooth: sort");
 	}
-	hipLaunchKernelGGL(smooth_rows_kernel, dim3((int)blocks_of((size_t)V + 1)), dim3(MESH_THREADS), 0, stream, keys[res], n, V, row_start);
+	hipLaunchKernelGGL(rows_from_sorted_keys_kernel<MESH_THREADS>, dim3((int)blocks_of((size_t)V + 1)), dim3(MESH_THREADS), 0, stream, keys[res], n, V,
+	                   (const int32_t*)nullptr, row_start);
 	if (F > 0)
 		hipLaunchKernelGGL(smooth_others_kernel, dim3((int)blocks_of((size_t)n)), dim3(MESH_THREADS), 0, stream, mesh->faces, vals[res], row_start, V, n, others);
 	uint8_t* boundary = out->boundary ? out->boundary : reinterpret_cast<uint8_t*>(base + L.boundary);

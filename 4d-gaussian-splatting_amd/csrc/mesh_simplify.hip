@@ -6,18 +6,17 @@
 //
 //   cells      one lane per vertex: (cell, vertex) pairs; a vertex with a non-finite coordinate carries the key nx ny nz
 //   sort       radix_sort_pairs by cell (stable: a row's members in ascending vertex index)
-//   heads      one lane per sorted position: "a row starts here", counted per workgroup
-//   scan       one workgroup: the workgroups' first ranks, the cluster count
-//   rank       vertex_map[vertex] = cluster (-1 without a cell), cluster_start[cluster] = the row's first position
+//   heads      (compact.h: count, scan, emit) one lane per sorted position: "a row starts here"; the total is the cluster count;
+//              emit: vertex_map[vertex] = cluster (-1 without a cell), cluster_start[cluster] = the row's first position
 //   -- the vertex count is known; with faces: --
 //   face keys  one lane per face: the mapped triple rotated to its smallest index, or (V, V, V) for a face that cannot survive
 //   3 x sort   by third, second, first index (the keys of the second and third sort are gathered through the order so far)
 //   unique     one lane per sorted position: keep[face] = "a candidate, and the triple differs from the previous position's"
-//   count / scan  -- the face count is known; the emitting call goes on: --
+//   kept faces (compact.h: count, scan)  -- the face count is known; the emitting call goes on: --
 //   cluster    one lane per cluster: mean position (cell units), colour, normal along the row; mean placement writes the vertex
 //   incidences / sort / rows / quadric   (quadric placement) (cluster, 3 face + corner) sorted by cluster, one lane per cluster sums
 //              its row's ten float64 numbers in order and solves the stabilised 3 x 3 system by Cramer's rule
-//   emit       one lane per face: survivors to their rank, as the mapped triple without rotation
+//   kept faces (emit)  one lane per face: survivors to their rank, as the mapped triple without rotation
 #include "mesh_common.h"
 #include <math.h>
 
@@ -39,7 +38,6 @@ namespace fdgs
 		int32_t* user_map;                  // the caller's copy of it, or NULL
 		int32_t* cluster_start;             // [V] the first sorted position of every cluster's row
 		float* mean;                        // [V, 3] every cluster's mean position in cell units
-		uint32_t *vcounts, *fcounts;        // per-workgroup counts -> (scan) first ranks
 		uint32_t* canon[3];                 // [F] each: the canonical triple
 		uint8_t* keep;                      // [F] 1 for a surviving face
 		int32_t *n_vertices, *n_faces;
@@ -84,42 +82,24 @@ namespace fdgs
 		vals[v] = (uint32_t)v;
 	}
 
-	__device__ __forceinline__ bool row_head(const uint32_t* __restrict__ keys, int i, int V, uint32_t ncells)
+	// the heads of the sorted cells' rows: position i starts a row if it has a cell and it differs from the one before
+	struct SimplifyHeads
 	{
-		return i < V && keys[i] != ncells && (i == 0 || keys[i - 1] != keys[i]);
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) simplify_heads_kernel(const SimplifyArgs a, const uint32_t* __restrict__ keys)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		uint32_t total;
-		block_rank<MESH_THREADS>(row_head(keys, blockIdx.x * MESH_THREADS + threadIdx.x, a.V, a.ncells) ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) a.vcounts[blockIdx.x] = total;
-	}
-
-	// one workgroup: counts[0 .. n) -> their exclusive scan in place, the sum to *total
-	__global__ void __launch_bounds__(MESH_SCAN_THREADS) simplify_scan_kernel(uint32_t* counts, const int n, int32_t* total)
-	{
-		__shared__ uint32_t s_wave[MESH_SCAN_THREADS / WAVE];
-		const uint32_t sum = block_scan_counts<MESH_SCAN_THREADS>(counts, n, s_wave);
-		if (threadIdx.x == 0) *total = (int32_t)sum;
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) simplify_rank_kernel(const SimplifyArgs a, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int i = blockIdx.x * MESH_THREADS + threadIdx.x;
-		const bool head = row_head(keys, i, a.V, a.ncells);
-		uint32_t total;
-		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank<MESH_THREADS>(head ? 1u : 0u, s_wave, total);
-		if (i >= a.V) return;
-		// the heads before a position that has a cell include its own row's, unless it is that head
-		const int32_t cluster = keys[i] == a.ncells ? -1 : (int32_t)(head ? rank : rank - 1u);
-		const uint32_t v = vals[i];
-		a.map[v] = cluster;
-		if (a.user_map) a.user_map[v] = cluster;
-		if (head) a.cluster_start[rank] = i;
-	}
+		SimplifyArgs a;
+		const uint32_t *keys, *vals;
+		struct Item {};
+		__host__ __device__ int size() const { return a.V; }
+		__device__ uint32_t count(int i, Item&, bool) const { return keys[i] != a.ncells && (i == 0 || keys[i - 1] != keys[i]) ? 1u : 0u; }
+		__device__ void emit(int i, uint32_t head, uint32_t rank, const Item&) const
+		{
+			// the heads before a position that has a cell include its own row's, unless it is that head
+			const int32_t cluster = keys[i] == a.ncells ? -1 : (int32_t)(head ? rank : rank - 1u);
+			const uint32_t v = vals[i];
+			a.map[v] = cluster;
+			if (a.user_map) a.user_map[v] = cluster;
+			if (head) a.cluster_start[rank] = i;
+		}
+	};
 
 	// one lane per cluster: the sums along its row, in ascending vertex index
 	__global__ void __launch_bounds__(MESH_THREADS) simplify_cluster_kernel(const SimplifyArgs a, const uint32_t* __restrict__ keys, const uint32_t* __restrict__ vals)
@@ -180,14 +160,6 @@ namespace fdgs
 			keys[3 * (size_t)f + k] = m >= 0 ? (uint32_t)m : (uint32_t)a.V;
 			vals[3 * (size_t)f + k] = 3u * (uint32_t)f + k;
 		}
-	}
-
-	// row_start[c], c in [0, C]: the first sorted incidence whose cluster is >= c
-	__global__ void __launch_bounds__(MESH_THREADS) simplify_rows_kernel(const SimplifyArgs a, const uint32_t* __restrict__ keys, const int n, int32_t* __restrict__ row_start)
-	{
-		const int c = blockIdx.x * MESH_THREADS + threadIdx.x;
-		if (c > a.V || c > *a.n_vertices) return;
-		row_start[c] = lower_bound_u32(keys, n, (uint32_t)c);
 	}
 
 	__global__ void __launch_bounds__(MESH_THREADS) simplify_quadric_kernel(const SimplifyArgs a, const uint32_t* __restrict__ cell_keys, const uint32_t* __restrict__ vals,
@@ -291,28 +263,22 @@ namespace fdgs
 		a.keep[f] = first ? 1 : 0;
 	}
 
-	__global__ void __launch_bounds__(MESH_THREADS) simplify_count_faces_kernel(const SimplifyArgs a)
+	// the faces simplify_unique_kernel kept, as their mapped triples
+	struct SimplifyFaces
 	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
-		uint32_t total;
-		block_rank<MESH_THREADS>(f < a.F && a.keep[f] ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) a.fcounts[blockIdx.x] = total;
-	}
-
-	__global__ void __launch_bounds__(MESH_THREADS) simplify_emit_faces_kernel(const SimplifyArgs a)
-	{
-		__shared__ uint32_t s_wave[MESH_THREADS / WAVE];
-		const int f = blockIdx.x * MESH_THREADS + threadIdx.x;
-		const bool kept = f < a.F && a.keep[f];
-		uint32_t total;
-		const uint32_t rank = a.fcounts[blockIdx.x] + block_rank<MESH_THREADS>(kept ? 1u : 0u, s_wave, total);
-		if (!kept || rank >= (uint32_t)a.fcap) return;
-		int i, j, k;
-		mapped_face(a, f, i, j, k);
-		const size_t d = 3 * (size_t)rank;
-		a.out_faces[d] = i; a.out_faces[d + 1] = j; a.out_faces[d + 2] = k;
-	}
+		SimplifyArgs a;
+		struct Item {};
+		__host__ __device__ int size() const { return a.F; }
+		__device__ uint32_t count(int f, Item&, bool) const { return a.keep[f] ? 1u : 0u; }
+		__device__ void emit(int f, uint32_t kept, uint32_t rank, const Item&) const
+		{
+			if (!kept || rank >= (uint32_t)a.fcap) return;
+			int i, j, k;
+			mapped_face(a, f, i, j, k);
+			const size_t d = 3 * (size_t)rank;
+			a.out_faces[d] = i; a.out_faces[d + 1] = j; a.out_faces[d + 2] = k;
+		}
+	};
 
 	// ---- host side ----
 	struct SimplifyLayout { size_t vkeys[2], vvals[2], fkeys[2], fvals[2], hist, map, cluster_start, mean, row_start, canon[3], keep, vcounts, fcounts, total; };
@@ -346,7 +312,6 @@ namespace fdgs
 		while (bits < 32 && (largest_key >> bits) != 0) bits++;
 		return div_up(bits, RADIX_BITS) * RADIX_BITS;
 	}
-	static bool finite_f(float x) { return x - x == 0.f; }
 }
 
 using namespace fdgs;
@@ -363,8 +328,6 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 	if (const int rc = mesh_in_args(fn, mesh)) return rc;
 	if (!params) return fail(FDGS_ERR_INVALID_ARG, "%s: params must not be NULL", fn);
 	CHECK_STRUCT_IN(fn, params, fdgs_mesh_simplify_params);
-	if (!out) return fail(FDGS_ERR_INVALID_ARG, "%s: out must not be NULL", fn);
-	CHECK_STRUCT_IN(fn, out, fdgs_surface_out);
 	if (!(params->cell > 0.f) || !finite_f(params->cell)) return fail(FDGS_ERR_INVALID_ARG, "%s: cell must be positive and finite", fn);
 	if (!finite_f(params->origin[0]) || !finite_f(params->origin[1]) || !finite_f(params->origin[2])) return fail(FDGS_ERR_INVALID_ARG, "%s: origin must be finite", fn);
 	if (params->nx < 1 || params->ny < 1 || params->nz < 1) return fail(FDGS_ERR_INVALID_ARG, "%s: the grid dimensions nx, ny, nz must be at least 1", fn);
@@ -372,20 +335,15 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 	if (ncells > SIMPLIFY_MAX_CELLS || ncells * params->nz > SIMPLIFY_MAX_CELLS) return fail(FDGS_ERR_INVALID_ARG, "%s: the grid must not have more than 2^30 cells", fn);
 	if (!(params->stabilise >= 0.f)) return fail(FDGS_ERR_INVALID_ARG, "%s: stabilise must not be negative or NaN", fn);
 	if (params->placement != FDGS_SIMPLIFY_MEAN && params->placement != FDGS_SIMPLIFY_QUADRIC) return fail(FDGS_ERR_INVALID_ARG, "%s: placement must be 0 (mean) or 1 (quadric)", fn);
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "%s: capacities must not be negative", fn);
-	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "%s: n_vertices and n_faces must not be NULL", fn);
+	SurfaceOut so;
+	if (const int rc = surface_out_args(fn, out, so)) return rc;
 	const int V = mesh->V, F = mesh->F;
 	if (V > 0 && !mesh->vertices) return fail(FDGS_ERR_INVALID_ARG, "%s: the mesh's vertices must not be NULL with V > 0", fn);
 	if ((out->normals && !mesh->normals) || (out->colors && !mesh->colors)) return fail(FDGS_ERR_INVALID_ARG, "%s: an output array needs its input array", fn);
 	if (V > 0 && !scratch) return fail(FDGS_ERR_INVALID_ARG, "%s: scratch must not be NULL with V > 0", fn);
 	hipStream_t stream = (hipStream_t)stream_v;
-	if (V == 0 || F == 0)
-	{
-		// no vertex: every face is absent
-		if (V == 0) HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_mesh_simplify: memset");
-		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_mesh_simplify: memset");
-		if (V == 0) return FDGS_OK;
-	}
+	if (V == 0) return surface_out_empty(fn, out, stream);        // no vertex: every face is absent
+	if (F == 0) HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_mesh_simplify: memset");
 	const SimplifyLayout L = simplify_layout(V, F);
 	char* base = reinterpret_cast<char*>(scratch);
 	auto u32 = [&](size_t off) { return reinterpret_cast<uint32_t*>(base + off); };
@@ -398,14 +356,11 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 	a.map = reinterpret_cast<int32_t*>(base + L.map); a.user_map = params->vertex_map;
 	a.cluster_start = reinterpret_cast<int32_t*>(base + L.cluster_start);
 	a.mean = reinterpret_cast<float*>(base + L.mean);
-	a.vcounts = u32(L.vcounts); a.fcounts = u32(L.fcounts);
 	for (int k = 0; k < 3; k++) a.canon[k] = u32(L.canon[k]);
 	a.keep = reinterpret_cast<uint8_t*>(base + L.keep);
 	a.n_vertices = out->n_vertices; a.n_faces = out->n_faces;
 	a.out_vertices = out->vertices; a.out_normals = out->normals; a.out_colors = out->colors; a.out_faces = out->faces;
-	const bool any_vertex = a.out_vertices || a.out_normals || a.out_colors;
-	a.vcap = any_vertex ? out->vertex_capacity : 0;
-	a.fcap = a.out_faces ? out->face_capacity : 0;
+	a.vcap = so.vcap; a.fcap = so.fcap;
 	const int vb = (int)blocks_of((size_t)V), fb = (int)blocks_of((size_t)F);
 	const dim3 T(MESH_THREADS);
 	uint32_t* hist = u32(L.hist);
@@ -418,11 +373,10 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 	hipLaunchKernelGGL(simplify_cells_kernel, dim3(vb), T, 0, stream, a, vkeys[0], vvals[0]);
 	HIP_TRY(radix_sort_pairs(vkeys, vvals, V, 0, bits_of(a.ncells), hist, stream, &vres), sort);
 	const uint32_t *cell_keys = vkeys[vres], *cell_vals = vvals[vres];
-	hipLaunchKernelGGL(simplify_heads_kernel, dim3(vb), T, 0, stream, a, cell_keys);
-	hipLaunchKernelGGL(simplify_scan_kernel, dim3(1), dim3(MESH_SCAN_THREADS), 0, stream, a.vcounts, vb, out->n_vertices);
-	hipLaunchKernelGGL(simplify_rank_kernel, dim3(vb), T, 0, stream, a, cell_keys, cell_vals);
+	compact_enqueue(Compaction<SimplifyHeads>{ { a, cell_keys, cell_vals }, u32(L.vcounts), out->n_vertices, 1u, true }, stream);
 
 	// faces: which survive
+	Compaction<SimplifyFaces> kept{ { a }, u32(L.fcounts), out->n_faces, 1u, false };
 	if (F > 0)
 	{
 		uint32_t* keys[2] = { u32(L.fkeys[0]), u32(L.fkeys[1]) };
@@ -437,12 +391,11 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 			if (component > 0) hipLaunchKernelGGL(simplify_gather_kernel, dim3(fb), T, 0, stream, a.canon[component - 1], vals[0], F, keys[0]);
 		}
 		hipLaunchKernelGGL(simplify_unique_kernel, dim3(fb), T, 0, stream, a, vals[0]);
-		hipLaunchKernelGGL(simplify_count_faces_kernel, dim3(fb), T, 0, stream, a);
-		hipLaunchKernelGGL(simplify_scan_kernel, dim3(1), dim3(MESH_SCAN_THREADS), 0, stream, a.fcounts, fb, out->n_faces);
+		compact_enqueue(kept, stream);                       // count and scan; the emit comes last
 	}
 
 	// the emitting call
-	if (any_vertex)
+	if (so.any_vertex)
 	{
 		hipLaunchKernelGGL(simplify_cluster_kernel, dim3(vb), T, 0, stream, a, cell_keys, cell_vals);
 		if (a.out_vertices && a.placement == FDGS_SIMPLIFY_QUADRIC)
@@ -457,10 +410,12 @@ extern "C" int fdgs_mesh_simplify(const fdgs_mesh_in* mesh, const fdgs_mesh_simp
 				hipLaunchKernelGGL(simplify_incidences_kernel, dim3(fb), T, 0, stream, a, keys[0], vals[0]);
 				HIP_TRY(radix_sort_pairs(keys, vals, n, 0, bits_of((uint32_t)V), hist, stream, &res), sort);
 			}
-			hipLaunchKernelGGL(simplify_rows_kernel, dim3((int)blocks_of((size_t)V + 1)), T, 0, stream, a, keys[res], n, row_start);
+			hipLaunchKernelGGL(rows_from_sorted_keys_kernel<MESH_THREADS>, dim3((int)blocks_of((size_t)V + 1)), T, 0, stream, keys[res], n, V,
+			                   (const int32_t*)out->n_vertices, row_start);
 			hipLaunchKernelGGL(simplify_quadric_kernel, dim3(vb), T, 0, stream, a, cell_keys, vals[res], row_start);
 		}
 	}
-	if (a.out_faces && F > 0) hipLaunchKernelGGL(simplify_emit_faces_kernel, dim3(fb), T, 0, stream, a);
+	kept.emit = a.out_faces != nullptr;
+	compact_emit(kept, stream);
 	return launched("fdgs_mesh_simplify");
 }

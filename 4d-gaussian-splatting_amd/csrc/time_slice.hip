@@ -7,7 +7,9 @@
 //
 // Three launches, no atomics, the output order is the input order:
 //   1 flags    one lane per Gaussian: the 17 geometry floats -> the cull decision; one ballot word per wave, one count per workgroup
-//   2 scan     one workgroup: exclusive scan of the workgroup counts (in place), n_live
+//   2 scan     one workgroup: exclusive scan of the workgroup counts (in place), n_live -- compact.h's, shared with the mesh kernels.
+//              Launches 1 and 3 are not on compact.h's frame: their ranks come from the saved ballot words, not from a block scan,
+//              so the write pass neither derives the cull decision again nor touches a culled Gaussian.
 //   3 write    one lane per Gaussian: rank = workgroup start + the earlier waves' counts + the ballot bits below the lane; the
 //              geometry is derived again (68 bytes read per Gaussian instead of 44 written and read back) and stored at the rank;
 //              then the wave walks its OUTPUT rows linearly -- they are contiguous -- and folds the SH rows of its live Gaussians,
@@ -22,6 +24,7 @@
 #include "fdgs_common.h"
 #include "fdgs_math.h"
 #include "sh_eval.h"
+#include "compact.h"
 
 namespace fdgs
 {
@@ -80,7 +83,7 @@ namespace fdgs
 		o.opacity *= marginal_t;
 	}
 
-	constexpr int SLICE_THREADS = 256;
+	constexpr int SLICE_THREADS = COMPACT_THREADS;       // one count per workgroup, as compact_scan takes them
 	constexpr int SLICE_WAVES = SLICE_THREADS / WAVE;
 	static_assert(WAVE == 64 && SLICE_THREADS % WAVE == 0, "one 64-bit ballot word per wave");
 
@@ -107,40 +110,6 @@ namespace fdgs
 			for (int w = 0; w < SLICE_WAVES; w++) total += s_cnt[w];
 			a.counts[blockIdx.x] = total;
 		}
-	}
-
-	constexpr int SCAN_THREADS = 1024;
-	__global__ void __launch_bounds__(SCAN_THREADS) slice_scan_kernel(uint32_t* __restrict__ counts, const int n, int32_t* __restrict__ n_live)
-	{
-		__shared__ uint32_t s_wave[SCAN_THREADS / WAVE];
-		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		uint32_t carry = 0;
-		for (int base = 0; base < n; base += SCAN_THREADS)
-		{
-			const int i = base + (int)threadIdx.x;
-			const uint32_t v = i < n ? counts[i] : 0u;
-			uint32_t x = v;
-#pragma unroll
-			for (int d = 1; d < WAVE; d <<= 1)
-			{
-				const uint32_t y = __shfl_up(x, d);
-				if (lane >= d) x += y;
-			}
-			if (lane == WAVE - 1) s_wave[wave] = x;
-			__syncthreads();
-			uint32_t before = 0, total = 0;
-#pragma unroll
-			for (int w = 0; w < SCAN_THREADS / WAVE; w++)
-			{
-				const uint32_t c = s_wave[w];
-				if (w < wave) before += c;
-				total += c;
-			}
-			if (i < n) counts[i] = carry + before + x - v;
-			carry += total;
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) *n_live = (int32_t)carry;
 	}
 
 	// ---- cov3D = R diag(s^2) R^T: cyclic Jacobi on the symmetric 3x3 (double: the result is as good as its fp32 rounding) ----
@@ -341,7 +310,7 @@ namespace fdgs
 		a.masks = reinterpret_cast<unsigned long long*>(scratch);
 		a.counts = reinterpret_cast<uint32_t*>(reinterpret_cast<char*>(scratch) + align_up((size_t)nb * SLICE_WAVES * sizeof(unsigned long long)));
 		hipLaunchKernelGGL(slice_flag_kernel, dim3(nb), dim3(SLICE_THREADS), 0, stream, a);
-		hipLaunchKernelGGL(slice_scan_kernel, dim3(1), dim3(SCAN_THREADS), 0, stream, a.counts, nb, out.n_live);
+		compact_scan(ScanJob{ a.counts, nb, 1u, out.n_live }, stream);
 		const bool vec = (reinterpret_cast<uintptr_t>(in.shs) & 15) == 0 && (reinterpret_cast<uintptr_t>(out.shs) & 15) == 0 && (3 * in.M) % 4 == 0;
 		if (vec) hipLaunchKernelGGL(slice_write_kernel<4>, dim3(nb), dim3(SLICE_THREADS), 0, stream, a);
 		else hipLaunchKernelGGL(slice_write_kernel<1>, dim3(nb), dim3(SLICE_THREADS), 0, stream, a);

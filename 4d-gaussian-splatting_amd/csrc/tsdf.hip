@@ -9,15 +9,14 @@
 // Every update is the same sequence of float32 operations whether it is the first of a chunk or not, and a float32 survives the trip
 // through memory unchanged: any chunking is bit-identical to one call per view.  No atomics.  A voxel no view reaches is not written.
 //
-// Extraction, shaped as time_slice.hip: flag + count per workgroup, a one-workgroup scan, emit.
-//   1 cells     one lane per voxel = per cell whose lowest corner it is: active?  -> map[voxel] = 0 / -1, vertices per workgroup
-//   2 edges     one lane per voxel: how many of its three +x / +y / +z grid edges give a quad (four active cells: the map) -> per workgroup
-//   3 scan      exclusive scans of both count arrays (one workgroup each), n_vertices, n_faces
-//   4 vertices  rank = workgroup start + rank in the workgroup; map[voxel] = rank; the vertex is computed and stored below the capacity
-//   5 faces     the quads of a voxel's edges, through the map, at 2 * (quad rank)
+// Extraction: two passes of compact.h, one lane per voxel each, that share their scan launch.
+//   1 cells     (count) a voxel = the cell whose lowest corner it is: active?  -> map[voxel] = 0 / -1, vertices per workgroup
+//   2 edges     (count) how many of the voxel's three +x / +y / +z grid edges give a quad (four active cells: the map) -> per workgroup
+//   3 scan      exclusive scans of both count arrays (one workgroup each), n_vertices, n_faces = 2 x the quads
+//   4 vertices  (emit) rank = workgroup start + rank in the workgroup; map[voxel] = rank; the vertex is computed and stored below the capacity
+//   5 faces     (emit) the quads of a voxel's edges, through the map, at 2 * (quad rank)
 // A count-only call stops after 3.  Float32 in the operation order of the written statement (built with FP contraction off).
-#include "fdgs_common.h"
-#include "block_scan.h"
+#include "mesh_common.h"
 #include <math.h>
 
 namespace fdgs
@@ -119,7 +118,6 @@ namespace fdgs
 		const float *tsdf, *weight, *color;
 		float min_weight;
 		int32_t* map;                 // [n] per cell (indexed by its lowest corner's voxel): -1 inactive, else 0 and later the vertex index
-		uint32_t *vcounts, *fcounts;  // [workgroups] vertices / quads per workgroup -> (scan) the workgroup's first rank
 		int vcap, fcap;
 		float *vertices, *normals, *colors;
 		int32_t* faces;
@@ -136,13 +134,52 @@ namespace fdgs
 		return idx + (m & 1) + ((m >> 1) & 1) * a.nx + (m >> 2) * a.nx * a.ny;
 	}
 
-	__global__ void __launch_bounds__(TSDF_THREADS) surf_cells_kernel(const SurfArgs a)
+	// what surf_edges finds at a voxel: which edges give a quad, the four cells around each, and whether the voxel itself is inside
+	struct SurfQuads
 	{
-		__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
-		const int idx = blockIdx.x * TSDF_THREADS + threadIdx.x;
-		bool active = false;
-		if (idx < a.n)
+		bool quad[3], inside0;
+		int cells[3][4];
+	};
+
+	// which of the voxel's three grid edges (towards +x, +y, +z) give a quad; returns how many
+	__device__ __forceinline__ uint32_t surf_edges(const SurfArgs& a, int idx, SurfQuads& q)
+	{
+		q.quad[0] = q.quad[1] = q.quad[2] = false;
+		q.inside0 = false;
+		const int i = idx % a.nx, jk = idx / a.nx, j = jk % a.ny, k = jk / a.ny;
+		const int c[3] = { i, j, k }, d[3] = { a.nx, a.ny, a.nz }, st[3] = { 1, a.nx, a.nx * a.ny };
+		if (!surf_known(a, idx)) return 0;
+		q.inside0 = a.tsdf[idx] < 0.f;
+		uint32_t count = 0;
+#pragma unroll
+		for (int ax = 0; ax < 3; ax++)
 		{
+			const int b = (ax + 1) % 3, e = (ax + 2) % 3;
+			if (!(c[ax] < d[ax] - 1 && c[b] >= 1 && c[b] <= d[b] - 2 && c[e] >= 1 && c[e] <= d[e] - 2)) continue;
+			const int v1 = idx + st[ax];
+			if (!surf_known(a, v1) || (a.tsdf[v1] < 0.f) == q.inside0) continue;
+			// the four cells around the edge, counter-clockwise seen from +ax (b x e = ax)
+			q.cells[ax][0] = a.map[idx - st[b] - st[e]];
+			q.cells[ax][1] = a.map[idx - st[e]];
+			q.cells[ax][2] = a.map[idx];
+			q.cells[ax][3] = a.map[idx - st[b]];
+			q.quad[ax] = q.cells[ax][0] >= 0 && q.cells[ax][1] >= 0 && q.cells[ax][2] >= 0 && q.cells[ax][3] >= 0;
+			count += q.quad[ax] ? 1u : 0u;
+		}
+		return count;
+	}
+
+	// the cells that carry a vertex.  The count pass decides it and leaves map[voxel] = 0 / -1 (the edges pass reads that); the emit
+	// pass reads the decision back from the map and replaces it by the vertex index.
+	struct SurfVertices
+	{
+		SurfArgs a;
+		struct Item {};
+		__host__ __device__ int size() const { return a.n; }
+		__device__ uint32_t count(int idx, Item&, bool emitting) const
+		{
+			if (emitting) return a.map[idx] >= 0 ? 1u : 0u;
+			bool active = false;
 			const int i = idx % a.nx, jk = idx / a.nx, j = jk % a.ny, k = jk / a.ny;
 			if (i < a.nx - 1 && j < a.ny - 1 && k < a.nz - 1)
 			{
@@ -158,160 +195,100 @@ namespace fdgs
 				active = all && inside > 0 && inside < 8;
 			}
 			a.map[idx] = active ? 0 : -1;
+			return active ? 1u : 0u;
 		}
-		uint32_t total;
-		block_rank<TSDF_THREADS>(active ? 1u : 0u, s_wave, total);
-		if (threadIdx.x == 0) a.vcounts[blockIdx.x] = total;
-	}
-
-	// which of the voxel's three grid edges (towards +x, +y, +z) give a quad; returns how many
-	__device__ __forceinline__ uint32_t surf_edges(const SurfArgs& a, int idx, bool (&quad)[3], int (&cells)[3][4], bool& inside0)
-	{
-		quad[0] = quad[1] = quad[2] = false;
-		inside0 = false;
-		if (idx >= a.n) return 0;
-		const int i = idx % a.nx, jk = idx / a.nx, j = jk % a.ny, k = jk / a.ny;
-		const int c[3] = { i, j, k }, d[3] = { a.nx, a.ny, a.nz }, st[3] = { 1, a.nx, a.nx * a.ny };
-		if (!surf_known(a, idx)) return 0;
-		inside0 = a.tsdf[idx] < 0.f;
-		uint32_t count = 0;
-#pragma unroll
-		for (int ax = 0; ax < 3; ax++)
+		__device__ void emit(int idx, uint32_t active, uint32_t rank, const Item&) const
 		{
-			const int b = (ax + 1) % 3, e = (ax + 2) % 3;
-			if (!(c[ax] < d[ax] - 1 && c[b] >= 1 && c[b] <= d[b] - 2 && c[e] >= 1 && c[e] <= d[e] - 2)) continue;
-			const int v1 = idx + st[ax];
-			if (!surf_known(a, v1) || (a.tsdf[v1] < 0.f) == inside0) continue;
-			// the four cells around the edge, counter-clockwise seen from +ax (b x e = ax)
-			cells[ax][0] = a.map[idx - st[b] - st[e]];
-			cells[ax][1] = a.map[idx - st[e]];
-			cells[ax][2] = a.map[idx];
-			cells[ax][3] = a.map[idx - st[b]];
-			quad[ax] = cells[ax][0] >= 0 && cells[ax][1] >= 0 && cells[ax][2] >= 0 && cells[ax][3] >= 0;
-			count += quad[ax] ? 1u : 0u;
-		}
-		return count;
-	}
-
-	__global__ void __launch_bounds__(TSDF_THREADS) surf_edges_kernel(const SurfArgs a)
-	{
-		__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
-		bool quad[3], inside0;
-		int cells[3][4];
-		const uint32_t nq = surf_edges(a, blockIdx.x * TSDF_THREADS + threadIdx.x, quad, cells, inside0);
-		uint32_t total;
-		block_rank<TSDF_THREADS>(nq, s_wave, total);
-		if (threadIdx.x == 0) a.fcounts[blockIdx.x] = total;
-	}
-
-	// workgroup 0: vertices, workgroup 1: quads.  Exclusive scan in place; the totals to *n_vertices and (two triangles per quad) *n_faces.
-	constexpr int SURF_SCAN_THREADS = 1024;
-	__global__ void __launch_bounds__(SURF_SCAN_THREADS) surf_scan_kernel(uint32_t* __restrict__ vcounts, uint32_t* __restrict__ fcounts, const int n,
-	                                                                      int32_t* __restrict__ n_vertices, int32_t* __restrict__ n_faces)
-	{
-		__shared__ uint32_t s_wave[SURF_SCAN_THREADS / WAVE];
-		const uint32_t carry = block_scan_counts<SURF_SCAN_THREADS>(blockIdx.x == 0 ? vcounts : fcounts, n, s_wave);
-		if (threadIdx.x == 0)
-		{
-			if (blockIdx.x == 0) *n_vertices = (int32_t)carry;
-			else *n_faces = (int32_t)(2u * carry);
-		}
-	}
-
-	__global__ void __launch_bounds__(TSDF_THREADS) surf_vertices_kernel(const SurfArgs a)
-	{
-		__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
-		const int idx = blockIdx.x * TSDF_THREADS + threadIdx.x;
-		const bool active = idx < a.n && a.map[idx] >= 0;
-		uint32_t total;
-		const uint32_t rank = a.vcounts[blockIdx.x] + block_rank<TSDF_THREADS>(active ? 1u : 0u, s_wave, total);
-		if (!active) return;
-		a.map[idx] = (int32_t)rank;
-		if (rank >= (uint32_t)a.vcap) return;
-		float tv[8];
+			if (!active) return;
+			a.map[idx] = (int32_t)rank;
+			if (rank >= (uint32_t)a.vcap) return;
+			float tv[8];
 #pragma unroll
-		for (int m = 0; m < 8; m++) tv[m] = a.tsdf[surf_corner(a, idx, m)];
-		// the 12 edges, axis by axis: corner m0 (without the axis bit) to m0 | axis bit
-		float sx = 0.f, sy = 0.f, sz = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
-		int crossings = 0;
-		const size_t plane = (size_t)a.n;
+			for (int m = 0; m < 8; m++) tv[m] = a.tsdf[surf_corner(a, idx, m)];
+			// the 12 edges, axis by axis: corner m0 (without the axis bit) to m0 | axis bit
+			float sx = 0.f, sy = 0.f, sz = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+			int crossings = 0;
+			const size_t plane = (size_t)a.n;
 #pragma unroll
-		for (int ax = 0; ax < 3; ax++)
-		{
-#pragma unroll
-			for (int q = 0; q < 4; q++)
+			for (int ax = 0; ax < 3; ax++)
 			{
-				const int lo = q & 1, hi = q >> 1;                 // the two other bits, in ascending bit order
-				const int m0 = ax == 0 ? (lo << 1) | (hi << 2) : (ax == 1 ? lo | (hi << 2) : lo | (hi << 1));
-				const int m1 = m0 | (1 << ax);
-				const float fa = tv[m0], fb = tv[m1];
-				if ((fa < 0.f) == (fb < 0.f)) continue;
-				const float t = fa / (fa - fb);
-				sx += ax == 0 ? t : (float)(m0 & 1);
-				sy += ax == 1 ? t : (float)((m0 >> 1) & 1);
-				sz += ax == 2 ? t : (float)(m0 >> 2);
-				crossings++;
-				if (a.colors && a.color)
+#pragma unroll
+				for (int q = 0; q < 4; q++)
 				{
-					const int v0 = surf_corner(a, idx, m0), v1 = surf_corner(a, idx, m1);
-					const float r0 = a.color[v0], g0 = a.color[plane + v0], b0 = a.color[2 * plane + v0];
-					const float r1 = a.color[v1], g1 = a.color[plane + v1], b1 = a.color[2 * plane + v1];
-					cr += r0 + t * (r1 - r0);
-					cg += g0 + t * (g1 - g0);
-					cb += b0 + t * (b1 - b0);
+					const int lo = q & 1, hi = q >> 1;                 // the two other bits, in ascending bit order
+					const int m0 = ax == 0 ? (lo << 1) | (hi << 2) : (ax == 1 ? lo | (hi << 2) : lo | (hi << 1));
+					const int m1 = m0 | (1 << ax);
+					const float fa = tv[m0], fb = tv[m1];
+					if ((fa < 0.f) == (fb < 0.f)) continue;
+					const float t = fa / (fa - fb);
+					sx += ax == 0 ? t : (float)(m0 & 1);
+					sy += ax == 1 ? t : (float)((m0 >> 1) & 1);
+					sz += ax == 2 ? t : (float)(m0 >> 2);
+					crossings++;
+					if (a.colors && a.color)
+					{
+						const int v0 = surf_corner(a, idx, m0), v1 = surf_corner(a, idx, m1);
+						const float r0 = a.color[v0], g0 = a.color[plane + v0], b0 = a.color[2 * plane + v0];
+						const float r1 = a.color[v1], g1 = a.color[plane + v1], b1 = a.color[2 * plane + v1];
+						cr += r0 + t * (r1 - r0);
+						cg += g0 + t * (g1 - g0);
+						cb += b0 + t * (b1 - b0);
+					}
 				}
 			}
-		}
-		const float nf = (float)crossings;                        // >= 3 in an active cell
-		const int i = idx % a.nx, jk = idx / a.nx, j = jk % a.ny, k = jk / a.ny;
-		const size_t r = (size_t)rank;
-		if (a.vertices)
-		{
-			a.vertices[3 * r + 0] = a.ox + (((float)i + 0.5f) + sx / nf) * a.s;
-			a.vertices[3 * r + 1] = a.oy + (((float)j + 0.5f) + sy / nf) * a.s;
-			a.vertices[3 * r + 2] = a.oz + (((float)k + 0.5f) + sz / nf) * a.s;
-		}
-		if (a.colors)
-		{
-			a.colors[3 * r + 0] = cr / nf; a.colors[3 * r + 1] = cg / nf; a.colors[3 * r + 2] = cb / nf;
-		}
-		if (a.normals)
-		{
-			// the trilinear gradient at the cell centre: the mean of the four corner differences per axis
-			const float gx = (((tv[1] - tv[0]) + (tv[3] - tv[2])) + ((tv[5] - tv[4]) + (tv[7] - tv[6]))) * 0.25f;
-			const float gy = (((tv[2] - tv[0]) + (tv[3] - tv[1])) + ((tv[6] - tv[4]) + (tv[7] - tv[5]))) * 0.25f;
-			const float gz = (((tv[4] - tv[0]) + (tv[5] - tv[1])) + ((tv[6] - tv[2]) + (tv[7] - tv[3]))) * 0.25f;
-			const float len2 = (gx * gx + gy * gy) + gz * gz;
-			float nx = 0.f, ny = 0.f, nz = 0.f;
-			if (len2 > 1e-20f)
+			const float nf = (float)crossings;                        // >= 3 in an active cell
+			const int i = idx % a.nx, jk = idx / a.nx, j = jk % a.ny, k = jk / a.ny;
+			const size_t r = (size_t)rank;
+			if (a.vertices)
 			{
-				const float len = sqrtf(len2);
-				nx = gx / len; ny = gy / len; nz = gz / len;
+				a.vertices[3 * r + 0] = a.ox + (((float)i + 0.5f) + sx / nf) * a.s;
+				a.vertices[3 * r + 1] = a.oy + (((float)j + 0.5f) + sy / nf) * a.s;
+				a.vertices[3 * r + 2] = a.oz + (((float)k + 0.5f) + sz / nf) * a.s;
 			}
-			a.normals[3 * r + 0] = nx; a.normals[3 * r + 1] = ny; a.normals[3 * r + 2] = nz;
+			if (a.colors)
+			{
+				a.colors[3 * r + 0] = cr / nf; a.colors[3 * r + 1] = cg / nf; a.colors[3 * r + 2] = cb / nf;
+			}
+			if (a.normals)
+			{
+				// the trilinear gradient at the cell centre: the mean of the four corner differences per axis
+				const float gx = (((tv[1] - tv[0]) + (tv[3] - tv[2])) + ((tv[5] - tv[4]) + (tv[7] - tv[6]))) * 0.25f;
+				const float gy = (((tv[2] - tv[0]) + (tv[3] - tv[1])) + ((tv[6] - tv[4]) + (tv[7] - tv[5]))) * 0.25f;
+				const float gz = (((tv[4] - tv[0]) + (tv[5] - tv[1])) + ((tv[6] - tv[2]) + (tv[7] - tv[3]))) * 0.25f;
+				const float len2 = (gx * gx + gy * gy) + gz * gz;
+				float nx = 0.f, ny = 0.f, nz = 0.f;
+				if (len2 > 1e-20f)
+				{
+					const float len = sqrtf(len2);
+					nx = gx / len; ny = gy / len; nz = gz / len;
+				}
+				a.normals[3 * r + 0] = nx; a.normals[3 * r + 1] = ny; a.normals[3 * r + 2] = nz;
+			}
 		}
-	}
+	};
 
-	__global__ void __launch_bounds__(TSDF_THREADS) surf_faces_kernel(const SurfArgs a)
+	// the quads of a voxel's three edges, two triangles each
+	struct SurfFaces
 	{
-		__shared__ uint32_t s_wave[TSDF_THREADS / WAVE];
-		bool quad[3], inside0;
-		int cells[3][4];
-		const uint32_t nq = surf_edges(a, blockIdx.x * TSDF_THREADS + threadIdx.x, quad, cells, inside0);
-		uint32_t total;
-		uint32_t rank = a.fcounts[blockIdx.x] + block_rank<TSDF_THREADS>(nq, s_wave, total);
-#pragma unroll
-		for (int ax = 0; ax < 3; ax++)
+		SurfArgs a;
+		typedef SurfQuads Item;
+		__host__ __device__ int size() const { return a.n; }
+		__device__ uint32_t count(int idx, Item& q, bool) const { return surf_edges(a, idx, q); }
+		__device__ void emit(int, uint32_t, uint32_t rank, const Item& q) const
 		{
-			if (!quad[ax]) continue;
-			// counter-clockwise seen from +ax: the normal points to +ax, right where this end is the inside one
-			const int q0 = cells[ax][0], q1 = inside0 ? cells[ax][1] : cells[ax][3], q2 = cells[ax][2], q3 = inside0 ? cells[ax][3] : cells[ax][1];
-			const size_t f = 2 * (size_t)rank;
-			if (f < (size_t)a.fcap) { a.faces[3 * f + 0] = q0; a.faces[3 * f + 1] = q1; a.faces[3 * f + 2] = q2; }
-			if (f + 1 < (size_t)a.fcap) { a.faces[3 * f + 3] = q0; a.faces[3 * f + 4] = q2; a.faces[3 * f + 5] = q3; }
-			rank++;
+#pragma unroll
+			for (int ax = 0; ax < 3; ax++)
+			{
+				if (!q.quad[ax]) continue;
+				// counter-clockwise seen from +ax: the normal points to +ax, right where this end is the inside one
+				const int q0 = q.cells[ax][0], q1 = q.inside0 ? q.cells[ax][1] : q.cells[ax][3], q2 = q.cells[ax][2], q3 = q.inside0 ? q.cells[ax][3] : q.cells[ax][1];
+				const size_t f = 2 * (size_t)rank;
+				if (f < (size_t)a.fcap) { a.faces[3 * f + 0] = q0; a.faces[3 * f + 1] = q1; a.faces[3 * f + 2] = q2; }
+				if (f + 1 < (size_t)a.fcap) { a.faces[3 * f + 3] = q0; a.faces[3 * f + 4] = q2; a.faces[3 * f + 5] = q3; }
+				rank++;
+			}
 		}
-	}
+	};
 
 	// scratch of fdgs_surface_extract for n voxels: the cells' vertex indices and the per-block vertex / face counts
 	struct SurfaceLayout { size_t map, vcounts, fcounts, total; };
@@ -319,14 +296,13 @@ namespace fdgs
 	{
 		SurfaceLayout L;
 		ScratchCursor c;
-		const size_t nb = (n + TSDF_THREADS - 1) / TSDF_THREADS;
+		const size_t nb = compact_blocks(n);
 		L.map = c.take(n * sizeof(int32_t));
 		L.vcounts = c.take(nb * sizeof(uint32_t));
 		L.fcounts = c.take(nb * sizeof(uint32_t));
 		L.total = c.o;
 		return L;
 	}
-	static bool finite_f(float v) { return fabsf(v) < INFINITY; }
 	static bool positive_f(float v) { return v > 0.f && v < INFINITY; }
 
 	// FDGS_OK: the volume is fine and `v` is filled in; otherwise the entry point `fn` fails with what is wrong with it
@@ -395,21 +371,12 @@ extern "C" int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_we
 {
 	TsdfVol vol;
 	if (const int rc = tsdf_volume_args("fdgs_surface_extract", volume, vol)) return rc;
-	if (!out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: out must not be NULL");
-	CHECK_STRUCT_IN("fdgs_surface_extract", out, fdgs_surface_out);
-	if (!out->n_vertices || !out->n_faces) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: n_vertices and n_faces must not be NULL");
-	if (out->vertex_capacity < 0 || out->face_capacity < 0) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: capacities must not be negative");
+	SurfaceOut so;
+	if (const int rc = surface_out_args("fdgs_surface_extract", out, so)) return rc;
 	if (min_weight != min_weight) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: min_weight must not be NaN");
 	hipStream_t stream = (hipStream_t)stream_v;
-	if (vol.nx < 2 || vol.ny < 2 || vol.nz < 2)
-	{
-		// no cell: nothing is launched that indexes the volume
-		HIP_TRY(hipMemsetAsync(out->n_vertices, 0, sizeof(int32_t), stream), "fdgs_surface_extract: memset");
-		HIP_TRY(hipMemsetAsync(out->n_faces, 0, sizeof(int32_t), stream), "fdgs_surface_extract: memset");
-		return FDGS_OK;
-	}
+	if (vol.nx < 2 || vol.ny < 2 || vol.nz < 2) return surface_out_empty("fdgs_surface_extract", out, stream);   // no cell: nothing is launched that indexes the volume
 	if (!scratch) return fail(FDGS_ERR_INVALID_ARG, "fdgs_surface_extract: scratch must not be NULL");
-	const int nb = div_up(vol.n, TSDF_THREADS);
 	SurfArgs a;
 	a.nx = vol.nx; a.ny = vol.ny; a.nz = vol.nz; a.n = vol.n;
 	a.ox = vol.ox; a.oy = vol.oy; a.oz = vol.oz; a.s = vol.s;
@@ -418,19 +385,10 @@ extern "C" int fdgs_surface_extract(const fdgs_tsdf_volume* volume, float min_we
 	const SurfaceLayout L = surface_layout((size_t)vol.n);
 	char* base = reinterpret_cast<char*>(scratch);
 	a.map = reinterpret_cast<int32_t*>(base + L.map);
-	a.vcounts = reinterpret_cast<uint32_t*>(base + L.vcounts);
-	a.fcounts = reinterpret_cast<uint32_t*>(base + L.fcounts);
 	a.vertices = out->vertices; a.normals = out->normals; a.colors = out->colors; a.faces = out->faces;
-	const bool any_vertex = a.vertices || a.normals || a.colors;
-	a.vcap = any_vertex ? out->vertex_capacity : 0;
-	a.fcap = a.faces ? out->face_capacity : 0;
-	hipLaunchKernelGGL(surf_cells_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
-	hipLaunchKernelGGL(surf_edges_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
-	hipLaunchKernelGGL(surf_scan_kernel, dim3(2), dim3(SURF_SCAN_THREADS), 0, stream, a.vcounts, a.fcounts, nb, out->n_vertices, out->n_faces);
-	if (any_vertex || a.faces)
-	{
-		hipLaunchKernelGGL(surf_vertices_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
-		if (a.faces) hipLaunchKernelGGL(surf_faces_kernel, dim3(nb), dim3(TSDF_THREADS), 0, stream, a);
-	}
+	a.vcap = so.vcap; a.fcap = so.fcap;
+	// the faces go through the map the vertex emit writes: asked for faces alone, the vertices are emitted too (into no array)
+	compact_enqueue(Compaction<SurfVertices>{ { a }, reinterpret_cast<uint32_t*>(base + L.vcounts), out->n_vertices, 1u, so.any_vertex || a.faces },
+	                Compaction<SurfFaces>{ { a }, reinterpret_cast<uint32_t*>(base + L.fcounts), out->n_faces, 2u, a.faces != nullptr }, stream);
 	return launched("fdgs_surface_extract");
 }

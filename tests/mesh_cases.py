@@ -2,8 +2,9 @@
 their references.  A case is built once (lru_cache) and never modified.
 
 The smallest shapes at which the kernels can go wrong: nothing at all, vertices without faces, one triangle, one vertex past a
-workgroup (257) and past a scan chunk (1025), a long chain in permuted and in natural numbering (the union-find's worst and best
+workgroup (257) and past four (1025), a long chain in permuted and in natural numbering (the union-find's worst and best
 case), equal components, absent faces, a fan of valence 80 (a row longer than a wave), a vertex of valence 1 and one in no face.
+One case is past a scan chunk: a chunk is 1024 workgroup counts, 262 144 elements, and "v262145" has one vertex more.
 """
 import functools
 
@@ -51,6 +52,20 @@ def blocks(V, seed, block=37, per_block=30):
         faces.append(rng.integers(lo, hi, (per_block, 3)))
     faces = rng.permutation(np.concatenate(faces))
     return make_mesh(rng.uniform(-1, 1, (V, 3)), faces, seed=seed)
+
+
+SCAN_CHUNK = 1024 * 256              # elements whose workgroup counts fill one chunk of the scan: one more needs its carry
+
+
+def islands(V, seed, groups=96, block=12, per_group=4):
+    """V vertices, nearly all in no face; ``groups`` windows of ``block`` consecutive vertices spread evenly over [0, V), the last one
+    ending at V - 1, each with ``per_group`` faces inside it.  A few hundred faces: the sequential union-find of the oracle takes them
+    in no time, the kernels' vertex scans run over all V."""
+    rng = np.random.default_rng(seed)
+    los = np.linspace(0, V - block, groups).astype(np.int64)
+    faces = np.concatenate([lo + np.stack([rng.permutation(block)[:3] for _ in range(per_group)]) for lo in los])
+    faces[-1] = [V - 1, V - 3, V - 2]
+    return make_mesh(rng.uniform(-1, 1, (V, 3)), rng.permutation(faces), seed=seed)
 
 
 def fan(rim, closed, seed=5):
@@ -142,6 +157,8 @@ def topology_case(name):
         return blocks(257, seed=257)
     if name == "v1025":
         return blocks(1025, seed=1025)
+    if name == "v262145":
+        return islands(SCAN_CHUNK + 1, seed=262145)
     if name == "strip_permuted":
         return strip(5000, permute_seed=11)
     if name == "strip_natural":
@@ -157,6 +174,7 @@ def topology_case(name):
 
 TOPOLOGY_CASES = ("sphere", "random", "min_weight", "empty", "no_faces", "triangle", "v257", "v1025", "strip_permuted", "strip_natural",
                   "equal_pair", "absent", "absent_random")
+CHUNK_CASES = ("v262145",)           # past a scan chunk: V = 1025 workgroups of vertices, F = 2 workgroups of faces (GPU tests only)
 CLEAN_CHOICES = ({}, {"keep_largest": 1}, {"keep_largest": 3, "min_faces": 5}, {"min_faces": 25})
 
 

@@ -6,6 +6,7 @@ cell and one across three, strips of 257 and 1025 vertices (one position past a 
 and permuted numbering on a grid of 92 160 cells (ten sort chunks, a third radix pass), a closed sphere at two cell sizes, a cube with
 sharp edges, two coincident sheets of opposite winding, literal and rotated duplicate faces, absent faces with a NaN and an Inf vertex,
 vertices exactly on cell boundaries, vertices outside the grid, a grid one cell thick, a fan of valence 80, faces of zero area.
+None of these is past a scan chunk (1024 workgroup counts, 262 144 elements); "grid_chunk", a flat grid of 262 145 vertices, is.
 """
 import functools
 
@@ -62,6 +63,9 @@ def cube(m=12, seed=41):
                     faces += [[q[0], q[1], q[2]], [q[0], q[2], q[3]]]
     verts = np.array(sorted(pos, key=pos.get), np.float64) / m
     return mc.make_mesh(verts, faces, seed=seed)
+
+
+CHUNK_GRID = (481, 545)               # 481 x 545 = 262 145 vertices = mc.SCAN_CHUNK + 1
 
 
 def _duplicates():
@@ -139,6 +143,8 @@ def case(name):
         return auto(mc.fan(80, True), 0.3)
     if name == "zero_area":
         return auto(_zero_area(), 0.5)
+    if name == "grid_chunk":
+        return auto(mc.grid(*CHUNK_GRID), 0.25)
     raise KeyError(name)
 
 
@@ -148,6 +154,10 @@ STABILISE = 1e-3
 # (case, placement, stabilise): every case under both placements, and stabilise = 0 where every cluster's A has full rank
 RUNS = tuple((n, p, STABILISE) for n in CASES for p in (so.MEAN, so.QUADRIC)) + (("sphere_coarse", so.QUADRIC, 0.0),)
 RUN_IDS = ["%s-%s-s%g" % (n, "quadric" if p else "mean", s) for n, p, s in RUNS]
+# past a scan chunk (1024 workgroup counts = 262 144 elements; GPU tests only): the head pass runs over the V = 262 145 sorted
+# positions (1025 counts), the face pass over F = 522 240 faces (2040 counts); about 42 000 clusters, fewer than a chunk of heads
+CHUNK_RUNS = (("grid_chunk", so.QUADRIC, STABILISE),)
+CHUNK_RUN_IDS = ["%s-%s-s%g" % (n, "quadric" if p else "mean", s) for n, p, s in CHUNK_RUNS]
 
 
 @functools.lru_cache(maxsize=None)

@@ -108,6 +108,8 @@ def plane_case():
 # ---- float32 volumes for the extraction ----
 EXTRACT_SHAPES = [(17, 9, 33), (2, 2, 2), (5, 1, 4)]
 EXTRACT_KINDS = ["sphere", "plane_slab", "random", "min_weight"]
+# past a scan chunk (1024 workgroup counts = 262 144 voxels; the shapes above are a few thousand voxels, a few workgroups): GPU tests only
+CHUNK_SHAPE, CHUNK_KINDS = (65, 64, 64), ["sphere", "random"]
 SPHERE_CENTRE, SPHERE_RADIUS = (0.37, 0.22, 0.41), 3.1       # offset from the volume's centre and radius, in voxels
 
 

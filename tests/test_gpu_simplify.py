@@ -42,7 +42,7 @@ def _simplify_guarded(mesh, origin, h, dims, placement, stabilise, vcap, fcap, d
     return [int(c) for c in counts[0].cpu()], res
 
 
-@pytest.mark.parametrize("name,placement,stabilise", sc.RUNS, ids=sc.RUN_IDS)
+@pytest.mark.parametrize("name,placement,stabilise", sc.RUNS + sc.CHUNK_RUNS, ids=sc.RUN_IDS + sc.CHUNK_RUN_IDS)
 def test_simplify_against_the_statement(name, placement, stabilise, gpu_device):
     from fdgs import surface
     m, origin, h, dims = sc.case(name)
@@ -79,7 +79,8 @@ def test_simplify_against_the_statement(name, placement, stabilise, gpu_device):
 
 
 # the cases whose grid is the one simplify() chooses by itself
-AUTO = ("no_faces", "strip257", "strip1025", "sphere_fine", "sphere_coarse", "two_sheets", "duplicates", "unusable", "fan", "zero_area")
+AUTO = ("no_faces", "strip257", "strip1025", "sphere_fine", "sphere_coarse", "two_sheets", "duplicates", "unusable", "fan", "zero_area",
+        "grid_chunk")
 
 
 @pytest.mark.parametrize("name,placement", [("sphere_fine", so.QUADRIC), ("strip_permuted", so.MEAN), ("unusable", so.QUADRIC)])

@@ -135,6 +135,33 @@ def test_live_set_and_values_against_the_float64_statement(gpu_device, P, rot_4d
     assert sl.P == P and sl.shs.shape == (sl.n, 16, 3) and sl.scales.shape == (sl.n, 3) and sl.rotations.shape == (sl.n, 4)
 
 
+CHUNK_P = 1024 * 256 + 1   # the scan takes 1024 workgroup counts per chunk: one Gaussian past a scan chunk
+
+
+def test_live_set_past_a_scan_chunk(gpu_device, rot_4d=True):
+    """P = 262 145 at SH degree 0, about half of it live: 1025 workgroup counts, the last one behind the scan's first chunk.  n_live
+    and ``index`` against the float64 statement off its cull cliff; the rows' own values at the bar of the smaller cases."""
+    from fdgs.slice import time_slice
+    scene = make_scene(CHUNK_P, rot_4d)
+    model = make_model(scene, gpu_device)
+    with torch.no_grad():
+        model._t[-1] = scene["timestamp"]          # the one Gaussian of the last workgroup is live: its rank is the scan's carry
+    sl = time_slice(model, scene["timestamp"])
+    o = oracle_of(model, scene["timestamp"])
+    assert o["cliff"].sum() <= 0.01 * CHUNK_P and o["live"][-1] and not o["cliff"][-1]
+    index = sl.index.cpu().numpy().astype(np.int64)
+    assert sl.n == index.size and 0.25 * CHUNK_P < sl.n < 0.75 * CHUNK_P
+    assert (np.diff(index) > 0).all() and index[0] >= 0 and index[-1] < CHUNK_P
+    got = np.zeros(CHUNK_P, bool)
+    got[index] = True
+    sure = ~o["cliff"]
+    assert np.array_equal(got[sure], o["live"][sure])
+    assert index[-1] == CHUNK_P - 1
+    for t, want in ((sl.xyz, o["xyz"]), (sl.cov3D, o["cov6"]), (sl.opacity, o["opacity"])):
+        w = want[index]
+        assert np.abs(t.cpu().numpy() - w).max() <= 1e-5 * max(1.0, np.abs(w).max())
+
+
 GUARD = 64
 NAN_BITS = 0x7FC00000
 SENTINEL = -7

@@ -136,6 +136,18 @@ def _extract_guarded(volume, min_weight, vcap, fcap, dev, with_arrays=True):
 @pytest.mark.parametrize("dims", sc.EXTRACT_SHAPES, ids=["%dx%dx%d" % d for d in sc.EXTRACT_SHAPES])
 @pytest.mark.parametrize("kind", sc.EXTRACT_KINDS)
 def test_extract_against_the_statement(kind, dims, gpu_device):
+    _check_extract(kind, dims, gpu_device)
+
+
+@pytest.mark.parametrize("kind", sc.CHUNK_KINDS)
+def test_extract_past_a_scan_chunk(kind, gpu_device):
+    """266 240 voxels = 1040 workgroup counts per scan, 16 of them behind the first chunk of 1024.  The sphere sits in the middle of
+    the volume: its counts reach the totals through the carry.  "random" has vertices and quads in every workgroup: the ranks of
+    the last z slice are the carry plus their own."""
+    _check_extract(kind, sc.CHUNK_SHAPE, gpu_device)
+
+
+def _check_extract(kind, dims, gpu_device):
     from fdgs import surface
     vol, mw = sc.extract_case(kind, dims)
     m64, m32 = sc.extract_refs(kind, dims)
