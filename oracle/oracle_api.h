@@ -126,6 +126,11 @@ void oracle_free(oracle_io* io);
  * blend's per-pixel test (forward.cu:585-590) in this oracle's arithmetic.  tuples [n][10] = mean x, y, conic xx, xy, yy,
  * opacity, rx0, rx1, ry0, ry1. */
 int oracle_block_any_pixel_passes(int n, const float* tuples, uint8_t* out);
+/* Port oracle only (test helper for the per-Gaussian chain): everything behind the blend backward's per-Gaussian sums (cov2D backward,
+ * SH / 4D-SH backward, covariance backward: rasterizer_impl.cu:455-493) on sums the CALLER filled -- dL_dmean2D, dL_dconic, dL_dopacity,
+ * dL_dcolor, dL_dflows -- after an oracle_forward on io.  The other backward outputs are zero-filled first; dL_dopacity is updated in
+ * place (the marginal-opacity chain). */
+int oracle_chain(oracle_io* io);
 /* "port" or "reference" */
 const char* oracle_kind(void);
 /* Number of OS threads the oracle uses (OpenMP). */

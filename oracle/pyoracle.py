@@ -108,6 +108,16 @@ def _load(kind):
     return lib
 
 
+def have_chain(kind="port"):
+    """Does this oracle library export oracle_chain (oracle_api.h: port only)?"""
+    lib = _load(kind)
+    if not hasattr(lib, "oracle_chain"):
+        return False
+    lib.oracle_chain.argtypes = [C.POINTER(OracleIO)]
+    lib.oracle_chain.restype = C.c_int
+    return True
+
+
 def _np(x, dtype=np.float32):
     """numpy view of a torch tensor / array-like, C-contiguous, or None."""
     if x is None:
@@ -235,6 +245,32 @@ class Oracle:
         rc = self.lib.oracle_backward(C.byref(self.io))
         if rc != 0:
             raise RuntimeError("oracle_backward failed: %d" % rc)
+        if M == 0:
+            g["dL_dsh"] = np.zeros((P, 0, 3), np.float32)
+        return g
+
+    def chain(self, dL_dmean2D, dL_dconic, dL_dopacity, dL_dcolor, dL_dflows):
+        """oracle_chain (oracle_api.h; port only): everything behind the blend backward's per-Gaussian sums, on sums the caller
+        gives ([P,3], [P,4], [P], [P,3], [P,2] float32; copied) after forward().  Returns the gradient dict of backward().
+        NotImplementedError if the library has no oracle_chain (the verbatim reference build)."""
+        assert self.R is not None, "call forward() first"
+        if not have_chain(self.kind):
+            raise NotImplementedError("the %r oracle library has no oracle_chain" % self.kind)
+        P, M = self.P, self.M
+        g = self.grads = {
+            "dL_dmean2D": _np(dL_dmean2D).reshape(P, 3).copy(), "dL_dconic": _np(dL_dconic).reshape(P, 4).copy(),
+            "dL_dopacity": _np(dL_dopacity).reshape(P).copy(), "dL_dcolor": _np(dL_dcolor).reshape(P, 3).copy(),
+            "dL_dmean3D": np.zeros((P, 3), np.float32), "dL_dcov3D": np.zeros((P, 6), np.float32),
+            "dL_dsh": np.zeros((P, max(M, 1), 3), np.float32), "dL_dflows": _np(dL_dflows).reshape(P, 2).copy(),
+            "dL_dts": np.zeros((P,), np.float32), "dL_dscale": np.zeros((P, 3), np.float32),
+            "dL_dscale_t": np.zeros((P,), np.float32), "dL_drot": np.zeros((P, 4), np.float32),
+            "dL_drot_r": np.zeros((P, 4), np.float32),
+        }
+        for k, a in g.items():
+            setattr(self.io, k, _ptr(a, C.c_float))
+        rc = self.lib.oracle_chain(C.byref(self.io))
+        if rc != 0:
+            raise RuntimeError("oracle_chain failed: %d" % rc)
         if M == 0:
             g["dL_dsh"] = np.zeros((P, 0, 3), np.float32)
         return g
