@@ -48,15 +48,18 @@ def _view(buf, ptr, count, dtype):
 
 def collect_forward(res, P, W, H):
     """numpy dict of every forward output + the introspection views of the opaque buffers (fdgs_debug_views)
-    from the 11-tuple the native forward returns."""
+    from the 11-tuple the native forward returns.  A lazy forward returns R = -1, and sparse lists are not packed back to back: the list
+    array is then read up to the end of the last range."""
     from fdgs import _capi
     (R, color, flow, depth, T, radii, geom, binb, img, covs_com, out_means3D) = res
     v = _capi.FdgsDebugView()
-    rc = _capi.lib.fdgs_debug_views(P, W, H, R, _capi._ptr(geom), _capi._ptr(binb), _capi._ptr(img), C.byref(v))
+    rc = _capi.lib.fdgs_debug_views(P, W, H, max(R, 0), _capi._ptr(geom), _capi._ptr(binb), _capi._ptr(img), C.byref(v))
     assert rc == 0, _capi.last_error()
     ntiles = ((W + 15) // 16) * ((H + 15) // 16)
     torch.cuda.synchronize()
     rec = _view(geom, v.records, P * 12, torch.float32).reshape(P, 12).cpu().numpy()
+    ranges = _view(img, v.ranges, ntiles * 2, torch.int32).reshape(ntiles, 2).cpu().numpy().astype(np.uint32)
+    extent = R if R >= 0 else (int(ranges[:, 1].max()) if ntiles else 0)
     out = {
         "R": R,
         "out_color": color.cpu().numpy(), "out_flow": flow.cpu().numpy(), "out_depth": depth.cpu().numpy()[0],
@@ -66,8 +69,8 @@ def collect_forward(res, P, W, H):
         "cov3D": _view(geom, v.cov3D, P * 6, torch.float32).reshape(P, 6).cpu().numpy(),
         "tiles_touched": _view(geom, v.tiles_touched, P, torch.int32).cpu().numpy().astype(np.uint32),
         "clamped_bits": _view(geom, v.clamped, P, torch.uint8).cpu().numpy(),
-        "point_list": _view(binb, v.point_list, R, torch.int32).cpu().numpy().astype(np.uint32),
-        "ranges": _view(img, v.ranges, ntiles * 2, torch.int32).reshape(ntiles, 2).cpu().numpy().astype(np.uint32),
+        "point_list": _view(binb, v.point_list, extent, torch.int32).cpu().numpy().astype(np.uint32),
+        "ranges": ranges,
         "n_contrib": _view(img, v.n_contrib, W * H, torch.int32).reshape(H, W).cpu().numpy().astype(np.uint32),
         "final_T": _view(img, v.final_T, W * H, torch.float32).reshape(H, W).cpu().numpy(),
         "tile_order": _view(img, v.tile_order, ntiles, torch.int32).cpu().numpy().astype(np.int64),
