@@ -24,18 +24,14 @@ from typing import Optional, Tuple
 
 import torch
 
+from .layout import group_table, group_view, segment
+
+# the reference's group name -> our parameter tensor, as fdgs.layout has it, under the names this module has always exported
+GROUPS_3D = group_table(3, False)
+GROUPS_4D = group_table(4, False)[len(GROUPS_3D):]
+GROUP_ROT4D = group_table(4, True)[len(GROUPS_3D) + len(GROUPS_4D):]
+_split = lambda name, t: group_view(t, name)  # noqa: E731
 from .train_host import FlatAdam, GaussianParams
-
-# the reference's group name -> our parameter tensor (f_dc / f_rest: the head and the rest of every _features row)
-GROUPS_3D = (("xyz", "_xyz"), ("f_dc", "_features"), ("f_rest", "_features"), ("opacity", "_opacity"), ("scaling", "_scaling"),
-             ("rotation", "_rotation"))
-GROUPS_4D = (("t", "_t"), ("scaling_t", "_scaling_t"))
-GROUP_ROT4D = (("rotation_r", "_rotation_r"),)
-
-
-def group_table(gaussian_dim: int, rot_4d: bool):
-    """``training_setup``'s parameter groups, in its order (scene/gaussian_model.py:336-353)."""
-    return GROUPS_3D + (GROUPS_4D if gaussian_dim == 4 else ()) + (GROUP_ROT4D if gaussian_dim == 4 and rot_4d else ())
 
 
 def reference_sh_channels(sh_degree: int, sh_degree_t: int, gaussian_dim: int, force_sh_3d: bool) -> int:
@@ -45,15 +41,6 @@ def reference_sh_channels(sh_degree: int, sh_degree_t: int, gaussian_dim: int, f
     if sh_degree_t == 0:
         return [1, 6, 16, 33][sh_degree]
     return (sh_degree + 1) ** 2 * (sh_degree_t + 1)
-
-
-def _split(name, t):
-    """A [P, M, 3]-shaped view of one of our tensors as the reference's group sees it."""
-    if name == "f_dc":
-        return t[:, :1, :]
-    if name == "f_rest":
-        return t[:, 1:, :]
-    return t
 
 
 def capture(model: GaussianParams, optimizer: Optional[FlatAdam], stats=None, spatial_lr_scale: float = 1.0) -> tuple:
@@ -75,25 +62,23 @@ def capture(model: GaussianParams, optimizer: Optional[FlatAdam], stats=None, sp
         lr = seg[pname]["lr_head"] if gname == "f_dc" else seg[pname]["lr"]
         groups.append(dict(params=[torch.nn.Parameter(torch.empty(0))], lr=float(lr), name=gname))
         if optimizer is not None and optimizer.step_count > 0:
-            b, e = model.offsets[pname]
-            shape = model.params[pname].shape
             state[k] = {"step": torch.tensor(float(optimizer.step_count)),
-                        "exp_avg": clone(_split(gname, optimizer.exp_avg[b:e].view(shape))),
-                        "exp_avg_sq": clone(_split(gname, optimizer.exp_avg_sq[b:e].view(shape)))}
+                        "exp_avg": clone(group_view(segment(optimizer.exp_avg, model, pname), gname)),
+                        "exp_avg_sq": clone(group_view(segment(optimizer.exp_avg_sq, model, pname), gname))}
     # the remaining keys of a group (amsgrad, weight_decay, foreach ...) as THIS torch's Adam fills them in
     opt_dict = {"state": state, "param_groups": torch.optim.Adam(groups, lr=0.0, betas=tuple(betas), eps=eps).state_dict()["param_groups"]}
 
     max_radii2D = clone(stats.max_radii2D) if stats is not None else zeros(P)
     xyz_acc = clone(stats.xyz_gradient_accum) if stats is not None else zeros(P, 1)
     denom = clone(stats.denom) if stats is not None else zeros(P, 1)
-    head = (int(model.active_sh_degree), clone(p["_xyz"]), clone(p["_features"][:, :1, :]), clone(p["_features"][:, 1:, :]),
+    head = (int(model.active_sh_degree), clone(p["_xyz"]), clone(group_view(p["_features"], "f_dc")), clone(group_view(p["_features"], "f_rest")),
             clone(p["_scaling"]), clone(p["_rotation"]), clone(p["_opacity"]), max_radii2D, xyz_acc)
     if model.gaussian_dim == 3:
         return head + (denom, opt_dict, float(spatial_lr_scale))
     t_acc = clone(stats.t_gradient_accum) if stats is not None else zeros(P, 1)
     env = getattr(model, "env_map", None)
     return head + (t_acc, denom, opt_dict, float(spatial_lr_scale), clone(p["_t"]), clone(p["_scaling_t"]),
-                   clone(p["_rotation_r"]) if model.rot_4d else torch.empty(0, device=dev), bool(model.rot_4d),
+                   clone(model._rotation_r) if model.rot_4d else torch.empty(0, device=dev), bool(model.rot_4d),
                    clone(env) if env is not None and env.numel() else torch.empty(0, device=dev), int(model.active_sh_degree_t))
 
 
@@ -120,7 +105,7 @@ def restore(model_args: tuple, device, *, sh_degree: int, sh_degree_t: int = 0, 
         (active, xyz, f_dc, f_rest, scaling, rotation, opacity, max_radii2D, xyz_acc, t_acc, denom, opt_dict, _scale, t, scaling_t,
          rotation_r, rot_4d, env_map, active_t) = model_args
         dim, rot_4d = 4, bool(rot_4d)
-        raw = {"_t": t, "_scaling_t": scaling_t, "_rotation_r": rotation_r if rot_4d else None}
+        raw = dict(_t=t, _scaling_t=scaling_t, _rotation_r=rotation_r if rot_4d else None)
     if (rot_4d or force_sh_3d) and dim != 4:
         raise ValueError("fdgs.checkpoint.restore: rot_4d / force_sh_3d need a 4D model (scene/gaussian_model.py:88-89)")
     M = int(f_dc.shape[1]) + int(f_rest.shape[1])
@@ -177,10 +162,8 @@ def _restore_optimizer(model, opt_dict, table) -> FlatAdam:
             steps[gname] = 0
             continue
         steps[gname] = int(float(st["step"]))
-        b, e = model.offsets[pname]
-        shape = model.params[pname].shape
         for key, flat in (("exp_avg", opt.exp_avg), ("exp_avg_sq", opt.exp_avg_sq)):
-            dst = _split(gname, flat[b:e].view(shape))
+            dst = group_view(segment(flat, model, pname), gname)
             if tuple(st[key].shape) != tuple(dst.shape):
                 raise ValueError("fdgs.checkpoint.restore: %s of group %s is %s, the parameter is %s" % (key, gname, tuple(st[key].shape), tuple(dst.shape)))
             dst.copy_(st[key].detach().to(device=flat.device, dtype=torch.float32))

@@ -25,14 +25,14 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from . import _capi
+from . import _capi, layout
 
 MAX_D = 192       # fdgs_kmeans_*: longest row
 MAX_K = 65536     # ... and largest codebook: an index fits uint16
 FORMAT_VERSION = 1
 
 # the segments of a model besides the non-DC SH rows: name -> columns ("dc" is _features[:, 0, :])
-SEGMENTS = (("_xyz", 3), ("_opacity", 1), ("_scaling", 3), ("_rotation", 4), ("_t", 1), ("_scaling_t", 1), ("_rotation_r", 4), ("dc", 3))
+SEGMENTS = tuple((s.name, s.tail[0]) for s in layout.GEOMETRY) + (("dc", layout.SEGMENTS[-1].head),)
 DEFAULT_BITS = {"_xyz": 32, "_t": 16, "_scaling": 16, "_scaling_t": 16, "_opacity": 8, "dc": 16, "_rotation": 8, "_rotation_r": 8}
 _QUATERNIONS = ("_rotation", "_rotation_r")
 
@@ -230,12 +230,9 @@ def compress(model, *, codebook_size: Optional[int] = 4096, iters: int = 10, wei
             cm.tensors["sh_index"] = torch.from_numpy(index.cpu().numpy().astype(np.uint16))
     cm.meta = {
         "format": FORMAT_VERSION, "P": P, "M": M, "codebook_size": K,
-        "max_sh_degree": int(model.max_sh_degree), "max_sh_degree_t": int(model.max_sh_degree_t),
-        "active_sh_degree": int(model.active_sh_degree), "active_sh_degree_t": int(model.active_sh_degree_t),
-        "time_duration": [float(model.time_duration[0]), float(model.time_duration[1])], "gaussian_dim": int(model.gaussian_dim),
-        "rot_4d": bool(model.rot_4d), "force_sh_3d": bool(model.force_sh_3d), "prefilter_var": float(model.prefilter_var),
-        "bits": use, "lo": lo_meta, "step": step_meta,
+        **layout.settings_of(model), "bits": use, "lo": lo_meta, "step": step_meta,
     }
+    cm.meta["time_duration"] = list(cm.meta["time_duration"])
     return cm
 
 
@@ -256,10 +253,7 @@ def decompress(cm: CompressedModel, device):
     meta, T = cm.meta, cm.tensors
     P, M = int(meta["P"]), int(meta["M"])
     D = 3 * (M - 1)
-    model = GaussianParams.__new__(GaussianParams)
-    model.M = M
-    total = P * model.floats_per_gaussian()
-    model._bind(torch.empty(total, dtype=torch.float32, device=device), torch.zeros(total, dtype=torch.float32, device=device), P)
+    model = GaussianParams.empty(P, M, device)
     flat = model.flat.detach()
     for name, C in SEGMENTS:
         b = int(meta["bits"][name])
@@ -277,14 +271,7 @@ def decompress(cm: CompressedModel, device):
             decode_into(flat[o0:o1], P, C, b, q, lo, step, rows=_upload(T["sh_codebook"], device), index=index)
         else:
             decode_into(flat[o0:o1], P, C, b, q, lo, step, rows=_upload(T["sh_rest"], device))
-    model.max_sh_degree, model.max_sh_degree_t = int(meta["max_sh_degree"]), int(meta["max_sh_degree_t"])
-    model.active_sh_degree, model.active_sh_degree_t = int(meta["active_sh_degree"]), int(meta["active_sh_degree_t"])
-    model.time_duration = [float(meta["time_duration"][0]), float(meta["time_duration"][1])]
-    model.rot_4d, model.gaussian_dim, model.force_sh_3d = bool(meta["rot_4d"]), int(meta["gaussian_dim"]), bool(meta["force_sh_3d"])
-    model.prefilter_var = float(meta["prefilter_var"])
-    model.env_map = None
-    model.get_max_sh_channels = M
-    return model
+    return model.apply_settings(**{k: meta[k] for k in layout.SETTINGS})
 
 
 def _meta_bytes(cm: CompressedModel) -> bytes:

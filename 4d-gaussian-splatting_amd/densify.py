@@ -8,12 +8,12 @@ come out in the reference's order: kept originals, clones, split children (copy 
 The decisions depend only on the statistics (identical on every rank, fdgs.harness.DensificationStats) and on the
 normal samples: with the same ``generator`` seed on every rank the replicas stay identical without a broadcast.
 """
-import ctypes as C
 from typing import Dict, Optional
 
 import torch
 
-from . import _capi
+from . import _capi, layout
+from .train_host import relayout
 
 CLONE, SPLIT, PRUNE, PRUNE_CHILD = 1, 2, 4, 8
 
@@ -69,36 +69,17 @@ def densify_and_prune(model, optimizer, stats, max_grad: float, min_opacity: flo
     P_new = int(src.numel())
     n_orig, n_clone, n_child = int(idx_orig.numel()), int(idx_clone.numel()), int(child_parent.numel())
 
-    # ---- new flat buffers in one gather ----
-    per = model.floats_per_gaussian()
-    f = dict(dtype=torch.float32, device=dev)
-    new_flat, new_m, new_v = (torch.empty(P_new * per, **f) for _ in range(3))
-    rows_arr = (C.c_int32 * len(model.row_floats()))(*model.row_floats())
-    old_flat, old = model.flat, {n: model.params[n] for n in model.NAMES}
-    _capi.call("fdgs_densify_gather", dev, len(model.row_floats()), rows_arr, P, P_new, _p(src), _p(kind), _p(old_flat), _p(optimizer.exp_avg),
-               _p(optimizer.exp_avg_sq), _p(new_flat), _p(new_m), _p(new_v))
-    model._bind(new_flat, torch.zeros(P_new * per, **f), P_new)
+    # ---- new flat buffers in one gather; the statistics restart from zero after a densification (densification_postfix) and
+    # follow the rows after prune_only ----
+    old = relayout(model, optimizer, src, kind, stats=(stats,) if prune_only else ())
+    if not prune_only:
+        stats.reset_(P_new)
     if n_child:
         first = n_orig + n_clone
         parent32 = child_parent.to(torch.int32).contiguous()
         _capi.call("fdgs_densify_split", dev, n_child, int(N), int(model.rot_4d), int(model.gaussian_dim), _p(parent32), _p(child_samples),
                    _p(child_samples_t), _p(old["_xyz"]), _p(old["_t"]), _p(old["_scaling"]), _p(old["_scaling_t"]), _p(old["_rotation"]),
                    _p(old["_rotation_r"]), _p(model._xyz[first:]), _p(model._t[first:]), _p(model._scaling[first:]), _p(model._scaling_t[first:]))
-    optimizer.rebind(new_m, new_v)
-
-    # ---- statistics: restart from zero after a densification (densification_postfix), masked after prune_only ----
-    if prune_only:
-        sel = src.long()
-        stats.xyz_gradient_accum = stats.xyz_gradient_accum[sel]
-        stats.t_gradient_accum = stats.t_gradient_accum[sel]
-        stats.denom = stats.denom[sel]
-        stats.max_radii2D = stats.max_radii2D[sel]
-    else:
-        stats.xyz_gradient_accum = torch.zeros((P_new, 1), **f)
-        stats.t_gradient_accum = torch.zeros((P_new, 1), **f)
-        stats.denom = torch.zeros((P_new, 1), **f)
-        stats.max_radii2D = torch.zeros((P_new,), **f)
-    del old, old_flat
     return {"P_old": P, "P_new": P_new, "kept": n_orig, "cloned": n_clone, "split_parents": k, "children": n_child}
 
 
@@ -108,6 +89,5 @@ def reset_opacity(model, optimizer):
     op = torch.sigmoid(model._opacity)
     new = torch.minimum(op, torch.full_like(op, 0.01))
     model._opacity.copy_(torch.log(new / (1 - new)))
-    b, e = model.offsets["_opacity"]
-    optimizer.exp_avg[b:e].zero_()
-    optimizer.exp_avg_sq[b:e].zero_()
+    for moment in (optimizer.exp_avg, optimizer.exp_avg_sq):
+        layout.segment(moment, model, "_opacity").zero_()

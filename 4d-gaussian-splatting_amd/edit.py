@@ -30,7 +30,7 @@ import math
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, layout
 
 SH_M = (1, 4, 9, 16, 32, 48)   # coefficients per Gaussian the SH pass knows how to walk
 _BANDS = ((1, 4), (4, 9), (9, 16))
@@ -204,11 +204,8 @@ def isoclinic_pair(R):
 
 
 # ---- the model pass ----
-_GEOM = ("_xyz", "_t", "_scaling", "_scaling_t", "_rotation", "_rotation_r")
-
-
-def _features_of(model):
-    return model.get_features if hasattr(model, "get_features") else model._features
+# the tensors fdgs_model_transform maps, in the order of its ABI structs: means3D, ts, scales, scales_t, rotations, rotations_r, shs
+_ORDER = tuple(layout.BY_KERNEL[k].name for k in ("means3D", "ts", "scales", "scales_t", "rotations", "rotations_r", "shs"))
 
 
 def _sh_rows(D):
@@ -265,7 +262,7 @@ def transform(model, sim, *, inplace=False):
         if feats is None:
             raise ValueError("transform(inplace=True): the model must hold its SH rows as one _features tensor [P, M, 3]")
     else:
-        feats = _features_of(model)
+        feats = model.get_features if hasattr(model, "get_features") else model._features
     xyz = model._xyz
     _capi.need_gpu(xyz, "_xyz", what="the model")
     P, M = int(xyz.shape[0]), int(feats.shape[1])
@@ -276,11 +273,10 @@ def transform(model, sim, *, inplace=False):
     pv = float(model.prefilter_var)
     pv = pv * sim.a * sim.a if pv > 0.0 else pv
     have = lambda n: getattr(model, n, None) is not None and getattr(model, n).numel() > 0  # noqa: E731
-    # the segments this model's mode reads: a 3D model's time columns and _rotation_r without rot_4d are placeholders
-    used = {"_xyz": True, "_t": gd == 4 and have("_t"), "_scaling": True, "_scaling_t": gd == 4 and have("_scaling_t"), "_rotation": True,
-            "_rotation_r": rot_4d}
-    src = {n: (getattr(model, n).detach() if used[n] else None) for n in _GEOM}
-    src["_features"] = feats.detach()
+    # the segments this model's mode reads: a 3D model's time columns and _rotation_r without rot_4d are placeholders (and a 4D
+    # model may come without its time columns)
+    reads = [n for n in layout.used(gd, rot_4d) if layout.BY_NAME[n].when != layout.DIM4 or have(n)]
+    src = {n: (feats if n == "_features" else getattr(model, n)).detach() if n in reads else None for n in _ORDER}
     for n, t in src.items():
         if t is not None and (t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda):
             if inplace:
@@ -289,22 +285,13 @@ def transform(model, sim, *, inplace=False):
     if inplace:
         out, dst = model, dict(src)
     else:
-        raw = {"_xyz": src["_xyz"], "_features": src["_features"], "_opacity": model._opacity.detach().reshape(P, 1),
-               "_scaling": src["_scaling"], "_rotation": src["_rotation"]}
-        for n, shape in (("_t", (P, 1)), ("_scaling_t", (P, 1)), ("_rotation_r", (P, 4))):
-            if have(n):
-                raw[n] = getattr(model, n).detach().reshape(shape)
         # from_raw copies every segment bit for bit; the pass below then overwrites the ones it maps
-        out = GaussianParams.from_raw(
-            raw, xyz.device, max_sh_degree=int(getattr(model, "max_sh_degree", model.active_sh_degree)),
-            max_sh_degree_t=int(getattr(model, "max_sh_degree_t", model.active_sh_degree_t)), active_sh_degree=int(model.active_sh_degree),
-            active_sh_degree_t=int(model.active_sh_degree_t), time_duration=(t0, t1), rot_4d=rot_4d, gaussian_dim=gd,
-            force_sh_3d=bool(model.force_sh_3d), prefilter_var=float(model.prefilter_var))
+        raw = dict(layout.raw_of(model), **{n: src[n] for n in ("_xyz", "_features", "_scaling", "_rotation")})
+        out = GaussianParams.from_raw(raw, xyz.device, **layout.settings_of(model))
         dst = {n: (getattr(out, n).detach() if src[n] is not None else None) for n in src}
     if P > 0:
-        order = ("_xyz", "_t", "_scaling", "_scaling_t", "_rotation", "_rotation_r", "_features")
         with torch.no_grad():
-            _enqueue(sim, gd, rot_4d, M, [src[n] for n in order], [dst[n] for n in order])
+            _enqueue(sim, gd, rot_4d, M, [src[n] for n in _ORDER], [dst[n] for n in _ORDER])
     out.time_duration = duration
     out.prefilter_var = pv
     return out
@@ -337,25 +324,6 @@ def transform_camera(camera, sim):
 
 
 # ---- torch glue: subsets and unions of models ----
-def _raw_of(model):
-    P = int(model._xyz.shape[0])
-    raw = {"_xyz": model._xyz.detach(), "_features": _features_of(model).detach(), "_opacity": model._opacity.detach().reshape(P, 1),
-           "_scaling": model._scaling.detach(), "_rotation": model._rotation.detach()}
-    for n, shape in (("_t", (P, 1)), ("_scaling_t", (P, 1)), ("_rotation_r", (P, 4))):
-        t = getattr(model, n, None)
-        if t is not None and t.numel() > 0:
-            raw[n] = t.detach().reshape(shape)
-    return raw
-
-
-def _settings_of(model):
-    return dict(max_sh_degree=int(getattr(model, "max_sh_degree", model.active_sh_degree)),
-                max_sh_degree_t=int(getattr(model, "max_sh_degree_t", model.active_sh_degree_t)),
-                active_sh_degree=int(model.active_sh_degree), active_sh_degree_t=int(model.active_sh_degree_t),
-                time_duration=(float(model.time_duration[0]), float(model.time_duration[1])), rot_4d=bool(model.rot_4d),
-                gaussian_dim=int(model.gaussian_dim), force_sh_3d=bool(model.force_sh_3d), prefilter_var=float(model.prefilter_var))
-
-
 def extract(model, mask):
     """The Gaussians of ``model`` that ``mask`` selects (a bool mask [P] or an index tensor), as a new model with the same settings."""
     from .train_host import GaussianParams
@@ -365,8 +333,8 @@ def extract(model, mask):
     mask = torch.as_tensor(mask, device=dev)
     if mask.dtype == torch.bool and mask.shape != (int(model._xyz.shape[0]),):
         raise ValueError("extract: the mask must have one entry per Gaussian")
-    raw = {n: t[mask] for n, t in _raw_of(model).items()}
-    return GaussianParams.from_raw(raw, dev, **_settings_of(model))
+    raw = {n: t[mask] for n, t in layout.raw_of(model).items()}
+    return GaussianParams.from_raw(raw, dev, **layout.settings_of(model))
 
 
 def merge(models):
@@ -379,8 +347,8 @@ def merge(models):
     models = list(models)
     if not models:
         raise ValueError("merge: no models")
-    sets = [_settings_of(m) for m in models]
-    raws = [_raw_of(m) for m in models]
+    sets = [layout.settings_of(m) for m in models]
+    raws = [layout.raw_of(m) for m in models]
     first = sets[0]
     for i, (m, s, r) in enumerate(zip(models, sets, raws)):
         if getattr(m, "env_map", None) is not None:

@@ -15,7 +15,7 @@ import ctypes as C
 
 import torch
 
-from . import _capi
+from . import _capi, layout
 
 
 def _flow_in(cam, cam_to, tensors, rot_4d, gaussian_dim, raw, scaling_modifier):
@@ -38,10 +38,12 @@ def _flow_in(cam, cam_to, tensors, rot_4d, gaussian_dim, raw, scaling_modifier):
 
 
 class _GaussianFlow(torch.autograd.Function):
+    ARGS = ("means3D", "ts", "scales", "scales_t", "rotations", "rotations_r")   # the kernels' tensors (fdgs_flow_in), by fdgs.layout's kernel names
+
     @staticmethod
     def forward(ctx, means3D, ts, scales, scales_t, rotations, rotations_r, cam, cam_to, rot_4d, gaussian_dim, raw, scaling_modifier):
         given = (means3D, ts, scales, scales_t, rotations, rotations_r)
-        names = ("means3D", "ts", "scales", "scales_t", "rotations", "rotations_r")
+        names = _GaussianFlow.ARGS
         _capi.need_gpu(means3D, "means3D")
         # without rot_4d the kernels read the mean only
         tensors = [_capi._dev_f32(t.detach(), n) if (t is not None and (rot_4d or n == "means3D")) else None for t, n in zip(given, names)]
@@ -95,8 +97,5 @@ def model_flow(cam, cam_to, pc, *, raw, scaling_modifier=1.0):
     if not rot_4d:
         return gaussian_flow(cam, cam_to, pc._xyz if raw else pc.get_xyz, None, None, None, None, None, rot_4d=False,
                              gaussian_dim=int(pc.gaussian_dim), raw=raw, scaling_modifier=scaling_modifier)
-    if raw:
-        t = (pc._xyz, pc._t, pc._scaling, pc._scaling_t, pc._rotation, pc._rotation_r)
-    else:
-        t = (pc.get_xyz, pc.get_t, pc.get_scaling, pc.get_scaling_t, pc.get_rotation, pc.get_rotation_r)
+    t = [getattr(pc, layout.BY_KERNEL[k].name if raw else "get" + layout.BY_KERNEL[k].name) for k in _GaussianFlow.ARGS]
     return gaussian_flow(cam, cam_to, *t, rot_4d=True, gaussian_dim=4, raw=raw, scaling_modifier=scaling_modifier)

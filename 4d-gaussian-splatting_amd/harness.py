@@ -85,6 +85,17 @@ class DensificationStats:
         self.max_radii2D = torch.zeros((P,), **f)
         self.world = int(world_size)
 
+    def select_(self, index: torch.Tensor) -> "DensificationStats":
+        """Keeps the rows ``index``: the statistics follow a model whose rows were gathered alike (train_host.relayout)."""
+        self.xyz_gradient_accum, self.t_gradient_accum = self.xyz_gradient_accum[index], self.t_gradient_accum[index]
+        self.denom, self.max_radii2D = self.denom[index], self.max_radii2D[index]
+        return self
+
+    def reset_(self, P: int) -> "DensificationStats":
+        """Restarts from zero for a model of P Gaussians (densification_postfix)."""
+        self.__init__(P, self.denom.device, self.world)
+        return self
+
     @torch.no_grad()
     def update(self, results: Sequence[Dict[str, torch.Tensor]], t_grad: Optional[torch.Tensor], global_batch: int):
         """``results``: this rank's per-view outputs of StepPipeline.step (radii, viewspace_grad = dL/dmeans2D with the
@@ -220,8 +231,7 @@ def train(model, optimizer, cameras: Sequence, gts: Sequence[torch.Tensor], pipe
         if on_resort is not None:
             on_resort(perm)
         if stats is not None:   # everything else that is indexed by Gaussian follows the model
-            stats.xyz_gradient_accum, stats.t_gradient_accum = stats.xyz_gradient_accum[perm], stats.t_gradient_accum[perm]
-            stats.denom, stats.max_radii2D = stats.denom[perm], stats.max_radii2D[perm]
+            stats.select_(perm)
 
     start_iteration = int(start_iteration)
     if start_iteration < 0:

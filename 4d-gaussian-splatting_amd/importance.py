@@ -20,6 +20,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _capi
+from .train_host import relayout
 
 
 class ContributionStats:
@@ -95,6 +96,7 @@ class ContributionStats:
 
     def select_(self, index: torch.Tensor) -> "ContributionStats":
         """Keeps the rows ``index`` (int64, ascending for a prune): the statistics follow a model whose rows were gathered alike."""
+        index = index.to(self.weight_sum.device)
         self.weight_sum, self.weight_max = self.weight_sum[index], self.weight_max[index]
         self.hits, self.dominant = self.hits[index], self.dominant[index]
         if self.scales is not None:
@@ -212,34 +214,5 @@ def prune_by_contribution(model, optimizer, stats: ContributionStats, *, keep_fr
     P_new = int(sel.numel())
     if P_new == P:
         return {"P_old": P, "P_new": P}
-    per = model.floats_per_gaussian()
-    f = dict(dtype=torch.float32, device=dev)
-    if optimizer is None:
-        # a finished model has no moments to carry: one index-select per segment of the flat bucket
-        new_flat = torch.cat([model.params[n].detach()[sel].reshape(-1) for n in model.NAMES])
-        model._bind(new_flat, torch.zeros(P_new * per, **f), P_new)
-        _follow(dens_stats, stats, sel)
-        return {"P_old": P, "P_new": P_new}
-    src = sel.to(torch.int32).contiguous()
-    kind = torch.zeros(P_new, dtype=torch.uint8, device=dev)   # 0: the survivors keep their Adam moments
-    new_flat, new_m, new_v = (torch.empty(P_new * per, **f) for _ in range(3))
-    rows = model.row_floats()
-    rows_arr = (C.c_int32 * len(rows))(*rows)
-    old_flat = model.flat
-    _capi.call("fdgs_densify_gather", dev, len(rows), rows_arr, P, P_new, src.data_ptr(), kind.data_ptr(), old_flat.data_ptr(),
-               optimizer.exp_avg.data_ptr(), optimizer.exp_avg_sq.data_ptr(), new_flat.data_ptr(), new_m.data_ptr(), new_v.data_ptr())
-    model._bind(new_flat, torch.zeros(P_new * per, **f), P_new)
-    optimizer.rebind(new_m, new_v)
-    _follow(dens_stats, stats, sel)
-    del old_flat
+    relayout(model, optimizer, sel, stats=(stats,) if dens_stats is None else (stats, dens_stats))
     return {"P_old": P, "P_new": P_new}
-
-
-def _follow(dens_stats, stats: ContributionStats, sel: torch.Tensor) -> None:
-    """Everything else that is indexed by Gaussian follows a model cut down to the rows ``sel``."""
-    if dens_stats is not None:
-        dens_stats.xyz_gradient_accum = dens_stats.xyz_gradient_accum[sel]
-        dens_stats.t_gradient_accum = dens_stats.t_gradient_accum[sel]
-        dens_stats.denom = dens_stats.denom[sel]
-        dens_stats.max_radii2D = dens_stats.max_radii2D[sel]
-    stats.select_(sel.to(stats.weight_sum.device))

@@ -41,13 +41,12 @@ from typing import Dict, Optional
 
 import torch
 
-from . import _capi
+from . import _capi, layout
 from .train_host import FlatAdam, GaussianParams
 
-# param-group name (scene/gaussian_model.py:331-350) -> GaussianParams segment
-_GEOMETRY = {"xyz": "_xyz", "opacity": "_opacity", "scaling": "_scaling", "rotation": "_rotation", "t": "_t",
-             "scaling_t": "_scaling_t", "rotation_r": "_rotation_r"}
-_REQUIRED = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation")
+# param-group name (scene/gaussian_model.py:331-350) -> GaussianParams segment, for the groups that are a whole segment
+_GEOMETRY = {g: s.name for s in layout.GEOMETRY for g in s.groups}
+_REQUIRED = tuple(g for g, _ in layout.group_table(3, False))
 
 
 class _StageSettings:
@@ -111,7 +110,7 @@ class Adam(torch.optim.Optimizer):
                 return False
             if st["exp_avg"].data_ptr() != aptr or st["exp_avg_sq"].data_ptr() != sptr:
                 return False
-        return len([n for n in g if n in _GEOMETRY or n in ("f_dc", "f_rest")]) == len(self._homed)
+        return len([n for n in g if n in layout.BY_GROUP]) == len(self._homed)
 
     def ensure_homed(self) -> bool:
         """Moves the reference's nine parameter tensors (and their Adam state) into the flat buckets if they are not there (any
@@ -140,26 +139,13 @@ class Adam(torch.optim.Optimizer):
                 step = max(step, int(float(st["step"])))
         if self._fa is not None:
             step = max(step, self._fa.step_count)
-        gp = GaussianParams.__new__(GaussianParams)
-        gp.M = M
-        total = P * gp.floats_per_gaussian()
-        gp._bind(torch.zeros(total, dtype=torch.float32, device=dev), torch.zeros(total, dtype=torch.float32, device=dev), P)
+        gp = GaussianParams.empty(P, M, dev, zero=True)
         betas, eps = g["xyz"]["betas"], g["xyz"]["eps"]
         fa = FlatAdam(gp, betas=tuple(betas), eps=float(eps))
         fa.step_count = step
-        shapes = {"_xyz": (P, 3), "_opacity": (P, 1), "_scaling": (P, 3), "_rotation": (P, 4), "_t": (P, 1), "_scaling_t": (P, 1), "_rotation_r": (P, 4)}
-
-        def seg(buf, name):
-            b, e = gp.offsets[name]
-            return buf[b:e]
-
-        views = {}
-        for gname, seg_name in _GEOMETRY.items():
-            if gname in g:
-                views[gname] = tuple(seg(buf, seg_name).view(shapes[seg_name]) for buf in (gp.flat, gp.flat_grad, fa.exp_avg, fa.exp_avg_sq))
-        feat = tuple(seg(buf, "_features").view(P, M, 3) for buf in (gp.flat, gp.flat_grad, fa.exp_avg, fa.exp_avg_sq))
-        views["f_dc"] = tuple(t[:, :1, :] for t in feat)
-        views["f_rest"] = tuple(t[:, 1:, :] for t in feat)
+        # every group's (data, grad, exp_avg, exp_avg_sq) views of the four buckets: the geometry groups, then f_dc and f_rest
+        views = {gname: tuple(layout.group_view(layout.segment(buf, gp, s.name), gname) for buf in (gp.flat, gp.flat_grad, fa.exp_avg, fa.exp_avg_sq))
+                 for s in layout.SEGMENTS for gname in s.groups if gname in g}
         self._homed = {}
         for gname, (vd, vg, va, vs) in views.items():
             p = g[gname]["params"][0]
@@ -177,7 +163,8 @@ class Adam(torch.optim.Optimizer):
             self.state[p] = {"step": torch.tensor(float(step)), "exp_avg": va, "exp_avg_sq": vs}
             self._homed[gname] = (p, vd.data_ptr(), va.data_ptr(), vs.data_ptr())
         self._views, self._gp, self._fa = views, gp, fa
-        self._features = feat[0]
+        self._sink = {layout.BY_GROUP[gname].sink: views[gname][1] for gname in _GEOMETRY if gname in views}   # the geometry gradients' destinations
+        self._features = layout.segment(gp.flat, gp, "_features")
         self._gacc = torch.zeros((P, 16), dtype=torch.float32, device=dev)
         if self._stages is not None and (self._stages.shape[1] != P or self._stages.device != dev):
             # the Gaussians changed: staged views of the old layout cannot be applied (the reference densifies between backward() and step(), train.py:239-249: every parameter is replaced, none has a gradient, and torch.optim.Adam skips the step too)
@@ -225,10 +212,7 @@ class Adam(torch.optim.Optimizer):
                 self._dense_sh = True
             self._fresh = False
         accumulate = not self._fresh
-        sink = {"dL_dmeans3D": v["xyz"][1], "dL_dopacity": v["opacity"][1], "dL_dscales": v["scaling"][1], "dL_drotations": v["rotation"][1]}
-        for key, gname in (("dL_dts", "t"), ("dL_dscales_t", "scaling_t"), ("dL_drotations_r", "rotation_r")):
-            if gname in v:
-                sink[key] = v[gname][1]
+        sink = dict(self._sink)
         stage = None
         if self.defer_sh:
             ss = _StageSettings(rs)

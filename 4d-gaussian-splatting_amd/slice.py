@@ -26,7 +26,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from . import _capi
+from . import _capi, layout
 
 SH_ROW = 16   # coefficients per row of a slice: a full degree-3 row, zero beyond the active degree
 
@@ -64,10 +64,8 @@ def time_slice(model, timestamp, scaling_modifier=1.0, *, decompose=False, capac
     rot_4d = bool(model.rot_4d)
     f = _capi._dev_f32
     feats = f(model.get_features.detach(), "features")
-    keep = [f(t.detach(), n) for t, n in ((xyz, "_xyz"), (model._opacity, "_opacity"), (model._t, "_t"), (model._scaling, "_scaling"),
-                                          (model._scaling_t, "_scaling_t"), (model._rotation, "_rotation"))]
-    keep.append(f(model._rotation_r.detach(), "_rotation_r") if rot_4d else None)
-    means3D, opacity_raw, ts, scaling, scaling_t, rotation, rotation_r = keep
+    live = layout.used(4, rot_4d)
+    g = {s.kernel: f(getattr(model, s.name).detach(), s.name) if s.name in live else None for s in layout.GEOMETRY}   # raw, by kernel name
     prefilter_var = float(model.prefilter_var) if float(model.prefilter_var) > 0.0 else -1.0
     D, D_t = int(model.active_sh_degree), int(model.active_sh_degree_t)
     fo = dict(dtype=torch.float32, device=dev)
@@ -76,7 +74,7 @@ def time_slice(model, timestamp, scaling_modifier=1.0, *, decompose=False, capac
     o_s = torch.empty((cap, 3), **fo) if decompose else None
     o_q = torch.empty((cap, 4), **fo) if decompose else None
     n_live = torch.empty((1,), dtype=torch.int32, device=dev)
-    inputs = (means3D, feats, opacity_raw, ts, scaling, scaling_t, rotation, rotation_r)
+    inputs = (g["means3D"], feats, g["opacities"], g["ts"], g["scales"], g["scales_t"], g["rotations"], g["rotations_r"])
     _enqueue(inputs, (D, D_t, float(scaling_modifier), prefilter_var, float(timestamp), float(model.time_duration[1] - model.time_duration[0]),
                       rot_4d, bool(model.force_sh_3d)), cap, (index, o_xyz, o_cov, o_op, o_sh, o_s, o_q), n_live)
     n = int(n_live.item())

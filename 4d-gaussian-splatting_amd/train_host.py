@@ -19,15 +19,26 @@ and the RCCL bench share:
 * ``l1_loss`` / ``ssim`` / ``photometric_loss`` -- utils/loss_utils.py:17-64 semantics
   (11x11 Gaussian window, sigma 1.5, C1 = 0.01^2, C2 = 0.03^2; lambda_dssim = 0.2).
 """
+import ctypes as C
 import math
-from typing import Dict, List, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 import torch.nn.functional as F
 
+from . import layout
+
 
 def _inv_sigmoid(x):
     return torch.log(x / (1 - x))
+
+
+def _raw_from_scene(scene: Dict[str, object]) -> Dict[str, torch.Tensor]:
+    """The raw parameters of a fdgs.synth.make_scene dict (it holds post-activation tensors under the kernels' argument names)."""
+    raw = {s.name: scene[s.kernel] for s in layout.SEGMENTS}
+    raw["_opacity"] = _inv_sigmoid(raw["_opacity"].clamp(1e-6, 1 - 1e-6))
+    raw["_scaling"], raw["_scaling_t"] = torch.log(raw["_scaling"]), torch.log(raw["_scaling_t"])
+    return raw
 
 
 class GaussianParams:
@@ -39,74 +50,74 @@ class GaussianParams:
     applied per coefficient by the optimizer's segment table instead.
     """
 
-    # bucket order: the small geometry tensors first (17 floats per Gaussian), the SH coefficients last (3 M = 144): the two
-    # parts are final at different moments of a backward pass and are all-reduced separately (allreduce_and_step)
-    NAMES = ("_xyz", "_opacity", "_scaling", "_rotation", "_t", "_scaling_t", "_rotation_r", "_features")
+    NAMES = layout.NAMES   # bucket order (fdgs.layout.SEGMENTS: geometry first, the SH coefficients last)
 
     def __init__(self, scene: Dict[str, object], device):
         """``scene``: post-activation tensors from fdgs.synth.make_scene; raw parameters are their inverses."""
-        P, M = int(scene["means3D"].shape[0]), int(scene["M"])
-        shapes = {"_xyz": (P, 3), "_features": (P, M, 3), "_opacity": (P, 1), "_scaling": (P, 3), "_rotation": (P, 4),
-                  "_t": (P, 1), "_scaling_t": (P, 1), "_rotation_r": (P, 4)}
-        init = {"_xyz": scene["means3D"], "_features": scene["shs"],
-                "_opacity": _inv_sigmoid(scene["opacities"].clamp(1e-6, 1 - 1e-6)), "_scaling": torch.log(scene["scales"]),
-                "_rotation": scene["rotations"], "_t": scene["ts"], "_scaling_t": torch.log(scene["scales_t"]),
-                "_rotation_r": scene["rotations_r"]}
-        self.M = M
-        total = P * self.floats_per_gaussian()
-        self._bind(torch.empty(total, dtype=torch.float32, device=device), torch.zeros(total, dtype=torch.float32, device=device), P)
+        self._allocate(int(scene["means3D"].shape[0]), int(scene["M"]), device)
         with torch.no_grad():
-            for name in self.NAMES:
-                self.params[name].copy_(init[name].to(device).reshape(shapes[name]))
+            for name, t in _raw_from_scene(scene).items():
+                self.params[name].copy_(t.to(device).reshape(self.params[name].shape))
         # the coefficient storage (M) is laid out for these maxima (scene["max_sh_degree*"]: synth.make_scene(alloc=...), the
         # reference's state from iteration 0: scene/gaussian_model.py:65,92); a model built from a scene starts at the scene's ACTIVE
         # degrees -- all of them for a trained model; training from scratch starts at (0, 0) and ramps with oneupSHdegree()
-        self.max_sh_degree = int(scene.get("max_sh_degree", scene["sh_degree"]))
-        self.max_sh_degree_t = int(scene.get("max_sh_degree_t", scene["sh_degree_t"]))
-        self.active_sh_degree = int(scene["sh_degree"])
-        self.active_sh_degree_t = int(scene["sh_degree_t"])
-        self.time_duration = [0.0, float(scene["time_duration"])]
-        self.rot_4d, self.gaussian_dim = bool(scene["rot_4d"]), int(scene["gaussian_dim"])
-        self.force_sh_3d = bool(scene["force_sh_3d"])
-        self.prefilter_var = -1.0
+        self.apply_settings(max_sh_degree=scene.get("max_sh_degree", scene["sh_degree"]),
+                            max_sh_degree_t=scene.get("max_sh_degree_t", scene["sh_degree_t"]), active_sh_degree=scene["sh_degree"],
+                            active_sh_degree_t=scene["sh_degree_t"], time_duration=(0.0, scene["time_duration"]), rot_4d=scene["rot_4d"],
+                            gaussian_dim=scene["gaussian_dim"], force_sh_3d=scene["force_sh_3d"])
+
+    def _allocate(self, P: int, M: int, device, zero: bool = False):
+        self.M = M
+        total = P * self.floats_per_gaussian()
+        self._bind((torch.zeros if zero else torch.empty)(total, dtype=torch.float32, device=device),
+                   torch.zeros(total, dtype=torch.float32, device=device), P)
         self.env_map = None
         self.get_max_sh_channels = M
 
     @classmethod
-    def from_raw(cls, tensors: Dict[str, torch.Tensor], device, *, max_sh_degree: int, max_sh_degree_t: int = 0, active_sh_degree: int = None,
-                 active_sh_degree_t: int = None, time_duration=(0.0, 1.0), rot_4d: bool = False, gaussian_dim: int = 3,
-                 force_sh_3d: bool = False, prefilter_var: float = -1.0) -> "GaussianParams":
-        """A model from RAW (pre-activation) tensors -- what a checkpoint holds (fdgs.checkpoint.restore): ``tensors`` maps the names
-        of ``NAMES`` to ``_xyz`` [P, 3], ``_features`` [P, M, 3], ``_opacity`` [P, 1], ``_scaling`` [P, 3], ``_rotation`` [P, 4] and,
-        where the model has them, ``_t`` [P, 1], ``_scaling_t`` [P, 1], ``_rotation_r`` [P, 4].  They are COPIED into the flat bucket
-        bit for bit.  The bucket always holds all eight segments: a tensor that is missing or empty (a 3D model's ``_t`` /
-        ``_scaling_t``, ``_rotation_r`` without ``rot_4d``) is filled with what ``create_from_pcd`` starts from -- t = 0,
-        log-scale 0, the identity quaternion; the kernels do not read it.  ``time_duration``: the reference's [t0, t1] pair."""
-        P, M = int(tensors["_xyz"].shape[0]), int(tensors["_features"].shape[1])
+    def empty(cls, P: int, M: int, device, zero: bool = False) -> "GaussianParams":
+        """A bucket of P Gaussians with M coefficients whose parameters are uninitialised (``zero``: zeros) and whose gradients are
+        zero; the caller fills it and calls ``apply_settings``."""
         self = cls.__new__(cls)
-        self.M = M
-        total = P * self.floats_per_gaussian()
-        self._bind(torch.empty(total, dtype=torch.float32, device=device), torch.zeros(total, dtype=torch.float32, device=device), P)
-        with torch.no_grad():
-            for name in self.NAMES:
-                dst, src = self.params[name], tensors.get(name, None)
-                if src is None or src.numel() == 0:
-                    dst.zero_()
-                    if name == "_rotation_r":
-                        dst[:, 0] = 1.0
-                elif tuple(src.shape) != tuple(dst.shape):
-                    raise ValueError("GaussianParams.from_raw: %s must be %s, got %s" % (name, tuple(dst.shape), tuple(src.shape)))
-                else:
-                    dst.copy_(src.detach().to(device=device, dtype=torch.float32))
+        self._allocate(int(P), int(M), device, zero)
+        return self
+
+    def apply_settings(self, *, max_sh_degree: int, max_sh_degree_t: int = 0, active_sh_degree: int = None, active_sh_degree_t: int = None,
+                       time_duration=(0.0, 1.0), rot_4d: bool = False, gaussian_dim: int = 3, force_sh_3d: bool = False,
+                       prefilter_var: float = -1.0) -> "GaussianParams":
+        """Everything a model is besides its tensors (``from_raw``'s keywords); active degrees default to the maximal ones."""
         self.max_sh_degree, self.max_sh_degree_t = int(max_sh_degree), int(max_sh_degree_t)
         self.active_sh_degree = self.max_sh_degree if active_sh_degree is None else int(active_sh_degree)
         self.active_sh_degree_t = self.max_sh_degree_t if active_sh_degree_t is None else int(active_sh_degree_t)
         self.time_duration = [float(time_duration[0]), float(time_duration[1])]
         self.rot_4d, self.gaussian_dim, self.force_sh_3d = bool(rot_4d), int(gaussian_dim), bool(force_sh_3d)
         self.prefilter_var = float(prefilter_var)
-        self.env_map = None
-        self.get_max_sh_channels = M
         return self
+
+    def settings(self) -> dict:
+        """The keyword dict ``from_raw`` / ``apply_settings`` take."""
+        return layout.settings_of(self)
+
+    @classmethod
+    def from_raw(cls, tensors: Dict[str, torch.Tensor], device, **settings) -> "GaussianParams":
+        """A model from RAW (pre-activation) tensors -- what a checkpoint holds (fdgs.checkpoint.restore): ``tensors`` maps the names
+        of ``NAMES`` to ``_xyz`` [P, 3], ``_features`` [P, M, 3], ``_opacity`` [P, 1], ``_scaling`` [P, 3], ``_rotation`` [P, 4] and,
+        where the model has them, ``_t`` [P, 1], ``_scaling_t`` [P, 1], ``_rotation_r`` [P, 4].  They are COPIED into the flat bucket
+        bit for bit.  The bucket always holds all eight segments: a tensor that is missing or empty (a 3D model's ``_t`` /
+        ``_scaling_t``, ``_rotation_r`` without ``rot_4d``) is filled with what ``create_from_pcd`` starts from -- t = 0,
+        log-scale 0, the identity quaternion; the kernels do not read it.  ``settings``: ``apply_settings``'s keywords
+        (``max_sh_degree`` is required; ``time_duration``: the reference's [t0, t1] pair)."""
+        self = cls.empty(tensors["_xyz"].shape[0], tensors["_features"].shape[1], device)
+        with torch.no_grad():
+            for name in self.NAMES:
+                dst, src = self.params[name], tensors.get(name, None)
+                if src is None or src.numel() == 0:
+                    layout.placeholder_(dst, name)
+                elif tuple(src.shape) != tuple(dst.shape):
+                    raise ValueError("GaussianParams.from_raw: %s must be %s, got %s" % (name, tuple(dst.shape), tuple(src.shape)))
+                else:
+                    dst.copy_(src.detach().to(device=device, dtype=torch.float32))
+        return self.apply_settings(**settings)
 
     def oneupSHdegree(self):
         """scene/gaussian_model.py:253-257: the spatial degree climbs to its maximum first, then the time degree."""
@@ -117,52 +128,46 @@ class GaussianParams:
 
     def row_floats(self) -> List[int]:
         """floats per Gaussian of every segment of the flat bucket, in NAMES order"""
-        return [3, 1, 3, 4, 1, 1, 4, self.M * 3]
+        return layout.row_floats(self.M)
 
     def floats_per_gaussian(self) -> int:
         return sum(self.row_floats())
 
     def _bind(self, flat: torch.Tensor, flat_grad: torch.Tensor, P: int):
         """(Re)creates the parameter views over ``flat`` / ``flat_grad`` for P Gaussians (segments back to back)."""
-        shapes = {"_xyz": (P, 3), "_features": (P, self.M, 3), "_opacity": (P, 1), "_scaling": (P, 3), "_rotation": (P, 4),
-                  "_t": (P, 1), "_scaling_t": (P, 1), "_rotation_r": (P, 4)}
-        assert self.NAMES[-1] == "_features"
         assert flat.numel() == flat_grad.numel() == P * self.floats_per_gaussian()
         self.flat, self.flat_grad = flat, flat_grad
         self.params = {}
         self.offsets = {}
         off = 0
-        for name, rf in zip(self.NAMES, self.row_floats()):
-            n = P * rf
-            p = self.flat[off:off + n].view(shapes[name]).requires_grad_(True)
-            p.grad = self.flat_grad[off:off + n].view(shapes[name])
+        for name, shape in layout.shapes(P, self.M).items():
+            n = math.prod(shape)
+            p = self.flat[off:off + n].view(shape).requires_grad_(True)
+            p.grad = self.flat_grad[off:off + n].view(shape)
             self.params[name] = p
             setattr(self, name, p)  # the reference's attribute names (scene/gaussian_model.py:70-80)
             self.offsets[name] = (off, off + n)
             off += n
+        self._sinks = [(s.sink, self.params[s.name]) for s in layout.SEGMENTS]
         self.P = P
 
     # ---- scene/gaussian_model.py:179-219 ----
-    get_xyz = property(lambda s: s.params["_xyz"])
-    get_t = property(lambda s: s.params["_t"])
-    get_scaling = property(lambda s: torch.exp(s.params["_scaling"]))
-    get_scaling_t = property(lambda s: torch.exp(s.params["_scaling_t"]))
-    get_rotation = property(lambda s: F.normalize(s.params["_rotation"]))
-    get_rotation_r = property(lambda s: F.normalize(s.params["_rotation_r"]))
-    get_opacity = property(lambda s: torch.sigmoid(s.params["_opacity"]))
-    get_features = property(lambda s: s.params["_features"])
+    get_xyz = property(lambda s: s._xyz)
+    get_t = property(lambda s: s._t)
+    get_scaling = property(lambda s: torch.exp(s._scaling))
+    get_scaling_t = property(lambda s: torch.exp(s._scaling_t))
+    get_rotation = property(lambda s: F.normalize(s._rotation))
+    get_rotation_r = property(lambda s: F.normalize(s._rotation_r))
+    get_opacity = property(lambda s: torch.sigmoid(s._opacity))
+    get_features = property(lambda s: s._features)
 
     def lr_segments(self) -> List[dict]:
-        """Learning rates of arguments/__init__.py:84-92 (spatial_lr_scale = 1) as a segment table."""
-        lr = {"_xyz": 1.6e-4, "_opacity": 5e-2, "_scaling": 5e-3, "_rotation": 1e-3, "_t": 1.6e-4, "_scaling_t": 5e-3,
-              "_rotation_r": 1e-3}
+        """Learning rates of arguments/__init__.py:84-92 (spatial_lr_scale = 1) as a segment table; a segment of two param groups
+        (``_features``: the DC coefficient at feature_lr, the rest at feature_lr / 20) has a head of its own rate in every row."""
         segs = []
-        for n in self.NAMES:
-            b, e = self.offsets[n]
-            if n == "_features":  # DC coefficient: feature_lr; the rest: feature_lr / 20
-                segs.append(dict(begin=b, end=e, lr=2.5e-3 / 20.0, lr_head=2.5e-3, period=self.M * 3, head=3))
-            else:
-                segs.append(dict(begin=b, end=e, lr=lr[n], lr_head=lr[n], period=0, head=0))
+        for s, rf in zip(layout.SEGMENTS, self.row_floats()):
+            b, e = self.offsets[s.name]
+            segs.append(dict(begin=b, end=e, lr=s.lr[-1], lr_head=s.lr[0], period=rf if s.head else 0, head=s.head))
         return segs
 
     def zero_grad(self):
@@ -171,10 +176,7 @@ class GaussianParams:
     def grad_sink(self) -> Dict[str, torch.Tensor]:
         """Gradient destinations for fdgs.fused.render_raw: the rasterizer backward writes each parameter's
         gradient straight into its slice of the flat bucket (no autograd accumulation pass, no zero_grad)."""
-        g = {n: self.params[n].grad for n in self.NAMES}
-        return {"dL_dmeans3D": g["_xyz"], "dL_dsh": g["_features"], "dL_dopacity": g["_opacity"],
-                "dL_dscales": g["_scaling"], "dL_drotations": g["_rotation"], "dL_dts": g["_t"],
-                "dL_dscales_t": g["_scaling_t"], "dL_drotations_r": g["_rotation_r"]}
+        return {sink: p.grad for sink, p in self._sinks}
 
 
 class ReferenceStyleModel:
@@ -186,31 +188,21 @@ class ReferenceStyleModel:
     def __init__(self, scene: Dict[str, object], device, optimizer: str = "torch"):
         """``optimizer``: "torch" = ``torch.optim.Adam`` as the reference builds it (scene/gaussian_model.py:353); "fdgs" =
         ``fdgs.optim.Adam`` over the same param groups (the one-line swap INTEGRATION.md describes)."""
-        M = int(scene["M"])
         mk = lambda t: torch.nn.Parameter(t.to(device).float().contiguous().requires_grad_(True))  # noqa: E731
-        self._xyz = mk(scene["means3D"])
-        self._features_dc = mk(scene["shs"][:, :1, :])
-        self._features_rest = mk(scene["shs"][:, 1:, :])
-        self._opacity = mk(_inv_sigmoid(scene["opacities"].clamp(1e-6, 1 - 1e-6)).reshape(-1, 1))
-        self._scaling = mk(torch.log(scene["scales"]))
-        self._rotation = mk(scene["rotations"])
-        self._t = mk(scene["ts"].reshape(-1, 1))
-        self._scaling_t = mk(torch.log(scene["scales_t"]).reshape(-1, 1))
-        self._rotation_r = mk(scene["rotations_r"])
+        raw = _raw_from_scene(scene)
+        for s in layout.SEGMENTS:
+            t = raw[s.name].reshape((-1,) + layout.tail(s, scene["M"]))
+            for g in s.groups:   # one nn.Parameter per param group of the reference: _features_dc [P,1,3] and _features_rest [P,M-1,3]
+                setattr(self, layout.GROUP_ATTR[g], mk(layout.group_view(t, g)))
         self.active_sh_degree, self.active_sh_degree_t = int(scene["sh_degree"]), int(scene["sh_degree_t"])
         self.time_duration = [0.0, float(scene["time_duration"])]
         self.rot_4d, self.gaussian_dim = bool(scene["rot_4d"]), int(scene["gaussian_dim"])
         self.force_sh_3d = bool(scene["force_sh_3d"])
         self.prefilter_var = -1.0
         self.env_map = None
-        self.get_max_sh_channels = M
-        groups = [dict(params=[self._xyz], lr=1.6e-4, name="xyz"), dict(params=[self._features_dc], lr=2.5e-3, name="f_dc"),
-                  dict(params=[self._features_rest], lr=2.5e-3 / 20.0, name="f_rest"), dict(params=[self._opacity], lr=5e-2, name="opacity"),
-                  dict(params=[self._scaling], lr=5e-3, name="scaling"), dict(params=[self._rotation], lr=1e-3, name="rotation")]
-        if self.gaussian_dim == 4:
-            groups += [dict(params=[self._t], lr=1.6e-4, name="t"), dict(params=[self._scaling_t], lr=5e-3, name="scaling_t")]
-            if self.rot_4d:
-                groups.append(dict(params=[self._rotation_r], lr=1e-3, name="rotation_r"))
+        self.get_max_sh_channels = int(scene["M"])
+        groups = [dict(params=[getattr(self, layout.GROUP_ATTR[g])], lr=layout.GROUP_LR[g], name=g)
+                  for g, _ in layout.group_table(self.gaussian_dim, self.rot_4d)]
         if optimizer == "fdgs":
             from .optim import Adam as FdgsAdam
             self.optimizer = FdgsAdam(groups, lr=0.0, eps=1e-15)
@@ -218,8 +210,7 @@ class ReferenceStyleModel:
             self.optimizer = torch.optim.Adam(groups, lr=0.0, eps=1e-15)
 
     # the attribute every parameter group's tensor lives under (scene/gaussian_model.py:411-425, 456-470)
-    _ATTR = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity", "scaling": "_scaling",
-             "rotation": "_rotation", "t": "_t", "scaling_t": "_scaling_t", "rotation_r": "_rotation_r"}
+    _ATTR = layout.GROUP_ATTR
 
     def _adopt(self, tensors: Dict[str, torch.Tensor]):
         for name, t in tensors.items():
@@ -439,10 +430,8 @@ class FlatAdam:
     def geometry_adam(self) -> dict:
         """The Adam step of the geometry segments (``step_range(0, features)``) for the CURRENT step_count, as the
         ``geometry_adam`` dict of the rasterizer backward (fdgs_backward_out.adam: taken inside the geometry backward)."""
-        lr = {s["name"]: s["lr"] for s in self.named_segments()}
         return dict(flat=self.model.flat, exp_avg=self.exp_avg, exp_avg_sq=self.exp_avg_sq, betas=self.betas, eps=self.eps,
-                    step=self.step_count, lr=dict(means3D=lr["_xyz"], opacities=lr["_opacity"], ts=lr["_t"], scales=lr["_scaling"],
-                                                  scales_t=lr["_scaling_t"], rotations=lr["_rotation"], rotations_r=lr["_rotation_r"]))
+                    step=self.step_count, lr={s.kernel: seg["lr"] for s, seg in zip(layout.GEOMETRY, self.segments)})
 
     @torch.no_grad()
     def step_sh_staged(self, stages: torch.Tensor, rs, analytic_sh_grad: bool = False, write_grad: bool = False) -> bool:
@@ -455,8 +444,8 @@ class FlatAdam:
         m = self.model
         b, e = m.offsets["_features"]
         seg = next(s for s in self.segments if s["begin"] == b and s["end"] == e)
-        shape = m.params["_features"].shape
-        return _capi.adam_step_sh(m.flat[b:e].view(shape), self.exp_avg[b:e].view(shape), self.exp_avg_sq[b:e].view(shape), stages,
+        flat, exp_avg, exp_avg_sq = (layout.segment(buf, m, "_features") for buf in (m.flat, self.exp_avg, self.exp_avg_sq))
+        return _capi.adam_step_sh(flat, exp_avg, exp_avg_sq, stages,
                                   rs.sh_degree, rs.sh_degree_t, rs.gaussian_dim, rs.force_sh_3d, analytic_sh_grad,
                                   seg["lr"], seg["lr_head"], self.betas[0], self.betas[1], self.eps, self.step_count,
                                   dL_dsh=m.params["_features"].grad if write_grad else None)
@@ -491,6 +480,48 @@ def reorder_gaussians(model: GaussianParams, optimizer: "FlatAdam", perm: torch.
         for buf in bufs:
             seg = buf[b:e].view(model.P, rf)
             seg.copy_(seg[perm])
+
+
+@torch.no_grad()
+def relayout(model: GaussianParams, optimizer: Optional["FlatAdam"], src: torch.Tensor, kind: torch.Tensor = None, stats=()) -> Dict[str, torch.Tensor]:
+    """Keep these rows, in this order: row j of every parameter tensor becomes the old row ``src[j]`` (an integer tensor; rows may
+    repeat), in NEW buffers that ``model`` and ``optimizer`` (or None) are rebound to.  ``kind`` (uint8 per new row, as
+    ``fdgs_densify_gather`` takes it): 0 carries the old row's Adam moments, anything else starts them at zero; None: all carried.
+    Every object in ``stats`` follows with its ``select_(src)``.  Returns the OLD parameter views (they keep the old bucket alive)."""
+    P, P_new, dev = model.P, int(src.numel()), model.flat.device
+    old = dict(model.params)
+    f = dict(dtype=torch.float32, device=dev)
+    total = P_new * model.floats_per_gaussian()
+    sel = src.long()
+    if optimizer is not None and model.flat.is_cuda:
+        from . import _capi
+        rows = model.row_floats()
+        src32 = src.to(torch.int32).contiguous()
+        kind = torch.zeros(P_new, dtype=torch.uint8, device=dev) if kind is None else kind.contiguous()
+        new_flat, new_m, new_v = (torch.empty(total, **f) for _ in range(3))
+        _capi.call("fdgs_densify_gather", dev, len(rows), (C.c_int32 * len(rows))(*rows), P, P_new, _capi._ptr(src32), _capi._ptr(kind),
+                   _capi._ptr(model.flat), _capi._ptr(optimizer.exp_avg), _capi._ptr(optimizer.exp_avg_sq), _capi._ptr(new_flat),
+                   _capi._ptr(new_m), _capi._ptr(new_v))
+    else:
+        # (CPU, or a finished model without moments to carry: one index-select per segment)
+        fresh = None if kind is None else kind.to(sel.device) != 0
+
+        def gather(buf, zero=None):
+            rows = [layout.segment(buf, model, n)[sel] for n in model.NAMES]
+            if zero is not None:
+                for t in rows:
+                    t[zero] = 0.0
+            return torch.cat([t.reshape(-1) for t in rows])
+
+        new_flat = gather(model.flat.detach())
+        if optimizer is not None:
+            new_m, new_v = gather(optimizer.exp_avg, fresh), gather(optimizer.exp_avg_sq, fresh)
+    model._bind(new_flat, torch.zeros(total, **f), P_new)
+    if optimizer is not None:
+        optimizer.rebind(new_m, new_v)
+    for st in stats:
+        st.select_(sel)
+    return old
 
 
 def spatial_sort(model: GaussianParams, optimizer: "FlatAdam" = None) -> torch.Tensor:

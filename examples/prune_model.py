@@ -120,7 +120,7 @@ def main():
     if args.bench:
         bench(dev)
         return
-    from fdgs import harness, importance, playback, synth, train_host
+    from fdgs import harness, importance, layout, playback, synth, train_host
     from fdgs.fused import render_raw
     cfg = synth.CONFIGS[args.workload]
     scenes = [synth.make_scene(cfg, seed=0, pose=p) for p in RIG]
@@ -144,10 +144,9 @@ def main():
     P = model.P
     print("%s: %d Gaussians, %d views; never contributing: %d, never dominant: %d" % (
         args.workload, P, stats.views, int((stats.hits == 0).sum()), int((stats.dominant == 0).sum())))
-    flat, geo = model.flat.detach().clone(), (stats.weight_sum.clone(), stats.weight_max.clone(), stats.hits.clone(), stats.dominant.clone())
+    geo = (stats.weight_sum.clone(), stats.weight_max.clone(), stats.hits.clone(), stats.dominant.clone())
     for frac in args.keep:
-        m = train_host.GaussianParams(scenes[0], dev)
-        m._bind(flat.clone(), torch.zeros_like(flat), P)
+        m = train_host.GaussianParams.from_raw(layout.raw_of(model), dev, **model.settings())   # a copy to cut down
         st = importance.ContributionStats(P, dev)
         st.weight_sum, st.weight_max, st.hits, st.dominant = (t.clone() for t in geo)
         rep = importance.prune_by_contribution(m, None, st, keep_fraction=frac)

@@ -3,7 +3,7 @@ gathers + torch.cat per tensor and per Adam moment).  Dev tool."""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
-from fdgs import synth, train_host, harness
+from fdgs import synth, train_host, harness, layout
 from fdgs.densify import densify_and_prune
 dev = torch.device("cuda:0")
 name = sys.argv[1] if len(sys.argv) > 1 else "C3"
@@ -36,8 +36,7 @@ scal = torch.exp(model._scaling).max(1).values
 clone = (grads[:, 0] >= 2e-4) & (scal <= 0.01 * extent)
 split = (grads[:, 0] >= 2e-4) & (scal > 0.01 * extent)
 tensors = [model.params[n].detach() for n in model.NAMES]
-moments = [[opt.exp_avg[slice(*model.offsets[n])].view(model.params[n].shape) for n in model.NAMES],
-           [opt.exp_avg_sq[slice(*model.offsets[n])].view(model.params[n].shape) for n in model.NAMES]]
+moments = [[layout.segment(buf, model, n) for n in model.NAMES] for buf in (opt.exp_avg, opt.exp_avg_sq)]
 for trial in range(3):
     torch.cuda.synchronize(); t0 = time.perf_counter()
     out = []
