@@ -452,21 +452,25 @@ namespace
 		if (plan.mode != Mode::Exact) g_sparse_stats[2].store((long long)lists->L.total);
 		return FDGS_OK;
 	}
+	// what the binning launches of a forward share; lists: NULL while there is no binning buffer yet (count, scan).  With sparse lists
+	// (plan.tile_cap != 0) the launchers leave the tile order alone until the sort's report workgroup writes it.
+	TileBinArgs bin_args(const FwdCall& f, const Plan& plan, const Lists* lists)
+	{
+		return TileBinArgs{ f.counters, lists ? (uint2*)(lists->bin + lists->L.pairs) : nullptr, lists ? (uint32_t*)(lists->bin + lists->L.point_list) : nullptr,
+		                    (uint2*)f.ranges, f.ctl, (uint32_t)plan.capacity, f.tile_order, f.T, f.gx, plan.tile_cap };
+	}
 	// [scatter ->] sort -> join the colour stream -> blend.  borrowed: a global sort scratch to use instead of the buffer's own.
 	int enqueue_lists(FwdCall& f, const Plan& plan, const Lists& lists, bool scatter, void* borrowed = nullptr)
 	{
-		const bool sparse = plan.mode == Mode::Sparse;   // the sort launch then reports num_rendered and writes the tile order, as the scan does otherwise
 		const hipStream_t stream = f.q.stream;
 		const BinLayout& BL = lists.L;
-		uint32_t* point_list = (uint32_t*)(lists.bin + BL.point_list);
-		uint32_t* pairs = (uint32_t*)(lists.bin + BL.pairs);
+		const TileBinArgs a = bin_args(f, plan, &lists);
+		// sparse lists: the sort launch reports num_rendered and writes the tile order, as the scan and the scatter launch do otherwise
+		const TileReport rep = plan.mode == Mode::Sparse ? TileReport{ f.ctl, f.mail_dev, f.ticket, f.tile_order } : TileReport{};
+		uint32_t* point_list = a.point_list;
 		void* sort_scratch = borrowed ? borrowed : (plan.scratch ? (void*)(lists.bin + BL.big_scratch) : nullptr);
-		if (scatter)
-			STAGE(f.q, FDGS_STAGE_TILE_SCATTER, launch_tile_scatter(f.rect, f.depths, f.s.P, f.gx, f.T, f.counters, pairs, f.ctl, (uint32_t)plan.capacity,
-			                          sparse ? nullptr : f.tile_order, stream, plan.tile_cap), "tile scatter");
-		STAGE(f.q, FDGS_STAGE_TILE_SORT, launch_tile_sort(f.counters, f.T, plan.sort_longest, pairs, point_list, f.ranges, sort_scratch, f.ctl, (uint32_t)plan.capacity,
-		                       sparse ? nullptr : f.tile_order, stream, plan.tile_cap, sparse ? f.ctl : nullptr, sparse ? f.mail_dev : nullptr,
-		                       sparse ? f.ticket : 0u, sparse ? f.tile_order : nullptr), "tile sort");
+		if (scatter) STAGE(f.q, FDGS_STAGE_TILE_SCATTER, launch_tile_scatter(f.rect, f.depths, f.s.P, a, stream), "tile scatter");
+		STAGE(f.q, FDGS_STAGE_TILE_SORT, launch_tile_sort(a, plan.sort_longest, sort_scratch, rep, stream), "tile sort");
 		if (f.join) { HIP_TRY(hipStreamWaitEvent(stream, f.join, 0), "hipStreamWaitEvent"); f.join = nullptr; }   // the blend must not start before the colours are there
 		STAGE(f.q, FDGS_STAGE_BLEND_FWD, launch_blend_fwd(f.s, f.out, f.records, point_list, f.ranges, f.tile_order, f.final_T, f.n_contrib,
 		                       (unsigned long long*)(lists.bin + BL.cull_bits), BL.cull_stride, (uint32_t)(BL.cull_bits / 8), f.ctl, stream), "blend_fwd");
@@ -614,8 +618,9 @@ extern "C" int fdgs_rasterize_forward(const fdgs_scene* scene, const fdgs_forwar
 	if (lazy && want_sparse) g_sparse_stats[plan.mode == Mode::Sparse ? 0 : 1]++;
 	if (plan.mode != Mode::Sparse)
 	{
-		STAGE(f.q, FDGS_STAGE_TILE_COUNT, launch_tile_count(f.rect, P, gx, T, f.counters, stream), "tile count");
-		STAGE(f.q, FDGS_STAGE_TILE_SCAN, launch_tile_scan(f.counters, T, f.ctl, f.mail_dev, f.ticket, f.tile_order, stream), "tile scan");
+		const TileBinArgs a = bin_args(f, plan, nullptr);
+		STAGE(f.q, FDGS_STAGE_TILE_COUNT, launch_tile_count(f.rect, P, a, stream), "tile count");
+		STAGE(f.q, FDGS_STAGE_TILE_SCAN, launch_tile_scan(a, TileReport{ f.ctl, f.mail_dev, f.ticket, nullptr }, stream), "tile scan");
 		rec.pending = true;
 	}
 	Lists lists{};
@@ -1088,28 +1093,27 @@ extern "C" int fdgs_debug_tile_bin(int32_t P, const uint16_t* rect, const float*
 	uint32_t* order = (uint32_t*)(s + L.order);
 	const int lds_cap = tile_sort_lds_cap();
 	const size_t tb = (size_t)T * 4;
+	const TileBinArgs a{ counters, (uint2*)pairs, point_list, (uint2*)ranges, ctl, (uint32_t)capacity, order, T, grid_x, (uint32_t)sparse_cap };
 	HIP_TRY(hipMemsetAsync(s, 0, L.big, stream), "tile bin debug: memset");   // counters (as preprocess_fwd leaves them), ctl, the order area
 	if (sparse_cap == 0)
 	{
-		HIP_TRY(launch_tile_count(rect, P, grid_x, T, counters, stream), "tile count");
+		HIP_TRY(launch_tile_count(rect, P, a, stream), "tile count");
 		HIP_TRY(hipMemcpyAsync(counts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
-		HIP_TRY(launch_tile_scan(counters, T, ctl, nullptr, 0u, order, stream), "tile scan");
+		HIP_TRY(launch_tile_scan(a, TileReport{ ctl, nullptr, 0u, nullptr }, stream), "tile scan");
 		HIP_TRY(hipMemcpyAsync(starts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
 		uint32_t h_ctl[2] = { 0u, 0u };
 		HIP_TRY(hipMemcpyAsync(h_ctl, ctl, 8, hipMemcpyDeviceToHost, stream), "tile bin debug: read ctl");
 		HIP_TRY(hipStreamSynchronize(stream), "tile bin debug: synchronize");
 		const int longest = (int)h_ctl[1];
-		HIP_TRY(launch_tile_scatter(rect, depths, P, grid_x, T, counters, pairs, ctl, (uint32_t)capacity, order, stream, 0u), "tile scatter");
-		HIP_TRY(launch_tile_sort(counters, T, longest, pairs, point_list, ranges, longest > lds_cap ? (void*)(s + L.big) : nullptr, ctl, (uint32_t)capacity, order, stream),
-		        "tile sort");
+		HIP_TRY(launch_tile_scatter(rect, depths, P, a, stream), "tile scatter");
+		HIP_TRY(launch_tile_sort(a, longest, longest > lds_cap ? (void*)(s + L.big) : nullptr, TileReport{}, stream), "tile sort");
 	}
 	else
 	{
 		const int longest = max_count > 0 ? max_count : sparse_cap;   // the longest list PROVIDED FOR (Plan::sort_longest)
-		HIP_TRY(launch_tile_scatter(rect, depths, P, grid_x, T, counters, pairs, ctl, (uint32_t)capacity, nullptr, stream, (uint32_t)sparse_cap), "tile scatter");
+		HIP_TRY(launch_tile_scatter(rect, depths, P, a, stream), "tile scatter");
 		HIP_TRY(hipMemcpyAsync(counts_out, counters, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
-		HIP_TRY(launch_tile_sort(counters, T, longest, pairs, point_list, ranges, longest > lds_cap ? (void*)(s + L.big) : nullptr, ctl, (uint32_t)capacity, nullptr, stream,
-		                         (uint32_t)sparse_cap, ctl, nullptr, 0u, order), "tile sort");
+		HIP_TRY(launch_tile_sort(a, longest, longest > lds_cap ? (void*)(s + L.big) : nullptr, TileReport{ ctl, nullptr, 0u, order }, stream), "tile sort");
 	}
 	HIP_TRY(hipMemcpyAsync(ctl_out, ctl, 8, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");
 	HIP_TRY(hipMemcpyAsync(order_out, order, tb, hipMemcpyDeviceToDevice, stream), "tile bin debug: copy out");

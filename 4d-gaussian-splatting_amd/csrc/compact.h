@@ -2,7 +2,7 @@
 //   count   every workgroup's number of outputs                               compact_count_kernel<THREADS, Pass>
 //   scan    one workgroup per count array: the workgroups' first ranks, the total       compact_scan_kernel
 //   emit    rank = the workgroup's first rank + the rank inside the workgroup            compact_emit_kernel<THREADS, Pass>
-// Integer sums in a fixed order: exact and reproducible.  What is counted and what is written is a Pass, a small trivially copyable
+// Integer sums in a fixed order (the workgroup scans of scan.h): exact and reproducible.  What is counted and what is written is a Pass, a small trivially copyable
 // struct handed to both kernels by value:
 //   __host__ __device__ int size() const                how many elements there are
 //   typename Item                                       what count() hands to emit() inside the emit kernel (registers of one thread)
@@ -10,55 +10,10 @@
 //                                                       stores for later passes it stores under !emitting (a constant where it is inlined)
 //   void emit(int i, uint32_t n, uint32_t rank, const Item& item)     for every i < size(): its n outputs go to rank, rank + 1, ...
 #pragma once
-#include "fdgs_common.h"
+#include "scan.h"
 
 namespace fdgs
 {
-	// exclusive rank of v among the workgroup's THREADS threads, in thread order; total: the workgroup's sum (every thread gets it).
-	// s_wave: THREADS / WAVE words of LDS; every thread of the workgroup must call.
-	template <int THREADS>
-	__device__ __forceinline__ uint32_t block_rank(uint32_t v, uint32_t* s_wave, uint32_t& total)
-	{
-		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-		uint32_t x = v;
-#pragma unroll
-		for (int d = 1; d < WAVE; d <<= 1)
-		{
-			const uint32_t y = __shfl_up(x, d);
-			if (lane >= d) x += y;
-		}
-		__syncthreads();                                  // the previous call's readers are done with s_wave[]
-		if (lane == WAVE - 1) s_wave[wave] = x;
-		__syncthreads();
-		uint32_t before = 0;
-		total = 0;
-#pragma unroll
-		for (int w = 0; w < THREADS / WAVE; w++)
-		{
-			const uint32_t c = s_wave[w];
-			if (w < wave) before += c;
-			total += c;
-		}
-		return before + x - v;
-	}
-
-	// one workgroup of THREADS threads: counts[0 .. n) -> their exclusive scan, in place; returns the sum (every thread gets it)
-	template <int THREADS>
-	__device__ __forceinline__ uint32_t block_scan_counts(uint32_t* __restrict__ counts, const int n, uint32_t* s_wave)
-	{
-		uint32_t carry = 0;
-		for (int base = 0; base < n; base += THREADS)
-		{
-			const int i = base + (int)threadIdx.x;
-			const uint32_t v = i < n ? counts[i] : 0u;
-			uint32_t total;
-			const uint32_t before = block_rank<THREADS>(v, s_wave, total);
-			if (i < n) counts[i] = carry + before;
-			carry += total;
-		}
-		return carry;
-	}
-
 	constexpr int COMPACT_THREADS = 256;                 // the count and emit kernels' workgroup
 	constexpr int COMPACT_SCAN_THREADS = 1024;           // one scan chunk: the counts of 1024 workgroups
 	static size_t compact_blocks(size_t n) { return (n + COMPACT_THREADS - 1) / COMPACT_THREADS; }

@@ -183,27 +183,39 @@ namespace fdgs
 		return n > 0 && bit_hi > bit_lo ? ((bit_hi - bit_lo + RADIX_BITS - 1) / RADIX_BITS) & 1 : 0;
 	}
 
-	// Tile binning (tilebin.hip).  counters: bin_counter_words(T) words, zero on entry of the count pass (cleared by
-	// preprocess_fwd, the forward's first kernel); after the scan they hold every tile list's start, after the
-	// scatter its end.  ctl[0] = R, ctl[1] = longest tile list.
-	hipError_t launch_tile_count(const uint16_t* rect, int P, int grid_x, int T, uint32_t* counters, hipStream_t stream);
-	// host_box (optional): device pointer of a pinned host mailbox {R, longest, ticket} the kernel writes directly
-	// tile_order (optional, 3 T + 16 words, see ImageLayout): the scan leaves a copy of the tile counts at tile_order + tile_order_counts_off(T)
-	hipError_t launch_tile_scan(uint32_t* counters, int T, uint32_t* ctl, uint32_t* host_box, uint32_t ticket, uint32_t* tile_order, hipStream_t stream);
-	// scatter / sort may be launched before the host knows num_rendered: they compare ctl[0] with `capacity` (the instances
-	// pairs / point_list hold) and leave everything alone -- the sort reports every tile empty -- when it does not fit
-	// tile_order (optional): one extra workgroup of this launch turns the scan's copy of the counts into the blend kernels' tile order
-	// sparse_cap != 0: SPARSE lists (fdgs_forward_out.sparse_lists): no count / scan pass ran, the counters are zero, tile t's list goes to
-	// [t * sparse_cap, (t + 1) * sparse_cap) of `pairs` / point_list; afterwards the counters hold the tiles' counts
-	hipError_t launch_tile_scatter(const uint16_t* rect, const float* depths, int P, int grid_x, int T, uint32_t* counters, uint32_t* pairs,
-	                               const uint32_t* ctl, uint32_t capacity, uint32_t* tile_order, hipStream_t stream, uint32_t sparse_cap = 0u);
-	// tile_order (optional): the order the scatter launch wrote -- the sort takes the tiles in it too (longest lists first)
-	// sparse lists: report_ctl / report_box / ticket / order_out -- the sort's main instance reports num_rendered and the longest list and
-	// writes the tile order (what the scan + scatter launches do for compact lists)
-	hipError_t launch_tile_sort(const uint32_t* counters, int T, int max_count, const uint32_t* pairs, uint32_t* point_list, uint32_t* ranges,
-	                            void* big_scratch, const uint32_t* ctl, uint32_t capacity, const uint32_t* tile_order, hipStream_t stream,
-	                            uint32_t sparse_cap = 0u, uint32_t* report_ctl = nullptr, uint32_t* report_box = nullptr, uint32_t ticket = 0u,
-	                            uint32_t* order_out = nullptr);
+	// Tile binning (tilebin.hip).  What its passes share, handed to the launchers and on to the kernels by value:
+	struct TileBinArgs
+	{
+		uint32_t* counters;    // bin_counter_words(T) words, zero on entry of the count pass (cleared by preprocess_fwd, the forward's first
+		                       // kernel); after the scan they hold every tile list's start, after the scatter its end
+		uint2* pairs;          // [capacity] unsorted (depth bits, id) pairs: scatter -> sort
+		uint32_t* point_list;  // [capacity] the tiles' sorted lists
+		uint2* ranges;         // [T] (start, end) of every tile's list
+		uint32_t* ctl;         // ctl[0] = R, ctl[1] = longest tile list
+		uint32_t capacity;     // the instances pairs / point_list hold
+		uint32_t* order;       // optional, the tile-order area (3 T + 16 words, see ImageLayout) of COMPACT lists: the scan leaves a copy of the
+		                       // tile counts at order + tile_order_counts_off(T), one extra workgroup of the scatter launch turns it into the
+		                       // blend kernels' tile order, and the sort takes the tiles in that order too (longest lists first)
+		int T, grid_x;
+		uint32_t sparse_cap;   // != 0: SPARSE lists (fdgs_forward_out.sparse_lists): no count / scan pass runs, the counters start from zero, tile
+		                       // t's list goes to [t * sparse_cap, (t + 1) * sparse_cap) of pairs / point_list; after the scatter the counters hold
+		                       // the tiles' counts
+	};
+	// Who tells the host {R, longest list}: the scan, or with sparse lists one extra workgroup of the sort's main instance (which then writes the
+	// tile order too: what the scan + scatter launches do for compact lists).  ctl == NULL: nobody (a sort launch of compact lists).
+	struct TileReport
+	{
+		uint32_t* ctl;         // ctl[0] = R, ctl[1] = longest tile list
+		uint32_t* box;         // optional: device pointer of a pinned host mailbox {R, longest, ticket} the kernel writes directly
+		uint32_t ticket;
+		uint32_t* order_out;   // sort only, optional: the tile-order area the blend kernels' order goes to
+	};
+	hipError_t launch_tile_count(const uint16_t* rect, int P, const TileBinArgs& a, hipStream_t stream);
+	hipError_t launch_tile_scan(const TileBinArgs& a, const TileReport& to, hipStream_t stream);
+	// scatter / sort may be launched before the host knows num_rendered (see lists_do_not_fit, tilebin.hip)
+	hipError_t launch_tile_scatter(const uint16_t* rect, const float* depths, int P, const TileBinArgs& a, hipStream_t stream);
+	// max_count: the longest list PROVIDED FOR; big_scratch: `capacity` 64-bit keys, needed when max_count > tile_sort_lds_cap()
+	hipError_t launch_tile_sort(const TileBinArgs& a, int max_count, void* big_scratch, const TileReport& rep, hipStream_t stream);
 	int tile_sort_lds_cap();                                   // lists longer than this need the global scratch
 	void tile_sort_debug_limits(int lds_cap, int rank_max);    // test hook (fdgs_debug_tile_sort_limits); <= 0 restores the default
 

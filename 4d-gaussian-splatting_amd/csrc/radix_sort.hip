@@ -7,7 +7,7 @@
 // workgroups -> stable scatter (wave64 match-any ranking via 8 ballots, per-wave
 // digit counters in LDS, LDS reorder so the global writes are contiguous per digit run).
 // Small inputs use 1024-key chunks so they still fill the chip.  All integer work, HBM-bound; no MFMA.
-#include "fdgs_common.h"
+#include "scan.h"
 
 namespace fdgs
 {
@@ -38,34 +38,9 @@ namespace fdgs
 	// chunks, in place; the digit total goes to totals[d].
 	__global__ void __launch_bounds__(256) radix_scan_kernel(uint32_t* __restrict__ hist, int nblocks, uint32_t* __restrict__ totals)
 	{
-		__shared__ uint32_t wave_sums[4];
-		__shared__ uint32_t carry_s;
-		uint32_t* row = hist + (size_t)blockIdx.x * nblocks;
-		const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-		if (threadIdx.x == 0) carry_s = 0;
-		__syncthreads();
-		for (int base = 0; base < nblocks; base += 256)
-		{
-			const int i = base + threadIdx.x;
-			const uint32_t v = (i < nblocks) ? row[i] : 0u;
-			uint32_t incl = v;
-#pragma unroll
-			for (int o = 1; o < 64; o <<= 1)
-			{
-				const uint32_t t = __shfl_up(incl, o);
-				if (lane >= o) incl += t;
-			}
-			if (lane == 63) wave_sums[wave] = incl;
-			__syncthreads();
-			uint32_t wbase = 0;
-			for (int w = 0; w < wave; w++) wbase += wave_sums[w];
-			const uint32_t carry = carry_s;
-			if (i < nblocks) row[i] = carry + wbase + incl - v;
-			__syncthreads();
-			if (threadIdx.x == 255) carry_s = carry + wbase + incl;
-			__syncthreads();
-		}
-		if (threadIdx.x == 0) totals[blockIdx.x] = carry_s;
+		__shared__ uint32_t s_wave[256 / WAVE];
+		const uint32_t total = block_scan_counts<256>(hist + (size_t)blockIdx.x * nblocks, nblocks, s_wave);
+		if (threadIdx.x == 0) totals[blockIdx.x] = total;
 	}
 
 	// Stable scatter.  Wave w of the workgroup owns the contiguous sub-chunk
@@ -96,21 +71,8 @@ namespace fdgs
 		for (int i = threadIdx.x; i < WAVES * RADIX; i += SORT_THREADS) (&cnt[0][0])[i] = 0;
 
 		// exclusive scan of the 256 digit totals -> global base of each digit, plus this chunk's offset in the run
-		{
-			const uint32_t v = totals[threadIdx.x];
-			uint32_t incl = v;
-#pragma unroll
-			for (int o = 1; o < 64; o <<= 1)
-			{
-				const uint32_t t = __shfl_up(incl, o);
-				if (lane >= o) incl += t;
-			}
-			if (lane == 63) ws[wave] = incl;
-			__syncthreads();
-			uint32_t wbase = 0;
-			for (int w = 0; w < wave; w++) wbase += ws[w];
-			run_gbase[threadIdx.x] = wbase + incl - v + hist[(size_t)threadIdx.x * nblocks + blockIdx.x];
-		}
+		uint32_t all;   // (the scans' totals: n and the chunk's size, not needed)
+		run_gbase[threadIdx.x] = block_rank<SORT_THREADS>(totals[threadIdx.x], ws, all) + hist[(size_t)threadIdx.x * nblocks + blockIdx.x];
 		__syncthreads();
 
 		const int wbase_idx = blockIdx.x * CHUNK + wave * PER_WAVE;
@@ -156,19 +118,7 @@ namespace fdgs
 				cnt[w][d] = run;      // offset of wave w inside the digit run of this workgroup
 				run += c;
 			}
-			// exclusive scan of the run lengths over the digits
-			uint32_t incl = run;
-#pragma unroll
-			for (int o = 1; o < 64; o <<= 1)
-			{
-				const uint32_t t = __shfl_up(incl, o);
-				if (lane >= o) incl += t;
-			}
-			if (lane == 63) ws[wave] = incl;
-			__syncthreads();
-			uint32_t wb = 0;
-			for (int w = 0; w < wave; w++) wb += ws[w];
-			run_start[d] = wb + incl - run;
+			run_start[d] = block_rank<SORT_THREADS>(run, ws, all);   // exclusive scan of the run lengths over the digits
 		}
 		__syncthreads();
 

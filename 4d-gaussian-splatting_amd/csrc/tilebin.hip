@@ -32,7 +32,7 @@
 //              of equal depths) the tile falls back to a bitonic sort of the 64-bit keys in LDS.
 //   n <= 16384 the same with 1024 threads per tile (8 or 16 keys per thread) for the few long lists of a clustered scene.
 //   n  > 16384 bitonic sort in global scratch (R keys, requested from the allocator only when such a list exists).
-#include "fdgs_common.h"
+#include "scan.h"
 
 namespace fdgs
 {
@@ -95,15 +95,14 @@ namespace fdgs
 	// evenly (round 5, profiles/HISTORY.md; runs of 1 ... 85 tiles dealt round-robin and this global order are within 1 % of each other:
 	// which XCD's L2 a tile's records pass through does not matter).
 	// Run by ONE extra workgroup of the scatter launch (off the forward's critical path: the scan only leaves a copy of the tile counts)
-	// or, with sparse lists, of the sort launch.
+	// or, with sparse lists, of the sort launch (tile_report_block).
 	// counts: [T] list lengths (left alone: a scatter pass that is launched a second time orders again); tmp: [T] scratch; order: [T];
 	// s_cls: ORDER_BUCKETS words of LDS.  T < 2^24 (the launchers check).
-	[[maybe_unused]] constexpr int NUM_XCDS_BIN = 8;     // blend_common.h NUM_XCDS
 	constexpr int ORDER_BUCKETS = 64;   // = WAVE: one wave scans the classes
 	__device__ __forceinline__ void tile_order_block(const uint32_t* __restrict__ counts, uint32_t* __restrict__ tmp, int T, uint32_t gmax,
 	                                                 uint32_t* __restrict__ order, uint32_t* s_cls)
 	{
-		const int nthreads = (int)blockDim.x, lane = threadIdx.x & 63;
+		const int nthreads = (int)blockDim.x;
 		for (int k = threadIdx.x; k < ORDER_BUCKETS; k += nthreads) s_cls[k] = 0u;
 		__syncthreads();
 		const float cls_scale = (float)ORDER_BUCKETS / ((float)gmax + 1.0f);
@@ -117,14 +116,7 @@ namespace fdgs
 		if (threadIdx.x < ORDER_BUCKETS)   // the first wave: exclusive scan of the class sizes (lane = class)
 		{
 			const uint32_t n = s_cls[threadIdx.x];
-			uint32_t inc = n;
-#pragma unroll
-			for (int o = 1; o < WAVE; o <<= 1)
-			{
-				const uint32_t u = __shfl_up(inc, o);
-				if (lane >= o) inc += u;
-			}
-			s_cls[threadIdx.x] = inc - n;
+			s_cls[threadIdx.x] = wave_inclusive_sum(n) - n;
 		}
 		__syncthreads();
 		for (int t = threadIdx.x; t < T; t += nthreads)
@@ -134,26 +126,72 @@ namespace fdgs
 		}
 	}
 
+	// {R, longest list} for everybody behind: into ctl and, where the caller has one, straight into its pinned, device-mapped mailbox,
+	// then the call's ticket with system-scope release -- the host spins on the ticket instead of paying a copy kernel and a stream
+	// sync.  The only place that writes either; ONE thread calls it (the scan's, or with sparse lists the sort's report workgroup's).
+	__device__ __forceinline__ void report_totals(const TileReport& to, uint32_t total, uint32_t longest)
+	{
+		to.ctl[0] = total; to.ctl[1] = longest;
+		if (to.box)
+		{
+			to.box[0] = total; to.box[1] = longest;
+			__hip_atomic_store(&to.box[2], to.ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+		}
+	}
+
+	// SPARSE lists, the extra workgroup of the sort's main instance: what the scan kernel does for compact lists -- num_rendered and the
+	// longest list from the tiles' counts (final since the scatter launch) into ctl and the caller's mailbox -- and then the blend
+	// kernels' tile order.
+	template <int THREADS>
+	__device__ __forceinline__ void tile_report_block(const uint32_t* __restrict__ counts, int T, const TileReport& rep)
+	{
+		__shared__ uint32_t s_cls[ORDER_BUCKETS];
+		__shared__ uint32_t s_sum[THREADS / WAVE], s_max[THREADS / WAVE];
+		uint32_t sum = 0u, mx = 0u;
+		for (int t = threadIdx.x; t < T; t += THREADS) { const uint32_t c = counts[t]; sum += c; mx = max(mx, c); }
+		sum = wave_sum(sum); mx = wave_max(mx);
+		if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_max[threadIdx.x >> 6] = mx; }
+		__syncthreads();
+		uint32_t gtot = 0u, gmax = 0u;
+#pragma unroll
+		for (int w = 0; w < THREADS / WAVE; w++) { gtot += s_sum[w]; gmax = max(gmax, s_max[w]); }
+		if (threadIdx.x == 0) report_totals(rep, gtot, gmax);
+		if (rep.order_out != nullptr) tile_order_block(counts, rep.order_out + tile_order_tmp_off(T), T, gmax, rep.order_out, s_cls);
+	}
+
+	// The run-ahead guard.  Scatter and sort may be launched before the host knows num_rendered (capi.hip), with pairs / point_list
+	// sized by a guess: `capacity` instances.  When ctl[0] = R turns out larger, the lists do not fit: the scatter leaves everything
+	// alone (the counters stay list starts), the sort reports every tile empty, so that whatever is queued behind reads nothing, and
+	// the host starts over with exact sizes.  COMPACT lists only: with sparse lists nobody has counted before the scatter -- the
+	// counters start from zero and a tile that outgrows its sparse_cap slots drops what does not fit; its count still says so (the
+	// report's longest list), and the host renders the view again.
+	__device__ __forceinline__ bool lists_do_not_fit(const TileBinArgs& a)
+	{
+		// (ctl[0] was written by an earlier launch: read as kernel-constant memory, so that it stays the scalar load a
+		// const __restrict__ kernel parameter gets -- as a plain member of the by-value struct it becomes a vector load in tile_bin_*)
+		typedef const __attribute__((address_space(4))) uint32_t* const_words;
+		const const_words ctl = (const_words)a.ctl;
+		const uint32_t capacity = a.capacity;
+		return a.sparse_cap == 0u && ctl[0] > capacity;
+	}
+
 	constexpr int BIN_T = 1024;
 	template <bool SCATTER>
 	__global__ void __launch_bounds__(BIN_T) tile_bin_lds_kernel(const ushort4* __restrict__ rect, const float* __restrict__ depths, int P,
-	                                                             int grid_x, int T, int rounds /* batch = rounds * BIN_T Gaussians per workgroup */,
-	                                                             uint32_t* __restrict__ counters, uint2* __restrict__ pairs,
-	                                                             const uint32_t* __restrict__ ctl, uint32_t capacity,
-	                                                             uint32_t* __restrict__ order /* [3 T + 16] or NULL */,
-	                                                             uint32_t sparse_cap /* 0, or SPARSE lists: tile t's list lives at [t * sparse_cap, (t + 1) * sparse_cap) */)
+	                                                             int rounds /* batch = rounds * BIN_T Gaussians per workgroup */, const TileBinArgs a)
 	{
 		extern __shared__ uint32_t s_hist[];   // max(T, ORDER_BUCKETS) words
-		if (SCATTER && order != nullptr && blockIdx.x == gridDim.x - 1)
+		const int T = a.T, grid_x = a.grid_x;
+		const uint32_t sparse_cap = a.sparse_cap;
+		uint32_t* __restrict__ const counters = a.counters;
+		uint2* __restrict__ const pairs = a.pairs;
+		if (SCATTER && a.order != nullptr && blockIdx.x == gridDim.x - 1)
 		{
 			// the extra workgroup of the scatter launch: the blend kernels' tile order from the scan's copy of the counts
-			tile_order_block(order + tile_order_counts_off(T), order + tile_order_tmp_off(T), T, ctl[1], order, s_hist);
+			tile_order_block(a.order + tile_order_counts_off(T), a.order + tile_order_tmp_off(T), T, a.ctl[1], a.order, s_hist);
 			return;
 		}
-		// launched before the host knew num_rendered (capi.hip): `pairs` holds `capacity` instances -- more than that: leave everything alone
-		// (sparse lists: nobody has counted yet -- the counters start from zero and a tile that outgrows its sparse_cap slots drops
-		// what does not fit; its count still says so, and the host renders the view again)
-		if (SCATTER && sparse_cap == 0u && ctl[0] > capacity) return;
+		if (SCATTER && lists_do_not_fit(a)) return;
 		const int lane = threadIdx.x & 63;
 		for (int t = threadIdx.x; t < T; t += BIN_T) s_hist[t] = 0u;
 		__syncthreads();
@@ -196,36 +234,29 @@ namespace fdgs
 			ushort4 r = make_ushort4(0, 0, 0, 0);
 			uint32_t key = 0u;
 			if (g < P) { r = rect[g]; key = __float_as_uint(depths[g]); }
-#if defined(FDGS_PROBE_NO_PASS_B)   // timing probes only (tools/probe/bin_probe.hip)
-			(void)r; (void)key;
-#elif defined(FDGS_PROBE_NO_STORE)
-			walk_rect_tiles(r, key, (uint32_t)g, grid_x, lane, [&](uint32_t tile, uint32_t k, uint32_t id) {
-				const uint32_t slot = atomicAdd(&s_hist[tile], 1u);
-				if (slot == 0xFFFFFFFFu) pairs[slot] = make_uint2(k, id);
-			});
-#else
 			walk_rect_tiles(r, key, (uint32_t)g, grid_x, lane, [&](uint32_t tile, uint32_t k, uint32_t id) {
 				const uint32_t slot = atomicAdd(&s_hist[tile], 1u);
 				if (sparse_cap == 0u || slot < (tile + 1u) * sparse_cap) pairs[slot] = make_uint2(k, id);
 			});
-#endif
 		}
 	}
 
 	// Images with more tiles than an LDS histogram holds: the same walk with one global atomic per instance.
 	template <bool SCATTER>
 	__global__ void __launch_bounds__(256) tile_bin_direct_kernel(const ushort4* __restrict__ rect, const float* __restrict__ depths, int P,
-	                                                              int grid_x, uint32_t* __restrict__ counters, uint2* __restrict__ pairs,
-	                                                              const uint32_t* __restrict__ ctl, uint32_t capacity,
-	                                                              uint32_t* __restrict__ order, int T, uint32_t sparse_cap)
+	                                                              const TileBinArgs a)
 	{
 		__shared__ uint32_t s_cls[ORDER_BUCKETS];
-		if (SCATTER && order != nullptr && blockIdx.x == gridDim.x - 1)
+		const int T = a.T, grid_x = a.grid_x;
+		const uint32_t sparse_cap = a.sparse_cap;
+		uint32_t* __restrict__ const counters = a.counters;
+		uint2* __restrict__ const pairs = a.pairs;
+		if (SCATTER && a.order != nullptr && blockIdx.x == gridDim.x - 1)
 		{
-			tile_order_block(order + tile_order_counts_off(T), order + tile_order_tmp_off(T), T, ctl[1], order, s_cls);
+			tile_order_block(a.order + tile_order_counts_off(T), a.order + tile_order_tmp_off(T), T, a.ctl[1], a.order, s_cls);
 			return;
 		}
-		if (SCATTER && sparse_cap == 0u && ctl[0] > capacity) return;
+		if (SCATTER && lists_do_not_fit(a)) return;
 		const int g = blockIdx.x * blockDim.x + threadIdx.x;
 		ushort4 r = make_ushort4(0, 0, 0, 0);
 		uint32_t key = 0u;
@@ -245,11 +276,12 @@ namespace fdgs
 	// exclusive scan of the tile counters by ONE workgroup; ctl[0] = R, ctl[1] = longest tile list
 	// ------------------------------------------------------------------------------------------------
 	constexpr int SCAN_T = 1024;
-	__global__ void __launch_bounds__(SCAN_T) tile_scan_kernel(uint32_t* __restrict__ counters, int T, int per_thread /* multiple of 4 */,
-	                                                           uint32_t* __restrict__ ctl, uint32_t* __restrict__ host_box, uint32_t ticket,
-	                                                           uint32_t* __restrict__ counts_copy /* [T + 3] or NULL: the counts, for tile_order_block */)
+	__global__ void __launch_bounds__(SCAN_T) tile_scan_kernel(const TileBinArgs a, int per_thread /* multiple of 4 */, const TileReport to)
 	{
 		__shared__ uint32_t s_w[SCAN_T / WAVE], s_m[SCAN_T / WAVE];
+		const int T = a.T;
+		uint32_t* __restrict__ const counters = a.counters;
+		uint32_t* __restrict__ const counts_copy = a.order ? a.order + tile_order_counts_off(T) : nullptr;   // [T + 3]: the counts, for tile_order_block
 		const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 		const int first = threadIdx.x * per_thread;
 		// the counter array is padded to a multiple of 4 words (zeros), so the uint4 accesses stay inside it
@@ -261,14 +293,8 @@ namespace fdgs
 			sum += (v.x + v.y) + (v.z + v.w);
 			m = max(max(m, max(v.x, v.y)), max(v.z, v.w));
 		}
-		uint32_t incl = sum;
-#pragma unroll
-		for (int o = 1; o < WAVE; o <<= 1)
-		{
-			const uint32_t t = __shfl_up(incl, o);
-			if (lane >= o) incl += t;
-			m = max(m, (uint32_t)__shfl_xor((int)m, o));
-		}
+		const uint32_t incl = wave_inclusive_sum(sum);
+		m = wave_max(m);
 		if (lane == WAVE - 1) { s_w[wave] = incl; s_m[wave] = m; }
 		__syncthreads();
 		uint32_t base = 0, gmax = 0, gtot = 0;
@@ -293,17 +319,7 @@ namespace fdgs
 			*p = o;
 			if (counts_copy) *reinterpret_cast<uint4*>(counts_copy + first + i) = v;   // 16-byte aligned (tile_order_counts_off), 3 words of slack behind T
 		}
-		if (threadIdx.x == 0)
-		{
-			ctl[0] = gtot; ctl[1] = gmax;
-			if (host_box)
-			{
-				// straight into the caller's pinned, device-mapped mailbox: {R, longest list}, then the call's ticket with
-				// system-scope release -- the host spins on the ticket instead of paying a copy kernel and a stream sync
-				host_box[0] = gtot; host_box[1] = gmax;
-				__hip_atomic_store(&host_box[2], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-			}
-		}
+		if (threadIdx.x == 0) report_totals(to, gtot, gmax);
 	}
 
 	// ------------------------------------------------------------------------------------------------
@@ -318,8 +334,8 @@ namespace fdgs
 	//   3. every key counts the smaller keys of its bucket (n / 65 entries on average, whatever the distribution, ties
 	//      in depth included since the id is part of the key) -> final position -> point_list.
 	// A bucket that still turns out crowded (> rank_max) sends the tile to a bitonic sort of its keys in LDS.
-	// Two instances: one WAVE per tile for lists of up to 1024 entries (no workgroup barriers at all), 256 threads per
-	// tile for up to 4096; longer lists are sorted by a bitonic network in global scratch.
+	// Five instances, 128 ... 1024 threads per tile and 8 or 16 keys per thread, for lists of up to 16384 entries (tile_sort_plan chooses);
+	// longer lists are sorted by a bitonic network in global scratch.
 	constexpr int TS_NS = 64;                   // splitters
 	constexpr int TS_G = 2;                     // keys a thread handles side by side (independent LDS chains in flight); 4 wastes half of
 	                                            // the lanes on the typical 470-entry list of a 256-thread instance, 1 serialises the chains
@@ -366,12 +382,6 @@ namespace fdgs
 			}
 	}
 
-#ifdef FDGS_TS_TIMELINE   // probe only: cycles between the phases of tile_sort_kernel, summed over the tiles (wave 0, lane 0)
-	__device__ unsigned int* g_tl;   // [T][16] cycles, written without atomics
-#define TL_MARK(k) do { if (tid == 0) { const unsigned long long now__ = __builtin_readcyclecounter(); g_tl[blockIdx.x * 16 + (k)] = (unsigned int)(now__ - tl_prev); tl_prev = now__; } } while (0)
-#else
-#define TL_MARK(k) do { } while (0)
-#endif
 	constexpr int TS_PAD = 128;                         // sentinel keys behind the list (>= the largest rank_max)
 
 	// One tile's list.  Returns true when the list is no longer than n_lo (not this instance's).
@@ -395,9 +405,6 @@ namespace fdgs
 		__shared__ uint32_t s_wmin[THREADS / WAVE], s_wmax[THREADS / WAVE];   // smallest / largest depth bits per wave (long lists)
 		const int tid = threadIdx.x, lane = tid & 63;
 		// after the scatter pass a tile's counter holds the END of its list = the start of the next tile's
-#ifdef FDGS_TS_TIMELINE
-		unsigned long long tl_prev = __builtin_readcyclecounter();
-#endif
 		// (sparse lists: the counter holds the tile's COUNT, its list starts at tile * sparse_cap; a count beyond sparse_cap = overflow,
 		// reported through the longest list: what fitted is sorted so that everything queued behind reads valid ids)
 		const uint32_t start = sparse_cap ? (uint32_t)tile * sparse_cap : (tile == 0 ? 0u : list_end[tile - 1]);
@@ -457,10 +464,6 @@ namespace fdgs
 #pragma unroll
 		for (int i = 0; i < ITEMS; i++) { key[i] = 0xFFFFFFFFu; id[i] = 0xFFFFFFFFu; }
 		FOR_ITEMS(if (valid) { const uint2 p = pairs[start + it * THREADS + tid]; key[it] = p.x; id[it] = p.y; })
-#ifdef FDGS_TS_TIMELINE
-		if (key[0] == 0x12345678u) s_flag[0] = 1u;   // forces the wait for the loads before the mark
-#endif
-		TL_MARK(0);
 		for (int i = tid; i < TS_NBK + 4; i += THREADS) s_hist[i] = 0u;
 		if (tid < 2) s_flag[tid] = 0u;
 		// The intervals below the first and above the last splitter have no second bound among the samples; each holds n / 65
@@ -493,7 +496,6 @@ namespace fdgs
 			s_split[lane] = v;
 		}
 		__syncthreads();
-		TL_MARK(1);
 
 		// bucket = (number of splitters < depth bits) * TS_SUB + linear position inside the splitter interval: monotone in
 		// the depth bits, so equal depths share a bucket; br = bucket << 16 | arrival index inside the bucket
@@ -531,7 +533,6 @@ namespace fdgs
 		}
 		FOR_ITEMS(if (valid) br[it] = (br[it] << 16) | atomicAdd(&s_hist[br[it]], 1u);)
 		__syncthreads();
-		TL_MARK(2);
 		if (tid < WAVE)
 		{
 			// exclusive scan of the bucket sizes by wave 0 (lane = splitter interval, TS_SUB sizes each); the largest bucket
@@ -541,15 +542,8 @@ namespace fdgs
 			uint32_t tail[TS_SUB];
 #pragma unroll
 			for (int q = 0; q < TS_SUB; q++) { tail[q] = s_hist[TS_NS * TS_SUB + q]; mb = max(mb, tail[q]); }
-			uint32_t incl = sum;
-#pragma unroll
-			for (int o = 1; o < WAVE; o <<= 1)
-			{
-				const uint32_t t = __shfl_up(incl, o);
-				if (lane >= o) incl += t;
-				mb = max(mb, (uint32_t)__shfl_xor((int)mb, o));
-			}
-			uint32_t run = incl - sum;
+			mb = wave_max(mb);
+			uint32_t run = wave_inclusive_sum(sum) - sum;
 #pragma unroll
 			for (int q = 0; q < TS_SUB; q++) { s_hist[lane * TS_SUB + q] = run; run += c[q]; }
 			if (lane == WAVE - 1)
@@ -561,7 +555,6 @@ namespace fdgs
 			}
 		}
 		__syncthreads();
-		TL_MARK(3);
 
 		if ((int)s_flag[0] > rank_max && !direct)
 		{
@@ -578,7 +571,6 @@ namespace fdgs
 		FOR_ITEMS(if (valid) { const uint32_t pos = s_hist[br[it] >> 16] + (br[it] & 0xFFFFu); s_key[pos] = key[it]; s_id[pos] = id[it]; })
 		for (int i = tid; i < TS_PAD; i += THREADS) s_key[n + i] = 0xFFFFFFFFu;
 		__syncthreads();
-		TL_MARK(4);
 		// Final position = start of the bucket + number of smaller keys in it.  All of a thread's keys walk their buckets
 		// side by side; a key whose bucket is shorter than its neighbours' keeps reading: whatever follows its bucket has
 		// larger depth bits (later bucket) or is a sentinel, and counts neither as smaller nor as equal.  Two instructions per
@@ -617,15 +609,11 @@ namespace fdgs
 			}
 			if (valid) fin[it] = bs[it] + lt[it];)
 		// ids through LDS in final order, so that point_list is written with contiguous stores
-		TL_MARK(5);
 		__syncthreads();
-		TL_MARK(6);
 		uint32_t* s_out = s_dyn;
 		FOR_ITEMS(if (fin[it] != 0xFFFFFFFFu) s_out[fin[it]] = id[it];)
 		__syncthreads();
-		TL_MARK(7);
 		for (int i = tid; i < n; i += THREADS) point_list[start + i] = s_out[i];
-		TL_MARK(8);
 #undef FOR_ITEMS
 		return false;
 	}
@@ -633,115 +621,86 @@ namespace fdgs
 	// The main instance (n_lo == 0: every tile, also writes `ranges`): workgroup b takes ONE tile -- with `order` (the blend kernels'
 	// tile order, written by the scatter launch: all tiles, the longest lists first) entry b of it, so that the long lists start first
 	// -- dealt round-robin to the XCDs, as the workgroups are -- and the launch ends on short ones; without: tile b.
+	// With a report to make (sparse lists, main instance only) the launch has one more workgroup, its first -- so that it is dispatched
+	// first and its ~7 us of serial work run next to the tiles' sorts, not behind them.
 	template <int THREADS, int ITEMS>
-	__global__ void __launch_bounds__(THREADS) tile_sort_kernel(const uint32_t* __restrict__ list_end, const uint2* __restrict__ pairs,
-	                                                           uint32_t* __restrict__ point_list, uint2* __restrict__ ranges,
-	                                                           u64* __restrict__ big_scratch, int n_lo /* handle lists longer than this */,
-	                                                           int lds_cap, int rank_max, const uint32_t* __restrict__ ctl, uint32_t capacity,
-	                                                           int last /* no further instance takes what this one leaves */,
-	                                                           const uint32_t* __restrict__ order /* [T] or NULL */, int T,
-	                                                           uint32_t sparse_cap, uint32_t* __restrict__ report_ctl /* sparse main instance: ctl (written) */,
-	                                                           uint32_t* __restrict__ report_box, uint32_t ticket, uint32_t* __restrict__ order_out)
+	__global__ void __launch_bounds__(THREADS) tile_sort_kernel(const TileBinArgs a, const TileReport rep, u64* __restrict__ big_scratch,
+	                                                           int n_lo /* handle lists longer than this */, int lds_cap, int rank_max,
+	                                                           int last /* no further instance takes what this one leaves */)
 	{
-		if (report_ctl != nullptr && blockIdx.x == 0)
+		if (rep.ctl != nullptr && blockIdx.x == 0)
 		{
-			// (workgroup 0, so that it is dispatched first and its ~7 us of serial work run next to the tiles' sorts, not behind them)
-			// SPARSE lists, the extra workgroup of the main instance: what the scan kernel does for compact lists -- num_rendered and the
-			// longest list from the tiles' counts (final since the scatter launch) into ctl and the caller's mailbox, and the blend
-			// kernels' tile order
-			__shared__ uint32_t s_rep[ORDER_BUCKETS];
-			__shared__ uint32_t s_sum[THREADS / WAVE], s_max[THREADS / WAVE];
-			uint32_t sum = 0u, mx = 0u;
-			for (int t = threadIdx.x; t < T; t += THREADS) { const uint32_t c = list_end[t]; sum += c; mx = max(mx, c); }
-#pragma unroll
-			for (int o = 32; o > 0; o >>= 1) { sum += (uint32_t)__shfl_xor((int)sum, o); mx = max(mx, (uint32_t)__shfl_xor((int)mx, o)); }
-			if ((threadIdx.x & 63) == 0) { s_sum[threadIdx.x >> 6] = sum; s_max[threadIdx.x >> 6] = mx; }
-			__syncthreads();
-			uint32_t gtot = 0u, gmax = 0u;
-#pragma unroll
-			for (int w = 0; w < THREADS / WAVE; w++) { gtot += s_sum[w]; gmax = max(gmax, s_max[w]); }
-			if (threadIdx.x == 0)
-			{
-				report_ctl[0] = gtot; report_ctl[1] = gmax;
-				if (report_box)
-				{
-					report_box[0] = gtot; report_box[1] = gmax;
-					__hip_atomic_store(&report_box[2], ticket, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-				}
-			}
-			if (order_out != nullptr) tile_order_block(list_end, order_out + tile_order_tmp_off(T), T, gmax, order_out, s_rep);
+			tile_report_block<THREADS>(a.counters, a.T, rep);
 			return;
 		}
-		const int wg = (int)blockIdx.x - (report_ctl != nullptr ? 1 : 0);
-		if (wg >= T) return;
-		const int tile = order != nullptr ? (int)order[wg] : wg;
-		// launched before the host knew num_rendered: if the buffers are too small the scatter pass did not run either (the counters
-		// are not list ends) -- every tile is reported empty, so that whatever is queued behind reads nothing, and the host starts over
-		if (sparse_cap == 0u && ctl[0] > capacity)
+		const int wg = (int)blockIdx.x - (rep.ctl != nullptr ? 1 : 0);
+		if (wg >= a.T) return;
+		const int tile = a.order != nullptr ? (int)a.order[wg] : wg;
+		if (lists_do_not_fit(a))
 		{
-			if (n_lo == 0 && threadIdx.x == 0) ranges[tile] = make_uint2(0u, 0u);
+			if (n_lo == 0 && threadIdx.x == 0) a.ranges[tile] = make_uint2(0u, 0u);
 			return;
 		}
-		tile_sort_one<THREADS, ITEMS>(tile, list_end, pairs, point_list, ranges, big_scratch, n_lo, lds_cap, rank_max, last, sparse_cap);
+		tile_sort_one<THREADS, ITEMS>(tile, a.counters, a.pairs, a.point_list, a.ranges, big_scratch, n_lo, lds_cap, rank_max, last, a.sparse_cap);
 	}
 
 	// ------------------------------------------------------------------------------------------------
 	// host side
 	// ------------------------------------------------------------------------------------------------
+	// A launch with more dynamic LDS than the default limit (48 KiB) needs the kernel's limit raised first.  The attribute belongs to
+	// the (kernel, device) pair: set once per device this process launches on.
+	template <auto KERNEL>
+	static hipError_t raise_dynamic_lds(int bytes)
+	{
+		static std::atomic<unsigned long long> done{0};   // bit d: set on device d (devices beyond the 64th: set every time)
+		int dev = 0;
+		hipError_t e = hipGetDevice(&dev);
+		if (e != hipSuccess) return e;
+		if (dev < 64 && ((done.load(std::memory_order_acquire) >> dev) & 1ull)) return hipSuccess;
+		e = hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+		if (e == hipSuccess && dev < 64) done.fetch_or(1ull << dev, std::memory_order_release);
+		return e;
+	}
+
 	constexpr int BIN_LDS_MAX_TILES = 36 * 1024;   // a 144 KiB histogram stays inside the 160 KiB of a CU
 	static inline int bin_rounds(int T) { return T <= 8192 ? 1 : 4; }   // bigger histograms: fewer, longer workgroups
 
 	template <bool SCATTER>
-	static hipError_t launch_tile_bin(const uint16_t* rect, const float* depths, int P, int grid_x, int T, uint32_t* counters, uint32_t* pairs,
-	                                  const uint32_t* ctl, uint32_t capacity, uint32_t* order, hipStream_t stream, uint32_t sparse_cap = 0u)
+	static hipError_t launch_tile_bin(const uint16_t* rect, const float* depths, int P, TileBinArgs a, hipStream_t stream)
 	{
 		if (P <= 0) return hipSuccess;
 		const ushort4* r4 = reinterpret_cast<const ushort4*>(rect);
-		uint2* p2 = reinterpret_cast<uint2*>(pairs);
-		if (T >= (1 << 24)) order = nullptr;   // (tile_order_block packs a rank into 24 bits)
-		const int extra = (SCATTER && order) ? 1 : 0;   // one more workgroup: tile_order_block
-		if (T <= BIN_LDS_MAX_TILES)
+		// sparse lists: the counters are still zero (no count / scan pass ran); the tile order is left to the sort launch (tile_report_block)
+		if (a.T >= (1 << 24) || a.sparse_cap) a.order = nullptr;   // (tile_order_block packs a rank into 24 bits)
+		const int extra = (SCATTER && a.order) ? 1 : 0;   // one more workgroup: tile_order_block
+		if (a.T <= BIN_LDS_MAX_TILES)
 		{
-			// the attribute belongs to the (kernel, device) pair: set once per device this process launches on
-			static std::atomic<unsigned long long> attr_done{0};   // bit d: set on device d
-			int dev = 0;
-			hipError_t e = hipGetDevice(&dev);
+			const hipError_t e = raise_dynamic_lds<&tile_bin_lds_kernel<SCATTER>>(BIN_LDS_MAX_TILES * 4);
 			if (e != hipSuccess) return e;
-			if (dev >= 64 || !((attr_done.load(std::memory_order_acquire) >> dev) & 1ull))
-			{
-				e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_bin_lds_kernel<SCATTER>),
-				                        hipFuncAttributeMaxDynamicSharedMemorySize, BIN_LDS_MAX_TILES * 4);
-				if (e != hipSuccess) return e;
-				if (dev < 64) attr_done.fetch_or(1ull << dev, std::memory_order_release);
-			}
-			const int rounds = bin_rounds(T);
+			const int rounds = bin_rounds(a.T);
 			hipLaunchKernelGGL(tile_bin_lds_kernel<SCATTER>, dim3(div_up(P, rounds * BIN_T) + extra), dim3(BIN_T),
-			                   (size_t)max(T, ORDER_BUCKETS) * 4, stream, r4, depths, P, grid_x, T, rounds, counters, p2, ctl, capacity, order, sparse_cap);
+			                   (size_t)max(a.T, ORDER_BUCKETS) * 4, stream, r4, depths, P, rounds, a);
 		}
 		else
-			hipLaunchKernelGGL(tile_bin_direct_kernel<SCATTER>, dim3(div_up(P, 256) + extra), dim3(256), 0, stream, r4, depths, P, grid_x, counters, p2,
-			                   ctl, capacity, order, T, sparse_cap);
+			hipLaunchKernelGGL(tile_bin_direct_kernel<SCATTER>, dim3(div_up(P, 256) + extra), dim3(256), 0, stream, r4, depths, P, a);
 		return hipGetLastError();
 	}
 
-	hipError_t launch_tile_count(const uint16_t* rect, int P, int grid_x, int T, uint32_t* counters, hipStream_t stream)
+	hipError_t launch_tile_count(const uint16_t* rect, int P, const TileBinArgs& a, hipStream_t stream)
 	{
-		return launch_tile_bin<false>(rect, nullptr, P, grid_x, T, counters, nullptr, nullptr, 0u, nullptr, stream);
+		return launch_tile_bin<false>(rect, nullptr, P, a, stream);
 	}
 
-	hipError_t launch_tile_scan(uint32_t* counters, int T, uint32_t* ctl, uint32_t* host_box, uint32_t ticket, uint32_t* tile_order, hipStream_t stream)
+	hipError_t launch_tile_scan(const TileBinArgs& a, const TileReport& to, hipStream_t stream)
 	{
-		const int per_thread = div_up(div_up(T, SCAN_T), 4) * 4;
-		hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, counters, T, per_thread, ctl, host_box, ticket,
-		                   tile_order ? tile_order + tile_order_counts_off(T) : nullptr);
+		const int per_thread = div_up(div_up(a.T, SCAN_T), 4) * 4;
+		hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(SCAN_T), 0, stream, a, per_thread, to);
 		return hipGetLastError();
 	}
 
-	hipError_t launch_tile_scatter(const uint16_t* rect, const float* depths, int P, int grid_x, int T, uint32_t* counters, uint32_t* pairs,
-	                               const uint32_t* ctl, uint32_t capacity, uint32_t* tile_order, hipStream_t stream, uint32_t sparse_cap)
+	hipError_t launch_tile_scatter(const uint16_t* rect, const float* depths, int P, const TileBinArgs& a, hipStream_t stream)
 	{
-		// sparse lists: the counters are still zero (no count / scan pass ran); the tile order is left to the sort launch (tile_sort_kernel)
-		return launch_tile_bin<true>(rect, depths, P, grid_x, T, counters, pairs, ctl, capacity, sparse_cap ? nullptr : tile_order, stream, sparse_cap);
+		return launch_tile_bin<true>(rect, depths, P, a, stream);
 	}
 
 	// test hook: cap the list length the LDS instances take, and the crowded-bucket threshold
@@ -753,88 +712,88 @@ namespace fdgs
 	}
 	int tile_sort_lds_cap() { return g_lds_cap.load(); }
 
-	template <int THREADS, int ITEMS = TS_ITEMS>
-	static hipError_t launch_sort_instance(const uint32_t* counters, int T, const uint2* pairs, uint32_t* point_list, uint2* ranges, u64* big,
-	                                 int n_lo, int cap, int rank_max, const uint32_t* ctl, uint32_t capacity, bool last, const uint32_t* order,
-	                                 hipStream_t stream, uint32_t sparse_cap = 0u, uint32_t* report_ctl = nullptr, uint32_t* report_box = nullptr,
-	                                 uint32_t ticket = 0u, uint32_t* order_out = nullptr)
+	// one launch of the sort: which instance, over the lists longer than n_lo, with LDS for lds_keys keys; last: no further launch
+	// takes what this one leaves
+	struct SortStep { int instance, n_lo, lds_keys; bool last; };
+
+	template <int THREADS, int ITEMS>
+	static hipError_t launch_sort_instance(const TileBinArgs& a, const TileReport& rep, u64* big, const SortStep& s, int rank_max, hipStream_t stream)
 	{
-		const size_t lds = (size_t)cap * 8 + TS_PAD * 4;
+		const size_t lds = (size_t)s.lds_keys * 8 + TS_PAD * 4;
 		if (lds > 48 * 1024)
 		{
-			// more dynamic LDS than the default limit: raise it once per (instance, device)
-			static std::atomic<unsigned long long> attr_done{0};   // bit d: set on device d
-			int dev = 0;
-			hipError_t e = hipGetDevice(&dev);
+			const hipError_t e = raise_dynamic_lds<&tile_sort_kernel<THREADS, ITEMS>>(THREADS * ITEMS * 8 + TS_PAD * 4);
 			if (e != hipSuccess) return e;
-			if (dev >= 64 || !((attr_done.load(std::memory_order_acquire) >> dev) & 1ull))
-			{
-				e = hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_sort_kernel<THREADS, ITEMS>), hipFuncAttributeMaxDynamicSharedMemorySize,
-				                        THREADS * ITEMS * 8 + TS_PAD * 4);
-				if (e != hipSuccess) return e;
-				if (dev < 64) attr_done.fetch_or(1ull << dev, std::memory_order_release);
-			}
 		}
-		hipLaunchKernelGGL((tile_sort_kernel<THREADS, ITEMS>), dim3(T + (report_ctl ? 1 : 0)), dim3(THREADS), lds, stream,
-		                   counters, pairs, point_list, ranges, big, n_lo, cap, rank_max, ctl, capacity, last ? 1 : 0, order, T,
-		                   sparse_cap, report_ctl, report_box, ticket, order_out);
+		hipLaunchKernelGGL((tile_sort_kernel<THREADS, ITEMS>), dim3(a.T + (rep.ctl ? 1 : 0)), dim3(THREADS), lds, stream,
+		                   a, rep, big, s.n_lo, s.lds_keys, rank_max, s.last ? 1 : 0);
 		return hipSuccess;
 	}
 
-	// sparse_cap != 0: SPARSE lists (see tile_bin_lds_kernel): `counters` hold the tiles' counts, tile t's list sits at t * sparse_cap;
-	// the main instance carries one extra workgroup (its first) that reports num_rendered / the longest list into `report_ctl` and the mailbox
-	// `report_box` (with `ticket`) and writes the blend kernels' tile order into `order_out`; max_count = the longest list PROVIDED FOR
-	hipError_t launch_tile_sort(const uint32_t* counters, int T, int max_count, const uint32_t* pairs, uint32_t* point_list, uint32_t* ranges,
-	                            void* big_scratch, const uint32_t* ctl, uint32_t capacity, const uint32_t* tile_order, hipStream_t stream,
-	                            uint32_t sparse_cap, uint32_t* report_ctl, uint32_t* report_box, uint32_t ticket, uint32_t* order_out)
+	// the instances: threads x keys per thread = the longest list each takes
+	struct SortInstance
 	{
-		const int lds_cap = g_lds_cap.load(), rank_max = g_rank_max.load();
-		const uint2* p2 = reinterpret_cast<const uint2*>(pairs);
-		uint2* r2 = reinterpret_cast<uint2*>(ranges);
-		u64* big = reinterpret_cast<u64*>(big_scratch);
-		// The main instance takes every tile and is sized by the longest list: 128 threads per tile while no list
-		// exceeds 1024 entries, else 256 (up to 2048 entries; measured at C3, where a quarter of the lists are longer than
-		// 1024: one 256-thread launch 62 us, a 128-thread launch plus a 256-thread launch for the long ones 88 us).  Lists
-		// beyond 2048 are rare on a uniform scene and the rule on a clustered one (a trained scene: most Gaussians on the
-		// subject; C3-clustered: 700 of 5440 tiles).  They are taken by up to two more instances, all in LDS: 512 threads x
-		// 8 keys for (2048, 4096], and for what is longer still 1024 threads x 8 keys while nothing exceeds 8192, else 1024 x
-		// 16 (up to 16384).  Every instance is a launch over all tiles whose workgroups leave at once when the list is not
-		// theirs (looping launches of a few hundred workgroups that walk the tile order from its long end were built and are
-		// slower: 146 against 99 us for the three launches on C3-clustered -- the loop costs the body 40-80 VGPRs).  Only what is
-		// longer than lds_cap (16384) still goes through the bitonic network in global scratch (91 rounds of global round trips
-		// for 8192 keys: it used to take everything beyond 4096 -- 0.33 ms for the sort on C3-clustered).  An instance's LDS is
-		// sized by the longest list it takes, in 64-key steps (a short longest list = more tiles in flight per CU).
+		int keys;
+		hipError_t (*launch)(const TileBinArgs&, const TileReport&, u64*, const SortStep&, int, hipStream_t);
+	};
+	template <int THREADS, int ITEMS>
+	static constexpr SortInstance sort_instance() { return SortInstance{ THREADS * ITEMS, &launch_sort_instance<THREADS, ITEMS> }; }
+	static const SortInstance TS_INSTANCES[5] = { sort_instance<128, TS_ITEMS>(), sort_instance<256, TS_ITEMS>(), sort_instance<512, TS_ITEMS>(),
+	                                              sort_instance<1024, TS_ITEMS>(), sort_instance<1024, TS_ITEMS_LONG>() };
+
+	// The launches that sort lists of up to max_count entries, of which the LDS instances take up to lds_cap; returns their number.
+	// The main instance takes every tile and is sized by the longest list: 128 threads per tile while no list
+	// exceeds 1024 entries, else 256 (up to 2048 entries; measured at C3, where a quarter of the lists are longer than
+	// 1024: one 256-thread launch 62 us, a 128-thread launch plus a 256-thread launch for the long ones 88 us).  Lists
+	// beyond 2048 are rare on a uniform scene and the rule on a clustered one (a trained scene: most Gaussians on the
+	// subject; C3-clustered: 700 of 5440 tiles).  They are taken by up to two more instances, all in LDS: 512 threads x
+	// 8 keys for (2048, 4096], and for what is longer still 1024 threads x 8 keys while nothing exceeds 8192, else 1024 x
+	// 16 (up to 16384).  Every instance is a launch over all tiles whose workgroups leave at once when the list is not
+	// theirs (looping launches of a few hundred workgroups that walk the tile order from its long end were built and are
+	// slower: 146 against 99 us for the three launches on C3-clustered -- the loop costs the body 40-80 VGPRs).  Only what is
+	// longer than lds_cap (16384) still goes through the bitonic network in global scratch (91 rounds of global round trips
+	// for 8192 keys: it used to take everything beyond 4096 -- 0.33 ms for the sort on C3-clustered); the scratch goes to the
+	// last launch.  An instance's LDS is sized by the longest list it takes, in 64-key steps (a short longest list = more
+	// tiles in flight per CU).
+	static int tile_sort_plan(int max_count, int lds_cap, SortStep steps[3])
+	{
 		const int longest_lds = min(max_count, lds_cap);
-		const int c1 = min(128 * TS_ITEMS, lds_cap), c2 = min(256 * TS_ITEMS, lds_cap), c3 = min(512 * TS_ITEMS, lds_cap);
-		const int c4 = min(1024 * TS_ITEMS, lds_cap), c5 = min(1024 * TS_ITEMS_LONG, lds_cap);
-		const auto lds_keys = [&](int c) { return min(c, max(64, div_up(longest_lds, 64) * 64)); };
-		const bool overflow = max_count > lds_cap;   // somebody has to take the global path
-		if (T >= (1 << 24)) { tile_order = nullptr; order_out = nullptr; }   // no order is written (launch_tile_bin; check_scene rejects such images anyway)
-		if (sparse_cap) tile_order = nullptr;   // the order is only being written by this launch: tiles by index
-		const uint32_t sc = sparse_cap;
-		hipError_t e = hipSuccess;
-		if (max_count <= c1 || c2 == c1)
-			e = launch_sort_instance<128>(counters, T, p2, point_list, r2, overflow ? big : nullptr, 0, lds_keys(c1), rank_max, ctl, capacity, true, tile_order, stream,
-			                              sc, report_ctl, report_box, ticket, order_out);
+		int c[5];
+		for (int i = 0; i < 5; i++) c[i] = min(TS_INSTANCES[i].keys, lds_cap);
+		int n = 0;
+		const auto add = [&](int instance, int n_lo) {
+			steps[n++] = SortStep{ instance, n_lo, min(c[instance], max(64, div_up(longest_lds, 64) * 64)), false };
+		};
+		if (max_count <= c[0] || c[1] == c[0]) add(0, 0);
 		else
 		{
-			const bool second = max_count > c2 && c3 > c2;
-			const bool third = second && longest_lds > c3 && c4 > c3;
-			e = launch_sort_instance<256>(counters, T, p2, point_list, r2, (overflow && !second) ? big : nullptr, 0, lds_keys(c2), rank_max, ctl, capacity, !second, tile_order, stream,
-			                              sc, report_ctl, report_box, ticket, order_out);
-			if (second && e == hipSuccess)
-				e = launch_sort_instance<512>(counters, T, p2, point_list, r2, (overflow && !third) ? big : nullptr, c2, lds_keys(c3), rank_max, ctl, capacity, !third, tile_order,
-				                              stream, sc);
-			if (third && e == hipSuccess)
+			add(1, 0);
+			if (max_count > c[1] && c[2] > c[1])
 			{
-				if (longest_lds <= c4 || c5 == c4)
-					e = launch_sort_instance<1024>(counters, T, p2, point_list, r2, overflow ? big : nullptr, c3, lds_keys(c4), rank_max, ctl, capacity, true, tile_order, stream, sc);
-				else
-					e = launch_sort_instance<1024, TS_ITEMS_LONG>(counters, T, p2, point_list, r2, overflow ? big : nullptr, c3, lds_keys(c5), rank_max, ctl, capacity, true,
-					                                              tile_order, stream, sc);
+				add(2, c[1]);
+				if (longest_lds > c[2] && c[3] > c[2]) add((longest_lds <= c[3] || c[4] == c[3]) ? 3 : 4, c[2]);
 			}
 		}
-		if (e != hipSuccess) return e;
+		steps[n - 1].last = true;
+		return n;
+	}
+
+	hipError_t launch_tile_sort(const TileBinArgs& args, int max_count, void* big_scratch, const TileReport& report, hipStream_t stream)
+	{
+		const int lds_cap = g_lds_cap.load(), rank_max = g_rank_max.load();
+		TileBinArgs a = args;
+		TileReport rep = report;
+		if (a.T >= (1 << 24)) { a.order = nullptr; rep.order_out = nullptr; }   // no order is written (launch_tile_bin; check_scene rejects such images anyway)
+		if (a.sparse_cap) a.order = nullptr;   // the order is only being written by this launch: tiles by index
+		SortStep steps[3];
+		const int n = tile_sort_plan(max_count, lds_cap, steps);
+		for (int k = 0; k < n; k++)
+		{
+			// somebody has to take the global path when a list is longer than the LDS takes: the last launch; the main instance reports
+			u64* big = steps[k].last && max_count > lds_cap ? reinterpret_cast<u64*>(big_scratch) : nullptr;
+			const hipError_t e = TS_INSTANCES[steps[k].instance].launch(a, k == 0 ? rep : TileReport{}, big, steps[k], rank_max, stream);
+			if (e != hipSuccess) return e;
+		}
 		return hipGetLastError();
 	}
 }

@@ -63,104 +63,70 @@ int main(int argc, char** argv)
 			}
 	std::sort(keys.begin(), keys.end());
 
-#ifdef FDGS_TS_TIMELINE
-	unsigned int* d_tl;
-	CK(hipMalloc(&d_tl, (size_t)T * 64));
-	CK(hipMemset(d_tl, 0, (size_t)T * 64));
-	CK(hipMemcpyToSymbol(HIP_SYMBOL(g_tl), &d_tl, sizeof d_tl));
-#endif
-	hipEvent_t ev[8];
+	hipEvent_t ev[7];
 	for (auto& e : ev) CK(hipEventCreate(&e));
-	const int per_thread = ((T + 1023) / 1024 + 3) / 4 * 4;
-	CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_bin_lds_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-	CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_bin_lds_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
-	// variant: rounds > 0: LDS-histogram kernels, rounds x 1024 Gaussians per workgroup; rounds == 0: one global atomic per instance
-	for (int rounds : { 0, 1, 2, 4 })
-		for (int caplim : { 0, 64 })
-			for (int rank_max : { 0, 1 })
+	// the library's own launchers with the library's own argument struct (compact lists, no tile order, capacity = whatever comes)
+	const TileBinArgs a{ d_cnt, d_pairs, d_pl, d_ranges, d_ctl, 0xFFFFFFFFu, nullptr, T, gx, 0u };
+	// variants: the default; lds_cap 64 (every longer list through the bitonic network in global scratch); rank_max 1 (the LDS bitonic fall-back)
+	for (int caplim : { 0, 64 })
+		for (int rank_max : { 0, 1 })
+		{
+			if (quick && (caplim != 0 || rank_max != 0)) continue;
+			if (caplim == 64 && rank_max == 1) continue;
+			tile_sort_debug_limits(caplim, rank_max);
+			float acc[5] = { 0, 0, 0, 0, 0 };
+			const int reps = 20;
+			uint32_t ctl[2];
+			for (int rep = 0; rep < reps + 2; rep++)
 			{
-				const int batch = rounds * 1024;
-				if ((caplim == 64 || rank_max == 1) && rounds != 1) continue;
-				if (quick && (rounds != 1 || caplim != 0 || rank_max != 0)) continue;
-				if (caplim == 64 && rank_max == 1) continue;
-				if (rounds > 0 && T > 36 * 1024) continue;
-				tile_sort_debug_limits(caplim, rank_max);
-				float acc[5] = { 0, 0, 0, 0, 0 };
-				const int reps = 20;
-				uint32_t ctl[2];
-				for (int rep = 0; rep < reps + 2; rep++)
+				CK(hipEventRecord(ev[0]));
+				CK(hipMemsetAsync(d_cnt, 0, (T + 4) * 4));
+				CK(hipEventRecord(ev[1]));
+				CK(launch_tile_count((const uint16_t*)d_rect, P, a, 0));
+				CK(hipEventRecord(ev[2]));
+				CK(launch_tile_scan(a, TileReport{ d_ctl, nullptr, 0u, nullptr }, 0));
+				CK(hipEventRecord(ev[3]));
+				CK(hipMemcpy(ctl, d_ctl, 8, hipMemcpyDeviceToHost));
+				CK(hipEventRecord(ev[6]));
+				CK(launch_tile_scatter((const uint16_t*)d_rect, d_depth, P, a, 0));
+				CK(hipEventRecord(ev[4]));
+				CK(launch_tile_sort(a, (int)ctl[1], d_big, TileReport{}, 0));
+				CK(hipEventRecord(ev[5]));
+				CK(hipDeviceSynchronize());
+				CK(hipGetLastError());
+				if (rep >= 2)
 				{
-					CK(hipEventRecord(ev[0]));
-					CK(hipMemsetAsync(d_cnt, 0, (T + 4) * 4));
-					CK(hipEventRecord(ev[1]));
-					if (rounds) hipLaunchKernelGGL(tile_bin_lds_kernel<false>, dim3((P + batch - 1) / batch), dim3(1024), (size_t)std::max(T, 8 * ORDER_BUCKETS) * 4, 0, d_rect, (const float*)nullptr, P, gx, T, rounds, d_cnt, (uint2*)nullptr, (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, (T + 7) / 8);
-					else hipLaunchKernelGGL(tile_bin_direct_kernel<false>, dim3((P + 255) / 256), dim3(256), 0, 0, d_rect, (const float*)nullptr, P, gx, d_cnt, (uint2*)nullptr, (const uint32_t*)nullptr, 0u, (uint32_t*)nullptr, T, (T + 7) / 8);
-					CK(hipEventRecord(ev[2]));
-					hipLaunchKernelGGL(tile_scan_kernel, dim3(1), dim3(1024), 0, 0, d_cnt, T, per_thread, d_ctl, (uint32_t*)nullptr, 0u, (uint32_t*)nullptr);
-					CK(hipEventRecord(ev[3]));
-					CK(hipMemcpy(ctl, d_ctl, 8, hipMemcpyDeviceToHost));
-					CK(hipEventRecord(ev[6]));
-					if (rounds) hipLaunchKernelGGL(tile_bin_lds_kernel<true>, dim3((P + batch - 1) / batch), dim3(1024), (size_t)std::max(T, 8 * ORDER_BUCKETS) * 4, 0, d_rect, d_depth, P, gx, T, rounds, d_cnt, d_pairs, (const uint32_t*)d_ctl, 0xFFFFFFFFu, (uint32_t*)nullptr, (T + 7) / 8);
-					else hipLaunchKernelGGL(tile_bin_direct_kernel<true>, dim3((P + 255) / 256), dim3(256), 0, 0, d_rect, d_depth, P, gx, d_cnt, d_pairs, (const uint32_t*)d_ctl, 0xFFFFFFFFu, (uint32_t*)nullptr, T, (T + 7) / 8);
-					CK(hipEventRecord(ev[4]));
-					CK(launch_tile_sort(d_cnt, T, (int)ctl[1], (const uint32_t*)d_pairs, d_pl, (uint32_t*)d_ranges, d_big, (const uint32_t*)d_ctl, 0xFFFFFFFFu, (const uint32_t*)nullptr, 0));
-					CK(hipEventRecord(ev[5]));
-					CK(hipDeviceSynchronize());
-					CK(hipGetLastError());
-					if (rep >= 2)
+					float ms;
+					for (int k = 0; k < 5; k++)
 					{
-						float ms;
-						for (int k = 0; k < 5; k++)
-						{
-							if (k == 3) CK(hipEventElapsedTime(&ms, ev[6], ev[4])); else CK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
-							acc[k] += ms;
-						}
+						if (k == 3) CK(hipEventElapsedTime(&ms, ev[6], ev[4])); else CK(hipEventElapsedTime(&ms, ev[k], ev[k + 1]));
+						acc[k] += ms;
 					}
 				}
-				std::vector<uint32_t> pl(R);
-				std::vector<uint2> rg(T);
-				CK(hipMemcpy(pl.data(), d_pl, R * 4, hipMemcpyDeviceToHost));
-				CK(hipMemcpy(rg.data(), d_ranges, T * 8, hipMemcpyDeviceToHost));
-				size_t bad = 0;
-				if (ctl[0] != R) bad++;
-				for (size_t s = 0; s < R; s++) if (pl[s] != (uint32_t)keys[s].second) bad++;
-				size_t pos = 0;
-				uint32_t maxc = 0;
-				for (int t = 0; t < T; t++)
-				{
-					size_t e = pos;
-					while (e < R && keys[e].first == (uint32_t)t) e++;
-					maxc = std::max<uint32_t>(maxc, e - pos);
-					if (e == pos) { if (rg[t].x != 0 || rg[t].y != 0) bad++; }
-					else if (rg[t].x != pos || rg[t].y != e) bad++;
-					pos = e;
-				}
-				if (maxc != ctl[1]) bad++;
-#ifdef FDGS_TS_TIMELINE
-				{
-					std::vector<unsigned int> tl((size_t)T * 16);
-					CK(hipMemcpy(tl.data(), d_tl, tl.size() * 4, hipMemcpyDeviceToHost));
-					const char* nm[9] = { "load", "splitters", "search+hist", "scan", "scatter", "rank", "barrier", "out", "store" };
-					printf("   tile_sort cycles per tile (wave 0, last launch):");
-					double tot = 0;
-					for (int k = 0; k < 9; k++) { double a2 = 0; for (int t = 0; t < T; t++) a2 += tl[(size_t)t * 16 + k]; printf(" %s %.0f", nm[k], a2 / T); tot += a2 / T; }
-					printf(" | total %.0f\n", tot);
-					// the same for the tiles of every length class
-					for (int lo : { 0, 1024, 2048, 4096, 8192 })
-					{
-						const int hi = lo == 0 ? 1024 : 2 * lo;
-						double a3[9] = { 0 }; int cnt = 0;
-						for (int t = 0; t < T; t++) { const int n = (int)(rg[t].y - rg[t].x); if (n > lo && n <= hi) { cnt++; for (int k = 0; k < 9; k++) a3[k] += tl[(size_t)t * 16 + k]; } }
-						if (!cnt) continue;
-						printf("   lists (%d, %d]: %d tiles:", lo, hi, cnt);
-						double t3 = 0; for (int k = 0; k < 9; k++) { printf(" %s %.0f", nm[k], a3[k] / cnt); t3 += a3[k] / cnt; }
-						printf(" | total %.0f cycles\n", t3);
-					}
-				}
-#endif
-				printf("batch %4d lds_cap_limit %4d rank_max %2d | memset %.1f  count %.1f  scan %.1f  scatter %.1f  sort %.1f us | max list %u | %s (%zu bad)\n",
-				       batch, caplim, rank_max, acc[0] / reps * 1e3, acc[1] / reps * 1e3, acc[2] / reps * 1e3, acc[3] / reps * 1e3, acc[4] / reps * 1e3,
-				       ctl[1], bad ? "MISMATCH" : "ok", bad);
 			}
+			std::vector<uint32_t> pl(R);
+			std::vector<uint2> rg(T);
+			CK(hipMemcpy(pl.data(), d_pl, R * 4, hipMemcpyDeviceToHost));
+			CK(hipMemcpy(rg.data(), d_ranges, T * 8, hipMemcpyDeviceToHost));
+			size_t bad = 0;
+			if (ctl[0] != R) bad++;
+			for (size_t s = 0; s < R; s++) if (pl[s] != (uint32_t)keys[s].second) bad++;
+			size_t pos = 0;
+			uint32_t maxc = 0;
+			for (int t = 0; t < T; t++)
+			{
+				size_t e = pos;
+				while (e < R && keys[e].first == (uint32_t)t) e++;
+				maxc = std::max<uint32_t>(maxc, e - pos);
+				if (e == pos) { if (rg[t].x != 0 || rg[t].y != 0) bad++; }
+				else if (rg[t].x != pos || rg[t].y != e) bad++;
+				pos = e;
+			}
+			if (maxc != ctl[1]) bad++;
+			printf("lds_cap_limit %4d rank_max %2d | memset %.1f  count %.1f  scan %.1f  scatter %.1f  sort %.1f us | max list %u | %s (%zu bad)\n",
+			       caplim, rank_max, acc[0] / reps * 1e3, acc[1] / reps * 1e3, acc[2] / reps * 1e3, acc[3] / reps * 1e3, acc[4] / reps * 1e3,
+			       ctl[1], bad ? "MISMATCH" : "ok", bad);
+		}
 	return 0;
 }
+
