@@ -20,6 +20,18 @@ namespace fdgs
 		}
 		return x;
 	}
+	// the same over 64-bit values (sums of 32-bit weights that no 32-bit word holds: mcmc.hip)
+	__device__ __forceinline__ uint64_t wave_inclusive_sum(uint64_t x)
+	{
+		const int lane = threadIdx.x & (WAVE - 1);
+#pragma unroll
+		for (int d = 1; d < WAVE; d <<= 1)
+		{
+			const uint64_t y = (uint64_t)__shfl_up((unsigned long long)x, d);
+			if (lane >= d) x += y;
+		}
+		return x;
+	}
 	// sum / maximum over the lanes of the calling wave; every lane gets it
 	__device__ __forceinline__ uint32_t wave_sum(uint32_t x)
 	{
@@ -50,6 +62,27 @@ namespace fdgs
 		for (int w = 0; w < THREADS / WAVE; w++)
 		{
 			const uint32_t c = s_wave[w];
+			if (w < wave) before += c;
+			total += c;
+		}
+		return before + x - v;
+	}
+
+	// block_rank over 64-bit values; s_wave: THREADS / WAVE 64-bit words of LDS
+	template <int THREADS>
+	__device__ __forceinline__ uint64_t block_rank(uint64_t v, uint64_t* s_wave, uint64_t& total)
+	{
+		const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
+		const uint64_t x = wave_inclusive_sum(v);
+		__syncthreads();
+		if (lane == WAVE - 1) s_wave[wave] = x;
+		__syncthreads();
+		uint64_t before = 0;
+		total = 0;
+#pragma unroll
+		for (int w = 0; w < THREADS / WAVE; w++)
+		{
+			const uint64_t c = s_wave[w];
 			if (w < wave) before += c;
 			total += c;
 		}

@@ -16,6 +16,7 @@
 #pragma clang fp contract(off)
 #include "fdgs_common.h"
 #include "compact.h"
+#include "philox.h"
 #include "../../include/fdgs_seed.h"
 #include <cmath>
 
@@ -125,19 +126,7 @@ namespace fdgs
 		__device__ static void st3(float* a, const size_t k, const float3 v) { a[3 * k] = v.x; a[3 * k + 1] = v.y; a[3 * k + 2] = v.z; }
 	};
 
-	// ---- Philox4x32-10 (Salmon et al., SC'11) ----
-	__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k)
-	{
-#pragma unroll
-		for (int r = 0; r < 10; r++)
-		{
-			const uint32_t hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-			const uint32_t hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-			c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-			k.x += 0x9E3779B9u; k.y += 0xBB67AE85u;
-		}
-		return c;
-	}
+	// ---- Philox4x32-10 (philox.h) ----
 	__device__ __forceinline__ float seed_uniform(const uint32_t w) { return (float)(w >> 8) * 5.9604644775390625e-08f; }   // 2^-24, exact
 
 	struct SeedRandomParams { float p[6]; };
@@ -281,7 +270,7 @@ extern "C" int fdgs_seed_random(int32_t N, uint64_t seed, uint32_t stream_id, in
 	if (!out) return fail(FDGS_ERR_INVALID_ARG, "fdgs_seed_random: out must not be NULL");
 	SeedRandomParams a;
 	for (int k = 0; k < 6; k++) a.p[k] = params[k];
-	const uint2 key = make_uint2((uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32));
+	const uint2 key = philox_key(seed);
 	hipLaunchKernelGGL(seed_random_kernel, dim3(div_up(N, SEED_THREADS)), dim3(SEED_THREADS), 0, (hipStream_t)stream_v, N, key, stream_id, shape, a, out,
 	                   words, uniforms);
 	return launched("fdgs_seed_random");

@@ -34,7 +34,7 @@ class StepPipeline:
                  fuse_sh_adam: bool = True, gather_max_views: int = 32, split_colour: bool = False, batch_views: bool = False,
                  sh_group: int = 1, tile_cull: bool = True, lazy: bool = True, sparse_lists: bool = True, overlap_steps: bool = False,
                  lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0, rigid_k: int = 20,
-                 env_optimizer=None):
+                 env_optimizer=None, grad_terms=None):
         """``fuse_sh_adam``: on one rank the SH coefficients are updated straight from the views'
         staged SH gradients (FlatAdam.step_sh_staged) and ``_features.grad`` is NOT materialised for the step; False keeps
         the flush into the gradient bucket followed by the plain Adam step (always the case on several ranks, where the
@@ -46,9 +46,16 @@ class StepPipeline:
         with the reference's defaults is made at the first such step).  Such a step rasterizes over black, composites the map behind
         every view on stream F right behind the view's forward (``results[b]["render"]`` is the composited image), takes the
         composite's backward on stream B between the loss gradient and the rasterizer backward (the alpha gradient; the map's gradient
-        is written by view 0 and added by the others) and steps the map's Adam in the tail (``step(..., optimize_env=)``)."""
+        is written by view 0 and added by the others) and steps the map's Adam in the tail (``step(..., optimize_env=)``).
+        ``grad_terms``: callables that add further loss terms' gradients into the gradient bucket (one rank only), each called once per
+        step with the sink dict (``GaussianParams.grad_sink()``'s names) while stream B is current, where the rigid / motion terms add
+        theirs: right after view 0's backward has written the bucket and before anything reads the geometry gradient
+        (``fdgs.mcmc.MCMCStrategy.add_regularizer_grads`` is one).  None: the step's launch sequence is exactly the plain one."""
         if int(world_size) > 1 and (lambda_rigid > 0 or lambda_motion > 0 or lambda_opa_mask > 0):
             raise NotImplementedError("StepPipeline: the rigid / motion / opacity-mask terms run on one rank only")
+        self.grad_terms = tuple(grad_terms) if grad_terms else ()
+        if int(world_size) > 1 and self.grad_terms:
+            raise NotImplementedError("StepPipeline: grad_terms run on one rank only")
         self.lam_rigid, self.lam_motion, self.lam_opa = float(lambda_rigid), float(lambda_motion), float(lambda_opa_mask)
         self.rigid_k = int(rigid_k)
         self.regularize = self.lam_rigid > 0 or self.lam_motion > 0
@@ -293,6 +300,15 @@ class StepPipeline:
                        g["dL_drotations"].data_ptr(), g["dL_drotations_r"].data_ptr(), st.reg_scratch.data_ptr(), guard=False)
         st.reg_done = True
 
+    def _grad_terms(self, st):
+        """The caller's gradient terms (``grad_terms``), at the same point of the step as ``_terms_backward`` and like it once per step."""
+        if not self.grad_terms or st.terms_done:
+            return
+        with torch.cuda.stream(self.sB):
+            for term in self.grad_terms:
+                term(self.sink)
+        st.terms_done = True
+
     def _opa_grad(self, st, b, T):
         """The opacity-mask term of view b (stream B is current): its value into last_terms["opa_mask"][b] and
         d (lambda_opa_mask L_opa / B) / d alpha, the upstream alpha gradient of the view's backward (None without the term)."""
@@ -372,9 +388,9 @@ class StepPipeline:
                             R_last = r_val
                 after_sh = partial(self._stages_final, st, [b], s_up) if st.final == "gather" or (last and st.final) else None
                 geo_adam = None
-                # (B = 1 with the rigid / motion terms: their gradient comes after the only view's backward, so the geometry Adam is the
-                # tail's for that step)
-                if last and st.final == "sh_update" and m.rot_4d and m.gaussian_dim == 4 and not (self.regularize and B == 1):
+                # (B = 1 with the rigid / motion terms or grad_terms: their gradient comes after the only view's backward, so the geometry
+                # Adam is the tail's for that step)
+                if last and st.final == "sh_update" and m.rot_4d and m.gaussian_dim == 4 and not ((self.regularize or self.grad_terms) and B == 1):
                     # the Adam step of the 17 geometry parameters per Gaussian INSIDE the last view's geometry backward (fdgs_backward_out.adam:
                     # the kernel has just completed their gradient) instead of by a launch of its own in the tail; bit-identical
                     def geo_adam():
@@ -390,6 +406,7 @@ class StepPipeline:
                                      sh_stage=st.stage[b] if st.defer_sh else None, per_view_outputs=False, geometry_adam=geo_adam)
                 if b == 0:
                     self._terms_backward(st)
+                    self._grad_terms(st)
                 loss = None if self.finish_on_F else l1_ssim_loss(loss_handle)
                 pend_loss.append(loss_handle)
             # buffers allocated on F are read on B: keep them alive until F has waited for B (end of the step)
@@ -438,6 +455,7 @@ class StepPipeline:
                         keep.append(_dgr._C.backward_finish(pend[v]))
                         results[v]["viewspace_grad"] = keep[-1][0]
                     self._terms_backward(st)   # (view 0's geometry backward has written the bucket by now)
+                    self._grad_terms(st)
             keep.append((geom, binb, img, out_means3D, g_color, T))
         self._optimizer_tail(st)
         self._join(st)
@@ -541,4 +559,5 @@ class _Step:
         self.sh_handle = None       # several ranks, dense: the all-reduce of the SH part of the bucket
         self.gathers = []           # gather: the work handles of the views' stage exchanges
         self.reg_done = False       # the rigid / motion gradient has been added to the bucket this step
+        self.terms_done = False     # the caller's grad_terms have been added to the bucket this step
         self.keep_masks = []        # the views' alpha masks and alpha gradients, alive until the step's end
