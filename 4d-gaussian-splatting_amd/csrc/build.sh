@@ -18,13 +18,13 @@ COMMON="--offload-arch=$ARCH -O3 -std=c++17 -fPIC -munsafe-fp-atomics -Wall -Wno
 # a time, bit-identical results (the whole GPU suite); step +0.4 % at C3, +0.9 % at C5, forward-only -3 %.
 # ssim: the SLP vectorizer pairs the scalar third channel of the backward's windows into packed multiplies that each need four register
 # moves to line their operands up (595 -> 568 instructions per thread without it; the forward is packed by hand either way)
-declare -A EXTRA=( [preprocess_fwd]="-ffp-contract=off -fno-slp-vectorize" [preprocess_bwd]="-ffp-contract=off -fno-slp-vectorize" [sh_bwd]="-ffp-contract=off -fno-slp-vectorize" [time_slice]="-ffp-contract=off -fno-slp-vectorize" [flow]="-ffp-contract=off -fno-slp-vectorize" [camera_bwd]="-ffp-contract=off -fno-slp-vectorize" [knn]="-ffp-contract=off" [regularize]="-ffp-contract=off" [ssim]="-fno-slp-vectorize" [frames]="-ffp-contract=off" [frame_encode]="-ffp-contract=off" [frame_resize]="-ffp-contract=off" [compress]="-ffp-contract=off" [model_transform]="-ffp-contract=off -fno-slp-vectorize" [depth_loss]="-ffp-contract=off" [tsdf]="-ffp-contract=off" [mesh]="-ffp-contract=off" [mesh_simplify]="-ffp-contract=off" [seed]="-ffp-contract=off" [mcmc]="-ffp-contract=off" )
+declare -A EXTRA=( [preprocess_fwd]="-ffp-contract=off -fno-slp-vectorize" [preprocess_bwd]="-ffp-contract=off -fno-slp-vectorize" [sh_bwd]="-ffp-contract=off -fno-slp-vectorize" [time_slice]="-ffp-contract=off -fno-slp-vectorize" [flow]="-ffp-contract=off -fno-slp-vectorize" [camera_bwd]="-ffp-contract=off -fno-slp-vectorize" [knn]="-ffp-contract=off" [regularize]="-ffp-contract=off" [ssim]="-fno-slp-vectorize" [frames]="-ffp-contract=off" [frame_encode]="-ffp-contract=off" [frame_resize]="-ffp-contract=off" [compress]="-ffp-contract=off" [model_transform]="-ffp-contract=off -fno-slp-vectorize" [depth_loss]="-ffp-contract=off" [tsdf]="-ffp-contract=off" [mesh]="-ffp-contract=off" [mesh_simplify]="-ffp-contract=off" [seed]="-ffp-contract=off" [mcmc]="-ffp-contract=off" [exposure]="-ffp-contract=off" )
 OBJS=()
 PIDS=()
-for src in preprocess_fwd tilebin radix_sort blend_fwd blend_bwd preprocess_bwd sh_bwd ssim adam densify knn regularize envmap metrics frames frame_encode frame_resize time_slice flow contribution features camera_bwd compress model_transform depth_loss tsdf mesh mesh_simplify seed mcmc capi; do
+for src in preprocess_fwd tilebin radix_sort blend_fwd blend_bwd preprocess_bwd sh_bwd ssim adam densify knn regularize envmap metrics frames frame_encode frame_resize time_slice flow contribution features camera_bwd compress model_transform depth_loss tsdf mesh mesh_simplify seed mcmc exposure capi; do
   obj=build/$src.o
   OBJS+=("$obj")
-  if [[ ! -f $obj || $src.hip -nt $obj || fdgs_common.h -nt $obj || ssim_window.h -nt $obj || blend_common.h -nt $obj || fdgs_math.h -nt $obj || sh_eval.h -nt $obj || compact.h -nt $obj || scan.h -nt $obj || mesh_common.h -nt $obj || ../../include/fdgs.h -nt $obj || philox.h -nt $obj || ../../include/fdgs_seed.h -nt $obj || ../../include/fdgs_mcmc.h -nt $obj ]]; then
+  if [[ ! -f $obj || $src.hip -nt $obj || fdgs_common.h -nt $obj || ssim_window.h -nt $obj || blend_common.h -nt $obj || fdgs_math.h -nt $obj || sh_eval.h -nt $obj || compact.h -nt $obj || scan.h -nt $obj || mesh_common.h -nt $obj || ../../include/fdgs.h -nt $obj || philox.h -nt $obj || ../../include/fdgs_seed.h -nt $obj || ../../include/fdgs_mcmc.h -nt $obj || ../../include/fdgs_exposure.h -nt $obj ]]; then
     $HIPCC $COMMON ${EXTRA[$src]:-} ${FDGS_EXTRA_FLAGS:-} -c $src.hip -o $obj &
     PIDS+=($!)
   fi

@@ -34,7 +34,7 @@ class StepPipeline:
                  fuse_sh_adam: bool = True, gather_max_views: int = 32, split_colour: bool = False, batch_views: bool = False,
                  sh_group: int = 1, tile_cull: bool = True, lazy: bool = True, sparse_lists: bool = True, overlap_steps: bool = False,
                  lambda_rigid: float = 0.0, lambda_motion: float = 0.0, lambda_opa_mask: float = 0.0, rigid_k: int = 20,
-                 env_optimizer=None, grad_terms=None):
+                 env_optimizer=None, grad_terms=None, exposure=None):
         """``fuse_sh_adam``: on one rank the SH coefficients are updated straight from the views'
         staged SH gradients (FlatAdam.step_sh_staged) and ``_features.grad`` is NOT materialised for the step; False keeps
         the flush into the gradient bucket followed by the plain Adam step (always the case on several ranks, where the
@@ -50,7 +50,21 @@ class StepPipeline:
         ``grad_terms``: callables that add further loss terms' gradients into the gradient bucket (one rank only), each called once per
         step with the sink dict (``GaussianParams.grad_sink()``'s names) while stream B is current, where the rigid / motion terms add
         theirs: right after view 0's backward has written the bucket and before anything reads the geometry gradient
-        (``fdgs.mcmc.MCMCStrategy.add_regularizer_grads`` is one).  None: the step's launch sequence is exactly the plain one."""
+        (``fdgs.mcmc.MCMCStrategy.add_regularizer_grads`` is one).  None: the step's launch sequence is exactly the plain one.
+        ``exposure``: a ``fdgs.exposure.ExposureModel`` (one rank only), a learned affine colour transform per training camera.  Every
+        view's image goes through its camera's row on stream F behind the forward (and the environment-map composite) into a second
+        buffer: ``results[b]["render"]`` is the corrected image the loss is taken on, ``results[b]["render_uncorrected"]`` the
+        rasterizer's.  On stream B the transform's backward runs between the loss gradient and the composite's backward: it turns the
+        colour gradient into that of the uncorrected image in place and WRITES the view's 12 sums into its slot of a [B, 12] buffer;
+        the table's Adam (its own: ``step(..., optimize_exposure=)``) is one launch in the tail.  None: the step's launch sequence is
+        exactly the plain one."""
+        if int(world_size) > 1 and exposure is not None:
+            raise NotImplementedError("StepPipeline: the exposure model runs on one rank only")
+        self.exposure = exposure
+        self._exp_idx = None    # this step's row of the exposure table per view, and whether the table's Adam runs
+        self._optimize_exposure = False
+        # recorded on stream B behind the table's Adam; the next step's first apply (stream F) waits for it (see _env_ev)
+        self._exp_ev = None
         if int(world_size) > 1 and (lambda_rigid > 0 or lambda_motion > 0 or lambda_opa_mask > 0):
             raise NotImplementedError("StepPipeline: the rigid / motion / opacity-mask terms run on one rank only")
         self.grad_terms = tuple(grad_terms) if grad_terms else ()
@@ -173,15 +187,19 @@ class StepPipeline:
         return self.sh_group > 1 and B > 1
 
     def step(self, cams: Sequence, gts: Sequence[torch.Tensor], pipe, bg: torch.Tensor, scaling_modifier: float = 1.0,
-             alpha_masks: Sequence[torch.Tensor] = None, optimize_env: bool = True):
+             alpha_masks: Sequence[torch.Tensor] = None, optimize_env: bool = True, camera_indices: Sequence[int] = None,
+             optimize_exposure: bool = True):
         """Runs forward + loss + backward of every view, the gradient all-reduce and the optimizer step.
         Returns (list of per-view results dict(render, radii, depth, alpha_T, flow, viewspace_grad, num_rendered), list
         of losses); the tensors may be used on the caller's stream until the next call of step().  ``losses`` are the views'
         L1 + SSIM values; the other terms (lambda_* > 0) are in ``last_terms``: "rigid", "motion" (device scalars) and "opa_mask"
         (device [B]), unweighted.  ``alpha_masks``: each view's ``gt_alpha_mask`` [1, H, W] (needed with lambda_opa_mask > 0).
         ``optimize_env`` (``pipe.env_map_res`` > 0): whether the environment map's Adam runs this step (train.py:250: iteration <
-        env_optimize_until); without it the map's gradient is not computed, the Gaussians still see the map through alpha."""
+        env_optimize_until); without it the map's gradient is not computed, the Gaussians still see the map through alpha.
+        ``camera_indices`` (with an exposure model): each view's row of the exposure table (default: ``exposure.index_of(cam)``);
+        ``optimize_exposure``: whether the table's Adam runs this step (the images are corrected either way)."""
         m, ctx = self.model, (pipe, bg, scaling_modifier)
+        self._exposure_begin(cams, camera_indices, optimize_exposure)
         if self.lam_opa > 0 and (alpha_masks is None or len(alpha_masks) != len(cams)):
             raise ValueError("StepPipeline: lambda_opa_mask > 0 needs one alpha mask per view (step(..., alpha_masks=))")
         if self.regularize and not (m.rot_4d and m.gaussian_dim == 4):
@@ -236,6 +254,36 @@ class StepPipeline:
             st.keep_masks.append(g_alpha)
         composite_backward(T, g_color, self._env, cam, g_alpha, acc, self.env_opt.grad if self._optimize_env else None, b > 0)
         return g_alpha
+
+    def _exposure_begin(self, cams, camera_indices, optimize_exposure):
+        """The rows of the exposure table this step's views go through, checked on the host."""
+        self._exp_idx = None
+        if self.exposure is None:
+            return
+        ex = self.exposure
+        idx = [ex.index_of(c) for c in cams] if camera_indices is None else [int(i) for i in camera_indices]
+        if len(idx) != len(cams) or any(not 0 <= i < ex.num_cameras for i in idx):
+            raise ValueError("StepPipeline: camera_indices must name one row of the exposure table's %d per view; got %s for %d views"
+                             % (ex.num_cameras, idx, len(cams)))
+        self._exp_idx, self._optimize_exposure = idx, bool(optimize_exposure)
+
+    def _exposure_apply(self, b, color):
+        """Stream F is current, behind the view's forward and its composite: the corrected image, in a buffer of its own (the backward
+        reads the uncorrected one).  The first apply after a step whose table Adam ran waits for it (see _env_composite)."""
+        from .exposure import apply_
+        if self._exp_ev is not None:
+            self.sF.wait_event(self._exp_ev)
+            self._exp_ev = None
+        return apply_(color, self.exposure.table, self._exp_idx[b], out=torch.empty_like(color))
+
+    def _exposure_backward(self, st, b, color, g_color):
+        """Stream B is current, right behind the view's loss gradient: ``g_color`` becomes the gradient of the uncorrected image
+        ``color`` in place, the view's 12 sums are written (never added: a lazy step that is given up and redone overwrites them)
+        into slot b."""
+        if self._exp_idx is None:
+            return
+        from .exposure import backward_
+        backward_(g_color, color, self.exposure.table, self._exp_idx[b], self._buffer("exp_slots", (st.B, 12))[b])
 
     def _begin(self, B):
         """Head of every step: the streams wait for the caller's (overlap_steps: see __init__), the step's state and buffers."""
@@ -332,18 +380,20 @@ class StepPipeline:
             sets = [raw_settings(c, self.model, *ctx) for c in cams]
             return raw_preprocess_batch([s[0] for s in sets], *sets[0][1], tile_cull=self.tile_cull)
 
-    def _forward(self, cam, ctx, **kw):
-        """One view's forward on stream F (raw_forward options ``kw``; with the environment map its composite behind), which stream B
-        then waits for: (settings, tensors, outputs)."""
+    def _forward(self, cam, ctx, view=0, **kw):
+        """Forward of view ``view`` on stream F (raw_forward options ``kw``; with the environment map its composite behind, with an
+        exposure model the corrected image behind that), which stream B then waits for: (settings, tensors, outputs, the image the
+        loss is taken on)."""
         with torch.cuda.stream(self.sF):
             rs, tens = raw_settings(cam, self.model, *ctx)
             out = raw_forward(rs, *tens, tile_cull=self.tile_cull, **kw)
             if self._env is not None:
                 self._env_composite(cam, out[1], out[4])
+            shown = out[1] if self._exp_idx is None else self._exposure_apply(view, out[1])
             ev = torch.cuda.Event()
             ev.record(self.sF)
         self.sB.wait_event(ev)
-        return rs, tens, out
+        return rs, tens, out, shown
 
     def _step_views(self, cams, gts, ctx, lazy):
         """step(); ``lazy``: see __init__ -- returns None when a view did not fit its run-ahead buffers (nothing of the optimizer step
@@ -361,14 +411,15 @@ class StepPipeline:
         for b in range(B):
             last, plain = b == B - 1, handles[b] is None
             first_on_A = b == 0 and self.sA is not None and st.fuse and plain
-            rs, tens, (R, color, flow, depth, T, radii, geom, binb, img, _covs, out_means3D) = self._forward(
-                cams[b], ctx, preprocessed=handles[b], split_colour=(self.split_colour or first_on_A) and plain,
+            rs, tens, (R, color, flow, depth, T, radii, geom, binb, img, _covs, out_means3D), shown = self._forward(
+                cams[b], ctx, b, preprocessed=handles[b], split_colour=(self.split_colour or first_on_A) and plain,
                 colour_stream=self.sA if first_on_A else None, lazy=lazy and plain, sparse_lists=self.sparse_lists and lazy and plain)
             st.rs = rs
             with torch.cuda.stream(self.sB):
                 if self.finish_on_F and b == 0:   # (see __init__; the views of a step share one image size)
                     parts = self._buffer("parts", (B, 2, _capi.lib.fdgs_l1_ssim_num_partials(*color.shape)))
-                g_color, loss_handle = l1_ssim_grad(color, gts[b], self.lam, st.up, parts=parts[b] if self.finish_on_F else None)
+                g_color, loss_handle = l1_ssim_grad(shown, gts[b], self.lam, st.up, parts=parts[b] if self.finish_on_F else None)
+                self._exposure_backward(st, b, color, g_color)
                 if self.finish_on_F and last:
                     ev_parts = torch.cuda.Event()
                     ev_parts.record(self.sB)   # every view's partial sums are there
@@ -410,9 +461,11 @@ class StepPipeline:
                 loss = None if self.finish_on_F else l1_ssim_loss(loss_handle)
                 pend_loss.append(loss_handle)
             # buffers allocated on F are read on B: keep them alive until F has waited for B (end of the step)
-            keep.append((geom, binb, img, out_means3D, g_color, T))
-            results.append({"render": color, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow,
+            keep.append((geom, binb, img, out_means3D, g_color, T, shown))
+            results.append({"render": shown, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow,
                             "viewspace_grad": grads[0], "num_rendered": R_last if (lazy and last and R < 0) else R})
+            if shown is not color:
+                results[-1]["render_uncorrected"] = color
             losses.append(loss)
         if self.finish_on_F:
             with torch.cuda.stream(self.sF):
@@ -436,12 +489,15 @@ class StepPipeline:
         handles = self._colour_pass(cams, ctx) if self.batch_views else [None] * B
         results, losses, keep, pend = [], [], [], []
         for b in range(B):
-            rs, tens, (R, color, flow, depth, T, radii, geom, binb, img, _covs, out_means3D) = self._forward(
-                cams[b], ctx, preprocessed=handles[b], split_colour=self.split_colour and handles[b] is None)
+            rs, tens, (R, color, flow, depth, T, radii, geom, binb, img, _covs, out_means3D), shown = self._forward(
+                cams[b], ctx, b, preprocessed=handles[b], split_colour=self.split_colour and handles[b] is None)
             st.rs = rs
-            results.append({"render": color, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow, "num_rendered": R})
+            results.append({"render": shown, "radii": radii, "depth": depth, "alpha_T": T, "flow": flow, "num_rendered": R})
+            if shown is not color:
+                results[-1]["render_uncorrected"] = color
             with torch.cuda.stream(self.sB):
-                g_color, loss_handle = l1_ssim_grad(color, gts[b], self.lam, st.up)
+                g_color, loss_handle = l1_ssim_grad(shown, gts[b], self.lam, st.up)
+                self._exposure_backward(st, b, color, g_color)
                 g_alpha = self._env_backward(st, b, cams[b], T, g_color, self._opa_grad(st, b, T))
                 pend.append(raw_backward(rs, tens[0], out_means3D, radii, *tens[1:], geom, R, binb, img, g_color, None, g_alpha, None,
                                          self.sink, b > 0, grad_accum=gacc[b], sh_stage=st.stage[b], begin_only=True, per_view_outputs=False))
@@ -456,7 +512,7 @@ class StepPipeline:
                         results[v]["viewspace_grad"] = keep[-1][0]
                     self._terms_backward(st)   # (view 0's geometry backward has written the bucket by now)
                     self._grad_terms(st)
-            keep.append((geom, binb, img, out_means3D, g_color, T))
+            keep.append((geom, binb, img, out_means3D, g_color, T, shown))
         self._optimizer_tail(st)
         self._join(st)
         return results, losses
@@ -496,6 +552,10 @@ class StepPipeline:
                 self.env_opt.step()
                 self._env_ev = torch.cuda.Event()
                 self._env_ev.record(self.sB)
+            if self._exp_idx is not None and self._optimize_exposure:   # (every view's slot is written: its exposure backward is behind)
+                self.exposure.step(self._exp_idx, self._buffer("exp_slots", (st.B, 12)))
+                self._exp_ev = torch.cuda.Event()
+                self._exp_ev.record(self.sB)
             # the losses were scaled by 1 / (B * world): SUM = mean; Adam on chunk k overlaps the all-reduce of chunk k+1
             if not (st.fuse or st.gather):
                 allreduce_and_step(m, self.opt, self.world, chunks=4, average=False, sh_handle=st.sh_handle, wait_pairs=self.exchange_pairs)
