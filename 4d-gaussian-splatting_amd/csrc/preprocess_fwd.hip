@@ -190,7 +190,11 @@ namespace fdgs
 					const int y0 = min(a.grid_y, max(0, (int)((pix.y - r) / TILE_Y)));
 					const int x1 = min(a.grid_x, max(0, (int)((pix.x + r + TILE_X - 1) / TILE_X)));
 					const int y1 = min(a.grid_y, max(0, (int)((pix.y + r + TILE_Y - 1) / TILE_Y)));
-					if ((x1 - x0) * (y1 - y0) == 0 || r <= 0) alive = false; // forward.cu:471
+					if ((x1 - x0) * (y1 - y0) == 0 || r <= 0) // forward.cu:471
+					{
+						// culled like every other culled Gaussian: position and conic words of the record are zero, not what was computed on the way
+						alive = false; pix = make_float2(0.f, 0.f); conic = make_float3(0.f, 0.f, 0.f);
+					}
 					else
 					{
 						radius = r;
