@@ -8,6 +8,7 @@ import pytest
 import torch
 
 import flow_cases as fc
+import chain_oracle as co
 import flow_oracle as fo
 import util
 
@@ -161,3 +162,130 @@ def test_python_argument_errors():
         gaussian_flow(cam, cam_to, *[par[n] for n in fo.NAMES], rot_4d=True, gaussian_dim=4, raw=False)
     empty = gaussian_flow(cam, cam_to, par["means3D"][:0], None, None, None, None, None, rot_4d=False, gaussian_dim=3, raw=False)
     assert empty.shape == (0, 2)
+
+
+# ---- the analytic float64 statement, the per-element bar and its K (tests/flow_oracle.py, tests/flow_cases.py) ----
+
+def _autograd(case):
+    b = fc.build(case)
+    scale = float(np.float32(fc.SCALE))
+    flow, g = fo.flow_with_grads(*b["cam"], b["par"], b["dL"].double() * scale, **fc.settings(case))
+    return dict({n: g[n].numpy() for n in fo.NAMES}, flows=flow.numpy())
+
+
+@pytest.mark.parametrize("case", fc.CASES, ids=lambda c: c.name)
+def test_analytic_statement_is_float64_autograd(case):
+    """Without a plant the hand-written backward is float64 autograd of the forward statement, element by element, to 1e-11 relative.
+    Relative to what the element is made of: max(|element|, 2^23 sens_e), the size of its first-order terms in the inputs.  Two float64
+    evaluations of a sum agree to 2^-53 of its TERMS, not of the sum: over the cases' 10^5 elements some are small against their terms
+    by chance or by construction (one camera: g_0 + g_1), and relative to the element alone the two statements differ by up to 4e-8
+    (hard_act_p1000 scales_t, temporal scale 60; 1.2e-10 on the generic two-camera cases) whichever is called the reference.  The
+    temporal scale of 60 cancels by structure (w does not depend on it to 1e-7), which no first-order term in the inputs sees: for
+    scales_t the size is also at least that of the two routes it is the difference of (flow_oracle.analytic's "scales_t_terms")."""
+    f64, sens = fc.oracle(case)
+    ref = _autograd(case)
+    worst_lit, worst = 0.0, 0.0
+    for k in fo.OUTPUTS:
+        a, r = f64[k].reshape(case.P, -1), ref[k].reshape(case.P, -1)
+        d = np.abs(a - r)
+        size = np.maximum(np.maximum(np.abs(a), np.abs(r)), 2.0 ** 23 * sens[k].reshape(case.P, -1))
+        if k == "scales_t" and case.rot_4d:
+            size = np.maximum(size, f64["scales_t_terms"].reshape(case.P, 1))
+        assert (size[d > 0] > 0).all(), k
+        with np.errstate(all="ignore"):
+            lit = np.where(d > 0, d / np.maximum(np.abs(a), np.abs(r)), 0.0)
+            rel = np.where(d > 0, d / size, 0.0)
+        worst_lit, worst = max(worst_lit, float(lit.max())), max(worst, float(rel.max()))
+        assert rel.max() <= 1e-11, "%s %s: element %s differs by %.3g of its terms" % (case.name, k, np.unravel_index(rel.argmax(), rel.shape), rel.max())
+    print("%s: analytic vs autograd, worst %.3g of the terms, %.3g of the element itself" % (case.name, worst, worst_lit))
+
+
+@pytest.mark.parametrize("case", [c for c in fc.CASES if c.family == "hard"], ids=lambda c: c.name)
+def test_every_population_is_present(case):
+    f64, _ = fc.oracle(case)
+    got = fc.assert_populations(case, f64)
+    print(case.name, got)
+    placed = fc.build(case)["placed"]
+    assert set(fc.need(case)) - {"dl_zero", "dl_one", "dl_big"} == set(placed)
+    for c in fc.CASES:
+        assert c.P <= 1000 and (c.family == "hard") == bool(fc.need(c))
+
+
+@pytest.fixture(scope="module")
+def r32():
+    """{family: {tensor: (r32, case, element)}}: the float32 statement's worst ratio over the family's cases."""
+    worst = {}
+    for case in fc.CASES:
+        f64, sens = fc.oracle(case)
+        f32 = fc.float32_statement(case)
+        assert np.array_equal(f32["ok"], f64["ok"]), case.name
+        for k, (r, at) in fc.ratios(f32, f64, sens).items():
+            w = worst.setdefault(case.family, {})
+            if r > w.get(k, (-1.0,))[0]:
+                w[k] = (r, case.name, tuple(int(i) for i in at))
+    return worst
+
+
+def test_float32_statement_pins_K(r32):
+    """K = 4 * r32 per output tensor and family, from the float32 statement on the CPU alone."""
+    assert set(r32) == set(fc.K) == {"generic", "hard"}
+    for fam in sorted(r32):
+        assert set(r32[fam]) == set(fc.K[fam]) == set(fo.OUTPUTS)
+        for k in fo.OUTPUTS:
+            r, name, at = r32[fam][k]
+            print("r32 %-8s %-12s %12.4g  (%s, element %s)   K = %g" % (fam, k, r, name, at, fc.K[fam][k]))
+            assert np.isfinite(r) and r > 0.0
+            assert abs(fc.K[fam][k] - 4.0 * r) <= fc.K_TOLERANCE * fc.K[fam][k], \
+                "flow_cases.K[%r][%r] = %g drifted from 4 * r32 = %g" % (fam, k, fc.K[fam][k], 4.0 * r)
+
+
+def _flags(case, plant):
+    """{tensor: number of elements beyond K times their bar} of the float64 statement with ``plant``, rounded to float32."""
+    f64, sens = fc.oracle(case)
+    b = fc.build(case)
+    bad = fo.analytic(*b["cam"], b["par"], b["dL"], scale=fc.SCALE, plant=plant, **fc.settings(case))
+    hits = {}
+    for k in fo.OUTPUTS:
+        n = len(co.flagged(bad[k].astype(np.float32), f64[k], sens[k], fc.K[case.family][k]))
+        if n:
+            hits[k] = n
+    return hits
+
+
+def _old_bar_passes(case, plant):
+    """Does ``plant`` pass the bar the gradients had before, 1e-4 * max(1, max|ref|) on the maximum over a tensor's elements?"""
+    f64, _ = fc.oracle(case)
+    b = fc.build(case)
+    bad = fo.analytic(*b["cam"], b["par"], b["dL"], scale=fc.SCALE, plant=plant, **fc.settings(case))
+    return all(np.abs(bad[n].astype(np.float32) - f64[n]).max() <= 1e-4 * max(1.0, np.abs(f64[n]).max()) for n in fo.NAMES)
+
+
+PLANT_GENERIC = "raw_p1000_two_mod0.7"
+PLANT_HARD = "hard_raw_p257"
+
+
+def test_the_projection_term_of_the_normalisation_backward_is_zero_here():
+    """Why "no_proj" cannot be flagged: w is homogeneous of degree 0 in either quaternion, so q . g = 0 and the term q (q . g) that
+    act_normalize_bwd subtracts is rounding.  With and without it the float64 statement is the same to 1e-11 of the element's terms."""
+    for name in (PLANT_GENERIC, PLANT_HARD):
+        case = fc.BY_NAME[name]
+        f64, sens = fc.oracle(case)
+        b = fc.build(case)
+        bad = fo.analytic(*b["cam"], b["par"], b["dL"], scale=fc.SCALE, plant="no_proj", **fc.settings(case))
+        for k in fo.OUTPUTS:
+            size = np.maximum(np.abs(f64[k]), 2.0 ** 23 * sens[k])
+            d = np.abs(bad[k] - f64[k])
+            assert (d <= 1e-11 * size).all(), (name, k, float((d / np.maximum(size, 1e-300)).max()))
+
+
+@pytest.mark.parametrize("plant", [p for p in fo.PLANTS if p not in fo.UNOBSERVABLE_PLANTS])
+def test_planted_errors(plant):
+    """The float64 statement with one wrong term stands in for a kernel with that bug: at the bar the GPU tests use it is flagged on a
+    generic case, and a plant in a raw-only or 4D-only term on the hard case too; the unplanted statement, rounded to float32, never."""
+    cases = [fc.BY_NAME[PLANT_GENERIC]] + ([fc.BY_NAME[PLANT_HARD]] if plant in fo.RAW_PLANTS + fo.ROT4D_PLANTS else [])
+    for case in cases:
+        assert case.raw and case.rot_4d and case.mod != 1.0
+        assert not _flags(case, None), case.name
+        hits = _flags(case, plant)
+        print("%s on %s: flagged %r; the old max-norm bar %s" % (plant, case.name, hits, "passes it" if _old_bar_passes(case, plant) else "catches it"))
+        assert hits, "%s: the planted error passes the bar on every tensor of %s" % (plant, case.name)

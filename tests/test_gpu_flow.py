@@ -382,3 +382,286 @@ def test_flow_to_none_is_todays_path(gpu_device, which):
     assert torch.equal(v0, v1)
     for n in g0:
         assert bool(g0[n].any()) and torch.equal(g0[n], g1[n]), n
+
+
+# ---- 6: element by element against the float64 statement (tests/flow_oracle.analytic, the cases of tests/flow_cases.CASES) ----
+# Every element of ``flows`` and of the six gradients within K[family][tensor] * (4 ulp32 of |f64_e| + sens_e); no element is exempt.
+
+import json  # noqa: E402
+
+import chain_oracle as co  # noqa: E402
+from guarded import Guarded  # noqa: E402
+
+CASE_NAMES = [c.name for c in fc.CASES]
+SHAPES = {"means3D": 3, "ts": 1, "scales": 3, "scales_t": 1, "rotations": 4, "rotations_r": 4}
+
+
+@pytest.fixture(scope="module")
+def worst_ratios():
+    """The kernels' worst |hip - f64| / (4 ulp32 + sens) per family and tensor over the cases that ran: printed."""
+    rep = {}
+    yield rep
+    print("\nflow kernels, worst ratio per family and tensor: " + json.dumps(
+        {fam: {k: float("%.4g" % v) for k, v in sorted(d.items())} for fam, d in sorted(rep.items())}))
+
+
+def case_cameras(case, b, form=None):
+    from fdgs.playback import with_timestamp
+    form = form or case.cams
+    cam = fc.Cam(b["s0"], DEV)
+    if form == "null":
+        return cam, with_timestamp(cam, b["s1"]["timestamp"])
+    cam_to = fc.Cam(b["s1"], DEV)    # "equal": the same pose in buffers of its own
+    assert cam_to.world_view_transform.data_ptr() != cam.world_view_transform.data_ptr()
+    assert form == "two" or torch.equal(cam_to.full_proj_transform, cam.full_proj_transform)
+    return cam, cam_to
+
+
+def case_inputs(case, b):
+    """The six device tensors as the C entry takes them (None for what a model without rot_4d does not have)."""
+    return [b["par"][n].to(DEV).contiguous() if (case.rot_4d or n == "means3D") else None for n in fo.NAMES]
+
+
+def c_forward(case, cams, tensors, flows_ptr):
+    from fdgs import _capi
+    from fdgs.flow import _flow_in
+    a, keep = _flow_in(cams[0], cams[1], tensors, case.rot_4d, case.dim, case.raw, case.mod)
+    assert a.P == case.P and (a.viewmatrix_to is None) == (cams[1].world_view_transform is cams[0].world_view_transform)
+    rc = _capi.lib.fdgs_gaussian_flow_forward(C.byref(a), flows_ptr, _capi.current_stream_handle(torch.device(DEV)))
+    assert rc == 0, _capi.last_error()
+    torch.cuda.synchronize()
+    del keep
+
+
+def c_backward(case, cams, tensors, dL, scale, out_ptrs):
+    from fdgs import _capi
+    from fdgs.flow import _flow_in
+    a, keep = _flow_in(cams[0], cams[1], tensors, case.rot_4d, case.dim, case.raw, case.mod)
+    out = _capi.FdgsFlowGrads(*out_ptrs)
+    rc = _capi.lib.fdgs_gaussian_flow_backward(C.byref(a), dL.data_ptr(), float(scale), C.byref(out), _capi.current_stream_handle(dL.device))
+    assert rc == 0, _capi.last_error()
+    torch.cuda.synchronize()
+    del keep
+
+
+def run_forward(case, b, form=None):
+    flows = torch.full((case.P, 2), float("nan"), device=DEV)
+    c_forward(case, case_cameras(case, b, form), case_inputs(case, b), flows.data_ptr())
+    return flows.cpu().numpy()
+
+
+def zero_bufs(case):
+    return [torch.zeros(case.P, SHAPES[n], device=DEV) for n in fo.NAMES]
+
+
+def run_backward(case, b, form=None, bufs=None, which=None, tensors=None):
+    """{name: array} of the buffers after one call at scale SCALE (``which``: the outputs that are not NULL; default all six)."""
+    bufs = zero_bufs(case) if bufs is None else bufs
+    ptrs = [t.data_ptr() if (which is None or n in which) else None for n, t in zip(fo.NAMES, bufs)]
+    c_backward(case, case_cameras(case, b, form), case_inputs(case, b) if tensors is None else tensors, b["dL"].to(DEV).contiguous(), fc.SCALE, ptrs)
+    return {n: t.cpu().numpy() for n, t in zip(fo.NAMES, bufs)}
+
+
+def hold(case, got, f64, sens, names, worst_ratios):
+    for k in names:
+        r = co.ratio(got[k], f64[k], sens[k])
+        w = float(r.max())
+        fam = worst_ratios.setdefault(case.family, {})
+        fam[k] = max(fam.get(k, 0.0), w)
+        print("%s %-11s worst ratio %.4g (K %g)" % (case.name, k, w, fc.K[case.family][k]))
+        assert w <= fc.K[case.family][k], "%s %s: element %s is %.4g bars from float64 (K = %g)" % (
+            case.name, k, np.unravel_index(int(r.argmax()), r.shape), w, fc.K[case.family][k])
+
+
+@pytest.mark.parametrize("name", CASE_NAMES)
+def test_forward_elements_against_float64(gpu_device, worst_ratios, name):
+    """``flows`` within K of the bar on every element; the validity mask is the oracle's; invalid rows are the bits of 0; two runs
+    give equal bits; one camera as equal matrices in buffers of their own gives the NULL form's bits."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    f64, sens = fc.oracle(case)
+    got = run_forward(case, b)
+    assert np.isfinite(got).all()
+    assert not fc.bits(got[~f64["ok"]]).any(), "a Gaussian behind a camera has a flow that is not the bits of 0"
+    mask = fc.bits(got).any(axis=1)
+    assert np.array_equal(mask, f64["ok"] & (f64["flows"] != 0).any(axis=1)), "the validity mask is not the oracle's"
+    hold(case, {"flows": got}, f64, sens, ("flows",), worst_ratios)
+    assert np.array_equal(fc.bits(got), fc.bits(run_forward(case, b))), "two runs differ"
+    if case.cams == "equal":
+        assert np.array_equal(fc.bits(got), fc.bits(run_forward(case, b, "null"))), "equal matrices and NULL matrices differ"
+    pops = fc.assert_populations(case, f64, got)
+    print(name, {k: v for k, v in pops.items() if v})
+
+
+@pytest.mark.parametrize("name", CASE_NAMES)
+def test_backward_elements_against_float64(gpu_device, worst_ratios, name):
+    """fdgs_gaussian_flow_backward itself, scale 0.37, the case's dL_dflows, zeroed buffers: all six gradients within K of the bar on
+    every element (without rot_4d the five others stay 0); two runs give equal bits; equal matrices give the NULL form's bits."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    f64, sens = fc.oracle(case)
+    got = run_backward(case, b)
+    hold(case, got, f64, sens, fo.NAMES, worst_ratios)
+    again = run_backward(case, b)
+    other = run_backward(case, b, "null") if case.cams == "equal" else again
+    for n in fo.NAMES:
+        assert np.array_equal(fc.bits(got[n]), fc.bits(again[n])), "%s: two runs differ" % n
+        assert np.array_equal(fc.bits(got[n]), fc.bits(other[n])), "%s: equal matrices and NULL matrices differ" % n
+        if not case.rot_4d and n != "means3D":
+            assert not fc.bits(got[n]).any(), n
+
+
+def prefilled(case, seed):
+    """Six buffers of a non-zero pattern (no element 0, magnitudes 0.25 .. 4)."""
+    g = torch.Generator().manual_seed(seed)
+    out = []
+    for n in fo.NAMES:
+        v = torch.exp2(4.0 * torch.rand(case.P, SHAPES[n], generator=g) - 2.0) * torch.where(torch.rand(case.P, SHAPES[n], generator=g) < 0.5, -1.0, 1.0)
+        out.append(v.to(DEV).contiguous())
+    return out
+
+
+@pytest.mark.parametrize("name", ("hard_raw_p257", "hard_act_p1000"))
+def test_backward_adds_and_leaves_culled_rows_alone(gpu_device, name):
+    """Buffers that already hold values: the rows of Gaussians behind either camera keep their bits in all six; the others are
+    prefill + gradient within the gradient's bar plus one float32 addition's rounding (one ulp32 of the larger addend)."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    f64, sens = fc.oracle(case)
+    bufs = prefilled(case, 3)
+    before = {n: t.cpu().numpy() for n, t in zip(fo.NAMES, bufs)}
+    got = run_backward(case, b, bufs=bufs)
+    culled = ~f64["ok"]
+    assert culled.sum() >= 12
+    for n in fo.NAMES:
+        pf = before[n].astype(np.float64)
+        assert np.array_equal(fc.bits(got[n][culled]), fc.bits(before[n][culled])), "%s: a culled Gaussian's row was written" % n
+        grad = f64[n].reshape(pf.shape)
+        bar = fc.K[case.family][n] * co.core_bar(grad, sens[n].reshape(pf.shape)) + co.ulp32(np.maximum(np.abs(pf), np.abs(grad)))
+        err = np.abs(got[n].astype(np.float64) - (pf + grad))
+        assert (err <= bar).all(), "%s: element %s is %.3g bars from prefill + gradient" % (
+            n, np.unravel_index(int((err / bar).argmax()), err.shape), float((err / bar).max()))
+
+
+@pytest.mark.parametrize("name", ("plain4d_p257", "plain3d_p65"))
+def test_backward_without_rot_4d_writes_the_means_only(gpu_device, name):
+    """Without rot_4d: NULL for ts / scales / scales_t / rotations / rotations_r is accepted, the five buffers that are not the mean's
+    keep every bit of a non-zero prefill, and the mean's is prefill + gradient."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    f64, sens = fc.oracle(case)
+    bufs = prefilled(case, 4)
+    before = {n: t.cpu().numpy() for n, t in zip(fo.NAMES, bufs)}
+    tensors = case_inputs(case, b)
+    assert all(t is None for t in tensors[1:])
+    got = run_backward(case, b, bufs=bufs, tensors=tensors)
+    for n in fo.NAMES[1:]:
+        assert np.array_equal(fc.bits(got[n]), fc.bits(before[n])), "%s was written without rot_4d" % n
+    pf, grad = before["means3D"].astype(np.float64), f64["means3D"]
+    bar = fc.K[case.family]["means3D"] * co.core_bar(grad, sens["means3D"]) + co.ulp32(np.maximum(np.abs(pf), np.abs(grad)))
+    assert (np.abs(got["means3D"].astype(np.float64) - (pf + grad)) <= bar).all() and f64["ok"].all()
+
+
+SUBSETS = (("ts",), ("rotations_r",), ("means3D",), ("scales", "scales_t", "rotations", "rotations_r"))
+
+
+@pytest.mark.parametrize("name", ("raw_p257_two_mod1", "hard_act_p257"))
+def test_output_subsets_have_the_full_calls_bits(gpu_device, name):
+    """NULL outputs: d_ts only (the return before the covariance chain), d_rotations_r only, d_means3D only, the four covariance
+    outputs without d_means3D: what is written has the full call's bits, what is NULL is not touched (the buffers stay 0)."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    full = run_backward(case, b)
+    for which in SUBSETS:
+        got = run_backward(case, b, which=which)
+        for n in fo.NAMES:
+            if n in which:
+                assert full[n].any() and np.array_equal(fc.bits(got[n]), fc.bits(full[n])), "%s of the call with only %s" % (n, which)
+            else:
+                assert not fc.bits(got[n]).any(), "%s was written by the call with only %s" % (n, which)
+
+
+@pytest.mark.parametrize("which", SUBSETS)
+def test_autograd_asks_for_the_needed_gradients_only(gpu_device, monkeypatch, which):
+    """Through autograd: an input that does not require grad gets None from the backward, the others the full call's bits."""
+    from fdgs.flow import _GaussianFlow, gaussian_flow
+    returned, inner = [], _GaussianFlow.backward
+
+    def spy(ctx, dL_dflows):
+        returned.append(inner(ctx, dL_dflows))
+        return returned[-1]
+
+    monkeypatch.setattr(_GaussianFlow, "backward", staticmethod(spy))
+    case = fc.BY_NAME["raw_p257_two_mod1"]
+    b = fc.build(case)
+    cam, cam_to = case_cameras(case, b)
+    dL = b["dL"].to(DEV)
+    res = []
+    for needed in (fo.NAMES, which):
+        leaves = {n: b["par"][n].to(DEV).clone().requires_grad_(n in needed) for n in fo.NAMES}
+        flows = gaussian_flow(cam, cam_to, *[leaves[n] for n in fo.NAMES], rot_4d=True, gaussian_dim=4, raw=case.raw, scaling_modifier=case.mod)
+        flows.backward(dL)
+        res.append(returned[-1][:6])
+    assert len(returned) == 2
+    full, part = res
+    for n, f, p in zip(fo.NAMES, full, part):
+        if n in which:
+            assert torch.equal(p, f) and bool(f.any()), n
+        else:
+            assert p is None and f is not None, n
+
+
+@pytest.mark.parametrize("name", ("raw_p63_two_mod0.7", "hard_raw_p257"))
+def test_slices_one_float_past_a_16_byte_boundary(gpu_device, name):
+    """All six inputs, dL_dflows, flows and all six outputs are slices of ONE flat buffer, each starting 4 bytes past a 16-byte
+    boundary (a parameter bucket's layout at its worst): the same bits as the call on separately allocated tensors."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    P = case.P
+    sizes = [("in_" + n, P * SHAPES[n]) for n in fo.NAMES] + [("dL", 2 * P), ("flows", 2 * P)] + [("out_" + n, P * SHAPES[n]) for n in fo.NAMES]
+    starts, at = {}, 1
+    for k, sz in sizes:
+        starts[k] = at
+        at = (at + sz + 3) // 4 * 4 + 1
+    flat = torch.zeros(at + 4, device=DEV)
+    assert flat.data_ptr() % 16 == 0
+    view = {k: flat[starts[k]:starts[k] + sz] for k, sz in sizes}
+    assert all(v.data_ptr() % 16 == 4 for v in view.values())
+    for n in fo.NAMES:
+        view["in_" + n].copy_(b["par"][n].to(DEV).reshape(-1))
+    view["dL"].copy_(b["dL"].to(DEV).reshape(-1))
+    tensors = [view["in_" + n].view(P, SHAPES[n]) for n in fo.NAMES]
+    cams = case_cameras(case, b)
+    c_forward(case, cams, tensors, view["flows"].data_ptr())
+    c_backward(case, cams, tensors, view["dL"], fc.SCALE, [view["out_" + n].data_ptr() for n in fo.NAMES])
+    assert np.array_equal(fc.bits(view["flows"].cpu().numpy().reshape(P, 2)), fc.bits(run_forward(case, b)))
+    want = run_backward(case, b)
+    for n in fo.NAMES:
+        assert np.array_equal(fc.bits(view["out_" + n].cpu().numpy().reshape(want[n].shape)), fc.bits(want[n])), n
+        assert torch.equal(view["in_" + n], b["par"][n].to(DEV).reshape(-1)), "%s: an input was written" % n
+    used = torch.zeros(flat.numel(), dtype=torch.bool, device=DEV)
+    for k, sz in sizes:
+        used[starts[k]:starts[k] + sz] = True
+    assert not bool(flat[~used].any()), "the padding between the slices was written"
+
+
+@pytest.mark.parametrize("name", ("raw_p1_two_mod1", "raw_p63_two_mod0.7", "raw_p65_null_mod0.7", "raw_p257_two_mod1"))
+def test_nothing_is_written_outside_the_rows(gpu_device, name):
+    """``flows`` and the six gradient buffers between guard bands (tests/guarded.py): the forward writes every element of ``flows``
+    over a NaN prefill, and neither kernel changes a guard element."""
+    case = fc.BY_NAME[name]
+    b = fc.build(case)
+    P = case.P
+    cams, tensors = case_cameras(case, b), case_inputs(case, b)
+    flows = Guarded(2 * P, DEV)
+    c_forward(case, cams, tensors, flows.ptr)
+    got = flows.check("flows").cpu().numpy().reshape(P, 2)
+    assert np.array_equal(fc.bits(got), fc.bits(run_forward(case, b)))
+    outs = [Guarded(P * SHAPES[n], DEV) for n in fo.NAMES]
+    for g in outs:
+        g.body().zero_()
+    c_backward(case, cams, tensors, b["dL"].to(DEV).contiguous(), fc.SCALE, [g.ptr for g in outs])
+    want = run_backward(case, b)
+    for n, g in zip(fo.NAMES, outs):
+        body = g.check("d_" + n, all_written=False).cpu().numpy()
+        assert np.array_equal(fc.bits(body.reshape(want[n].shape)), fc.bits(want[n])), n
